@@ -27,7 +27,17 @@ CWIPC_BENCH_PIPELINE=0 (join and downsample one after the other), CWIPC_BENCH_JO
 waits for every frame's collective before it takes the next frame).
 
 One JSON line on rank 0, the only thing written to stdout.  `value` = points filtered by all ranks / wall time of the K
-timed steps (max over ranks), inputs resident in HBM.  `roofline` = algorithmic bytes of the dominant kernel (16 B per
+timed steps (max over ranks), inputs resident in HBM; `ms_per_step` = that wall time / K.  A plain run does only this: set-up,
+W warm-up steps, the K timed steps, the dump of --dump-outputs DIR if given, the line.  Everything below is measured only with
+--full (each part can still be left out there with its --no-* option).
+
+--dump-outputs DIR: after the timed steps, what the last step handed its caller -- the filtered cloud (the fused cloud for
+N > 1), rank 0 -- as DIR/<name>.npy: points_xyz (float32, n x 3), points_rgb and points_tile (the 8-bit fields as float32),
+cellsize, timestamp and count (float64).  The inputs are the same from run to run, so two builds can be compared output for
+output.  A cloud of more than 64 MB in these arrays is written as a fixed, seeded sample of its points (in their order, with
+their positions in points_index).
+
+--full adds: `roofline` = algorithmic bytes of the dominant kernel (16 B per
 input point + 16 B per output point, all N points in one launch) / its mean launch duration, measured with hipEvents on
 the library's stream during a second pass over the same steps (each call waited for, so the kernel runs alone);
 `traffic` = HBM bytes per launch from the newest committed PMC passes (profiles/rNN_traffic.json).  `cpu_baseline` = the
@@ -56,6 +66,8 @@ NPOINTS_ARG = 10_000_000
 CELLSIZE = 0.01
 NCOPIES = 4
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261016
 
 
 def make_input(cwipc, npoints_arg: int, angle: float):
@@ -68,6 +80,36 @@ def make_input(cwipc, npoints_arg: int, angle: float):
     pc = src.get()
     src.stop()
     return pc
+
+
+def output_arrays(points: np.ndarray, cellsize: float, timestamp: int, limit_bytes: int = DUMP_LIMIT_BYTES):
+    """The arrays --dump-outputs writes for a cloud (a numpy array of the point dtype): float32 / float64 only, at most
+    limit_bytes in all.  Above that a fixed, seeded sample of the points, kept in their order, and their positions."""
+    n = len(points)
+    per_point = 7 * 4
+    keep = None
+    if n * per_point > limit_bytes - 4096:
+        rows = (limit_bytes - 4096) // (per_point + 8)
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, rows, replace=False))
+        points = points[keep]
+    arrays = {
+        "points_xyz": np.stack([points["x"], points["y"], points["z"]], axis=1).astype(np.float32),
+        "points_rgb": np.stack([points["r"], points["g"], points["b"]], axis=1).astype(np.float32),
+        "points_tile": points["tile"].astype(np.float32),
+        "cellsize": np.array([cellsize], dtype=np.float64),
+        "timestamp": np.array([timestamp], dtype=np.float64),
+        "count": np.array([n], dtype=np.float64),
+    }
+    if keep is not None:
+        arrays["points_index"] = keep.astype(np.float64)
+    return arrays
+
+
+def dump_outputs(outdir: str, pc) -> None:
+    """--dump-outputs: the cloud the timed path's last step handed its caller, as outdir/<name>.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in output_arrays(pc.get_numpy_array(), pc.cellsize(), pc.timestamp()).items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def measured_traffic(n_points: int, kernel: str):
@@ -385,19 +427,31 @@ def bench_config3(cwipc, pc, n: int, runs: int = 5):
     }
 
 
-def main() -> None:
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--npoints", type=int, default=NPOINTS_ARG)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config4", action="store_true", help="skip the 8-tile capture sub-record")
-    ap.add_argument("--no-config3", action="store_true", help="skip the outlier-removal sub-record (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (e.g. DIR = bench_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel roofline pass, config3 / config4 / config5 "
+                         "sub-records, call-then-count, CPU baseline and parity against the oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity records")
+    ap.add_argument("--no-config4", action="store_true", help="with --full: skip the 8-tile capture sub-record")
+    ap.add_argument("--no-config3", action="store_true", help="with --full: skip the outlier-removal sub-record (N = 1 only)")
     ap.add_argument("--config4-steps", type=int, default=30)
-    ap.add_argument("--no-config5", action="store_true", help="skip the live-size stream sub-record")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip the live-size stream sub-record")
     ap.add_argument("--config5-frames", type=int, default=300)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main() -> None:
+    args = parse_args()
 
     # Exactly ONE line goes to stdout: the JSON line.  Libraries that print there on their own (RCCL writes a five-line
     # version banner to stdout when a communicator is made) are sent to stderr: descriptor 1 points at stderr until the
@@ -637,24 +691,29 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    fused_points = (last_fused[0] if lib_comm is not None else joiner.drain() if joiner is not None else out).count()
+    last = last_fused[0] if lib_comm is not None else joiner.drain() if joiner is not None else out
+    fused_points = last.count()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
-    # ---- second pass over the same steps with per-kernel hipEvent timing ----
-    with cwipc.cwipc_hip_profile() as prof:
-        for i in range(args.steps):
-            cwipc.cwipc_downsample(clouds[i % NCOPIES], CELLSIZE)
-    kernels = {k: {"ms_total": v[0], "launches": v[1], "ms_avg": v[0] / max(v[1], 1)} for k, v in prof.kernels.items()}
-    dominant = max(kernels, key=lambda k: kernels[k]["ms_total"])
-    dom_ms = kernels[dominant]["ms_avg"]
-    all_ms = sum(v["ms_total"] for v in kernels.values()) / args.steps
-    algorithmic_bytes = 16 * n + 16 * n_out
-    achieved = algorithmic_bytes / (dom_ms * 1e-3) / 1e9
+    # ---- --full: second pass over the same steps with per-kernel hipEvent timing ----
+    kernels = None
+    if args.full:
+        with cwipc.cwipc_hip_profile() as prof:
+            for i in range(args.steps):
+                cwipc.cwipc_downsample(clouds[i % NCOPIES], CELLSIZE)
+        kernels = {k: {"ms_total": v[0], "launches": v[1], "ms_avg": v[0] / max(v[1], 1)} for k, v in prof.kernels.items()}
+        dominant = max(kernels, key=lambda k: kernels[k]["ms_total"])
+        dom_ms = kernels[dominant]["ms_avg"]
+        all_ms = sum(v["ms_total"] for v in kernels.values()) / args.steps
+        algorithmic_bytes = 16 * n + 16 * n_out
+        achieved = algorithmic_bytes / (dom_ms * 1e-3) / 1e9
 
-    traffic, traffic_src = measured_traffic(n, dominant)
+        traffic, traffic_src = measured_traffic(n, dominant)
 
-    # ---- sub-records: BASELINE configs[3] (8-tile capture, strong scaling over ranks) and configs[2] (outlier removal) ----
+    # ---- --full: sub-records: BASELINE configs[3] (8-tile capture, strong scaling over ranks) and configs[2] (outlier removal) ----
     config4 = None
-    if not args.no_config4:
+    if args.full and not args.no_config4:
         if joiner is not None:
             joiner.drain()
         # (N > 1 with the library's exchange: cwipc_hip_comm_submit, so that the join of frame i overlaps the tiles of frame i + 1;
@@ -675,7 +734,7 @@ def main() -> None:
             "fused_points": c4_fused, "inputs_resident_in_hbm": True, "tile_threads_per_rank": c4_threads,
         }
     config5 = None
-    if not args.no_config5:
+    if args.full and not args.no_config5:
         c5_join = (lib_comm.submit if lib_comm is not None else join_across_ranks) if joining else None
         c5 = bench_config5(cwipc, rank, world, args.config5_frames, 10, fence, c5_join)
         c5_elapsed = c5["elapsed"]
@@ -699,7 +758,7 @@ def main() -> None:
             "h2d_d2h_share_of_that": (1.0 - ms_frame / c5["host_io_ms_per_frame"]) if c5["host_io_ms_per_frame"] else None,
         }
     config3 = None
-    if world == 1 and not args.no_config3 and args.npoints == NPOINTS_ARG:
+    if args.full and world == 1 and not args.no_config3 and args.npoints == NPOINTS_ARG:
         config3 = bench_config3(cwipc, clouds[0], n)
 
     if rank == 0:
@@ -716,6 +775,7 @@ def main() -> None:
             "vs_baseline": None,
             "dtype": "f32 coordinates in, i64 fixed-point sums, u8 colours",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": f"cwipc_synthetic({args.npoints}) -> cwipc_downsample(+{CELLSIZE}) [BASELINE configs[1]]"
                             + (f" per rank, tile masks 1<<rank, + all-gatherv join over {world} ranks"
@@ -729,7 +789,9 @@ def main() -> None:
                 **({"voxel_kernel_spare_cus": int(os.environ.get("CWIPC_SPARE_CUS", "0")), "exchange": exchange} if joining else {}),
                 **({"exchange_fallback": True, "exchange_note": exchange_note} if exchange_note else {}),
             },
-            "roofline": {
+        }
+        if kernels is not None:
+            result["roofline"] = {
                 "bound": "hbm",
                 "kernel": dominant,
                 "achieved": achieved,
@@ -752,20 +814,19 @@ def main() -> None:
                         "thread's calls rotate over three workspaces and streams and up to three accumulate kernels are in flight at once: a "
                         "call completes every ms_per_step (achieved_pipelined), while a kernel's own duration in a trace of that region is "
                         "longer than alone -- profiles/rNN_bench_rocprofv3_summary.txt gives both parts and the run with one workspace",
-            },
-            "kernels": kernels,
-        }
+            }
+            result["kernels"] = kernels
         if config4 is not None:
             result["config4"] = config4
         if config3 is not None:
             result["config3"] = config3
         if config5 is not None:
             result["config5"] = config5
-        if world == 1:
+        if args.full and world == 1:
             # a single call with its result settled, both signs of the cell size (the stream figure above never settles one)
             result["call_then_count_us"] = {"+0.01": call_then_count(cwipc, clouds, CELLSIZE), "-0.01": call_then_count(cwipc, clouds, -CELLSIZE),
                                             "note": "one cwipc_downsample followed by count(), median of 40 calls on rotating inputs, wall"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(pts, pc_cellsize)
             result["parity"] = parity_record(pts, pc_cellsize, cwipc.cwipc_downsample(clouds[0], CELLSIZE).get_numpy_array())
         sys.stdout.flush()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # K1 ablation study: time voxel_accumulate with parts switched off (results are wrong then; timing only)
 for a in 0 1 2 18 22 6 4 8 12 16; do
-  CWIPC_VOXEL_ABLATE=$a timeout -k 10 120 python bench.py --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
+  CWIPC_VOXEL_ABLATE=$a timeout -k 10 120 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

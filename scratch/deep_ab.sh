@@ -2,7 +2,7 @@
 # the accumulate kernel with two steps in flight behind the one being processed (-DCWIPC_K1_DEEP, scratch/lib_deep) against the shipped one
 for lib in "" scratch/lib_deep "" scratch/lib_deep; do
   echo "== lib=${lib:-shipped}"
-  env ${lib:+CWIPC_LIBRARY_DIR=$PWD/$lib} python bench.py --steps 200 --warmup 30 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
+  env ${lib:+CWIPC_LIBRARY_DIR=$PWD/$lib} python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 run() { # label, env...
   label=$1; shift
-  env "$@" python3 bench.py --steps ${STEPS:-100} --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --steps ${STEPS:-100} --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$label', 'K1 alone us', round(d['kernels']['voxel_accumulate']['ms_avg']*1e3,1), 'step us', round(d['ms_per_step']*1e3,1), 'Gpts/s', round(d['value']/1e3,1), {k:round(v['ms_avg']*1e3,1) for k,v in d['kernels'].items()})"
 }

@@ -6,7 +6,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 for a in ${ABLS:-0 2 4 20 52 116 8}; do
   export CWIPC_VOXEL_ABLATE=$a
-  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_INSTS_BRANCH --output-format csv -d $OUT/a$a -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/a$a.log 2>&1 || exit 1
+  rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_INSTS_BRANCH --output-format csv -d $OUT/a$a -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/a$a.log 2>&1 || exit 1
 done
 python3 - <<'PY'
 import csv, glob, collections, os

@@ -6,7 +6,7 @@ out = sys.argv[1]
 rnd = sys.argv[2] if len(sys.argv) > 2 else "rNN"
 traffic_only = "--traffic-only" in sys.argv
 if not traffic_only:
-    print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5")
+    print("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5")
     for l in open(os.path.join(out, "bench_trace.json")):
         if l.startswith("{"):
             d = json.loads(l)
@@ -86,7 +86,7 @@ if "fetch" in means and "write" in means:
             n_points = json.loads(l)["config"]["points_per_gpu"]
     rec = {
         "round": int(rnd.lstrip("r") or 0),
-        "command": "rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-config4 --no-config3 --no-config5 ; same with --pmc WRITE_SIZE (separate passes; scratch/profile_round.sh %s)" % rnd,
+        "command": "rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-config4 --no-config3 --no-config5 ; same with --pmc WRITE_SIZE (separate passes; scratch/profile_round.sh %s)" % rnd,
         "workload_points": n_points,
         "kernel": "voxel_accumulate",
         "kernel_symbol": symbol,

@@ -4,7 +4,7 @@
 for cfg in "0 0" "20 0" "25 0" "30 0" "20 1" "25 1" "30 1" "0 0" "25 0" "25 1"; do
   set -- $cfg
   echo "== STAGGER=$1 REV=$2"
-  env CWIPC_K1_STAGGER=$1 CWIPC_K1_STAGGER_REV=$2 python bench.py --steps 200 --warmup 30 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
+  env CWIPC_K1_STAGGER=$1 CWIPC_K1_STAGGER_REV=$2 python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline --no-config4 --no-config3 --no-config5 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

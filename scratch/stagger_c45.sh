@@ -1,7 +1,7 @@
 #!/bin/bash
 for s in 0 25 0 25; do
   echo "== STAGGER=$s"
-  env CWIPC_K1_STAGGER=$s python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-config3 2>/dev/null | python3 -c "
+  env CWIPC_K1_STAGGER=$s python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-config3 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

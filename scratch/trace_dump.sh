@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 for m in 0 2; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/trace_dump$m
   rm -rf $OUT; mkdir -p $OUT
-  CWIPC_K1_DUMP=$m rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5 > $OUT/bench.log 2>&1
+  CWIPC_K1_DUMP=$m rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-config4 --no-config3 --no-config5 > $OUT/bench.log 2>&1
   python3 - $OUT <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/*/*kernel_trace.csv')[0]

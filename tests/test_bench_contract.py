@@ -52,3 +52,45 @@ def test_committed_profile_files_are_from_one_run():
     assert int(m.group(1)) == int(k1[0]["Calls"]) and abs(int(m.group(3)) - avg_csv) <= 1.0, (m.groups(), avg_csv)
     assert "# bench line under the profiler:" in summary
     assert os.path.exists(os.path.join(prof, newest + "_bench_line.json")) and os.path.exists(os.path.join(prof, newest + "_traffic.json"))
+
+
+def _bench():
+    sys.path.insert(0, ROOT)
+    import bench
+    return bench
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    bench = _bench()
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 3, False, None)
+    args = bench.parse_args(["--steps", "7", "--warmup", "3", "--full", "--dump-outputs", "out", "--no-config5"])
+    assert args.full and args.dump_outputs == "out" and args.no_config5
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dumped_outputs_are_float_arrays_within_the_limit():
+    import numpy as np
+    bench = _bench()
+    dtype = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('r', 'u1'), ('g', 'u1'), ('b', 'u1'), ('tile', 'u1')])
+    rng = np.random.default_rng(5)
+    pts = np.zeros(1000, dtype=dtype)
+    for f in ("x", "y", "z"):
+        pts[f] = rng.random(1000, dtype=np.float32)
+    for f in ("r", "g", "b", "tile"):
+        pts[f] = rng.integers(0, 256, 1000)
+    a = bench.output_arrays(pts, 0.01, 1000)
+    assert set(a) == {"points_xyz", "points_rgb", "points_tile", "cellsize", "timestamp", "count"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert (a["points_xyz"][:, 1] == pts["y"]).all() and (a["points_rgb"][:, 2] == pts["b"]).all() and (a["points_tile"] == pts["tile"]).all()
+    assert a["cellsize"][0] == 0.01
+    assert a["count"][0] == 1000 and a["timestamp"][0] == 1000
+    # above the limit: the same fixed sample every time, in input order, with the points' positions
+    small = bench.output_arrays(pts, 0.01, 1000, limit_bytes=4096 + 100 * 36)
+    again = bench.output_arrays(pts, 0.01, 1000, limit_bytes=4096 + 100 * 36)
+    assert sum(v.nbytes for v in small.values()) <= 4096 + 100 * 36
+    idx = small["points_index"].astype(np.int64)
+    assert len(idx) == 100 and (np.diff(idx) > 0).all() and (idx == again["points_index"]).all()
+    assert (small["points_xyz"][:, 0] == pts["x"][idx]).all() and small["count"][0] == 1000
