@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 
 #include <algorithm>
 #include <cstring>
@@ -608,5 +609,84 @@ extern "C" int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, flo
     }
     pool_free(dist);
     if (ok && threshold) *threshold = thr;
+    return ok ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------
+// reference python/cwipc/registration/util.py:114-143 (cwipc_direction_filter)
+// ---------------------------------------------------------------------------
+namespace {
+
+bool direction_args_ok(const char *who, float radius, int max_nn) {
+    if (radius > 0.f && std::isfinite(radius) && max_nn >= 1 && max_nn <= DIRECTION_MAX_NN) return true;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "radius must be positive and finite, max_nn between 1 and 128");
+    return false;
+}
+
+}  // namespace
+
+extern "C" cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud *pc, double dx, double dy, double dz, double threshold, float radius, int max_nn) {
+    if (pc == nullptr) return nullptr;
+    if (!direction_args_ok("cwipc_hip_direction_filter", radius, max_nn)) return nullptr;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input("cwipc_hip_direction_filter", pc, keep);
+    if (!src) return nullptr;
+    const size_t n = src->npoints;
+    if (n == 0) return wrap(soa_alloc(0), pc->timestamp(), pc->cellsize());
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    // the reference divides by the norm unless it is 0 (a zero direction: every dot product is 0)
+    double dir[3] = {dx, dy, dz};
+    const double len = sqrt(dx * dx + dy * dy + dz * dz);
+    if (len != 0.0) for (double &v : dir) v /= len;
+    // the decision as a float plane (0 keep, 1 drop) and the outlier filter's compaction (mode 3: keep iff !(plane > 0.5))
+    float *drop = (float *)pool_alloc(n * sizeof(float) + 256);
+    if (!drop) return nullptr;
+    double *cen = reinterpret_cast<double *>(reinterpret_cast<char *>(drop) + ((n * sizeof(float) + 127) & ~(size_t)127));
+    std::shared_ptr<DeviceSoA> out;
+    if (direction_normals(*src, radius, max_nn, dir, threshold, drop, nullptr, 0, nullptr, cen)) out = sor_select(*src, drop, 0.5);
+    if (!out) (void)c.sync();   // kernels that write `drop` may still be in flight
+    pool_free(drop);
+    return wrap(out, pc->timestamp(), pc->cellsize());
+}
+
+extern "C" int cwipc_hip_estimate_normals(cwipc_pointcloud *pc, float radius, int max_nn, float *normals, uint32_t *nn_count, float *centroid, size_t cap) {
+    if (pc == nullptr || (normals == nullptr && nn_count != nullptr)) return -1;
+    if (!direction_args_ok("cwipc_hip_estimate_normals", radius, max_nn)) return -1;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input("cwipc_hip_estimate_normals", pc, keep);
+    if (!src) return -1;
+    const size_t n = src->npoints;
+    if (normals && cap < n) return -1;
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    // one block: normals (3 x n floats) | counts (n words) | centroid (3 doubles)
+    const size_t nb = 3 * n * sizeof(float), cb = n * sizeof(uint32_t);
+    const size_t cen_at = (nb + cb + 127) & ~(size_t)127, bytes = cen_at + 3 * sizeof(double);
+    char *block = (char *)pool_alloc(bytes);
+    if (!block) return -1;
+    float *dn = (float *)block;
+    uint32_t *dc = (uint32_t *)(block + nb);
+    double *dcen = (double *)(block + cen_at);
+    const double zero[3] = {0, 0, 0};
+    bool ok = direction_normals(*src, radius, max_nn, zero, 0.0, nullptr, normals ? dn : nullptr, n, normals ? dc : nullptr, dcen);
+    if (ok) {
+        char *stage = (char *)c.staging(bytes);
+        ok = stage && hipMemcpyAsync(stage, block, bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = c.sync() && ok;
+        if (ok) {
+            // the caller's normals are three planes of `cap` floats
+            if (normals) for (int a = 0; a < 3; a++) memcpy(normals + (size_t)a * cap, stage + (size_t)a * n * sizeof(float), n * sizeof(float));
+            if (nn_count) memcpy(nn_count, stage + nb, cb);
+            if (centroid) {
+                const double *hc = (const double *)(stage + cen_at);
+                for (int a = 0; a < 3; a++) centroid[a] = (float)hc[a];
+            }
+        }
+    } else {
+        (void)c.sync();
+    }
+    pool_free(block);
     return ok ? 0 : -1;
 }

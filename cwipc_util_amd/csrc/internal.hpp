@@ -405,6 +405,14 @@ std::shared_ptr<DeviceSoA> sor_select(const DeviceSoA &src, const float *dev_dis
 // The outlier filter's last steps on the device: statistics, threshold, compaction.  Small clouds: the statistics' second kernel rides with the compaction's count.
 std::shared_ptr<DeviceSoA> sor_threshold_and_select(const DeviceSoA &src, const float *dev_dist, float stddev_mul, double *thr_dev);
 
+// The direction filter's per-point work (kernels_sor.hip): the centroid into centroid_dev (3 device doubles), then per point the
+// normal of its neighbourhood (the max_nn nearest within radius), turned away from the centroid.  Each output may be nullptr:
+// drop[i] = 0 if normal . dir >= threshold else 1; normals = planes x, y, z of `stride` floats; nn_count[i] = |neighbourhood|.
+// No wait inside.  Returns false on failure (logged), also for radius <= 0, a non-finite radius or max_nn outside 1..DIRECTION_MAX_NN.
+constexpr int DIRECTION_MAX_NN = 128;
+bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const double dir[3], double threshold, float *drop, float *normals,
+                       size_t stride, uint32_t *nn_count, double *centroid_dev);
+
 // Generic stable compaction driver used by tilefilter / crop / masked filter.
 // may_return_early: the call may come back with the scatter kernel still running (the result carries a
 // `ready` event); only for predicates that refer to nothing the caller frees afterwards.

@@ -27,6 +27,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <functional>
 #include <mutex>
 
 namespace cwipc_amd {
@@ -1012,10 +1013,24 @@ static inline unsigned grid_for(size_t n) {
     return (unsigned)g;
 }
 
+// A search other than the outlier filter's on the grid a flow below has built (the direction filter's): the flows call it where
+// they would launch the k-NN kernel, on the same stream, and free the grid's arrays behind it as they do behind that kernel.
+// gm: the device-decided grid (slot 1 holds the coarser grid when gm[1].refine is set and counts2 is given), or nullptr and g.
+// sparse: counts is the segment table (seg_pack_kernel), starts is indexed by the cells that exist.
+struct GridView {
+    Grid g;
+    const GridMeta *gm;
+    const float4 *sorted;
+    size_t n;
+    const uint32_t *starts, *counts, *counts2;
+    bool sparse;
+};
+typedef std::function<bool(const GridView &, hipStream_t)> GridSearch;
+
 // The dense layout, driven from the device: box -> grid -> census -> (coarser grid, second count) -> counting sort -> k-NN,
 // sixteen launches and no wait (the caller has one further down, behind the compaction).  Arrays are sized for the largest
 // grid the rules allow (a few cells per point), whatever the kernels then decide.
-bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *partial, unsigned nb, ThreadCtx &c) {
+bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *partial, unsigned nb, ThreadCtx &c, const GridSearch *search) {
     const size_t n = src.npoints;
     static const size_t cells_per_point = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();   // tuning knob
     const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, cells_per_point * n));
@@ -1060,7 +1075,9 @@ bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *pa
         CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts, cursor,
                   sorted);
         const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-        if (k + 1 <= 17) {
+        if (search) {
+            ok = (*search)(GridView{unused, meta, sorted, n, starts, counts, nullptr, false}, c.stream);
+        } else if (k + 1 <= 17) {
             CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist);
         } else if (k + 1 <= 33) {
             CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist);
@@ -1082,7 +1099,7 @@ bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *pa
 }
 
 // The same for small clouds (cap <= 2^19 cells: up to 64 k points; k + 1 <= 33): ten launches with the compaction behind it, see small_bbox_zero_kernel.
-bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t cap, ThreadCtx &c) {
+bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t cap, ThreadCtx &c, const GridSearch *search) {
     const size_t n = src.npoints;
     double target = (double)(k + 1) / 2.0;
     if (const char *t = getenv("CWIPC_SOR_CELL_TARGET")) target = (double)(k + 1) * atof(t);   // tuning knob: points per occupied cell / (k + 1)
@@ -1112,14 +1129,17 @@ bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t ca
     CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(pgrid), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts, cursor, sorted);
     const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
     static const bool pair_off = []() { const char *e = getenv("CWIPC_SOR_PAIR"); return e && atoi(e) == 0; }();   // test knob: a lane per query
-    if (k == 16 && !pair_off) {
+    bool searched = true;
+    if (search) {
+        searched = (*search)(GridView{unused, meta, sorted, n, starts, counts, counts2, false}, c.stream);
+    } else if (k == 16 && !pair_off) {
         CW_LAUNCH("sor_knn_mean_dist", knn_pair_kernel, dim3((unsigned)((2 * n + QB - 1) / QB)), dim3(QB), 0, c.stream, meta, sorted, n, starts, counts, counts2, dev_dist);
     } else if (k + 1 <= 17) {
         CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist, counts2);
     } else {
         CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist, counts2);
     }
-    if (hipGetLastError() != hipSuccess) {
+    if (hipGetLastError() != hipSuccess || !searched) {
         hip_failed(hipGetLastError(), "sor k-NN", __FILE__, __LINE__);
         (void)c.sync();
         give_back(false);
@@ -1131,7 +1151,11 @@ bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t ca
 
 }  // namespace
 
-bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) {
+namespace {
+
+// The grid (three flows: small clouds, the dense layout decided on the device, the sparse layout) and the search on it: the
+// outlier filter's k-NN (search == nullptr, d_i into dev_dist) or the caller's.  k sets the grid's cell size in both cases.
+bool grid_and_search(const DeviceSoA &src, int k, float *dev_dist, const GridSearch *search) {
     ThreadCtx &c = tctx();
     if (!c.ensure()) return false;
     const size_t n = src.npoints;
@@ -1150,14 +1174,14 @@ bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) {
         static const size_t cells_per_point = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();   // tuning knob
         static const size_t small_cells = []() { const char *e = getenv("CWIPC_SOR_SMALL_CELLS"); return e ? (size_t)atol(e) : (size_t)1 << 19; }();   // 0: never (test knob)
         const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, cells_per_point * n));
-        if (cap <= small_cells) return sor_small_on_device(src, k, dev_dist, cap, c);
+        if (cap <= small_cells) return sor_small_on_device(src, k, dev_dist, cap, c, search);
     }
     // 1. bounding box
     const unsigned nb = grid_for(n);
     float *partial = (float *)pool_alloc((size_t)nb * 6 * sizeof(float));
     if (!partial) return false;
     CW_LAUNCH("sor_bbox", bbox_kernel, dim3(nb), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, partial);
-    if (!sparse && !host_grid) return sor_dense_on_device(src, k, dev_dist, partial, nb, c);
+    if (!sparse && !host_grid) return sor_dense_on_device(src, k, dev_dist, partial, nb, c, search);
     float *hpart = (float *)c.staging((size_t)nb * 6 * sizeof(float));
     bool ok = hpart && hipMemcpyAsync(hpart, partial, (size_t)nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
     ok = c.sync() && ok;
@@ -1276,7 +1300,9 @@ bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) {
             CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts,
                       cursor, sorted);
             const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-            if (k + 1 <= 17) {
+            if (search) {
+                ok = (*search)(GridView{g, nullptr, sorted, n, starts, info, nullptr, true}, c.stream);
+            } else if (k + 1 <= 17) {
                 CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, true>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, info, k, dev_dist);
             } else {
                 CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, true>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, info, k, dev_dist);
@@ -1356,7 +1382,9 @@ bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) {
                   cursor, sorted);
         // 4. the k-NN pass
         const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-        if (k + 1 <= 17) {
+        if (search) {
+            ok = (*search)(GridView{g, nullptr, sorted, n, starts, counts, nullptr, false}, c.stream);
+        } else if (k + 1 <= 17) {
             CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, counts, k, dev_dist);
         } else if (k + 1 <= 33) {
             CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, counts, k, dev_dist);
@@ -1376,6 +1404,10 @@ bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) {
     }
     return ok;
 }
+
+}  // namespace
+
+bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist) { return grid_and_search(src, k, dev_dist, nullptr); }
 
 // mean, variance and threshold from the 1024 partial sums: a pairwise tree (s[i] = s[2i] + s[2i+1], ten
 // levels), the order the host version (sor_threshold) follows too, then the same f64 expressions
@@ -1473,6 +1505,333 @@ std::shared_ptr<DeviceSoA> sor_select(const DeviceSoA &src, const float *dev_dis
     p.thr = thr;
     p.thr_dev = thr_dev;
     return compact(src, p);   // (waits for its kernels: the caller frees dev_dist afterwards)
+}
+
+
+// ---- the direction filter: a normal per point, oriented away from the centroid, kept when it faces a direction ----
+// Reference: cwipc_direction_filter (python/cwipc/registration/util.py:114-143), whose normals come from open3d's EstimateNormals
+// with KDTreeSearchParamHybrid(radius, max_nn) and orient_normals_towards_camera_location(centroid), then are negated.
+//   N(p)   = the points q with |q - p| < radius, the max_nn nearest of them (p itself included, at distance 0)
+//   n_raw  = (0, 0, 1) if |N| < 3 or the covariance of N is 0, else the unit eigenvector of its smallest eigenvalue
+//   n      = -(n_raw, negated if n_raw . (c - p) < 0),  c = the cloud's centroid (f64 sum)
+//   keep p iff n . d >= threshold  (d: the direction, unit length unless it is 0)
+// The neighbourhood comes from the outlier filter's grid (grid_and_search) and its shell search in two passes over the same rows:
+// pass 1 keeps the max_nn smallest fp32 distances (the list in registers, its empty slots holding radius^2, so nothing at or beyond
+// the radius enters and the shell loop's exit test also ends the search once the shells reach the radius); its last slot is the
+// cutoff.  Pass 2 visits the same rows again and sums, for every point at or under the cutoff (all of a tie at the cutoff: the
+// result does not depend on the order of the points in a cell), count, sum(q - p) and sum((q - p)(q - p)^T) in int64 fixed point
+// (2^-20 of the cutoff distance), which no order of the candidates changes: the normals are the same bits run after run.
+namespace {
+
+constexpr double DIR_FIX = 1048576.0;   // fixed-point units per cutoff distance
+
+// The eigenvector of the smallest eigenvalue of a symmetric 3x3 (cyclic Jacobi in f64: rotations until the off-diagonal part is
+// negligible against the whole, at most 12 sweeps; three are usually enough).  The smallest diagonal entry at the end names it,
+// the lowest index on a tie.
+__host__ __device__ inline void smallest_eigvec(double a[3][3], double out[3]) {
+    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int sweep = 0; sweep < 12; sweep++) {
+        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
+        const double all = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2] + 2.0 * off;
+        if (!(off > 1e-32 * all)) break;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const int p = r == 2 ? 1 : 0, q = r == 0 ? 1 : 2;
+            const double apq = a[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {   // columns p and q
+                const double akp = a[k][p], akq = a[k][q];
+                a[k][p] = c * akp - s * akq;
+                a[k][q] = s * akp + c * akq;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {   // rows p and q
+                const double apk = a[p][k], aqk = a[q][k];
+                a[p][k] = c * apk - s * aqk;
+                a[q][k] = s * apk + c * aqk;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double vkp = v[k][p], vkq = v[k][q];
+                v[k][p] = c * vkp - s * vkq;
+                v[k][q] = s * vkp + c * vkq;
+            }
+        }
+    }
+    int m = 0;
+    if (a[1][1] < a[m][m]) m = 1;
+    if (a[2][2] < a[m][m]) m = 2;
+    const double len = sqrt(v[0][m] * v[0][m] + v[1][m] * v[1][m] + v[2][m] * v[2][m]);
+    for (int k = 0; k < 3; k++) out[k] = v[k][m] / len;
+}
+
+// centroid: f64 sums over contiguous slices (fixed order for the fixed launch shape), then the pairwise tree of stats_final_kernel
+constexpr int CEN_BLOCKS = 1024;
+__global__ void __launch_bounds__(BLK) centroid_partial_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, size_t n,
+                                                              double *__restrict__ partial /* [CEN_BLOCKS][3] */) {
+    __shared__ double red[3][BLK / 64];
+    double s[3] = {0, 0, 0};
+    const size_t per = (n + gridDim.x - 1) / gridDim.x;
+    const size_t lo = (size_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
+    for (size_t i = lo + threadIdx.x; i < hi; i += BLK) { s[0] += (double)x[i]; s[1] += (double)y[i]; s[2] += (double)z[i]; }
+    for (int a = 0; a < 3; a++) {
+        for (int off = 32; off > 0; off >>= 1) s[a] += __shfl_down(s[a], off, 64);
+        if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = s[a];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double t = 0;
+        for (int w = 0; w < BLK / 64; w++) t += red[threadIdx.x][w];
+        partial[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(CEN_BLOCKS) centroid_final_kernel(const double *__restrict__ partial, size_t n, double *__restrict__ cen) {
+    __shared__ double s[3][CEN_BLOCKS];
+    for (int a = 0; a < 3; a++) s[a][threadIdx.x] = partial[threadIdx.x * 3 + a];
+    __syncthreads();
+    for (unsigned width = CEN_BLOCKS / 2; width >= 1; width >>= 1) {
+        double v[3] = {0, 0, 0};
+        if (threadIdx.x < width)
+            for (int a = 0; a < 3; a++) v[a] = s[a][2 * threadIdx.x] + s[a][2 * threadIdx.x + 1];
+        __syncthreads();
+        if (threadIdx.x < width)
+            for (int a = 0; a < 3; a++) s[a][threadIdx.x] = v[a];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) cen[threadIdx.x] = s[threadIdx.x][0] / (double)n;
+}
+
+struct DirectionArgs {
+    float r2;                 // radius^2 in fp32: no candidate at or beyond it is taken
+    int want;                 // max_nn
+    const double *cen;        // device: the centroid
+    double dir[3], threshold;
+    float *drop;              // per input point: 0 keep, 1 drop (nullptr: not written)
+    float *normals;           // planes x, y, z of `stride` floats each (nullptr: not written)
+    size_t stride;
+    uint32_t *nn;             // |N(p)| (nullptr: not written)
+};
+
+// One lane per point in cell order, as knn_mean_dist_reg_kernel.  KCAP >= want; the first KCAP - want slots hold -inf.
+template <int KCAP, bool SPARSE>
+__global__ void __launch_bounds__(QB) direction_kernel(Grid gv, const GridMeta *__restrict__ gm, const float4 *__restrict__ sorted, size_t n,
+                                                      const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ cell_count,
+                                                      const uint32_t *__restrict__ cell_count2, DirectionArgs A) {
+    if (cell_count2 && gm[1].refine) { gm += 1; cell_count = cell_count2; }   // the small clouds' flow: the coarser grid's slot and counts
+    const Grid g = gm ? gm->g : gv;
+    const size_t qi = (size_t)blockIdx.x * QB + threadIdx.x;
+    if (qi >= n) return;
+    const float4 q = sorted[qi];
+    const int cx = cell_coord(g, q.x, 0), cy = cell_coord(g, q.y, 1), cz = cell_coord(g, q.z, 2);
+    const int pad = KCAP - A.want;
+    float best[KCAP];
+#pragma unroll
+    for (int j = 0; j < KCAP; j++) best[j] = j < pad ? -INFINITY : A.r2;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const f32x2 qxy = {q.x, q.y};
+    auto dist2 = [&](const float4 p) {   // the outlier filter's fp32 distance, the same operations in the same order
+        const f32x2 dxy = qxy - f32x2{p.x, p.y};
+        const f32x2 sq = dxy * dxy;
+        const float dz = __fsub_rn(q.z, p.z);
+        return __fadd_rn(__fadd_rn(sq.x, sq.y), __fmul_rn(dz, dz));
+    };
+    auto row_range = [&](int x0, int x1, int y, int z, uint32_t &first, uint32_t &last) {   // (as in knn_mean_dist_reg_kernel)
+        if (SPARSE) {
+            const uint32_t rowseg = (uint32_t)g.nsegx * ((uint32_t)y + (uint32_t)g.dim[1] * (uint32_t)z);
+            const uint32_t i0 = cell_count[rowseg + ((uint32_t)x0 >> SEG_SHIFT)], i1 = cell_count[rowseg + ((uint32_t)x1 >> SEG_SHIFT)];
+            first = cell_start[((i0 >> 1) << SEG_SHIFT) + ((i0 & 1u) ? ((uint32_t)x0 & (SEG - 1)) : 0u)];
+            last = cell_start[((i1 >> 1) << SEG_SHIFT) + ((i1 & 1u) ? ((uint32_t)x1 & (SEG - 1)) + 1u : 0u)];
+            return;
+        }
+        const uint32_t base = (uint32_t)g.dim[0] * ((uint32_t)y + (uint32_t)g.dim[1] * (uint32_t)z);
+        const uint32_t c1 = base + (uint32_t)x1;
+        first = cell_start[base + (uint32_t)x0];
+        last = cell_start[c1] + cell_count[c1];
+    };
+    // The rows of shell `ring` (ring 1: shells 0 and 1 together, the query's own row first), a row only if its nearest face is
+    // not beyond bound() -- strictly beyond for pass 2, which takes candidates AT the cutoff too.  scan(first, last) takes the points.
+    auto visit = [&](int ring, auto bound, bool strict, auto scan) {
+        auto beyond = [&](float gap) { return strict ? gap > bound() : gap >= bound(); };
+        if (ring == 1) {
+            const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
+            const float eps = (float)(g.h * 1e-5), hf = (float)g.h;
+            const float ylo = (float)((double)g.mn[1] + (double)cy * g.h), zlo = (float)((double)g.mn[2] + (double)cz * g.h);
+            auto gap = [&](float v, float lo_face, int o) {
+                const float d = o == 0 ? 0.f : (o < 0 ? v - lo_face : lo_face + hf - v);
+                const float t = fmaxf(d - eps, 0.f);
+                return t * t;
+            };
+            constexpr int order[9] = {4, 1, 3, 5, 7, 0, 2, 6, 8};
+            for (int o = 0; o < 9; o++) {
+                const int r = order[o];
+                const int y = cy + (r % 3) - 1, z = cz + (r / 3) - 1;
+                if (y < 0 || y >= g.dim[1] || z < 0 || z >= g.dim[2]) continue;
+                if (o > 0 && beyond(gap(q.y, ylo, r % 3 - 1) + gap(q.z, zlo, r / 3 - 1))) continue;
+                uint32_t first, last;
+                row_range(x0, x1, y, z, first, last);
+                scan(first, last);
+            }
+            return;
+        }
+        const int x0 = max(cx - ring, 0), x1 = min(cx + ring, g.dim[0] - 1);
+        auto gap2 = [&](float v, int a, int cell, int o) -> float {   // (as in knn_mean_dist_reg_kernel)
+            if (o == 0) return 0.f;
+            const double face = (double)g.mn[a] + (double)(o < 0 ? cell + o + 1 : cell + o) * g.h;
+            const double d = o < 0 ? (double)v - face : face - (double)v;
+            return d > 0.0 ? (float)(d * d * (1.0 - 1e-6)) : 0.f;
+        };
+        const float gx_lo = gap2(q.x, 0, cx, -ring), gx_hi = gap2(q.x, 0, cx, ring);
+        for (int dz = -ring; dz <= ring; dz++) {
+            const int z = cz + dz;
+            if (z < 0 || z >= g.dim[2]) continue;
+            const float gz = gap2(q.z, 2, cz, dz);
+            for (int dy = -ring; dy <= ring; dy++) {
+                const int y = cy + dy;
+                if (y < 0 || y >= g.dim[1]) continue;
+                const float gyz = gz + gap2(q.y, 1, cy, dy);
+                if (beyond(gyz)) continue;
+                const bool face = dz == -ring || dz == ring || dy == -ring || dy == ring;
+                uint32_t first, last;
+                if (face) {
+                    row_range(x0, x1, y, z, first, last);
+                    scan(first, last);
+                } else {
+                    if (cx - ring >= 0 && !beyond(gyz + gx_lo)) { row_range(cx - ring, cx - ring, y, z, first, last); scan(first, last); }
+                    if (cx + ring < g.dim[0] && !beyond(gyz + gx_hi)) { row_range(cx + ring, cx + ring, y, z, first, last); scan(first, last); }
+                }
+            }
+        }
+    };
+    // pass 1: the want smallest distances under radius^2
+    auto take = [&](const float4 p) {
+        const float d2 = dist2(p);
+        if (d2 < best[KCAP - 1]) {
+#pragma unroll
+            for (int j = KCAP - 1; j >= 1; j--) best[j] = __builtin_amdgcn_fmed3f(best[j - 1], best[j], d2);
+            best[0] = fminf(best[0], d2);
+        }
+    };
+    auto scan1 = [&](uint32_t first, uint32_t last) {
+        uint32_t e = first;
+        for (; e + 4 <= last; e += 4) {
+            const float4 p0 = sorted[e], p1 = sorted[e + 1], p2 = sorted[e + 2], p3 = sorted[e + 3];
+            take(p0); take(p1); take(p2); take(p3);
+        }
+        for (; e < last; e++) take(sorted[e]);
+    };
+    auto worst = [&]() { return best[KCAP - 1]; };
+    const int maxring = max(g.dim[0], max(g.dim[1], g.dim[2]));
+    int last_ring = 1;
+    for (int ring = 1; ring <= maxring; ring++) {
+        visit(ring, worst, false, scan1);
+        last_ring = ring;
+        // every point not yet seen lies beyond ring * h: the list is final once its last slot (the radius^2 while it is not full) is under that
+        const double reach = (double)ring * g.h;
+        if ((double)best[KCAP - 1] < reach * reach * (1.0 - 1e-6)) break;
+    }
+    const float cutoff = best[KCAP - 1];
+    // pass 2: the moments of the points at or under the cutoff (and under the radius), in fixed point
+    const double scale = cutoff > 0.f ? DIR_FIX / sqrt((double)cutoff) : 0.0;
+    uint32_t cnt = 0;
+    long long s1[3] = {0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
+    auto accumulate = [&](const float4 p) {
+        const float d2 = dist2(p);
+        if (!(d2 <= cutoff && d2 < A.r2)) return;
+        cnt++;
+        const long long u0 = llrint(((double)p.x - (double)q.x) * scale), u1 = llrint(((double)p.y - (double)q.y) * scale),
+                        u2 = llrint(((double)p.z - (double)q.z) * scale);
+        s1[0] += u0; s1[1] += u1; s1[2] += u2;
+        s2[0] += u0 * u0; s2[1] += u0 * u1; s2[2] += u0 * u2; s2[3] += u1 * u1; s2[4] += u1 * u2; s2[5] += u2 * u2;
+    };
+    auto scan2 = [&](uint32_t first, uint32_t last) {
+        uint32_t e = first;
+        for (; e + 4 <= last; e += 4) {
+            const float4 p0 = sorted[e], p1 = sorted[e + 1], p2 = sorted[e + 2], p3 = sorted[e + 3];
+            accumulate(p0); accumulate(p1); accumulate(p2); accumulate(p3);
+        }
+        for (; e < last; e++) accumulate(sorted[e]);
+    };
+    auto cut = [&]() { return cutoff; };
+    for (int ring = 1; ring <= last_ring; ring++) visit(ring, cut, true, scan2);
+    // covariance * cnt^2 (the scale does not matter to the eigenvector): cnt * S2 - S1 S1^T
+    double nrm[3] = {0.0, 0.0, 1.0};
+    if (cnt >= 3) {
+        const double m = (double)cnt;
+        double a[3][3];
+        a[0][0] = m * (double)s2[0] - (double)s1[0] * (double)s1[0];
+        a[0][1] = a[1][0] = m * (double)s2[1] - (double)s1[0] * (double)s1[1];
+        a[0][2] = a[2][0] = m * (double)s2[2] - (double)s1[0] * (double)s1[2];
+        a[1][1] = m * (double)s2[3] - (double)s1[1] * (double)s1[1];
+        a[1][2] = a[2][1] = m * (double)s2[4] - (double)s1[1] * (double)s1[2];
+        a[2][2] = m * (double)s2[5] - (double)s1[2] * (double)s1[2];
+        const bool zero = a[0][0] == 0.0 && a[0][1] == 0.0 && a[0][2] == 0.0 && a[1][1] == 0.0 && a[1][2] == 0.0 && a[2][2] == 0.0;
+        if (!zero) smallest_eigvec(a, nrm);
+    }
+    // towards the centroid, then turned round: away from it
+    const double tc = nrm[0] * (A.cen[0] - (double)q.x) + nrm[1] * (A.cen[1] - (double)q.y) + nrm[2] * (A.cen[2] - (double)q.z);
+    const double sg = tc < 0.0 ? 1.0 : -1.0;
+    for (int a = 0; a < 3; a++) nrm[a] *= sg;
+    const double dot = nrm[0] * A.dir[0] + nrm[1] * A.dir[1] + nrm[2] * A.dir[2];
+    const uint32_t at = __float_as_uint(q.w);
+    if (A.drop) A.drop[at] = dot >= A.threshold ? 0.f : 1.f;
+    if (A.normals) {
+        A.normals[at] = (float)nrm[0];
+        A.normals[A.stride + at] = (float)nrm[1];
+        A.normals[2 * A.stride + at] = (float)nrm[2];
+    }
+    if (A.nn) A.nn[at] = cnt;
+}
+
+template <int KCAP>
+void launch_direction(const GridView &v, const DirectionArgs &A, hipStream_t s) {
+    const unsigned qgrid = (unsigned)((v.n + QB - 1) / QB);
+    if (v.sparse)
+        CW_LAUNCH("direction_normals", (direction_kernel<KCAP, true>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, v.counts2, A);
+    else
+        CW_LAUNCH("direction_normals", (direction_kernel<KCAP, false>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, v.counts2, A);
+}
+
+}  // namespace
+
+bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const double dir[3], double threshold, float *drop, float *normals,
+                       size_t stride, uint32_t *nn_count, double *centroid_dev) {
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    const size_t n = src.npoints;
+    if (n == 0) return true;
+    if (!(radius > 0.f) || !std::isfinite(radius) || max_nn < 1 || max_nn > DIRECTION_MAX_NN) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip_direction_filter", "radius must be positive and finite, max_nn between 1 and 128");
+        return false;
+    }
+    double *partial = (double *)pool_alloc(CEN_BLOCKS * 3 * sizeof(double));
+    if (!partial) return false;
+    CW_LAUNCH("direction_centroid", centroid_partial_kernel, dim3(CEN_BLOCKS), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, partial);
+    CW_LAUNCH("direction_centroid", centroid_final_kernel, dim3(1), dim3(CEN_BLOCKS), 0, c.stream, partial, n, centroid_dev);
+    c.free_later(partial);
+    if (!drop && !normals && !nn_count) return hipGetLastError() == hipSuccess;   // the centroid alone (cwipc_center)
+    DirectionArgs A{};
+    A.r2 = radius * radius;   // (one fp32 product: -ffp-contract=off)
+    A.want = max_nn;
+    A.cen = centroid_dev;
+    for (int a = 0; a < 3; a++) A.dir[a] = dir[a];
+    A.threshold = threshold;
+    A.drop = drop;
+    A.normals = normals;
+    A.stride = stride;
+    A.nn = nn_count;
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        if (max_nn <= 32) launch_direction<33>(v, A, s);
+        else if (max_nn <= 64) launch_direction<65>(v, A, s);
+        else launch_direction<129>(v, A, s);
+        return hipGetLastError() == hipSuccess;
+    };
+    // the grid's cell size as for the outlier filter's k-NN of the same width (max_nn points, the query among them)
+    return grid_and_search(src, std::max(max_nn - 1, 1), nullptr, &search);
 }
 
 }  // namespace cwipc_amd

@@ -19,7 +19,7 @@ import functools
 import os
 import sys
 import warnings
-from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple, Union
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy
 import numpy.typing
@@ -42,6 +42,7 @@ __all__ = [
     'cwipc_hip_device_count', 'cwipc_hip_set_device', 'cwipc_hip_upload', 'cwipc_hip_pinned_points', 'cwipc_hip_pin_array', 'cwipc_hip_colorize', 'cwipc_tilefilter_masked', 'cwipc_hip_device_planes',
     'cwipc_hip_profile', 'cwipc_hip_knn_mean_dist', 'cwipc_hip_from_device_aos', 'cwipc_hip_from_device_slots', 'cwipc_hip_copy_device_aos',
     'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
+    'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
 ]
 
 # reference util.py:86, 346, 348
@@ -219,6 +220,8 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_offset_scale': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double], cwipc_pointcloud_p),
     'cwipc_hip_tiles_used': ([cwipc_pointcloud_p, _c.POINTER(_c.c_ubyte)], _c.c_int),
     'cwipc_hip_knn_mean_dist': ([cwipc_pointcloud_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_double), _c.c_float], _c.c_int),
+    'cwipc_hip_direction_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_float, _c.c_int], cwipc_pointcloud_p),
+    'cwipc_hip_estimate_normals': ([cwipc_pointcloud_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1051,6 +1054,42 @@ def cwipc_hip_knn_mean_dist(pc: cwipc_pointcloud_wrapper, kNeighbors: int, stdde
     if rc != 0:
         raise CwipcError("cwipc_hip_knn_mean_dist failed")
     return out[:n], float(thr.value)
+
+
+def cwipc_direction_filter(pc: cwipc_pointcloud_wrapper, direction: Union[Tuple[float, float, float], Sequence[float], numpy.ndarray], threshold: float, *,
+                           radius: float = 0.02, max_nn: int = 30) -> cwipc_pointcloud_wrapper:
+    """Filter a point cloud to keep only points that are somewhat facing a direction (reference registration/util.py:114-143).
+
+    Per point the normal of its neighbourhood (the max_nn nearest points within radius: the reference's open3d
+    KDTreeSearchParamHybrid(0.02, 30)), turned to point away from the centroid; kept iff normal . direction / |direction| >= threshold."""
+    d = numpy.asarray(direction, dtype=numpy.float64).reshape(-1)
+    assert d.shape == (3,)
+    rv = cwipc_util_dll_load().cwipc_hip_direction_filter(pc.as_cwipc_p(), float(d[0]), float(d[1]), float(d[2]), float(threshold), float(radius), int(max_nn))
+    return _wrap_filter_result('cwipc_hip_direction_filter', rv)
+
+
+def cwipc_center(pc: cwipc_pointcloud_wrapper) -> Tuple[float, float, float]:
+    """Compute the center of a point cloud (reference registration/util.py:84-89): the mean of the points, summed in f64 on the device."""
+    if pc.count() == 0:
+        return (float('nan'), float('nan'), float('nan'))
+    cen = numpy.zeros(3, dtype=numpy.float32)
+    if cwipc_util_dll_load().cwipc_hip_estimate_normals(pc.as_cwipc_p(), 0.02, 30, None, None, cen.ctypes.data, 0) != 0:
+        raise CwipcError("cwipc_center failed")
+    return (float(cen[0]), float(cen[1]), float(cen[2]))
+
+
+def cwipc_hip_estimate_normals(pc: cwipc_pointcloud_wrapper, radius: float = 0.02, max_nn: int = 30) -> Tuple[numpy.ndarray, numpy.ndarray, numpy.ndarray]:
+    """Intermediate result of the direction filter: (normals float32 (n, 3) in their final orientation, neighbourhood size per point
+    uint32 (n,), centroid float32 (3,)).  For parity tests."""
+    n = pc.count()
+    cap = max(n, 1)
+    planes = numpy.zeros((3, cap), dtype=numpy.float32)
+    nn = numpy.zeros(cap, dtype=numpy.uint32)
+    cen = numpy.full(3, numpy.nan, dtype=numpy.float32)
+    rc = cwipc_util_dll_load().cwipc_hip_estimate_normals(pc.as_cwipc_p(), float(radius), int(max_nn), planes.ctypes.data, nn.ctypes.data, cen.ctypes.data, cap)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_estimate_normals failed")
+    return numpy.ascontiguousarray(planes[:, :n].T), nn[:n], cen
 
 
 def cwipc_hip_from_device_aos(dev_ptr: int, npoint: int, timestamp: int, cellsize: float) -> cwipc_pointcloud_wrapper:

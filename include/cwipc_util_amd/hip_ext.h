@@ -132,10 +132,20 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_offset_scale(cwipc_pointcloud *pc
 _CWIPC_UTIL_EXPORT int cwipc_hip_tiles_used(cwipc_pointcloud *pc, uint8_t *used256);
 /* cwipc_tilefilter_masked (reference python/cwipc/registration/util.py:98-112): keep points with (tile & mask) != 0. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_tilefilter_masked(cwipc_pointcloud *pc, int mask);
+/* cwipc_direction_filter (reference python/cwipc/registration/util.py:114-143): the points whose normal faces (dx, dy, dz).  Normal =
+ * unit eigenvector of the smallest eigenvalue of the covariance of the max_nn nearest points within radius (the point itself among
+ * them; (0, 0, 1) for fewer than 3 such points or a zero covariance), turned to point away from the cloud's centroid; a point is
+ * kept iff normal . d / |d| >= threshold (d unnormalised when it is 0).  Input order, rgb, tile, timestamp and cellsize are kept.
+ * The reference's radius and max_nn are 0.02 and 30.  NULL on error (logged), also for radius <= 0 or not finite, max_nn < 1 or > 128. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud *pc, double dx, double dy, double dz, double threshold, float radius, int max_nn);
 
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
+/* The direction filter's normals, in their final orientation, as three planes of cap floats (x then y then z), the size of every
+ * point's neighbourhood into nn_count (cap words, may be NULL) and the centroid into centroid (3 floats, may be NULL); 0 ok, -1 error.
+ * normals and nn_count both NULL: the centroid alone (the mean of the points, summed in f64; cwipc_center). */
+_CWIPC_UTIL_EXPORT int cwipc_hip_estimate_normals(cwipc_pointcloud *pc, float radius, int max_nn, float *normals, uint32_t *nn_count, float *centroid, size_t cap);
 
 /* ---- per-kernel device timing (hipEvents on the calling thread's stream) ---- */
 _CWIPC_UTIL_EXPORT void cwipc_hip_profile_enable(int on);
