@@ -177,11 +177,11 @@ __device__ __forceinline__ WaveRun wave_run(uint32_t c, bool active) {
 
 // census: also count the cells that get their first point here (the adds then return what was there), one atomic per workgroup
 // on *census -- a separate pass over the whole cell array for it was a launch of its own
-__global__ void __launch_bounds__(BLK) cell_count_kernel(Grid gv, const GridMeta *__restrict__ gm, int second_count, const float *__restrict__ x,
+__global__ void __launch_bounds__(BLK) cell_count_kernel(const GridMeta *__restrict__ gm, int second_count, const float *__restrict__ x,
                                                         const float *__restrict__ y, const float *__restrict__ z, size_t n, uint32_t *__restrict__ counts,
                                                         uint32_t *__restrict__ cell_id, uint32_t *__restrict__ census) {
-    if (gm && second_count && !gm->refine) return;   // the census's grid stands: its counts do too
-    const Grid g = gm ? gm->g : gv;
+    if (second_count && !gm->refine) return;   // the census's grid stands: its counts do too
+    const Grid g = gm->g;
     uint32_t fresh = 0;
     for (size_t base = (size_t)blockIdx.x * BLK; base < n; base += (size_t)gridDim.x * BLK) {
         const size_t i = base + threadIdx.x;
@@ -207,27 +207,6 @@ __global__ void __launch_bounds__(BLK) cell_count_kernel(Grid gv, const GridMeta
         uint32_t t = 0;
         for (int w = 0; w < BLK / 64; w++) t += wsum[w];
         if (t) atomicAdd(census, t);
-    }
-}
-
-__global__ void __launch_bounds__(BLK) count_nonzero_kernel(const uint32_t *__restrict__ counts, size_t ncells, uint32_t *__restrict__ out) {
-    // one atomic per workgroup: thousands of adds to one address serialise (about 6 ns each)
-    __shared__ uint32_t wsum[BLK / 64];
-    uint32_t c = 0;
-    const size_t nvec = ncells / 4;
-    const uint4 *v = reinterpret_cast<const uint4 *>(counts);
-    for (size_t i = (size_t)blockIdx.x * BLK + threadIdx.x; i < nvec; i += (size_t)gridDim.x * BLK) {
-        const uint4 q = v[i];
-        c += (q.x != 0) + (q.y != 0) + (q.z != 0) + (q.w != 0);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (ncells & 3)) c += counts[nvec * 4 + threadIdx.x] != 0;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < BLK / 64; w++) t += wsum[w];
-        if (t) atomicAdd(out, t);
     }
 }
 
@@ -1027,15 +1006,50 @@ struct GridView {
 };
 typedef std::function<bool(const GridView &, hipStream_t)> GridSearch;
 
+// The search on the grid a flow has built: the caller's, or the outlier filter's k-NN (d_i into dev_dist) -- candidate lists in
+// registers up to k + 1 = 33 (small clouds' flow, the one that gives counts2, with k = 16: two lanes per query), beyond that
+// launch_knn_list.  False: the search failed.
+bool launch_knn(const GridView &v, int k, float *dev_dist, const GridSearch *search, hipStream_t s) {
+    if (search) return (*search)(v, s);
+    static const bool pair_off = []() { const char *e = getenv("CWIPC_SOR_PAIR"); return e && atoi(e) == 0; }();   // test knob: a lane per query
+    const unsigned qgrid = (unsigned)((v.n + QB - 1) / QB);
+    if (v.counts2 && k == 16 && !pair_off) {
+        CW_LAUNCH("sor_knn_mean_dist", knn_pair_kernel, dim3((unsigned)((2 * v.n + QB - 1) / QB)), dim3(QB), 0, s, v.gm, v.sorted, v.n, v.starts, v.counts, v.counts2, dev_dist);
+    } else if (k + 1 <= 17 && v.sparse) {
+        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, true>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, k, dev_dist, v.counts2);
+    } else if (k + 1 <= 17) {
+        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, k, dev_dist, v.counts2);
+    } else if (k + 1 <= 33 && v.sparse) {
+        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, true>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, k, dev_dist, v.counts2);
+    } else if (k + 1 <= 33) {
+        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.n, v.starts, v.counts, k, dev_dist, v.counts2);
+    } else {   // (the dense layout only: the other two take k + 1 <= 33)
+        void *slab = nullptr;
+        const bool ok = launch_knn_list(v.g, v.gm, v.sorted, v.n, v.starts, v.counts, k, dev_dist, s, &slab);
+        tctx().free_later(slab);
+        return ok;
+    }
+    return true;
+}
+
+// Tuning knobs: cells per point that a dense grid may have at most, and the points an occupied cell should hold, as a fraction of
+// k + 1 (`fraction` when CWIPC_SOR_CELL_TARGET is not set)
+size_t sor_cells_per_point() {
+    static const size_t cpp = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();
+    return cpp;
+}
+double sor_cell_target(int k, double fraction) {
+    static const double knob = []() { const char *e = getenv("CWIPC_SOR_CELL_TARGET"); return e ? atof(e) : NAN; }();
+    return (double)(k + 1) * (std::isnan(knob) ? fraction : knob);
+}
+
 // The dense layout, driven from the device: box -> grid -> census -> (coarser grid, second count) -> counting sort -> k-NN,
 // sixteen launches and no wait (the caller has one further down, behind the compaction).  Arrays are sized for the largest
 // grid the rules allow (a few cells per point), whatever the kernels then decide.
 bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *partial, unsigned nb, ThreadCtx &c, const GridSearch *search) {
     const size_t n = src.npoints;
-    static const size_t cells_per_point = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();   // tuning knob
-    const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, cells_per_point * n));
-    double target = (double)(k + 1) / 2.0;
-    if (const char *t = getenv("CWIPC_SOR_CELL_TARGET")) target = (double)(k + 1) * atof(t);   // tuning knob: points per occupied cell / (k + 1)
+    const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, sor_cells_per_point() * n));
+    const double target = sor_cell_target(k, 0.5);
     GridMeta *meta = (GridMeta *)pool_alloc(sizeof(GridMeta));
     uint32_t *counts = (uint32_t *)pool_alloc(cap * sizeof(uint32_t));
     uint32_t *starts = (uint32_t *)pool_alloc(cap * sizeof(uint32_t));
@@ -1063,9 +1077,9 @@ bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *pa
     CW_LAUNCH("sor_grid_setup", grid_setup_zero_kernel, dim3(cap_grid), dim3(BLK), 0, c.stream, partial, nb, cap, meta, counts, cursor);
     bool ok = true;
     if (ok) {
-        CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, unused, meta, 0, src.x(), src.y(), src.z(), n, counts, cell_id, &meta->occ);
+        CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, meta, 0, src.x(), src.y(), src.z(), n, counts, cell_id, &meta->occ);
         CW_LAUNCH("sor_grid_refine", grid_refine_zero_kernel, dim3(cap_grid), dim3(BLK), 0, c.stream, meta, n, target, counts, cap);
-        CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, unused, meta, 1, src.x(), src.y(), src.z(), n, counts, cell_id, (uint32_t *)nullptr);
+        CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, meta, 1, src.x(), src.y(), src.z(), n, counts, cell_id, (uint32_t *)nullptr);
         if (profiling_enabled()) profile_begin("sor_exclusive_scan", c.stream);
         e = rocprim::exclusive_scan(scan_tmp, tmp_bytes, counts, starts, 0u, cap, rocprim::plus<uint32_t>(), c.stream);
         if (profiling_enabled()) profile_end(c.stream);
@@ -1074,18 +1088,7 @@ bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *pa
     if (ok) {
         CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts, cursor,
                   sorted);
-        const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-        if (search) {
-            ok = (*search)(GridView{unused, meta, sorted, n, starts, counts, nullptr, false}, c.stream);
-        } else if (k + 1 <= 17) {
-            CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist);
-        } else if (k + 1 <= 33) {
-            CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist);
-        } else {
-            void *slab = nullptr;
-            ok = launch_knn_list(unused, meta, sorted, n, starts, counts, k, dev_dist, c.stream, &slab);
-            c.free_later(slab);
-        }
+        ok = launch_knn(GridView{unused, meta, sorted, n, starts, counts, nullptr, false}, k, dev_dist, search, c.stream);
     }
     ok = hipGetLastError() == hipSuccess && ok;
     if (!ok) {
@@ -1101,8 +1104,7 @@ bool sor_dense_on_device(const DeviceSoA &src, int k, float *dev_dist, float *pa
 // The same for small clouds (cap <= 2^19 cells: up to 64 k points; k + 1 <= 33): ten launches with the compaction behind it, see small_bbox_zero_kernel.
 bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t cap, ThreadCtx &c, const GridSearch *search) {
     const size_t n = src.npoints;
-    double target = (double)(k + 1) / 2.0;
-    if (const char *t = getenv("CWIPC_SOR_CELL_TARGET")) target = (double)(k + 1) * atof(t);   // tuning knob: points per occupied cell / (k + 1)
+    const double target = sor_cell_target(k, 0.5);
     const unsigned nb = std::min(256u, grid_for(n));
     float *partial = (float *)pool_alloc((size_t)nb * 6 * sizeof(float));
     GridMeta *meta = (GridMeta *)pool_alloc(2 * sizeof(GridMeta));
@@ -1127,18 +1129,7 @@ bool sor_small_on_device(const DeviceSoA &src, int k, float *dev_dist, size_t ca
     CW_LAUNCH("sor_cell_count", small_count_kernel<1>, dim3(pgrid), dim3(BLK), 0, c.stream, partial, nb, cap, target, meta, src.x(), src.y(), src.z(), n, counts2, cell_id);
     CW_LAUNCH("sor_exclusive_scan", small_scan_kernel, dim3(1), dim3(SCAN1_THREADS), 0, c.stream, meta, counts, counts2, starts, cap);
     CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(pgrid), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts, cursor, sorted);
-    const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-    static const bool pair_off = []() { const char *e = getenv("CWIPC_SOR_PAIR"); return e && atoi(e) == 0; }();   // test knob: a lane per query
-    bool searched = true;
-    if (search) {
-        searched = (*search)(GridView{unused, meta, sorted, n, starts, counts, counts2, false}, c.stream);
-    } else if (k == 16 && !pair_off) {
-        CW_LAUNCH("sor_knn_mean_dist", knn_pair_kernel, dim3((unsigned)((2 * n + QB - 1) / QB)), dim3(QB), 0, c.stream, meta, sorted, n, starts, counts, counts2, dev_dist);
-    } else if (k + 1 <= 17) {
-        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist, counts2);
-    } else {
-        CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, unused, meta, sorted, n, starts, counts, k, dev_dist, counts2);
-    }
+    const bool searched = launch_knn(GridView{unused, meta, sorted, n, starts, counts, counts2, false}, k, dev_dist, search, c.stream);
     if (hipGetLastError() != hipSuccess || !searched) {
         hip_failed(hipGetLastError(), "sor k-NN", __FILE__, __LINE__);
         (void)c.sync();
@@ -1168,20 +1159,19 @@ bool grid_and_search(const DeviceSoA &src, int k, float *dev_dist, const GridSea
 
     static const int sparse_knob = []() { const char *e = getenv("CWIPC_SOR_SPARSE"); return e ? atoi(e) : -1; }();   // test knob: 1 always, 0 never
     const bool sparse = (sparse_knob == 1 || (sparse_knob != 0 && n >= ((size_t)1 << 20))) && k + 1 <= 33;
-    static const bool host_grid = []() { const char *e = getenv("CWIPC_SOR_HOST_GRID"); return e && atoi(e) != 0; }();   // test knob: the dense layout decided by the host
-    if (!sparse && !host_grid && k + 1 <= 33) {
+    if (!sparse && k + 1 <= 33) {
         // (r4) small clouds: two launches fewer and a one-workgroup scan over the cells the grid really has
-        static const size_t cells_per_point = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();   // tuning knob
         static const size_t small_cells = []() { const char *e = getenv("CWIPC_SOR_SMALL_CELLS"); return e ? (size_t)atol(e) : (size_t)1 << 19; }();   // 0: never (test knob)
-        const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, cells_per_point * n));
+        const size_t cap = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, sor_cells_per_point() * n));
         if (cap <= small_cells) return sor_small_on_device(src, k, dev_dist, cap, c, search);
     }
-    // 1. bounding box
+    // bounding box (the dense layout reads it on the device, the sparse one on the host)
     const unsigned nb = grid_for(n);
     float *partial = (float *)pool_alloc((size_t)nb * 6 * sizeof(float));
     if (!partial) return false;
     CW_LAUNCH("sor_bbox", bbox_kernel, dim3(nb), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, partial);
-    if (!sparse && !host_grid) return sor_dense_on_device(src, k, dev_dist, partial, nb, c, search);
+    if (!sparse) return sor_dense_on_device(src, k, dev_dist, partial, nb, c, search);
+    // ---- big clouds: the sparse layout (segments of 16 cells, only those that hold points), on the box the host has read back ----
     float *hpart = (float *)c.staging((size_t)nb * 6 * sizeof(float));
     bool ok = hpart && hipMemcpyAsync(hpart, partial, (size_t)nb * 6 * sizeof(float), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
     ok = c.sync() && ok;
@@ -1213,196 +1203,95 @@ bool grid_and_search(const DeviceSoA &src, int k, float *dev_dist, const GridSea
         return g;
     };
     auto cells_of = [](const Grid &g) { return (size_t)g.dim[0] * (size_t)g.dim[1] * (size_t)g.dim[2]; };
-    // ---- big clouds: the sparse layout (segments of 16 cells, only those that hold points) ----
-    if (sparse) {
-        static const size_t sparse_cpp = []() { const char *e = getenv("CWIPC_SOR_SPARSE_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)16; }();
-        // cells of the (virtual) fine grid: a few dozen per point, and segment numbers must fit 27 bits
-        const size_t budget = std::min<size_t>((size_t)1 << 30, std::max<size_t>((size_t)1 << 16, sparse_cpp * n));
-        auto segs_of = [](const Grid &gg) { return (size_t)gg.nsegx * (size_t)gg.dim[1] * (size_t)gg.dim[2]; };
-        double hs = maxext / 2048.0;
-        while (cells_of(make_grid(hs)) > budget || segs_of(make_grid(hs)) >= ((size_t)1 << 27)) hs *= 1.25;
-        Grid g = make_grid(hs);
-        size_t nseg = segs_of(g);
-        uint32_t *cell_id = (uint32_t *)pool_alloc(n * sizeof(uint32_t));
-        float4 *sorted = (float4 *)pool_alloc(n * sizeof(float4));
-        uint32_t *masks = nullptr, *flags = nullptr, *before = nullptr, *info = nullptr, *counts = nullptr, *starts = nullptr, *cursor = nullptr;
-        void *scan_tmp = nullptr;
-        auto give_back = [&](bool later) {
-            void *all[] = {cell_id, sorted, masks, flags, before, info, counts, starts, cursor, scan_tmp};
-            for (void *b : all) { if (later) c.free_later(b); else pool_free(b); }
-        };
-        auto fail = [&]() { (void)c.sync(); give_back(false); return false; };
-        if (!cell_id || !sorted) return fail();
-        uint32_t occ_cells = 0, occ_segs = 0;
-        auto census = [&]() -> bool {
-            pool_free(masks); pool_free(flags);
-            masks = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t) + 256);
-            flags = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
-            if (!masks || !flags) return false;
-            uint32_t *out = masks + nseg;
-            bool good = hipMemsetAsync(masks, 0, nseg * sizeof(uint32_t) + 8, c.stream) == hipSuccess;
-            if (!good) return false;
-            CW_LAUNCH("sor_seg_mark", seg_mark_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, g, src.x(), src.y(), src.z(), n, masks, cell_id);
-            CW_LAUNCH("sor_seg_census", seg_census_kernel, dim3(std::min(1024u, grid_for(nseg))), dim3(BLK), 0, c.stream, masks, nseg, flags, out);
-            good = hipMemcpyAsync(c.host_words, out, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
-            good = c.sync() && good;
-            occ_cells = c.host_words[0];
-            occ_segs = c.host_words[1];
-            return good;
-        };
-        if (!census()) return fail();
-        {
-            // coarsen so that an occupied cell holds about 0.3 (k + 1) points (surface-like data: points per cell grow with h^2).
-            // (r4: 0.5 (k + 1) until the shells beyond the first got their bound per row; with it finer cells pay: 2 M points 0.71 -> 0.66 ms,
-            // profiles/r04_sor_small_flow.txt.  10 M points are at the segment budget's cell size either way.)
-            const double ppc = (double)n / (double)(occ_cells ? occ_cells : 1);
-            double target = 0.3 * (double)(k + 1);
-            if (const char *t = getenv("CWIPC_SOR_CELL_TARGET")) target = (double)(k + 1) * atof(t);
-            if (ppc < target) {
-                double h = hs * sqrt(target / ppc);
-                if (h > maxext) h = maxext;
-                g = make_grid(h);
-                nseg = segs_of(g);
-                if (!census()) return fail();
-            }
-        }
-        const size_t ncomp = (size_t)occ_segs << SEG_SHIFT;
-        before = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
-        info = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
-        counts = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
-        starts = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
-        cursor = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
-        if (!before || !info || !counts || !starts || !cursor) return fail();
-        size_t tmp_a = 0, tmp_b = 0;
-        hipError_t e = rocprim::exclusive_scan(nullptr, tmp_a, flags, before, 0u, nseg, rocprim::plus<uint32_t>(), c.stream);
-        if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_b, counts, starts, 0u, ncomp + 1, rocprim::plus<uint32_t>(), c.stream);
-        const size_t tmp_bytes = std::max(tmp_a, tmp_b);
-        if (e == hipSuccess) {
-            scan_tmp = pool_alloc(tmp_bytes ? tmp_bytes : 256);
-            if (!scan_tmp) e = hipErrorOutOfMemory;
-        }
-        if (e != hipSuccess) { hip_failed(e, "rocprim::exclusive_scan", __FILE__, __LINE__); return fail(); }
-        if (profiling_enabled()) profile_begin("sor_exclusive_scan", c.stream);
-        e = rocprim::exclusive_scan(scan_tmp, tmp_a, flags, before, 0u, nseg, rocprim::plus<uint32_t>(), c.stream);
-        if (profiling_enabled()) profile_end(c.stream);
-        bool ok = e == hipSuccess;
-        if (ok) CW_LAUNCH("sor_seg_pack", seg_pack_kernel, dim3(std::min(2048u, grid_for(nseg))), dim3(BLK), 0, c.stream, flags, before, nseg, info);
-        ok = ok && hipMemsetAsync(counts, 0, (ncomp + 1) * sizeof(uint32_t), c.stream) == hipSuccess &&
-             hipMemsetAsync(cursor, 0, (ncomp + 1) * sizeof(uint32_t), c.stream) == hipSuccess;
-        if (ok) {
-            CW_LAUNCH("sor_cell_count", seg_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, info, n, cell_id, counts);
-            if (profiling_enabled()) profile_begin("sor_exclusive_scan", c.stream);
-            e = rocprim::exclusive_scan(scan_tmp, tmp_b, counts, starts, 0u, ncomp + 1, rocprim::plus<uint32_t>(), c.stream);
-            if (profiling_enabled()) profile_end(c.stream);
-            ok = e == hipSuccess;
-        }
-        if (ok) {
-            CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts,
-                      cursor, sorted);
-            const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-            if (search) {
-                ok = (*search)(GridView{g, nullptr, sorted, n, starts, info, nullptr, true}, c.stream);
-            } else if (k + 1 <= 17) {
-                CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, true>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, info, k, dev_dist);
-            } else {
-                CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, true>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, info, k, dev_dist);
-            }
-        }
-        ok = hipGetLastError() == hipSuccess && ok;
-        if (!ok) { hip_failed(e != hipSuccess ? e : hipGetLastError(), "sor k-NN (sparse grid)", __FILE__, __LINE__); return fail(); }
-        give_back(true);   // (no wait here: every caller has one further down, and the temporaries go back to the pool there)
-        return true;
-    }
-
-    // finest cell size whose dense grid stays within MAX_CELLS
-    // (and, for small clouds, within a few cells per point: the probe is a pass over the grid)
-    static const size_t cells_per_point = []() { const char *e = getenv("CWIPC_SOR_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8; }();   // tuning knob
-    const size_t probe_cells = std::min<size_t>(MAX_CELLS, std::max<size_t>((size_t)1 << 16, cells_per_point * n));
-    double h_min = maxext / 1024.0;
-    while (cells_of(make_grid(h_min)) > probe_cells) h_min *= 1.25;
-
-    uint32_t *counts = (uint32_t *)pool_alloc(probe_cells * sizeof(uint32_t) + 256);
-    uint32_t *fill = (uint32_t *)pool_alloc(probe_cells * sizeof(uint32_t));
+    static const size_t sparse_cpp = []() { const char *e = getenv("CWIPC_SOR_SPARSE_CELLS_PER_POINT"); return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)16; }();
+    // cells of the (virtual) fine grid: a few dozen per point, and segment numbers must fit 27 bits
+    const size_t budget = std::min<size_t>((size_t)1 << 30, std::max<size_t>((size_t)1 << 16, sparse_cpp * n));
+    auto segs_of = [](const Grid &gg) { return (size_t)gg.nsegx * (size_t)gg.dim[1] * (size_t)gg.dim[2]; };
+    double hs = maxext / 2048.0;
+    while (cells_of(make_grid(hs)) > budget || segs_of(make_grid(hs)) >= ((size_t)1 << 27)) hs *= 1.25;
+    Grid g = make_grid(hs);
+    size_t nseg = segs_of(g);
     uint32_t *cell_id = (uint32_t *)pool_alloc(n * sizeof(uint32_t));
     float4 *sorted = (float4 *)pool_alloc(n * sizeof(float4));
+    uint32_t *masks = nullptr, *flags = nullptr, *before = nullptr, *info = nullptr, *counts = nullptr, *starts = nullptr, *cursor = nullptr;
     void *scan_tmp = nullptr;
-    auto cleanup = [&]() { pool_free(counts); pool_free(fill); pool_free(cell_id); pool_free(sorted); pool_free(scan_tmp); };
-    if (!counts || !fill || !cell_id || !sorted) { cleanup(); return false; }
-
-    // 2. occupancy probe at h_min, then coarsen so that an occupied cell holds about (k+1)/3 points
-    //    (surface-like data: points per cell grow with h^2)
-    Grid g = make_grid(h_min);
-    size_t ncells = cells_of(g);
-    uint32_t *occ_dev = counts + probe_cells;
-    ok = hipMemsetAsync(counts, 0, ncells * sizeof(uint32_t), c.stream) == hipSuccess &&
-         hipMemsetAsync(occ_dev, 0, sizeof(uint32_t), c.stream) == hipSuccess;
-    if (ok) {
-        CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, g, (const GridMeta *)nullptr, 0, src.x(), src.y(), src.z(), n, counts, cell_id, (uint32_t *)nullptr);
-        CW_LAUNCH("sor_count_nonzero", count_nonzero_kernel, dim3(std::min(1024u, grid_for(ncells / 4 + 1))), dim3(BLK), 0, c.stream, counts, ncells, occ_dev);
-        ok = hipMemcpyAsync(c.host_words, occ_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    auto give_back = [&](bool later) {
+        void *all[] = {cell_id, sorted, masks, flags, before, info, counts, starts, cursor, scan_tmp};
+        for (void *b : all) { if (later) c.free_later(b); else pool_free(b); }
+    };
+    auto fail = [&]() { (void)c.sync(); give_back(false); return false; };
+    if (!cell_id || !sorted) return fail();
+    uint32_t occ_cells = 0, occ_segs = 0;
+    auto census = [&]() -> bool {
+        pool_free(masks); pool_free(flags);
+        masks = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t) + 256);
+        flags = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
+        if (!masks || !flags) return false;
+        uint32_t *out = masks + nseg;
+        bool good = hipMemsetAsync(masks, 0, nseg * sizeof(uint32_t) + 8, c.stream) == hipSuccess;
+        if (!good) return false;
+        CW_LAUNCH("sor_seg_mark", seg_mark_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, g, src.x(), src.y(), src.z(), n, masks, cell_id);
+        CW_LAUNCH("sor_seg_census", seg_census_kernel, dim3(std::min(1024u, grid_for(nseg))), dim3(BLK), 0, c.stream, masks, nseg, flags, out);
+        good = hipMemcpyAsync(c.host_words, out, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        good = c.sync() && good;
+        occ_cells = c.host_words[0];
+        occ_segs = c.host_words[1];
+        return good;
+    };
+    if (!census()) return fail();
+    {
+        // coarsen so that an occupied cell holds about 0.3 (k + 1) points (surface-like data: points per cell grow with h^2).
+        // (r4: 0.5 (k + 1) until the shells beyond the first got their bound per row; with it finer cells pay: 2 M points 0.71 -> 0.66 ms,
+        // profiles/r04_sor_small_flow.txt.  10 M points are at the segment budget's cell size either way.)
+        const double ppc = (double)n / (double)(occ_cells ? occ_cells : 1);
+        const double target = sor_cell_target(k, 0.3);
+        if (ppc < target) {
+            double h = hs * sqrt(target / ppc);
+            if (h > maxext) h = maxext;
+            g = make_grid(h);
+            nseg = segs_of(g);
+            if (!census()) return fail();
+        }
     }
-    ok = c.sync() && ok;
-    if (!ok) { cleanup(); return false; }
-    double ppc = (double)n / (double)(c.host_words[0] ? c.host_words[0] : 1);
-    double target = (double)(k + 1) / 2.0;
-    if (const char *t = getenv("CWIPC_SOR_CELL_TARGET")) target = (double)(k + 1) * atof(t);   // tuning knob: points per occupied cell / (k + 1)
-    if (ppc < target) {
-        double h = h_min * sqrt(target / ppc);
-        if (h > maxext) h = maxext;
-        g = make_grid(h);
-        ncells = cells_of(g);
-        ok = hipMemsetAsync(counts, 0, ncells * sizeof(uint32_t), c.stream) == hipSuccess;
-        if (ok) CW_LAUNCH("sor_cell_count", cell_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, g, (const GridMeta *)nullptr, 0, src.x(), src.y(), src.z(), n, counts, cell_id, (uint32_t *)nullptr);
-    }
-
-    // 3. counting sort: exclusive scan of the counts, scatter
-    size_t tmp_bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tmp_bytes, counts, fill, 0u, ncells, rocprim::plus<uint32_t>(), c.stream);
+    const size_t ncomp = (size_t)occ_segs << SEG_SHIFT;
+    before = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
+    info = (uint32_t *)pool_alloc(nseg * sizeof(uint32_t));
+    counts = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
+    starts = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
+    cursor = (uint32_t *)pool_alloc((ncomp + 1) * sizeof(uint32_t));
+    if (!before || !info || !counts || !starts || !cursor) return fail();
+    size_t tmp_a = 0, tmp_b = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, tmp_a, flags, before, 0u, nseg, rocprim::plus<uint32_t>(), c.stream);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, tmp_b, counts, starts, 0u, ncomp + 1, rocprim::plus<uint32_t>(), c.stream);
+    const size_t tmp_bytes = std::max(tmp_a, tmp_b);
     if (e == hipSuccess) {
         scan_tmp = pool_alloc(tmp_bytes ? tmp_bytes : 256);
         if (!scan_tmp) e = hipErrorOutOfMemory;
     }
-    if (e == hipSuccess) {
+    if (e != hipSuccess) { hip_failed(e, "rocprim::exclusive_scan", __FILE__, __LINE__); return fail(); }
+    if (profiling_enabled()) profile_begin("sor_exclusive_scan", c.stream);
+    e = rocprim::exclusive_scan(scan_tmp, tmp_a, flags, before, 0u, nseg, rocprim::plus<uint32_t>(), c.stream);
+    if (profiling_enabled()) profile_end(c.stream);
+    ok = e == hipSuccess;
+    if (ok) CW_LAUNCH("sor_seg_pack", seg_pack_kernel, dim3(std::min(2048u, grid_for(nseg))), dim3(BLK), 0, c.stream, flags, before, nseg, info);
+    ok = ok && hipMemsetAsync(counts, 0, (ncomp + 1) * sizeof(uint32_t), c.stream) == hipSuccess &&
+         hipMemsetAsync(cursor, 0, (ncomp + 1) * sizeof(uint32_t), c.stream) == hipSuccess;
+    if (ok) {
+        CW_LAUNCH("sor_cell_count", seg_count_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, info, n, cell_id, counts);
         if (profiling_enabled()) profile_begin("sor_exclusive_scan", c.stream);
-        // fill <- starts ; counts stays ; a second buffer then serves as the fill cursor
-        e = rocprim::exclusive_scan(scan_tmp, tmp_bytes, counts, fill, 0u, ncells, rocprim::plus<uint32_t>(), c.stream);
+        e = rocprim::exclusive_scan(scan_tmp, tmp_b, counts, starts, 0u, ncomp + 1, rocprim::plus<uint32_t>(), c.stream);
         if (profiling_enabled()) profile_end(c.stream);
+        ok = e == hipSuccess;
     }
-    if (e != hipSuccess || !ok) {
-        hip_failed(e, "rocprim::exclusive_scan", __FILE__, __LINE__);
-        cleanup();
-        return false;
-    }
-    uint32_t *starts = fill;
-    uint32_t *cursor = (uint32_t *)pool_alloc(ncells * sizeof(uint32_t));
-    if (!cursor) { cleanup(); return false; }
-    ok = hipMemsetAsync(cursor, 0, ncells * sizeof(uint32_t), c.stream) == hipSuccess;
     if (ok) {
         CW_LAUNCH("sor_cell_scatter", cell_scatter_kernel, dim3(grid_for(n)), dim3(BLK), 0, c.stream, src.x(), src.y(), src.z(), n, cell_id, starts,
                   cursor, sorted);
-        // 4. the k-NN pass
-        const unsigned qgrid = (unsigned)((n + QB - 1) / QB);
-        if (search) {
-            ok = (*search)(GridView{g, nullptr, sorted, n, starts, counts, nullptr, false}, c.stream);
-        } else if (k + 1 <= 17) {
-            CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<17, false>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, counts, k, dev_dist);
-        } else if (k + 1 <= 33) {
-            CW_LAUNCH("sor_knn_mean_dist", (knn_mean_dist_reg_kernel<33, false>), dim3(qgrid), dim3(QB), 0, c.stream, g, (const GridMeta *)nullptr, sorted, n, starts, counts, k, dev_dist);
-        } else {
-            void *slab = nullptr;
-            ok = launch_knn_list(g, nullptr, sorted, n, starts, counts, k, dev_dist, c.stream, &slab);
-            c.free_later(slab);
-        }
+        ok = launch_knn(GridView{g, nullptr, sorted, n, starts, info, nullptr, true}, k, dev_dist, search, c.stream);
     }
-    // no wait here: every caller has one further down (the compaction, a copy to the host), and the
-    // temporaries go back to the pool there
     ok = hipGetLastError() == hipSuccess && ok;
-    c.free_later(cursor); c.free_later(counts); c.free_later(fill); c.free_later(cell_id); c.free_later(sorted); c.free_later(scan_tmp);
-    if (!ok) {
-        hip_failed(hipGetLastError(), "sor k-NN", __FILE__, __LINE__);
-        (void)c.sync();
-    }
-    return ok;
+    if (!ok) { hip_failed(e != hipSuccess ? e : hipGetLastError(), "sor k-NN (sparse grid)", __FILE__, __LINE__); return fail(); }
+    give_back(true);   // (no wait here: every caller has one further down, and the temporaries go back to the pool there)
+    return true;
 }
 
 }  // namespace

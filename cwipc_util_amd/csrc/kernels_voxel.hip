@@ -161,8 +161,6 @@ struct VoxWork {
     uint32_t *seg_count;             // [leaf hash][RANK_SEGS] occupied cells per bitmap slice (accumulated by K1's flush)
     unsigned long long *hash_keys;   // [4 x leaf grids] leaf -> id: open addressing on the packed coordinates ...
     uint32_t *hash_ids;              //   ... and the id + 1 of the entry's leaf (0: not published yet, ~0: no grid left)
-    uint32_t *dump_head;             // r4, fast accumulate kernel with FastParams::dump: per workgroup a DumpHead ...
-    uint32_t *dump_ent;              //   ... and room for the entries of its table, DUMP_ENTRY_WORDS words each (voxel_k1_fast.inc)
 };
 
 // Ranges of growing length (r4, the fast accumulate kernel's workgroups: they then reach their flush one after the other instead of
@@ -1928,8 +1926,6 @@ struct Workspace {
     uint32_t *gprefix = nullptr, *gblock = nullptr;
     size_t gwords_cap = 0;
     float *bboxes = nullptr;           // [2][bbox_cap][6]: the ranges' boxes the replay kernel reads; behind them room for boxes nobody reads
-    uint32_t *dump_head = nullptr, *dump_ent = nullptr;   // what the fast accumulate kernel leaves for the merge kernel (r4) ...
-    size_t dump_blocks = 0, dump_entries = 0;             //   ... for this many workgroups of this many table entries
     float *part = nullptr;             // partition pass: the cloud moved into spatial buckets, four planes of part_stride elements
     size_t part_stride = 0;
     uint32_t *part_hist = nullptr;     //   ... and its table: a row of PART_BUCKETS counts per range, the rows' sums by segments, the buckets' starts
@@ -1947,14 +1943,8 @@ struct Workspace {
         if (part_hist) (void)hipFree(part_hist);
         part = nullptr; part_hist = nullptr; part_stride = 0; part_rows = 0;
     }
-    void drop_dump_buffers() {
-        if (dump_head) (void)hipFree(dump_head);
-        if (dump_ent) { (void)hipFree(dump_ent); g_workspace_bytes -= dump_blocks * dump_entries * DUMP_ENTRY_WORDS * 4; }
-        dump_head = dump_ent = nullptr; dump_blocks = dump_entries = 0;
-    }
     void release() {
         // also runs at thread exit, when the runtime may be gone: errors ignored
-        drop_dump_buffers();
         if (head) (void)hipFree(head);
         if (records) (void)hipFree(records);
         if (occupied) (void)hipFree(occupied);
@@ -2061,12 +2051,8 @@ bool ensure_workspace(Workspace &ws, size_t n, uint32_t leaf_cap, uint32_t nrang
         CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         const int lds_fast = (int)sizeof(FastTable);
-        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<0, K1_THREADS, LTAB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fast));
-        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<1, K1_THREADS, LTAB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fast));
-        const int lds_pair = (int)sizeof(PairTable);
-        static_assert(2 * sizeof(PairTable) <= 160 * 1024, "two workgroups of the paired accumulate kernel share a CU's LDS");
-        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<0, PAIR_THREADS, PAIR_LTAB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_pair));
-        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<1, PAIR_THREADS, PAIR_LTAB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_pair));
+        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fast));
+        CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&voxel_accumulate_fast_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_fast));
         CW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&partition_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PartLds)));
         ws.device = dev;
     }
@@ -2296,7 +2282,7 @@ std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &sr
             if (p->leaf_split) ws.last_m = 0; else ws.last_m_grid = 0;
             ws.streak = 0;
             if (p->err & (ERR_FAST_PATH | ERR_CELL_RANGE)) ws.no_fast = true;
-            VoxWork W{ws.leaf_keys, ws.records, ws.occupied, ws.ctrl, ws.bboxes, ws.faces, ws.bitmaps, ws.seg_count, ws.hash_keys, ws.hash_ids, ws.dump_head, ws.dump_ent};
+            VoxWork W{ws.leaf_keys, ws.records, ws.occupied, ws.ctrl, ws.bboxes, ws.faces, ws.bitmaps, ws.seg_count, ws.hash_keys, ws.hash_ids};
             CW_LAUNCH("clean_by_bitmap", clean_by_bitmap_kernel, dim3(ws.leaf_cap * RANK_SEGS), dim3(RANK_THREADS), 0, c.stream, W);
             if (!c.sync()) { hip_failed(hipGetLastError(), "voxel workspace clean-up", __FILE__, __LINE__); return nullptr; }
         }
@@ -2470,7 +2456,7 @@ std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &sr
         ws.seg_count = (uint32_t *)(head + HEAD_CTRL_BYTES + (size_t)ws.leaf_cap * 8);
         ws.hash_keys = (unsigned long long *)(head + HEAD_CTRL_BYTES + (size_t)ws.leaf_cap * 8 + (size_t)ws.leaf_cap * RANK_SEGS * sizeof(uint32_t));
         ws.hash_ids = (uint32_t *)((char *)ws.hash_keys + (size_t)ws.leaf_cap * 4 * 8);
-        VoxWork W{ws.leaf_keys, ws.records, ws.occupied, ws.ctrl, ws.bboxes, ws.faces, ws.bitmaps, ws.seg_count, ws.hash_keys, ws.hash_ids, ws.dump_head, ws.dump_ent};
+        VoxWork W{ws.leaf_keys, ws.records, ws.occupied, ws.ctrl, ws.bboxes, ws.faces, ws.bitmaps, ws.seg_count, ws.hash_keys, ws.hash_ids};
         bool ok = true;
         if (!ws.head_clean[blk]) ok = hipMemsetAsync(head, 0, ws.head_bytes, c.stream) == hipSuccess;
         ws.head_clean[blk] = false;
@@ -2532,13 +2518,7 @@ std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &sr
             // The workgroups' ranges: the cloud's steps dealt evenly over the CUs the grid may use (a workgroup's waves share its
             // range step by step, so a range need not be a multiple of sixteen steps): a 300 k-point cloud gets 235 workgroups
             // of 5 steps, five busy waves each, instead of 74 workgroups whose sixteen waves queue up on four SIMDs.
-            // CWIPC_K1_PAIR=1 (experiments): two workgroups of 8 waves and half the range per CU instead of one of 16 (voxel_k1_fast.inc)
-            static const int pair_knob = []() { const char *e = getenv("CWIPC_K1_PAIR"); return e ? atoi(e) : 0; }();
-            // CWIPC_K1_PAIR=2: the 8-wave workgroups with FULL ranges, one per CU and kernel -- in a stream of calls a CU then holds a workgroup
-            // of each of two consecutive kernels, and one streams while the other sets up or flushes
-            const bool pair = pair_knob != 0;
-            const size_t slots = (size_t)cus * (pair_knob == 1 ? 2 : 1);
-            const size_t wg_steps = std::min<size_t>(std::max<size_t>((steps_total + slots - 1) / slots, 1), MAX_POINTS_PER_WAVE * K1_WAVES / WAVE_STEP);
+            const size_t wg_steps = std::min<size_t>(std::max<size_t>((steps_total + cus - 1) / cus, 1), MAX_POINTS_PER_WAVE * K1_WAVES / WAVE_STEP);
             fast_blocks = (uint32_t)((steps_total + wg_steps - 1) / wg_steps);
             fast_per_wg = (uint32_t)(wg_steps * WAVE_STEP);
             // r4: the ranges' lengths grow linearly with the workgroup's number, from (1 - p %) to (1 + p %) of the mean, so that the
@@ -2550,7 +2530,7 @@ std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &sr
             // 66.0 -> 64.2 (profiles/r04_k1_stagger.txt).  CWIPC_K1_STAGGER=p overrides (0: equal ranges, rounds 1-3).  Only for
             // ranges of 24 steps or more (clouds from 1.5 M points): a short range is mostly set-up and flush.
             static const int stagger_knob = []() { const char *e = getenv("CWIPC_K1_STAGGER"); return e ? atoi(e) : 25; }();
-            if (stagger_knob > 0 && stagger_knob < 60 && fast_blocks >= 64 && !pair && steps_total >= (size_t)24 * fast_blocks && n < ((size_t)1 << 31)) {
+            if (stagger_knob > 0 && stagger_knob < 60 && fast_blocks >= 64 && steps_total >= (size_t)24 * fast_blocks && n < ((size_t)1 << 31)) {
                 const double mean_q = (double)steps_total * 1024.0 / (double)fast_blocks, s_frac = stagger_knob / 100.0;
                 const size_t max_steps = MAX_POINTS_PER_WAVE * K1_WAVES / WAVE_STEP;
                 uint32_t inc = (uint32_t)ceil(2.0 * s_frac * mean_q / (double)(fast_blocks - 1));
@@ -2564,64 +2544,20 @@ std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &sr
             }
             F.n = K.n; F.per_wg = fast_per_wg; F.inv_leaf = K.inv_leaf;
             F.range_base_q = range_base_q; F.range_inc_q = range_inc_q;
-            static const bool stagger_rev = []() { const char *e = getenv("CWIPC_K1_STAGGER_REV"); return e && atoi(e) != 0; }();
-            F.range_reverse = range_base_q != 0u && stagger_rev ? 1u : 0u;
             F.ib0 = K.ib0; F.ib1 = K.ib1; F.ib2 = K.ib2;
             F.fb0 = K.fb0; F.fb1 = K.fb1; F.fb2 = K.fb2;
             F.leaf_mask = K.leaf_mask; F.list_cap = K.list_cap; F.want_list = K.want_list;
-            // r4: the accumulate kernel may leave its tables' entries in the workspace, for a kernel of small workgroups right behind it to
-            // take to the records (voxel_k1_fast.inc, fast_dump / voxel_merge_kernel): the accumulate kernel alone 53.4 -> 48.1 us, the merge
-            // kernel 20 us alone -- a loss for a call that is waited for (64.6 -> 78.7 us with count()), possibly a gain in a stream of calls,
-            // where the merge workgroups (one wave per SIMD, 64 registers, 19 KB of LDS) run beside the NEXT call's accumulate kernel.
-            // CWIPC_K1_DUMP: 0 never, 1 always, 2 when this call is going to return with its kernels in flight (a stream); default 0
-            // until the stream figure says otherwise (profiles/r04_k1_dump_merge.txt)
-            static const int dump_mode = []() { const char *e = getenv("CWIPC_K1_DUMP"); return e ? atoi(e) : 0; }();
-            static const bool defer_allowed = []() { const char *e = getenv("CWIPC_DEFER"); return !e || atoi(e) != 0; }();
-            const bool will_defer = deferred && defer_allowed && attempt == 0 && ws.streak >= 2 && !profiling_enabled() &&
-                                    (leaf_split ? ws.last_m > 0 : (ws.last_m_grid > 0 && ws.gwords_cap > 0));
-            const bool dump_knob = dump_mode == 1 || (dump_mode == 2 && will_defer);
-            const size_t table_entries = pair ? (size_t)PAIR_LTAB : (size_t)LTAB;
-            bool dump = dump_knob;
-            if (dump && (ws.dump_blocks < fast_blocks || ws.dump_entries != table_entries)) {
-                ws.drop_dump_buffers();
-                const size_t blocks_cap = std::max<size_t>(fast_blocks, 256);
-                if (hipMalloc((void **)&ws.dump_head, blocks_cap * sizeof(DumpHead)) != hipSuccess ||
-                    hipMalloc((void **)&ws.dump_ent, blocks_cap * table_entries * DUMP_ENTRY_WORDS * 4) != hipSuccess) {
-                    (void)hipGetLastError();
-                    if (ws.dump_head) (void)hipFree(ws.dump_head);
-                    ws.dump_head = ws.dump_ent = nullptr;
-                    dump = false;   // no room for the tables: this pass updates the records from the accumulate kernel
-                } else {
-                    ws.dump_blocks = blocks_cap; ws.dump_entries = table_entries;
-                    g_workspace_bytes += blocks_cap * table_entries * DUMP_ENTRY_WORDS * 4;
-                }
-            }
-            W.dump_head = ws.dump_head; W.dump_ent = ws.dump_ent;
-            F.dump = dump ? 1u : 0u;
 #ifdef CWIPC_DEBUG_KNOBS
             static const uint32_t fast_dbg = []() { const char *e = getenv("CWIPC_FAST_DBG"); return e ? (uint32_t)atoi(e) : 0u; }();
             if (fast_dbg) cwipc_log(CWIPC_LOG_LEVEL_WARNING, "cwipc_downsample", "CWIPC_FAST_DBG is set: results are WRONG (timing experiments only)");
             F.dbg = fast_dbg;
 #endif
-            // (a workgroup that leaves its table needs the LDS up to the list of entries in use only: 105 instead of 151 KB)
-            const size_t lds_pair = dump ? PairTable::DUMP_LDS_BYTES : sizeof(PairTable), lds_one = dump ? FastTable::DUMP_LDS_BYTES : sizeof(FastTable);
-            if (pair && mode == 0) {
-                CW_LAUNCH("voxel_accumulate", (voxel_accumulate_fast_kernel<0, PAIR_THREADS, PAIR_LTAB>), dim3(fast_blocks), dim3(PAIR_THREADS), lds_pair, c.stream, F,
-                          src.x(), src.y(), src.z(), src.rgbt(), W);
-            } else if (pair) {
-                CW_LAUNCH("voxel_accumulate", (voxel_accumulate_fast_kernel<1, PAIR_THREADS, PAIR_LTAB>), dim3(fast_blocks), dim3(PAIR_THREADS), lds_pair, c.stream, F,
-                          src.x(), src.y(), src.z(), src.rgbt(), W);
-            } else if (mode == 0) {
-                CW_LAUNCH("voxel_accumulate", (voxel_accumulate_fast_kernel<0, K1_THREADS, LTAB>), dim3(fast_blocks), dim3(K1_THREADS), lds_one, c.stream, F, src.x(),
+            if (mode == 0) {
+                CW_LAUNCH("voxel_accumulate", voxel_accumulate_fast_kernel<0>, dim3(fast_blocks), dim3(K1_THREADS), sizeof(FastTable), c.stream, F, src.x(),
                           src.y(), src.z(), src.rgbt(), W);
             } else {
-                CW_LAUNCH("voxel_accumulate", (voxel_accumulate_fast_kernel<1, K1_THREADS, LTAB>), dim3(fast_blocks), dim3(K1_THREADS), lds_one, c.stream, F, src.x(),
+                CW_LAUNCH("voxel_accumulate", voxel_accumulate_fast_kernel<1>, dim3(fast_blocks), dim3(K1_THREADS), sizeof(FastTable), c.stream, F, src.x(),
                           src.y(), src.z(), src.rgbt(), W);
-            }
-            if (dump && mode == 0) {
-                CW_LAUNCH("voxel_merge", voxel_merge_kernel<0>, dim3(fast_blocks), dim3(MERGE_THREADS), 0, c.stream, F, (uint32_t)table_entries, W);
-            } else if (dump) {
-                CW_LAUNCH("voxel_merge", voxel_merge_kernel<1>, dim3(fast_blocks), dim3(MERGE_THREADS), 0, c.stream, F, (uint32_t)table_entries, W);
             }
         } else if (mode == 0) {
             CW_LAUNCH("voxel_accumulate_general", voxel_accumulate_kernel<0>, dim3(nblocks), dim3(K1_THREADS), sizeof(LdsTable), c.stream, K, kx, ky, kz, kw, Wk);

@@ -55,52 +55,35 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct FastParams {
     uint32_t n, per_wg;   // per_wg: points of a workgroup's contiguous range (multiple of WAVE_STEP); its waves share it step by step
     uint32_t range_base_q, range_inc_q;   // != 0: ranges of growing length instead (range_first_step, kernels_voxel.hip); per_wg is then the longest
-    uint32_t range_reverse;               // 1: workgroup b takes range (workgroups - 1 - b): the longest ranges start first
     float inv_leaf;
     int ib0, ib1, ib2;
     int fb0, fb1, fb2;
     uint32_t leaf_mask, list_cap, want_list;
-    uint32_t dump;    // 1: the workgroup leaves its table's entries in the workspace (W.dump_*) and voxel_merge_kernel takes them to the records
     uint32_t dbg;   // -DCWIPC_DEBUG_KNOBS builds only (CWIPC_FAST_DBG): 1 no table inserts, 2 no run merge, 4 loads and boxes only, 8 no flush
 };
 
-// The workgroup's table and what goes with it (NTAB entries, NWAVES waves); the flush's scratch lists (rec, used, fresh: NTAB words
-// each) are handed to fast_finish separately.
-template <int NTAB, int NWAVES>
-struct FastCore {
-    static constexpr int ENTRIES = NTAB;
-    static constexpr int TF_BASE = FT_TF;   // where in `faces` the table of cut voxels starts (the flush's decode reads that third only)
-    unsigned long long key[NTAB];   // side bits << 32 | linear voxel key; KEY64_EMPTY = free
-    uint32_t tile[NTAB];
-    unsigned long long a[NTAB];   // sum qx
-    unsigned long long b[NTAB];   // sum qy
-    unsigned long long c[NTAB];   // sum qz | sum b << 40
-    unsigned long long d[NTAB];   // count | sum r << 16 | sum g << 40
+// The workgroup's table (LTAB entries, K1_WAVES waves), what goes with it and the flush's lists.  One workgroup per CU.
+struct FastTable {
+    unsigned long long key[LTAB];   // side bits << 32 | linear voxel key; KEY64_EMPTY = free
+    uint32_t tile[LTAB];
+    unsigned long long a[LTAB];   // sum qx
+    unsigned long long b[LTAB];   // sum qy
+    unsigned long long c[LTAB];   // sum qz | sum b << 40
+    unsigned long long d[LTAB];   // count | sum r << 16 | sum g << 40
     uint32_t faces[FACE_TABLE_WORDS];
     uint32_t htag[HIST], hcnt[HIST];
     unsigned long long leaf_tab[LOCAL_LEAVES];
     uint32_t leaf_gid[LOCAL_LEAVES];
-    alignas(16) float slab[NWAVES][12];   // per wave and axis: tlo, tmid, tv, thi (see fast_refit); 16-byte aligned: three ds_read_b128 per step
-    int slab_j[NWAVES][4];        // ... and the table index of tlo (-1: none yet)
+    alignas(16) float slab[K1_WAVES][12];   // per wave and axis: tlo, tmid, tv, thi (see fast_refit); 16-byte aligned: three ds_read_b128 per step
+    int slab_j[K1_WAVES][4];      // ... and the table index of tlo (-1: none yet)
     int tmin[3], tmax[3];         // voxel index range of the workgroup's points
     uint32_t nfresh, fresh_base, nused, err;
     uint32_t next_step;           // the next step of the workgroup's range nobody has taken yet
-    float wbox[NWAVES][6];        // the waves' boxes, reduced to the range's box before the flush
+    float wbox[K1_WAVES][6];      // the waves' boxes, reduced to the range's box before the flush
+    alignas(16) uint32_t used[LTAB];   // flush: the entries in use (16-byte aligned: the LDS layout the profiles/ figures were taken with)
+    uint32_t rec[LTAB];           // flush: leaf id << 19 | cell of the entry's record, ~0 = none
+    uint32_t fresh[LTAB];         // records this workgroup touched first (plain grid: they are listed)
 };
-
-template <int NTAB, int NWAVES>
-struct FastTableT : FastCore<NTAB, NWAVES> {
-    uint32_t used[NTAB];          // flush: the entries in use
-    // (a workgroup that leaves its table to the merge kernel needs nothing below this line: its dynamic LDS ends at offsetof(rec))
-    uint32_t rec[NTAB];           // flush: leaf id << 19 | cell of the entry's record, ~0 = none
-    uint32_t fresh[NTAB];         // records this workgroup touched first (plain grid: they are listed)
-    static constexpr size_t DUMP_LDS_BYTES = sizeof(FastCore<NTAB, NWAVES>) + sizeof(uint32_t) * NTAB;   // = the offset of rec
-};
-using FastTable = FastTableT<LTAB, K1_WAVES>;   // one workgroup per CU: 16 waves, 2048 entries, 151 KB
-// Two workgroups per CU (round 4): 8 waves and 1024 entries each, 66 KB -- so that one of a CU's two streams while the other
-// flushes (see voxel_accumulate_fast_kernel)
-constexpr int PAIR_THREADS = 512, PAIR_WAVES = PAIR_THREADS / 64, PAIR_LTAB = 1024;
-using PairTable = FastTableT<PAIR_LTAB, PAIR_WAVES>;
 
 // ((iz << 10) + iy << 10) + ix in two v_lshl_add_u32 (the compiler's own choice is two shifts and a three-operand add)
 __device__ __forceinline__ uint32_t linear_key(int ix, int iy, int iz) {
@@ -127,27 +110,23 @@ __device__ __forceinline__ int cvt_floor_i32(float v) {
 }
 
 // 11 bits from a linear key: fold the upper fields down, multiply by a 24-bit odd constant (full-rate v_mul_u32_u24)
-template <int NTAB>
 __device__ __forceinline__ uint32_t fast_hash(uint32_t key, uint32_t side) {
-    static_assert(NTAB <= 2048 && (NTAB & (NTAB - 1)) == 0, "11 bits at most");
+    static_assert(LTAB <= 2048 && (LTAB & (LTAB - 1)) == 0, "11 bits at most");
     const uint32_t t = key ^ (key >> 13) ^ (side << 7);
-    return (__umul24(t, 0x9E3779u) >> 13) & (uint32_t)(NTAB - 1);
+    return (__umul24(t, 0x9E3779u) >> 13) & (uint32_t)(LTAB - 1);
 }
 
 // The whole wave calls these (active = this lane has a run to add): the slot of `key` in the workgroup table, claimed if
 // new.  In two halves, so that the round trip of the first compare-and-swap (which finds the slot nine times out of ten)
 // lies behind the work between them; fast_find_end returns false for lanes that found no room (table full: this cloud is
 // for the general variant).
-template <class Table>
-__device__ __forceinline__ unsigned long long fast_find_begin(Table &L, uint32_t key, uint32_t side, bool active, uint32_t &slot) {
-    slot = fast_hash<Table::ENTRIES>(key, side);
+__device__ __forceinline__ unsigned long long fast_find_begin(FastTable &L, uint32_t key, uint32_t side, bool active, uint32_t &slot) {
+    slot = fast_hash(key, side);
     unsigned long long old = KEY64_EMPTY;
     if (active) old = atomicCAS(&L.key[slot], KEY64_EMPTY, u64_of(key, side));
     return old;
 }
-template <class Table>
-__device__ __forceinline__ bool fast_find_end(Table &L, uint32_t key, uint32_t side, bool active, unsigned long long old, uint32_t &slot, uint32_t &err) {
-    constexpr int LTAB = Table::ENTRIES;
+__device__ __forceinline__ bool fast_find_end(FastTable &L, uint32_t key, uint32_t side, bool active, unsigned long long old, uint32_t &slot, uint32_t &err) {
     const unsigned long long key64 = u64_of(key, side);
     bool pending = active && !(old == KEY64_EMPTY || old == key64);
 #pragma unroll 1
@@ -162,15 +141,13 @@ __device__ __forceinline__ bool fast_find_end(Table &L, uint32_t key, uint32_t s
     if (__ballot(active && pending) != 0ull) err |= ERR_FAST_PATH;
     return active && !pending;
 }
-template <class Table>
-__device__ __forceinline__ bool fast_find(Table &L, uint32_t key, uint32_t side, bool active, uint32_t &slot, uint32_t &err) {
+__device__ __forceinline__ bool fast_find(FastTable &L, uint32_t key, uint32_t side, bool active, uint32_t &slot, uint32_t &err) {
     const unsigned long long old = fast_find_begin(L, key, side, active, slot);
     return fast_find_end(L, key, side, active, old, slot, err);
 }
 
 // the colour / count part and the z sum of a run into its entry (x and y go on their own, as soon as they are known)
-template <class Table>
-__device__ __forceinline__ void fast_add_rest(Table &L, uint32_t slot, bool ok, uint32_t qz, uint32_t cr, uint32_t gb, uint32_t tile) {
+__device__ __forceinline__ void fast_add_rest(FastTable &L, uint32_t slot, bool ok, uint32_t qz, uint32_t cr, uint32_t gb, uint32_t tile) {
     if (ok) {
         atomicAdd(&L.c[slot], u64_of(qz, (gb & 0xffffu) << 8));                                      // | sum b << 40
         atomicAdd(&L.d[slot], u64_of(__builtin_amdgcn_alignbit(cr, cr, 16), (gb >> 16) << 8));      // count | sum r << 16 | sum g << 40
@@ -180,8 +157,7 @@ __device__ __forceinline__ void fast_add_rest(Table &L, uint32_t slot, bool ok, 
 }
 
 // Slot of leaf k in the workgroup's leaf table (LDS only), claimed if new; ~0 when the table is full.
-template <class Table>
-__device__ __forceinline__ uint32_t fast_leaf_slot(Table &L, unsigned long long k) {
+__device__ __forceinline__ uint32_t fast_leaf_slot(FastTable &L, unsigned long long k) {
     uint32_t pos = (((uint32_t)k ^ (uint32_t)(k >> 21) ^ (uint32_t)(k >> 42)) * 0x9E3779B1u) >> 26;   // LOCAL_LEAVES = 2^6
     for (int probe = 0; probe < LOCAL_LEAVES; probe++) {
         unsigned long long cur = L.leaf_tab[pos];
@@ -216,10 +192,9 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
 // Called by the whole wave with the lanes' extremes (lanes without a valid point: +inf / -inf); false: the step lies off
 // the threshold table or is wider than a slab -- not for the fast variant.  Out of line on purpose: it runs a few times
 // per wave, and inlined into the step its temporaries cost the hot loop 30 registers.
-template <class Table>
-__device__ __attribute__((noinline)) bool fast_refit(Table *Lp, int wave, float mn0, float mn1, float mn2, float mx0, float mx1, float mx2, float inv,
+__device__ __attribute__((noinline)) bool fast_refit(FastTable *Lp, int wave, float mn0, float mn1, float mn2, float mx0, float mx1, float mx2, float inv,
                                                       int ib0, int ib1, int ib2, int fb0, int fb1, int fb2) {
-    Table &L = *Lp;
+    FastTable &L = *Lp;
     float lo[3] = {mn0, mn1, mn2}, hi[3] = {mx0, mx1, mx2};
     for (int sft = 32; sft > 0; sft >>= 1) {
 #pragma unroll
@@ -260,11 +235,11 @@ __device__ __attribute__((noinline)) bool fast_refit(Table *Lp, int wave, float 
 // kernel's rule (point_key_lookup: the two face thresholds around the voxel), claims its slot in the workgroup's leaf table and asks the
 // global table right away; the flush asks only for leaves that have no id yet.  Out of line: it runs once per workgroup.
 // (Everything by value: a pointer to the kernel's parameter blocks would put them into scratch memory for the whole kernel.)
-template <int MODE, class Table>
-__device__ __attribute__((noinline)) void fast_scout(Table *Lp, float inv_leaf, int ib0, int ib1, int ib2, int fb0, int fb1, int fb2, uint32_t leaf_mask,
+template <int MODE>
+__device__ __attribute__((noinline)) void fast_scout(FastTable *Lp, float inv_leaf, int ib0, int ib1, int ib2, int fb0, int fb1, int fb2, uint32_t leaf_mask,
                                                       unsigned long long *hash_keys, uint32_t *hash_ids, unsigned long long *leaf_keys, uint32_t *ctrl,
                                                       float f0, float f1, float f2) {
-    Table &L = *Lp;
+    FastTable &L = *Lp;
     const float f[3] = {f0, f1, f2};
     if (!__builtin_isfinite(f0 + f1 + f2)) return;
     const int ib[3] = {ib0, ib1, ib2}, fb[3] = {fb0, fb1, fb2};
@@ -316,8 +291,8 @@ __device__ __forceinline__ void wave_box_to_63(float &n0, float &n1, float &n2, 
 }
 
 // The end of a workgroup's pass: every wave hands in its error bits and the box of the points it has seen; then the table is
-// flushed into the leaf grids' records (see the kernel's header).  rec_list / used_list / fresh_list: Core::ENTRIES words of LDS
-// each that nobody else uses any more.  path_err: the error bit that hands the cloud to the next, more general accumulate kernel.
+// flushed into the leaf grids' records (see the kernel's header).  Errors that the general accumulate kernel does not have set
+// ERR_FAST_PATH: the host then reruns the pass with that kernel.
 // Returns false when nothing of this workgroup may reach the records (an error has been recorded: the whole workgroup leaves).
 // A workgroup may flush more than once (round 4: its range in two sub-ranges): the boxes are those of everything its waves have
 // seen so far -- what the octree replay wants of the last flush, and a superset of the keys' span for the earlier ones -- and the
@@ -332,9 +307,8 @@ __device__ __forceinline__ void wave_box_to_63(float &n0, float &n1, float &n2, 
 // Part 1 of the end of a workgroup's pass: errors, the range's box (out to W.bboxes), the voxel span of its points.
 // Returns 0: the range held no point that counts (nothing to flush); 1: go on, tmn = the lowest voxel index per axis (the base of
 // the linear keys); 2: an error has been recorded, nothing of this workgroup may reach the records.
-template <int NTHREADS, class Core>
-__device__ __forceinline__ int fast_finish_head(Core &L, const FastParams &P, const VoxWork &W, uint32_t err, float bn0, float bn1, float bn2, float bx0, float bx1,
-                                                float bx2, uint32_t path_err, int &tmn0, int &tmn1, int &tmn2) {
+__device__ __forceinline__ int fast_finish_head(FastTable &L, const FastParams &P, const VoxWork &W, uint32_t err, float bn0, float bn1, float bn2, float bx0, float bx1,
+                                                float bx2, int &tmn0, int &tmn1, int &tmn2) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv = P.inv_leaf;
     // ---- errors of this wave, bounding box of its range (input of the octree replay), extent in voxels ----
@@ -362,8 +336,8 @@ __device__ __forceinline__ int fast_finish_head(Core &L, const FastParams &P, co
     FAST_STAMP(3);
     if (threadIdx.x < 6) {   // the range's box (input of the octree replay): the waves' boxes reduced
         float v = L.wbox[0][threadIdx.x];
-        for (int w = 1; w < (NTHREADS / 64); w++) v = threadIdx.x < 3 ? fminf(v, L.wbox[w][threadIdx.x]) : fmaxf(v, L.wbox[w][threadIdx.x]);
-        W.bboxes[(size_t)(P.range_reverse ? gridDim.x - 1u - blockIdx.x : blockIdx.x) * 6 + threadIdx.x] = v;
+        for (int w = 1; w < K1_WAVES; w++) v = threadIdx.x < 3 ? fminf(v, L.wbox[w][threadIdx.x]) : fmaxf(v, L.wbox[w][threadIdx.x]);
+        W.bboxes[(size_t)blockIdx.x * 6 + threadIdx.x] = v;
     }
     tmn0 = L.tmin[0]; tmn1 = L.tmin[1]; tmn2 = L.tmin[2];
     const bool any_points = tmn0 <= L.tmax[0];
@@ -371,7 +345,7 @@ __device__ __forceinline__ int fast_finish_head(Core &L, const FastParams &P, co
     if (any_points) {
         // the linear keys are unique only inside this span; also keep indices where int arithmetic on them is safe
         const long long span0 = (long long)L.tmax[0] - tmn0, span1 = (long long)L.tmax[1] - tmn1, span2 = (long long)L.tmax[2] - tmn2;
-        if (span0 >= KEY_SPAN_X - 1 || span1 >= KEY_SPAN_Y - 1 || span2 >= KEY_SPAN_Z - 1) wg_err |= path_err;
+        if (span0 >= KEY_SPAN_X - 1 || span1 >= KEY_SPAN_Y - 1 || span2 >= KEY_SPAN_Z - 1) wg_err |= ERR_FAST_PATH;
         const int big = 1 << 28;
         if (tmn0 < -big || tmn1 < -big || tmn2 < -big || L.tmax[0] > big || L.tmax[1] > big || L.tmax[2] > big) wg_err |= ERR_RANGE;
     }
@@ -383,27 +357,26 @@ __device__ __forceinline__ int fast_finish_head(Core &L, const FastParams &P, co
     return any_points ? 1 : 0;
 }
 
-// Part 2: the table's entries (linear keys relative to tmn) -> the leaf grids' records, first touches counted.  The table may be
-// the accumulate kernel's own (fast_finish) or a copy of what it left in the workspace (voxel_merge_kernel).
-template <int MODE, int NTHREADS, class Core, int UU = 2>   // UU: entries a group of eight lanes has in flight in the record loop
-__device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, uint32_t *used_list, uint32_t *fresh_list, const FastParams &P, const VoxWork &W,
-                                                   const int tmn0, const int tmn1, const int tmn2, uint32_t path_err) {
+// Part 2: the table's entries (linear keys relative to tmn) -> the leaf grids' records, first touches counted.
+template <int MODE>
+__device__ __forceinline__ void fast_flush_records(FastTable &L, const FastParams &P, const VoxWork &W, const int tmn0, const int tmn1, const int tmn2) {
+    constexpr int UU = 2;   // entries a group of eight lanes has in flight in the record loop
     const int lane = threadIdx.x & 63;
     const uint32_t key_base = (uint32_t)((((tmn2 << 10) + tmn1) << 10) + tmn0);
     // ---- the entries in use: decoded to (local leaf slot << 19 | cell) and compacted in one pass ----
     // (every lane runs the arithmetic, whatever its entry holds; only entries in use claim a leaf slot and a place in the lists:
     // one LDS atomic per wave for the places, not per entry -- many lanes on one counter serialise)
     uint32_t bad = 0;
-    constexpr int PER_THREAD = (Core::ENTRIES + NTHREADS - 1) / NTHREADS;
+    constexpr int PER_THREAD = (LTAB + K1_THREADS - 1) / K1_THREADS;
     unsigned long long kk[PER_THREAD];
 #pragma unroll
     for (int q = 0; q < PER_THREAD; q++) {
-        const int e = (int)threadIdx.x + q * NTHREADS;
-        kk[q] = e < Core::ENTRIES ? L.key[e] : KEY64_EMPTY;
+        const int e = (int)threadIdx.x + q * K1_THREADS;
+        kk[q] = e < LTAB ? L.key[e] : KEY64_EMPTY;
     }
 #pragma unroll
     for (int q = 0; q < PER_THREAD; q++) {
-        const int e = (int)threadIdx.x + q * NTHREADS;
+        const int e = (int)threadIdx.x + q * K1_THREADS;
         const unsigned long long k64 = kk[q];
         const bool in_use = k64 != KEY64_EMPTY;
         const uint32_t dk = (uint32_t)k64 - key_base, side = (uint32_t)(k64 >> 32);
@@ -419,7 +392,7 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
                 // leaf of the voxel's lower part: l with tf(l) < t <= tf(l + 1); plus the side bit.  tf(l) is ib + 64 l give
                 // or take a voxel, so the estimate is off by one at most: the four table words around it decide (read side by
                 // side, not one after the other)
-                const int *TF = reinterpret_cast<const int *>(&L.faces[Core::TF_BASE + a * FACES]);
+                const int *TF = reinterpret_cast<const int *>(&L.faces[FT_TF + a * FACES]);
                 int j = ((t[a] - ib[a] - 1) >> 6) - fb[a];
                 j = max(1, min(j, FACES - 3));
                 const int fm = TF[j - 1], f0 = TF[j], f1 = TF[j + 1], f2 = TF[j + 2];
@@ -441,7 +414,7 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
             if (ok) {
                 const uint32_t ls = fast_leaf_slot(L, pack_leaf(leaf[0], leaf[1], leaf[2]));
                 if (ls != 0xffffffffu) rec = (ls << CELL_BITS) | (uint32_t)((cell[2] * GRID_DIM + cell[1]) * GRID_DIM + cell[0]);
-                else bad |= path_err;   // more than 64 leaves in one workgroup
+                else bad |= ERR_FAST_PATH;   // more than 64 leaves in one workgroup
             } else {
                 bad |= ERR_CELL_RANGE;
             }
@@ -452,8 +425,8 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if (in_use) {
             const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(vote >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vote, 0u));
-            used_list[at] = (uint32_t)e;
-            rec_list[at] = rec;
+            L.used[at] = (uint32_t)e;
+            L.rec[at] = rec;
         }
     }
     if (__ballot(bad != 0u) != 0ull) {
@@ -484,10 +457,10 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
     uint32_t okey[PER_THREAD], oold[PER_THREAD];
 #pragma unroll
     for (int q = 0; q < PER_THREAD; q++) {
-        const uint32_t i = threadIdx.x + (uint32_t)q * NTHREADS;
+        const uint32_t i = threadIdx.x + (uint32_t)q * K1_THREADS;
         okey[q] = 0xffffffffu; oold[q] = 0xffffffffu;
         if (i >= nused) continue;
-        const uint32_t ks = rec_list[i];
+        const uint32_t ks = L.rec[i];
         if (ks == 0xffffffffu) continue;
         const uint32_t gid = L.leaf_gid[ks >> CELL_BITS];
         if (gid == 0xffffffffu) continue;
@@ -511,13 +484,13 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
         const uint32_t m2 = sub == 2 ? 0xffu : sub == 3 ? 0xffffu : sub == 4 ? 0xffffffu : 0xffffffffu;
         const bool tile_word = sub == 5 || sub == 6;
         const unsigned long long *const w1p = f1 == 0 ? L.a : f1 == 1 ? L.b : f1 == 2 ? L.c : L.d, *const w2p = f2 == 0 ? L.a : f2 == 1 ? L.b : f2 == 2 ? L.c : L.d;
-        for (uint32_t i0 = threadIdx.x >> 3; i0 < nused; i0 += UU * (NTHREADS / 8)) {
+        for (uint32_t i0 = threadIdx.x >> 3; i0 < nused; i0 += UU * (K1_THREADS / 8)) {
             uint32_t e[UU], ks[UU];
 #pragma unroll
             for (int u = 0; u < UU; u++) {
-                const uint32_t i = i0 + (uint32_t)u * (NTHREADS / 8);
-                e[u] = used_list[i < nused ? i : i0];
-                ks[u] = i < nused ? rec_list[i] : 0xffffffffu;
+                const uint32_t i = i0 + (uint32_t)u * (K1_THREADS / 8);
+                e[u] = L.used[i < nused ? i : i0];
+                ks[u] = i < nused ? L.rec[i] : 0xffffffffu;
             }
             uint32_t gid[UU], tl[UU];
             unsigned long long w1[UU], w2[UU];
@@ -556,7 +529,7 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
         if (lane == 0) base = atomicAdd(&L.nfresh, (uint32_t)__popcll(fv));   // (one LDS atomic per wave)
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
         if (fresh) {
-            if (P.want_list) fresh_list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(fv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fv, 0u))] = k;
+            if (P.want_list) L.fresh[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(fv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fv, 0u))] = k;
             const uint32_t sl = slice_of(k);
             uint32_t hs = (sl * 0x9E3779B1u) >> 24;   // HIST = 2^8
             bool counted = false;
@@ -583,71 +556,27 @@ __device__ __forceinline__ void fast_flush_records(Core &L, uint32_t *rec_list, 
     if (threadIdx.x == 0 && nfresh) L.fresh_base = atomicAdd(&W.ctrl[C_COUNT], nfresh);
     __syncthreads();
     FAST_STAMP(8);
-    for (uint32_t i = threadIdx.x; i < nfresh; i += NTHREADS) {
+    for (uint32_t i = threadIdx.x; i < nfresh; i += K1_THREADS) {
         const uint32_t idx = L.fresh_base + i;
-        if (idx < P.list_cap) W.occupied[idx] = fresh_list[i];
+        if (idx < P.list_cap) W.occupied[idx] = L.fresh[i];
         else atomicOr(&W.ctrl[C_ERR], ERR_LIST_FULL);
     }
 }
 
-template <int MODE, int NTHREADS, class Core>
-__device__ __forceinline__ void fast_finish(Core &L, uint32_t *rec_list, uint32_t *used_list, uint32_t *fresh_list, const FastParams &P, const VoxWork &W,
-                                            uint32_t err, float bn0, float bn1, float bn2, float bx0, float bx1, float bx2, uint32_t path_err) {
+template <int MODE>
+__device__ __forceinline__ void fast_finish(FastTable &L, const FastParams &P, const VoxWork &W, uint32_t err, float bn0, float bn1, float bn2, float bx0, float bx1,
+                                            float bx2) {
     int tmn0, tmn1, tmn2;
-    if (fast_finish_head<NTHREADS>(L, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2, path_err, tmn0, tmn1, tmn2) != 1) return;
-    fast_flush_records<MODE, NTHREADS>(L, rec_list, used_list, fresh_list, P, W, tmn0, tmn1, tmn2, path_err);
-}
-
-// Round 4: the accumulate kernel's tail WITHOUT the records.  What made the tail of round 3's kernel 8.5 us in the middle
-// workgroup (4 to 13.5) were the decode, the leaf ids' round trip to the global table, the occupancy bits' round trip and 112 k
-// records x 6 atomics that all 248 workgroups sent within the same two microseconds (the memory side retires them at ~1.3 TB/s of
-// touched lines, whoever sends them).  None of that needs the accumulate kernel's 16 waves, its 151 KB of LDS or its CUs: the
-// workgroup now leaves its table's entries -- compacted, 48 bytes each, plain 16-byte stores -- and a header (count, key base) in
-// the workspace and ends; voxel_merge_kernel, small workgroups right behind it on the stream (and beside the next call's
-// accumulate kernel in a stream of frames), runs fast_flush_records on copies of them.  Same integer sums into the same records.
-struct DumpHead { uint32_t nused; int tmn0, tmn1, tmn2; };   // one per workgroup of the accumulate kernel (16 bytes)
-constexpr int DUMP_ENTRY_WORDS = 12;                        // key64, a, b, c, d, tile, (pad)
-
-template <int NTHREADS, class Core>
-__device__ __forceinline__ void fast_dump(Core &L, uint32_t *used_list, const FastParams &P, const VoxWork &W, uint32_t err, float bn0, float bn1, float bn2,
-                                          float bx0, float bx1, float bx2, uint32_t path_err) {
-    const int lane = threadIdx.x & 63;
-    int tmn0, tmn1, tmn2;
-    const int state = fast_finish_head<NTHREADS>(L, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2, path_err, tmn0, tmn1, tmn2);
-    DumpHead *const head = reinterpret_cast<DumpHead *>(W.dump_head) + blockIdx.x;
-    if (state != 1) {
-        if (threadIdx.x == 0) *head = DumpHead{0u, 0, 0, 0};
-        return;
-    }
-    // the entries in use, compacted (one LDS atomic per wave for the places)
-    constexpr int PER_THREAD = (Core::ENTRIES + NTHREADS - 1) / NTHREADS;
-#pragma unroll
-    for (int q = 0; q < PER_THREAD; q++) {
-        const int e = (int)threadIdx.x + q * NTHREADS;
-        const bool in_use = e < Core::ENTRIES && L.key[e] != KEY64_EMPTY;
-        const unsigned long long vote = __ballot(in_use);
-        uint32_t base = 0;
-        if (lane == 0 && vote != 0ull) base = atomicAdd(&L.nused, (uint32_t)__popcll(vote));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (in_use) used_list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(vote >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vote, 0u))] = (uint32_t)e;
-    }
-    __syncthreads();
-    FAST_STAMP(5);
-    const uint32_t nused = L.nused;
-    if (threadIdx.x == 0) *head = DumpHead{nused, tmn0, tmn1, tmn2};
-    uint4 *const out = reinterpret_cast<uint4 *>(W.dump_ent) + (size_t)blockIdx.x * Core::ENTRIES * (DUMP_ENTRY_WORDS / 4);
-    for (uint32_t i = threadIdx.x; i < nused; i += NTHREADS) {
-        const uint32_t e = used_list[i];
-        const unsigned long long k = L.key[e], a = L.a[e], b = L.b[e], c = L.c[e], d = L.d[e];
-        out[3 * i + 0] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)a, (uint32_t)(a >> 32));
-        out[3 * i + 1] = make_uint4((uint32_t)b, (uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32));
-        out[3 * i + 2] = make_uint4((uint32_t)d, (uint32_t)(d >> 32), L.tile[e], 0u);
-    }
-    FAST_STAMP(7);
+    if (fast_finish_head(L, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2, tmn0, tmn1, tmn2) != 1) return;
+    fast_flush_records<MODE>(L, P, W, tmn0, tmn1, tmn2);
 }
 
 // MODE 0: plain grid (bricks of 64 voxels on the voxel lattice), 1: octree leaves by face thresholds.
-// NT threads and an NTAB-entry table per workgroup: 1024 / 2048 = one workgroup per CU (rounds 2 and 3), 512 / 1024 = two.
+// K1_THREADS threads and an LTAB-entry table per workgroup: one workgroup per CU.
+//
+// Round 4, measured and removed again (commit 78186d1 has the code): two workgroups of 8 waves and 1024 entries per CU
+// (profiles/r04_k1_pair_experiment.txt); the table left in the workspace for a merge kernel to take to the records
+// (profiles/r04_k1_dump_merge.txt); the staggered ranges in reverse order (profiles/r04_k1_stagger.txt).
 //
 // Round 4, measured and NOT kept (commit bbddfb3 has the code, profiles/r04_k1_pair_experiment.txt the figures): two workgroups of
 // 8 waves per CU, each taking its range as two sub-ranges with a flush after each -- a third and two thirds for the one, two
@@ -656,13 +585,11 @@ __device__ __forceinline__ void fast_dump(Core &L, uint32_t *used_list, const Fa
 // flush each: 55.1-56.0).  A range's table holds about as many entries whether the range is 13 scan lines or 4 (a scan line of
 // this cloud meets ~190 voxels and the lines of a range meet the same ones): four flushes per CU are 1.5 x the records and four
 // times the barriers and round trips of one, and the eight waves that stream meanwhile have half the loads in flight.
-template <int MODE, int NT, int NTAB>
-__global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams P, const float *__restrict__ x, const float *__restrict__ y,
-                                                                     const float *__restrict__ z, const uint32_t *__restrict__ rgbt, VoxWork W) {
-    constexpr int NWAVES = NT / 64;
-    using Table = FastTableT<NTAB, NWAVES>;
+template <int MODE>
+__global__ void __launch_bounds__(K1_THREADS, 4) voxel_accumulate_fast_kernel(FastParams P, const float *__restrict__ x, const float *__restrict__ y,
+                                                                             const float *__restrict__ z, const uint32_t *__restrict__ rgbt, VoxWork W) {
     extern __shared__ __align__(16) unsigned char k1_smem[];
-    Table &L = *reinterpret_cast<Table *>(k1_smem);
+    FastTable &L = *reinterpret_cast<FastTable *>(k1_smem);
     FAST_STAMP(0);
 
     const int lane = threadIdx.x & 63;
@@ -673,9 +600,8 @@ __global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams
     const int wave = threadIdx.x >> 6;
     uint32_t chunk_lo = blockIdx.x * P.per_wg, chunk_hi = min(chunk_lo + P.per_wg, P.n);
     if (P.range_base_q != 0u) {
-        const uint32_t rb = P.range_reverse ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
-        chunk_lo = min(range_first_step(rb, P.range_base_q, P.range_inc_q) * (uint32_t)WAVE_STEP, P.n);
-        chunk_hi = min(range_first_step(rb + 1u, P.range_base_q, P.range_inc_q) * (uint32_t)WAVE_STEP, P.n);
+        chunk_lo = min(range_first_step(blockIdx.x, P.range_base_q, P.range_inc_q) * (uint32_t)WAVE_STEP, P.n);
+        chunk_hi = min(range_first_step(blockIdx.x + 1u, P.range_base_q, P.range_inc_q) * (uint32_t)WAVE_STEP, P.n);
     }
     const int chunk_pts = chunk_lo < chunk_hi ? (int)(chunk_hi - chunk_lo) : 0;
     const int nsteps = (chunk_pts + WAVE_STEP - 1) / WAVE_STEP;
@@ -694,24 +620,24 @@ __global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams
 #ifdef CWIPC_DEBUG_KNOBS
     // timing experiment: only 12 / 8 of the 16 waves take steps (the others help with the flush): how much does the streaming
     // phase owe to the waves that hide each other's waits?
-    const int streamers = NWAVES == 16 ? ((P.dbg & 0x20000u) ? 8 : (P.dbg & 0x10000u) ? 12 : NWAVES) : NWAVES;
+    const int streamers = (P.dbg & 0x20000u) ? 8 : (P.dbg & 0x10000u) ? 12 : K1_WAVES;
     if (wave >= streamers) cur = -1;
 #else
-    constexpr int streamers = NWAVES;
+    constexpr int streamers = K1_WAVES;
 #endif
     if (cur >= 0) load_step(cur, cx, cy, cz, cw);
 
     // (the threshold table's words are requested before the table is cleared and stored behind it: their round trip lies
     // behind the clearing)
-    constexpr int FT_PER_LANE = (FACE_TABLE_WORDS + NT - 1) / NT;
+    constexpr int FT_PER_LANE = (FACE_TABLE_WORDS + K1_THREADS - 1) / K1_THREADS;
     uint32_t ftw[FT_PER_LANE];
     if (MODE == 1) {
         const uint32_t *ft = reinterpret_cast<const uint32_t *>(W.faces);
 #pragma unroll
-        for (int q = 0; q < FT_PER_LANE; q++) ftw[q] = (int)threadIdx.x + q * NT < FACE_TABLE_WORDS ? ft[threadIdx.x + q * NT] : 0u;
+        for (int q = 0; q < FT_PER_LANE; q++) ftw[q] = (int)threadIdx.x + q * K1_THREADS < FACE_TABLE_WORDS ? ft[threadIdx.x + q * K1_THREADS] : 0u;
     }
     auto clear_table = [&]() __attribute__((always_inline)) {
-        for (int i = threadIdx.x; i < NTAB; i += NT) {
+        for (int i = threadIdx.x; i < LTAB; i += K1_THREADS) {
             L.key[i] = KEY64_EMPTY; L.tile[i] = 0;
             L.a[i] = 0; L.b[i] = 0; L.c[i] = 0; L.d[i] = 0;
         }
@@ -722,12 +648,12 @@ __global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams
     if (MODE == 1) {
 #pragma unroll
         for (int q = 0; q < FT_PER_LANE; q++)
-            if ((int)threadIdx.x + q * NT < FACE_TABLE_WORDS) L.faces[threadIdx.x + q * NT] = ftw[q];
+            if ((int)threadIdx.x + q * K1_THREADS < FACE_TABLE_WORDS) L.faces[threadIdx.x + q * K1_THREADS] = ftw[q];
     }
     if (threadIdx.x < LOCAL_LEAVES) { L.leaf_tab[threadIdx.x] = 0ull; L.leaf_gid[threadIdx.x] = 0xffffffffu; }
     if (threadIdx.x < 3) { L.tmin[threadIdx.x] = INT32_MAX; L.tmax[threadIdx.x] = INT32_MIN; }
-    if (threadIdx.x < NWAVES * 12) (&L.slab[0][0])[threadIdx.x] = INFINITY;   // cover nothing yet: the first step sets the slabs
-    if (threadIdx.x < NWAVES * 4) (&L.slab_j[0][0])[threadIdx.x] = -1;
+    if (threadIdx.x < K1_WAVES * 12) (&L.slab[0][0])[threadIdx.x] = INFINITY;   // cover nothing yet: the first step sets the slabs
+    if (threadIdx.x < K1_WAVES * 4) (&L.slab_j[0][0])[threadIdx.x] = -1;
     if (threadIdx.x == 0) { L.err = 0; L.next_step = (uint32_t)streamers; }
     __syncthreads();
     FAST_STAMP(1);
@@ -736,7 +662,7 @@ __global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams
     // (ONE scout per workgroup: every wave without a step scouting a point of its own, spread over the range, so that the range's second and third leaf are
     // there too, made the kernel slower -- 100 k points 23.6 -> 28.6-31.5 us, 300 k 26 -> 29: eleven lookups per workgroup at the kernel's start are the crowd
     // at the leaf table over again.)
-    if (wave == NWAVES - 1 && lane == 0 && chunk_pts > 0 && nsteps < NWAVES && !P.dump)
+    if (wave == K1_WAVES - 1 && lane == 0 && chunk_pts > 0 && nsteps < K1_WAVES)
         fast_scout<MODE>(&L, P.inv_leaf, P.ib0, P.ib1, P.ib2, P.fb0, P.fb1, P.fb2, P.leaf_mask, W.hash_keys, W.hash_ids, W.leaf_keys, W.ctrl, x[chunk_lo], y[chunk_lo], z[chunk_lo]);
 
     const float inv = P.inv_leaf;
@@ -1010,60 +936,5 @@ __global__ void __launch_bounds__(NT, 4) voxel_accumulate_fast_kernel(FastParams
 #ifdef CWIPC_DEBUG_KNOBS
     if (blockIdx.x == 0 && lane == 0 && wave < K1_WAVES) g_fast_wave_done[wave] = wall_clock64();
 #endif
-    if (P.dump) fast_dump<NT>(L, L.used, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2, ERR_FAST_PATH);
-    else fast_finish<MODE, NT>(L, L.rec, L.used, L.fresh, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2, ERR_FAST_PATH);
-}
-
-// The records' side of a pass whose accumulate kernel left its tables in the workspace (FastParams::dump): one workgroup per
-// workgroup of that kernel, MERGE_THREADS threads, the entries in chunks of MERGE_LTAB through a table in LDS and
-// fast_flush_records.  The leaf table (and the ids it has fetched) stays from chunk to chunk.
-constexpr int MERGE_THREADS = 256, MERGE_LTAB = 256;
-// what fast_flush_records needs of a table, and no more: 19 KB, so that eight such workgroups fit a CU's LDS and the compiler keeps
-// the kernel at 64 registers per lane -- one wave per SIMD of it then finds room on a CU that a workgroup of the next call's
-// accumulate kernel (16 waves x 112 registers, 105 KB when it leaves its table) occupies
-struct MergeTable {
-    static constexpr int ENTRIES = MERGE_LTAB;
-    static constexpr int TF_BASE = 0;
-    unsigned long long key[MERGE_LTAB];
-    uint32_t tile[MERGE_LTAB];
-    unsigned long long a[MERGE_LTAB], b[MERGE_LTAB], c[MERGE_LTAB], d[MERGE_LTAB];
-    uint32_t faces[3 * FACES];      // the cut voxels' table only
-    uint32_t htag[HIST], hcnt[HIST];
-    unsigned long long leaf_tab[LOCAL_LEAVES];
-    uint32_t leaf_gid[LOCAL_LEAVES];
-    uint32_t nfresh, fresh_base, nused, err;
-    uint32_t used[MERGE_LTAB], rec[MERGE_LTAB], fresh[MERGE_LTAB];
-};
-static_assert(sizeof(MergeTable) <= 20 * 1024, "eight merge workgroups per CU");
-
-// One wave per SIMD, 64 registers per lane.
-template <int MODE>
-__global__ void __launch_bounds__(MERGE_THREADS) voxel_merge_kernel(FastParams P, uint32_t src_entries, VoxWork W) {
-    __shared__ MergeTable L;
-    const uint4 *const in = reinterpret_cast<const uint4 *>(W.dump_ent) + (size_t)blockIdx.x * src_entries * (DUMP_ENTRY_WORDS / 4);
-    const DumpHead head = reinterpret_cast<const DumpHead *>(W.dump_head)[blockIdx.x];
-    if (head.nused == 0u) return;
-    if (MODE == 1) {
-        const uint32_t *ft = reinterpret_cast<const uint32_t *>(W.faces) + FT_TF;
-        for (int i = threadIdx.x; i < 3 * FACES; i += MERGE_THREADS) L.faces[i] = ft[i];
-    }
-    if (threadIdx.x < LOCAL_LEAVES) { L.leaf_tab[threadIdx.x] = 0ull; L.leaf_gid[threadIdx.x] = 0xffffffffu; }
-    for (uint32_t at = 0; at < head.nused; at += MERGE_LTAB) {
-        const uint32_t cnt = min(head.nused - at, (uint32_t)MERGE_LTAB);
-        if (at) __syncthreads();   // the chunk before has been read to the end
-        for (uint32_t i = threadIdx.x; i < (uint32_t)MERGE_LTAB; i += MERGE_THREADS) {
-            if (i < cnt) {
-                const uint4 q0 = in[3 * (size_t)(at + i) + 0], q1 = in[3 * (size_t)(at + i) + 1], q2 = in[3 * (size_t)(at + i) + 2];
-                L.key[i] = u64_of(q0.x, q0.y); L.a[i] = u64_of(q0.z, q0.w);
-                L.b[i] = u64_of(q1.x, q1.y); L.c[i] = u64_of(q1.z, q1.w);
-                L.d[i] = u64_of(q2.x, q2.y); L.tile[i] = q2.z;
-            } else {
-                L.key[i] = KEY64_EMPTY;
-            }
-        }
-        if (threadIdx.x < HIST) { L.htag[threadIdx.x] = 0; L.hcnt[threadIdx.x] = 0; }
-        if (threadIdx.x == 0) { L.nfresh = 0; L.nused = 0; }
-        __syncthreads();
-        fast_flush_records<MODE, MERGE_THREADS, MergeTable, 1>(L, L.rec, L.used, L.fresh, P, W, head.tmn0, head.tmn1, head.tmn2, ERR_FAST_PATH);
-    }
+    fast_finish<MODE>(L, P, W, err, bn0, bn1, bn2, bx0, bx1, bx2);
 }
