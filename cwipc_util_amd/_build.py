@@ -34,6 +34,7 @@ SOURCES = [
     "kernels_basic.hip",
     "kernels_voxel.hip",
     "kernels_sor.hip",
+    "kernels_kde.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

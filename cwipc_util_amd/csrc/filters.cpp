@@ -690,3 +690,61 @@ extern "C" int cwipc_hip_estimate_normals(cwipc_pointcloud *pc, float radius, in
     pool_free(block);
     return ok ? 0 : -1;
 }
+
+// ---------------------------------------------------------------------------
+// reference python/cwipc/registration/analyze.py:116-123 (the KD-tree query) and :171-179 (gaussian_kde)
+// ---------------------------------------------------------------------------
+extern "C" int cwipc_hip_nn_distance2(cwipc_pointcloud *source, cwipc_pointcloud *reference, int nth, double max_distance, double *dist2, size_t cap) {
+    const char *who = "cwipc_hip_nn_distance2";
+    if (source == nullptr || reference == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return -1;
+    }
+    if (nth < 0 || nth > NN_MAX_NTH || !(max_distance > 0.0)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "nth must lie between 0 and 31, max_distance must be positive (inf: no bound)");
+        return -1;
+    }
+    std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+    auto src = device_input(who, source, keep_src);
+    if (!src) return -1;
+    auto ref = source == reference ? src : device_input(who, reference, keep_ref);
+    if (!ref) return -1;
+    const size_t n = src->npoints;
+    if (cap < n || (n && dist2 == nullptr)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result array is too small");
+        return -1;
+    }
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    double *dev = (double *)pool_alloc(n * sizeof(double));
+    if (!dev) return -1;
+    bool ok = nn_distance2(*src, *ref, nth, max_distance, dev);
+    ok = ok && hipMemcpyAsync(dist2, dev, n * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;   // (also on failure: kernels that write `dev` may still be in flight)
+    pool_free(dev);
+    return ok ? 0 : -1;
+}
+
+extern "C" int cwipc_hip_gaussian_kde(const double *samples, size_t n, double h, const double *at, size_t m, double *density) {
+    const char *who = "cwipc_hip_gaussian_kde";
+    if (n == 0 || samples == nullptr || !(h > 0.0) || !std::isfinite(h) || (m && (at == nullptr || density == nullptr))) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "needs at least one sample, a positive, finite bandwidth and arrays for the evaluation points");
+        return -1;
+    }
+    if (m == 0) return 0;
+    if (!device_available(who)) return -1;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    // one block: samples | evaluation points | densities
+    double *block = (double *)pool_alloc((n + 2 * m) * sizeof(double));
+    if (!block) return -1;
+    double *ds = block, *da = block + n, *dd = block + n + m;
+    bool ok = hipMemcpyAsync(ds, samples, n * sizeof(double), hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+              hipMemcpyAsync(da, at, m * sizeof(double), hipMemcpyHostToDevice, c.stream) == hipSuccess;
+    ok = ok && gaussian_kde(ds, n, h, da, m, dd);
+    ok = ok && hipMemcpyAsync(density, dd, m * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(block);
+    return ok ? 0 : -1;
+}

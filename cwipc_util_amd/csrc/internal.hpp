@@ -413,6 +413,16 @@ constexpr int DIRECTION_MAX_NN = 128;
 bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const double dir[3], double threshold, float *drop, float *normals,
                        size_t stride, uint32_t *nn_count, double *centroid_dev);
 
+// The registration analyzer's search (kernels_sor.hip): per point of `source` the squared f64 distance to its (nth + 1)-th nearest
+// point of `reference` among those closer than max_distance (inf: no bound), +inf when there are fewer, into dev_out (source.npoints
+// device doubles, the source's order).  No wait inside.  False on failure (logged), also for nth outside 0..NN_MAX_NTH and a
+// max_distance that is NaN or <= 0.
+constexpr int NN_MAX_NTH = 31;
+bool nn_distance2(const DeviceSoA &source, const DeviceSoA &reference, int nth, double max_distance, double *dev_out);
+// 1-D Gaussian kernel density estimate (kernels_kde.hip): density[j] = sum_i exp(-0.5 ((at[j] - samples[i]) / h)^2) / (n h sqrt(2 pi)),
+// all arrays device memory.  No wait inside.
+bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);
+
 // Generic stable compaction driver used by tilefilter / crop / masked filter.
 // may_return_early: the call may come back with the scatter kernel still running (the result carries a
 // `ready` event); only for predicates that refer to nothing the caller frees afterwards.

@@ -43,6 +43,7 @@ __all__ = [
     'cwipc_hip_profile', 'cwipc_hip_knn_mean_dist', 'cwipc_hip_from_device_aos', 'cwipc_hip_from_device_slots', 'cwipc_hip_copy_device_aos',
     'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
+    'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
 ]
 
 # reference util.py:86, 346, 348
@@ -222,6 +223,8 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_knn_mean_dist': ([cwipc_pointcloud_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_double), _c.c_float], _c.c_int),
     'cwipc_hip_direction_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_float, _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_estimate_normals': ([cwipc_pointcloud_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1090,6 +1093,45 @@ def cwipc_hip_estimate_normals(pc: cwipc_pointcloud_wrapper, radius: float = 0.0
     if rc != 0:
         raise CwipcError("cwipc_hip_estimate_normals failed")
     return numpy.ascontiguousarray(planes[:, :n].T), nn[:n], cen
+
+
+def cwipc_hip_nn_distance(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, nth: int = 0, max_distance: float = float('inf')) -> numpy.ndarray:
+    """Per point of `source` the distance to its (nth + 1)-th nearest point of `reference`, inf when fewer than nth + 1 reference
+    points lie closer than max_distance: scipy.spatial.KDTree(reference).query(source, k=[nth + 1], distance_upper_bound=max_distance)
+    as the reference's registration analyzer calls it (registration/analyze.py:120-123), bit for bit -- the search runs on the
+    GPU and returns squared f64 distances, the root is numpy's, on the host.  float64, shape (count(source),)."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_nn_distance: NULL pointcloud")
+    n = source.count()
+    out = numpy.zeros(max(n, 1), dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_nn_distance2(source.as_cwipc_p(), reference.as_cwipc_p(), int(nth), float(max_distance), out.ctypes.data, out.size)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_nn_distance2 failed")
+    return numpy.sqrt(out[:n])
+
+
+def cwipc_hip_gaussian_kde(samples: Any, at: Any, bw_method: Union[None, str, float] = None) -> numpy.ndarray:
+    """scipy.stats.gaussian_kde(samples, bw_method).evaluate(at) for one-dimensional samples, the sum on the GPU: the bandwidth is
+    h = std(samples, ddof=1) * factor, factor = n**-0.2 (None, 'scott'), (n * 3 / 4)**-0.2 ('silverman') or the number given."""
+    s = numpy.ascontiguousarray(numpy.asarray(samples, dtype=numpy.float64).reshape(-1))
+    x = numpy.ascontiguousarray(numpy.asarray(at, dtype=numpy.float64).reshape(-1))
+    n = s.size
+    if n < 2:
+        raise CwipcError("cwipc_hip_gaussian_kde: needs at least two samples")
+    if bw_method is None or bw_method == 'scott':
+        factor = float(n) ** -0.2
+    elif bw_method == 'silverman':
+        factor = (float(n) * 3.0 / 4.0) ** -0.2
+    elif numpy.isscalar(bw_method) and not isinstance(bw_method, str):
+        factor = float(bw_method)
+    else:
+        raise ValueError("bw_method should be 'scott', 'silverman' or a scalar")
+    h = float(numpy.std(s, ddof=1)) * factor
+    out = numpy.zeros(max(x.size, 1), dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_gaussian_kde(s.ctypes.data, n, h, x.ctypes.data, x.size, out.ctypes.data)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_gaussian_kde failed")
+    return out[:x.size]
 
 
 def cwipc_hip_from_device_aos(dev_ptr: int, npoint: int, timestamp: int, cellsize: float) -> cwipc_pointcloud_wrapper:

@@ -139,6 +139,19 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_tilefilter_masked(cwipc_pointclou
  * The reference's radius and max_nn are 0.02 and 30.  NULL on error (logged), also for radius <= 0 or not finite, max_nn < 1 or > 128. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud *pc, double dx, double dy, double dz, double threshold, float radius, int max_nn);
 
+/* ---- the registration analyzer's arithmetic (reference python/cwipc/registration/analyze.py) ---- */
+/* Per point of `source` the SQUARED distance, in f64, to its (nth + 1)-th nearest point of `reference` among those closer than
+ * max_distance (strictly; INFINITY: no bound), +inf when there are fewer: d2 = (dx*dx + dy*dy) + dz*dz with dx = (double)qx - (double)px,
+ * every operation rounded on its own -- sqrt(d2) is what scipy.spatial.KDTree.query(points, k=[nth + 1], distance_upper_bound=max_distance)
+ * returns, bit for bit.  dist2: host array of cap >= count(source) doubles, in the source's order.  The clouds may be the same one
+ * (the point itself is then the nearest, at 0) and are neither consumed nor changed.  An empty source writes nothing, an empty
+ * reference gives +inf everywhere.  0 ok; -1 (logged) for a NULL cloud, nth < 0 or > 31, max_distance NaN or <= 0, cap too small. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_nn_distance2(cwipc_pointcloud *source, cwipc_pointcloud *reference, int nth, double max_distance, double *dist2, size_t cap);
+/* 1-D Gaussian kernel density estimate: density[j] = sum_i exp(-0.5 ((at[j] - samples[i]) / h)^2) / (n h sqrt(2 pi)) in f64, summed in
+ * an order fixed by n (what scipy.stats.gaussian_kde(samples).evaluate(at) computes for h = std(samples, ddof=1) * factor).  Host
+ * arrays: n samples, m evaluation points, m densities.  0 ok; -1 (logged) for n == 0, h not finite or <= 0, a NULL array. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_gaussian_kde(const double *samples, size_t n, double h, const double *at, size_t m, double *density);
+
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
