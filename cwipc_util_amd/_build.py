@@ -33,7 +33,10 @@ SOURCES = [
     "exchange.cpp",
     "kernels_basic.hip",
     "kernels_voxel.hip",
+    "kernels_grid.hip",
     "kernels_sor.hip",
+    "kernels_direction.hip",
+    "kernels_nn.hip",
     "kernels_kde.hip",
 ]
 

@@ -315,7 +315,8 @@ void count_alloc();
 void count_dealloc();
 
 // ---------------------------------------------------------------------------
-// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip)
+// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip;
+// the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
 namespace k {
@@ -393,7 +394,7 @@ void voxel_sample_streams();   // which of the calling thread's workspace stream
 std::shared_ptr<DeviceSoA> voxel_downsample(const std::shared_ptr<DeviceSoA> &src, float cellsize, bool leaf_split, int *error_code,
                                             std::shared_ptr<DeferredResult> *deferred = nullptr);
 
-// Statistical outlier removal (kernels_sor.hip).  Computes d_i into dev_dist
+// Statistical outlier removal (kernels_sor.hip, on the grid of kernels_grid.hip).  Computes d_i into dev_dist
 // (n floats, device), returns false on failure.
 bool sor_mean_distances(const DeviceSoA &src, int k, float *dev_dist);
 // mean/stddev threshold from d_i exactly as pcl::StatisticalOutlierRemoval; result in *thr.
@@ -405,7 +406,7 @@ std::shared_ptr<DeviceSoA> sor_select(const DeviceSoA &src, const float *dev_dis
 // The outlier filter's last steps on the device: statistics, threshold, compaction.  Small clouds: the statistics' second kernel rides with the compaction's count.
 std::shared_ptr<DeviceSoA> sor_threshold_and_select(const DeviceSoA &src, const float *dev_dist, float stddev_mul, double *thr_dev);
 
-// The direction filter's per-point work (kernels_sor.hip): the centroid into centroid_dev (3 device doubles), then per point the
+// The direction filter's per-point work (kernels_direction.hip): the centroid into centroid_dev (3 device doubles), then per point the
 // normal of its neighbourhood (the max_nn nearest within radius), turned away from the centroid.  Each output may be nullptr:
 // drop[i] = 0 if normal . dir >= threshold else 1; normals = planes x, y, z of `stride` floats; nn_count[i] = |neighbourhood|.
 // No wait inside.  Returns false on failure (logged), also for radius <= 0, a non-finite radius or max_nn outside 1..DIRECTION_MAX_NN.
@@ -413,7 +414,7 @@ constexpr int DIRECTION_MAX_NN = 128;
 bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const double dir[3], double threshold, float *drop, float *normals,
                        size_t stride, uint32_t *nn_count, double *centroid_dev);
 
-// The registration analyzer's search (kernels_sor.hip): per point of `source` the squared f64 distance to its (nth + 1)-th nearest
+// The registration analyzer's search (kernels_nn.hip): per point of `source` the squared f64 distance to its (nth + 1)-th nearest
 // point of `reference` among those closer than max_distance (inf: no bound), +inf when there are fewer, into dev_out (source.npoints
 // device doubles, the source's order).  No wait inside.  False on failure (logged), also for nth outside 0..NN_MAX_NTH and a
 // max_distance that is NaN or <= 0.

@@ -3,7 +3,7 @@
 # Builds an instrumented copy in /tmp and runs the tests that need no GPU against it.
 set -e
 OUT=/tmp/asan_build; mkdir -p $OUT/obj $OUT/lib
-for f in device.cpp filters.cpp logging.cpp pointcloud.cpp stubs.cpp synthetic.cpp kernels_basic.hip kernels_sor.hip kernels_voxel.hip; do
+for f in device.cpp filters.cpp logging.cpp pointcloud.cpp stubs.cpp synthetic.cpp kernels_basic.hip kernels_grid.hip kernels_sor.hip kernels_direction.hip kernels_nn.hip kernels_voxel.hip; do
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fvisibility=hidden -DCWIPC_VERSION=amd-gfx950-asan \
     -Iinclude -Icwipc_util_amd/csrc -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -x hip -c cwipc_util_amd/csrc/$f -o $OUT/obj/$f.o
 done

@@ -1162,7 +1162,7 @@ def test_staggered_ranges_change_no_result(gpu, synth, env, tmp_path):
 
 def test_sor_sparse_and_dense_grid_layouts_agree(gpu, oracle, synth):
     """The k-NN grid has two layouts: dense (small clouds) and segments of 16 cells that exist only where points are (big
-    clouds, kernels_sor.hip).  d_i is a property of the cloud, not of the search structure: both layouts, forced through
+    clouds, kernels_grid.hip).  d_i is a property of the cloud, not of the search structure: both layouts, forced through
     CWIPC_SOR_SPARSE in processes of their own, must give the oracle's d_i bit for bit -- on the synthetic figure, on a thin
     wide cloud whose rows cross many empty segments, on a cloud with far outliers (empty space between), with non-finite
     points, and for k beyond 16 (the 33-slot variant)."""
@@ -1308,7 +1308,7 @@ def test_remove_outliers_tiny_clouds(gpu, oracle):
 @pytest.mark.parametrize("n", [65535, 65536, 65537, 150000])
 @pytest.mark.parametrize("kind", ["sheet", "box", "edge"])
 def test_remove_outliers_either_side_of_the_small_flow(gpu, oracle, n, kind):
-    """Clouds up to 65 536 points (8 cells per point = 2^19 cells) take the ten-launch flow of round 4 (kernels_sor.hip,
+    """Clouds up to 65 536 points (8 cells per point = 2^19 cells) take the ten-launch flow of round 4 (kernels_grid.hip,
     sor_small_on_device: the grid derived by every workgroup of the count kernels, a one-workgroup scan), bigger ones the twelve-launch
     flow; both search with the k-NN kernel whose shells beyond the first are bounded row by row.  d_i bit for bit on both sides of the
     line: a sheet (the grid is coarsened after the census), a box (it is not: ~1 point per cell of the finest grid is already volume-like),
