@@ -14,6 +14,7 @@
 // result does not depend on the order of the points in a cell), count, sum(q - p) and sum((q - p)(q - p)^T) in int64 fixed point
 // (2^-20 of the cutoff distance), which no order of the candidates changes: the normals are the same bits run after run.
 #include "point_grid.hpp"
+#include "smallest_eigvec.hpp"
 
 #include <algorithm>
 
@@ -22,50 +23,6 @@ namespace cwipc_amd {
 namespace {
 
 constexpr double DIR_FIX = 1048576.0;   // fixed-point units per cutoff distance
-
-// The eigenvector of the smallest eigenvalue of a symmetric 3x3 (cyclic Jacobi in f64: rotations until the off-diagonal part is
-// negligible against the whole, at most 12 sweeps; three are usually enough).  The smallest diagonal entry at the end names it,
-// the lowest index on a tie.
-__host__ __device__ inline void smallest_eigvec(double a[3][3], double out[3]) {
-    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; sweep++) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-        const double all = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2] + 2.0 * off;
-        if (!(off > 1e-32 * all)) break;
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const int p = r == 2 ? 1 : 0, q = r == 0 ? 1 : 2;
-            const double apq = a[p][q];
-            if (apq == 0.0) continue;
-            const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {   // columns p and q
-                const double akp = a[k][p], akq = a[k][q];
-                a[k][p] = c * akp - s * akq;
-                a[k][q] = s * akp + c * akq;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {   // rows p and q
-                const double apk = a[p][k], aqk = a[q][k];
-                a[p][k] = c * apk - s * aqk;
-                a[q][k] = s * apk + c * aqk;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double vkp = v[k][p], vkq = v[k][q];
-                v[k][p] = c * vkp - s * vkq;
-                v[k][q] = s * vkp + c * vkq;
-            }
-        }
-    }
-    int m = 0;
-    if (a[1][1] < a[m][m]) m = 1;
-    if (a[2][2] < a[m][m]) m = 2;
-    const double len = sqrt(v[0][m] * v[0][m] + v[1][m] * v[1][m] + v[2][m] * v[2][m]);
-    for (int k = 0; k < 3; k++) out[k] = v[k][m] / len;
-}
 
 // centroid: f64 sums over contiguous slices (fixed order for the fixed launch shape), then the pairwise tree of stats_final_kernel (kernels_sor.hip)
 constexpr int CEN_BLOCKS = 1024;

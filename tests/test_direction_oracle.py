@@ -99,3 +99,131 @@ def test_factory_knows_the_direction_filter():
     assert f.direction == (0, 0, 1) and f.threshold == 0.5
     assert factory("direction(1, 0, 0)").threshold == 0.0
     assert any(m.CustomFilter is DirectionFilter for m in all_filters)
+
+
+# ---------------------------------------------------------------------------
+# the exact-neighbourhood oracle (estimate_exact): the kernel's definition of N(p)
+# ---------------------------------------------------------------------------
+def angle(a, b):
+    """The angle between the lines of a and b (up to sign), accurate for small angles."""
+    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=-1), np.abs((a * b).sum(axis=-1)))
+
+
+def brute_neighbourhoods(xyz, radius, max_nn):
+    """N(p) of every point over all pairs, straight from the definition: a list of sorted index arrays."""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    r2 = do.r2_of(radius)
+    out = []
+    for i in range(len(xyz)):
+        d2 = do.flann_d2(xyz[i], xyz)
+        under = np.sort(d2[d2 < r2])
+        cutoff = under[max_nn - 1] if len(under) >= max_nn else r2
+        out.append(np.flatnonzero((d2 <= cutoff) & (d2 < r2)))
+    return out
+
+
+def small_clouds():
+    rng = np.random.default_rng(11)
+    g = np.arange(10, dtype=np.float64) * 0.125
+    yield "box", rng.uniform(0, 0.2, (2000, 3)), 0.02
+    yield "lattice at the radius", np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3), 0.125
+    yield "lattice above the radius", np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3), float(np.nextafter(np.float32(0.125), np.float32(1)))
+    yield "lattice, decimal spacing", np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3) * 0.16, 0.02 * 2
+    yield "dupes", rng.uniform(0, 1, (30, 3))[rng.integers(0, 30, 1500)], 0.3
+    yield "shifted sheet", np.column_stack([rng.uniform(0, 1, (1500, 2)), np.full(1500, 0.25)]) + 100.0, 0.08
+    yield "radius above the cloud", rng.uniform(-1, 1, (100, 3)), 10.0
+    yield "radius of many cells", rng.uniform(0, 1, (2000, 3)), 0.5
+
+
+@pytest.mark.parametrize("max_nn", [1, 3, 30, 128])
+def test_exact_neighbourhoods_equal_brute_force_over_all_pairs(max_nn):
+    """... so the bucket grid's candidates (27 cells a little wider than the radius) are a superset of N(p)."""
+    for name, xyz, radius in small_clouds():
+        xyz = xyz.astype(np.float32)
+        est = do.estimate_exact(xyz, radius=radius, max_nn=max_nn)
+        want = brute_neighbourhoods(xyz, radius, max_nn)
+        assert list(est["nn"]) == [len(w) for w in want], name
+        for j in range(len(xyz)):
+            assert np.array_equal(np.sort(do.neighbours_of(est, j)), want[j]), (name, j)
+
+
+def test_exact_and_f64_estimators_agree_where_the_f64_one_flags_nothing():
+    rng = np.random.default_rng(12)
+    v = rng.normal(size=(40000, 3))
+    clouds = [(rng.uniform(0, 0.2, (20000, 3)).astype(np.float32), 0.02, 30),
+              ((v / np.linalg.norm(v, axis=1, keepdims=True) * 0.3).astype(np.float32), 0.03, 50),
+              (rng.uniform(0, 0.2, (20000, 3)).astype(np.float32), 0.01, 4)]
+    for xyz, radius, max_nn in clouds:
+        query = rng.choice(len(xyz), 2000, replace=False)
+        old = do.estimate(xyz, radius=radius, max_nn=max_nn, query=query)
+        new = do.estimate_exact(xyz, radius=radius, max_nn=max_nn, query=query)
+        clean = ~old["tie"] & ~old["boundary"]
+        assert clean.mean() > 0.95
+        assert np.array_equal(new["nn"][clean], old["nn"][clean])
+        for j in np.flatnonzero(clean):
+            assert set(do.neighbours_of(new, j).tolist()) == set(old["neighbours"][j].tolist())
+        good = clean & (old["gap"] >= 1e-2) & (old["orient"] >= 2e-3)
+        assert np.all(angle(new["normals"][good], old["normals"][good]) <= 1e-9)
+        assert np.all((new["normals"][good] * old["normals"][good]).sum(axis=1) > 0)
+        assert np.allclose(new["gap"][good], old["gap"][good], rtol=1e-6, atol=1e-9)
+
+
+def test_quantised_and_unquantised_normals_differ_by_what_the_fixed_point_predicts():
+    """Offsets are rounded to 2^-20 of the cutoff distance R: an error e, |e| <= sqrt(3)/2 units, per neighbour at |x| <= R = 2^20
+    units moves its term x x^T by at most 2 |x| |e| + |e|^2 and the mean's term by as much again, so the covariance by
+    |dC| <= 2 sqrt(3) 2^-20 R^2 (second order aside); the eigenvector of w0 then turns by at most |dC| / (w1 - w0) (Davis-Kahan,
+    to first order).  Twice that is asserted: angle <= 4 sqrt(3) 2^-20 R^2 / (w1 - w0), where the relative gap is at least 1e-2."""
+    rng = np.random.default_rng(13)
+    v = rng.normal(size=(40000, 3))
+    sphere = (v / np.linalg.norm(v, axis=1, keepdims=True) * 0.3).astype(np.float32)
+    box = rng.uniform(0, 0.2, (20000, 3)).astype(np.float32)
+    worst = {}
+    for xyz, radius, max_nn in ((sphere, 0.02, 30), (sphere, 0.08, 128), (box, 0.02, 30), (box, 0.01, 4), (sphere + np.float32(100), 0.02, 30)):
+        est = do.estimate_exact(xyz, radius=radius, max_nn=max_nn, query=rng.choice(len(xyz), 3000, replace=False))
+        ok = (est["gap"] >= 1e-2) & np.isfinite(est["gap"])
+        ang = angle(est["raw_q"][ok], est["raw"][ok])
+        bound = 4 * np.sqrt(3) * 2.0 ** -20 * est["cutoff"][ok].astype(np.float64) / est["split"][ok]
+        assert np.all(ang <= bound), float((ang / bound).max())
+        for dec in (-2, -1):
+            sel = (est["gap"][ok] >= 10.0 ** dec) & ((est["gap"][ok] < 10.0 ** (dec + 1)) | (dec == -1))
+            if sel.any():
+                worst[dec] = max(worst.get(dec, 0.0), float(ang[sel].max()))
+    print("quantised against unquantised normal, largest angle per gap decade: %s" % worst)
+    assert worst[-2] < 1e-3 and worst[-1] < 1e-4   # (far inside the GPU tests' outer bar of 1e-3 rad)
+
+
+def test_exact_known_answers():
+    g = np.arange(6, dtype=np.float32) * np.float32(0.125)
+    lattice = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    est = do.estimate_exact(lattice, radius=0.125, max_nn=30)
+    assert np.all(est["nn"] == 1)                            # points exactly at the radius are out: d2 < r2 is strict
+    up = do.estimate_exact(lattice, radius=float(np.nextafter(np.float32(0.125), np.float32(1))), max_nn=30)
+    inner = np.all((lattice > 0) & (lattice < 0.6), axis=1)
+    assert np.all(up["nn"][inner] == 7) and up["nn"].min() == 4
+    stack = np.vstack([np.zeros((40, 3)), [[1.0, 1.0, 1.0]]]).astype(np.float32)
+    est = do.estimate_exact(stack, max_nn=30)
+    assert list(est["nn"]) == [40] * 40 + [1]                # every point tied at the cutoff is in
+    assert np.array_equal(est["normals_q"][:40], np.tile([0, 0, -1.0], (40, 1)))
+    rng = np.random.default_rng(14)
+    xyz = rng.uniform(0, 0.1, (3000, 3)).astype(np.float32)
+    for max_nn in (1, 2):                                    # fewer than 3 points: always the z rule
+        est = do.estimate_exact(xyz, radius=0.02, max_nn=max_nn)
+        assert np.all(est["nn"] == max_nn)
+        for key in ("normals", "normals_q"):
+            assert np.all(np.abs(est[key][:, 2]) == 1.0) and np.all(est[key][:, :2] == 0)
+        assert np.all(np.isinf(est["gap"]))
+    est = do.estimate_exact(xyz, radius=0.02, max_nn=3)      # and from 3 on the eigenvector
+    assert np.all(est["nn"] == 3) and np.all(np.isfinite(est["gap"]))
+
+
+def test_exact_oracle_at_a_wide_radius():
+    """3 000 queries at radius 0.3 on a 40 k-point sphere shell, a third of the cloud in reach of each (10^8 candidate pairs):
+    the per-query loop of estimate() takes a minute on this."""
+    v = np.random.default_rng(15).normal(size=(40000, 3))
+    xyz = (v / np.linalg.norm(v, axis=1, keepdims=True) * 0.3).astype(np.float32)
+    query = np.arange(0, 40000, 13)[:3000]
+    est = do.estimate_exact(xyz, radius=0.3, max_nn=128, query=query)
+    assert np.all(est["nn"] == 128)
+    j = 1234
+    d2 = do.flann_d2(xyz[query[j]], xyz)
+    assert np.array_equal(np.sort(do.neighbours_of(est, j)), np.flatnonzero(d2 <= np.sort(d2)[127]))
