@@ -44,8 +44,6 @@ __device__ unsigned long long g_wg_times[1024][4];         // every workgroup: s
 #define FAST_STAMP(i) do { } while (0)
 #endif
 
-constexpr uint32_t ERR_FAST_PATH = 1024;   // the fast variant cannot take this cloud (host reruns the general variant)
-
 constexpr int KEY_SPAN_X = 1024, KEY_SPAN_Y = 1024, KEY_SPAN_Z = 4096;
 constexpr unsigned long long KEY64_EMPTY = ~0ull;
 constexpr uint32_t Q_NEG_ONE_BITS = 0u - Q_ONE_BITS;
@@ -54,7 +52,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct FastParams {
     uint32_t n, per_wg;   // per_wg: points of a workgroup's contiguous range (multiple of WAVE_STEP); its waves share it step by step
-    uint32_t range_base_q, range_inc_q;   // != 0: ranges of growing length instead (range_first_step, kernels_voxel.hip); per_wg is then the longest
+    uint32_t range_base_q, range_inc_q;   // != 0: ranges of growing length instead (range_first_step, voxel_common.hpp); per_wg is then the longest
     float inv_leaf;
     int ib0, ib1, ib2;
     int fb0, fb1, fb2;

@@ -33,7 +33,6 @@
 constexpr int PART_BUCKETS = 4096;
 constexpr int PART_CHUNK = 4096;     // points per workgroup of the scatter kernel (4 per lane)
 constexpr int PART_SEG_ROWS = 16;    // rows (workgroups) per segment of the histogram table
-constexpr int C_SCATTER = 18;        // control word: wave steps of the cloud as it came whose points spread over many buckets
 
 __device__ __forceinline__ uint32_t part_bucket(float fx, float fy, float fz, float inv) {
     // (non-finite coordinates convert to something: such points do not count anywhere, they only have to be moved somewhere)
