@@ -38,6 +38,7 @@ SOURCES = [
     "kernels_direction.hip",
     "kernels_nn.hip",
     "kernels_kde.hip",
+    "kernels_floor.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -748,3 +748,167 @@ extern "C" int cwipc_hip_gaussian_kde(const double *samples, size_t n, double h,
     pool_free(block);
     return ok ? 0 : -1;
 }
+
+// ---------------------------------------------------------------------------
+// reference python/cwipc/registration/util.py:146-229: the floor and tile helpers (kernels_floor.hip)
+// ---------------------------------------------------------------------------
+namespace {
+
+// count -> scan -> (wait: the two totals size the result) -> scatter -> wait
+std::shared_ptr<DeviceSoA> floor_partition(const std::shared_ptr<DeviceSoA> &src, const k::FloorArgs &a, uint64_t *n_first) {
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    if (n_first) *n_first = 0;
+    const size_t n = src->npoints;
+    if (n == 0) return soa_alloc(0);
+    const size_t nb = k::floor_blocks(n);
+    uint32_t *counts = (uint32_t *)c.device_scratch((2 * nb + 2) * sizeof(uint32_t));
+    if (!counts) return nullptr;
+    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
+    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    words[0] = words[1] = 0ull;
+    k::floor_count(*src, a, counts, c.stream);
+    k::floor_scan(counts, nb, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = c.sync() && ok;
+    if (!ok || (uint32_t)(words[0] >> 32) != tag || (uint32_t)(words[1] >> 32) != tag) {
+        hip_failed(hipGetLastError(), "floor partition", __FILE__, __LINE__);
+        return nullptr;
+    }
+    const size_t na = (uint32_t)words[0], nrest = (uint32_t)words[1];
+    if (na + nrest > n) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip", "floor partition: inconsistent count");
+        return nullptr;
+    }
+    if (n_first) *n_first = na;
+    if (na == n || nrest == n) {
+        // one class holds every point: the result is the input, point for point -- it holds the input's planes (clouds are immutable)
+        auto same = std::make_shared<DeviceSoA>();
+        same->xyz_block = src->xyz_block;
+        same->rgbt_block = src->rgbt_block;
+        same->npoints = src->npoints;
+        same->stride = src->stride;
+        same->device = src->device;
+        same->set_tiles_from(*src);
+        return same;
+    }
+    auto dst = soa_alloc(na + nrest);
+    if (!dst) return nullptr;
+    if (na + nrest) {
+        k::floor_scatter(*src, a, counts, *dst, c.stream);
+        ok = hipGetLastError() == hipSuccess;
+        ok = c.sync() && ok;
+        if (!ok) { hip_failed(hipGetLastError(), "floor partition", __FILE__, __LINE__); return nullptr; }
+    }
+    dst->set_tiles_from(*src);   // (a subset of the points: what could not occur still cannot)
+    return dst;
+}
+
+std::shared_ptr<DeviceSoA> floor_input(const char *who, cwipc_pointcloud *pc, std::unique_ptr<cwipc_hip_pointcloud> &keep) {
+    if (pc == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return nullptr;
+    }
+    return device_input(who, pc, keep);
+}
+
+}  // namespace
+
+extern "C" cwipc_pointcloud *cwipc_hip_floor_partition(cwipc_pointcloud *pc, double level, int flags, double radius, uint64_t *n_first) {
+    if (n_first) *n_first = 0;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = floor_input("cwipc_hip_floor_partition", pc, keep);
+    if (!src) return nullptr;
+    // (cellsize 0: the reference builds its result with cwipc_from_numpy_matrix and does not copy the cellsize, util.py:154, :228)
+    return wrap(floor_partition(src, k::FloorArgs{level, radius, flags}, n_first), pc->timestamp(), 0.f);
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_randomize_floor(cwipc_pointcloud *pc, double level, uint64_t seed) {
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = floor_input("cwipc_hip_randomize_floor", pc, keep);
+    if (!src) return nullptr;
+    uint64_t n_first = 0;
+    auto parted = floor_partition(src, k::FloorArgs{level, 0.0, k::FLOOR_KEEP_FLOOR | k::FLOOR_KEEP_REST}, &n_first);
+    if (!parted) return nullptr;
+    if (n_first < 2) return wrap(parted, pc->timestamp(), 0.f);   // nothing to permute
+    ThreadCtx &c = tctx();
+    auto dst = soa_with_new_rgbt(parted);   // the coordinates do not change: the result holds the very same planes
+    if (!dst) return nullptr;
+    bool ok = k::floor_shuffle(parted->rgbt(), (size_t)n_first, parted->npoints, seed, dst->rgbt(), c.stream);
+    ok = ok && hipGetLastError() == hipSuccess;
+    ok = c.sync() && ok;
+    if (!ok) return nullptr;
+    dst->set_tiles_from(*parted);   // (the same tile bytes in another order)
+    return wrap(dst, pc->timestamp(), 0.f);
+}
+
+extern "C" int cwipc_hip_floor_radius_stats(cwipc_pointcloud *pc, double level, uint64_t count[2], float stat[4]) {
+    if (count) count[0] = count[1] = 0;
+    if (stat) for (int i = 0; i < 4; i++) stat[i] = NAN;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = floor_input("cwipc_hip_floor_radius_stats", pc, keep);
+    if (!src || count == nullptr || stat == nullptr) return -1;
+    if (src->npoints == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    uint32_t *state = (uint32_t *)pool_alloc(k::floor_radius_state_bytes());
+    if (!state) return -1;
+    k::floor_radius_select(*src, level, state, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(c.host_words, state, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;   // (also on failure: kernels that write `state` may still be in flight)
+    pool_free(state);
+    if (!ok) return -1;
+    count[0] = c.host_words[0];
+    count[1] = c.host_words[1];
+    memcpy(stat, c.host_words + 2, 4 * sizeof(float));
+    return 0;
+}
+
+extern "C" int cwipc_hip_tile_counts(cwipc_pointcloud *pc, int nonfloor_only, double level, uint64_t counts[256]) {
+    if (counts) memset(counts, 0, 256 * sizeof(uint64_t));
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = floor_input("cwipc_hip_tile_counts", pc, keep);
+    if (!src || counts == nullptr) return -1;
+    if (src->npoints == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    unsigned long long *dev = (unsigned long long *)pool_alloc(256 * sizeof(unsigned long long));
+    void *stage = c.staging(256 * sizeof(unsigned long long));
+    if (!dev || !stage) { pool_free(dev); return -1; }
+    k::tile_histogram(*src, nonfloor_only ? 1 : 0, level, dev, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(stage, dev, 256 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(dev);
+    if (!ok) return -1;
+    memcpy(counts, stage, 256 * sizeof(uint64_t));
+    return 0;
+}
+
+extern "C" int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]) {
+    if (minmax) for (int a = 0; a < 3; a++) { minmax[a] = INFINITY; minmax[3 + a] = -INFINITY; }
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = floor_input("cwipc_hip_bounds", pc, keep);
+    if (!src || minmax == nullptr) return -1;
+    if (src->npoints == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const unsigned nb = k::bounds_blocks(src->npoints);
+    const size_t bytes = (size_t)nb * 6 * sizeof(float);
+    float *partial = (float *)pool_alloc(bytes);
+    float *host = (float *)c.staging(bytes);
+    if (!partial || !host) { pool_free(partial); return -1; }
+    k::bounds_partial(*src, partial, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(host, partial, bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(partial);
+    if (!ok) return -1;
+    for (unsigned b = 0; b < nb; b++)
+        for (int a = 0; a < 3; a++) {
+            minmax[a] = fminf(minmax[a], host[b * 6 + a]);
+            minmax[3 + a] = fmaxf(minmax[3 + a], host[b * 6 + 3 + a]);
+        }
+    return 0;
+}

@@ -384,6 +384,36 @@ struct JoinPart {
 };
 void join_copy(const JoinPart &part, const DeviceSoA &dst, hipStream_t s);
 
+// ---- kernels_floor.hip: the floor and tile helpers of the registration pipeline (python/cwipc/registration/util.py:146-229) ----
+// A point is floor iff (double)y < level.  Class A of the partition comes first in the output, class B behind it, both in
+// input order: A = floor points (FLOOR_KEEP_FLOOR), with FLOOR_LIMIT_RADIUS only those with (double)d < radius, d the float32
+// norm of (x, y, z); B = the other points (FLOOR_KEEP_REST).
+struct FloorArgs {
+    double level;
+    double radius;
+    int flags;   // CWIPC_HIP_FLOOR_* of hip_ext.h
+};
+constexpr int FLOOR_KEEP_FLOOR = CWIPC_HIP_FLOOR_KEEP_FLOOR, FLOOR_KEEP_REST = CWIPC_HIP_FLOOR_KEEP_REST, FLOOR_LIMIT_RADIUS = CWIPC_HIP_FLOOR_LIMIT_RADIUS;
+size_t floor_blocks(size_t n);
+// counts: 2 * floor_blocks(n) + 2 device words -- per-workgroup counts of A, then of B; the scan turns both into offsets, leaves the
+// totals in the last two words and in two pinned 64-bit host words (the count below `tag`); the scatter writes dst (A + B points)
+void floor_count(const DeviceSoA &src, const FloorArgs &a, uint32_t *counts, hipStream_t s);
+void floor_scan(uint32_t *counts, size_t nblocks, unsigned long long *total_host, uint32_t tag, hipStream_t s);
+void floor_scatter(const DeviceSoA &src, const FloorArgs &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s);
+// out_rgbt[j] for j < n_first: rgbt[j]'s colour with the tile byte of rgbt[perm[j]], perm the stable ascending argsort of the
+// splitmix64 keys of seed; for j >= n_first a copy.  The scratch blocks are freed at the calling thread's next sync().
+bool floor_shuffle(const uint32_t *rgbt, size_t n_first, size_t n, uint64_t seed, uint32_t *out_rgbt, hipStream_t s);
+// Exact radix selection per class (0 floor, 1 rest) on d = sqrt((x*x + 0) + z*z): state (floor_radius_state_bytes() of device
+// memory) ends with the two class counts in words 0-1 and sorted(d)[lo], sorted(d)[min(lo + 1, n - 1)] per class as float bits
+// in words 2-5 (NaN for an empty class), lo = floor((n - 1) * 0.99f) in float32 as numpy.percentile computes it.
+size_t floor_radius_state_bytes();
+void floor_radius_select(const DeviceSoA &src, double level, uint32_t *state, hipStream_t s);
+// counts of the tile byte (256 x 64 bit, device), optionally of the non-floor points only
+void tile_histogram(const DeviceSoA &src, int nonfloor_only, double level, unsigned long long *dev_counts256, hipStream_t s);
+// per workgroup min x, y, z, max x, y, z (NaN skipped per coordinate; +inf / -inf where there is nothing): bounds_blocks(n) x 6 floats
+unsigned bounds_blocks(size_t n);
+void bounds_partial(const DeviceSoA &src, float *partial, hipStream_t s);
+
 }  // namespace k
 
 // Voxel-grid downsample (kernels_voxel.hip).  Returns the new cloud's planes or

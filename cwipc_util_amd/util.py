@@ -44,6 +44,9 @@ __all__ = [
     'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
+    'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
+    'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
+    'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
 ]
 
 # reference util.py:86, 346, 348
@@ -225,6 +228,11 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_estimate_normals': ([cwipc_pointcloud_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
+    'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
+    'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
+    'cwipc_hip_floor_radius_stats': ([cwipc_pointcloud_p, _c.c_double, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_float)], _c.c_int),
+    'cwipc_hip_tile_counts': ([cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], _c.c_int),
+    'cwipc_hip_bounds': ([cwipc_pointcloud_p, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1010,6 +1018,131 @@ class cwipc_hip_comm:
 def cwipc_tilefilter_masked(pc: cwipc_pointcloud_wrapper, mask: int) -> cwipc_pointcloud_wrapper:
     """Points whose tile number ANDed with mask is non-zero (reference python/cwipc/registration/util.py:98-112)."""
     return _wrap_filter_result('cwipc_tilefilter_masked', cwipc_util_dll_load().cwipc_hip_tilefilter_masked(pc.as_cwipc_p(), mask))
+
+
+# ---- the floor and tile helpers of the registration pipeline (reference python/cwipc/registration/util.py:146-229) ----
+CWIPC_HIP_FLOOR_KEEP_FLOOR = 1
+CWIPC_HIP_FLOOR_KEEP_REST = 2
+CWIPC_HIP_FLOOR_LIMIT_RADIUS = 4
+
+
+def _threshold(value: Any) -> float:
+    """The double the kernels compare (double)v against so that the outcome is numpy's `float32_column < value`: numpy compares in
+    result_type(float32, value) -- float32 for a Python float or int and for an np.float32 (weak scalars are rounded to the
+    column's type first), float64 for an np.float64 scalar, which is passed as it is."""
+    dtype = numpy.result_type(numpy.float32, value)
+    if dtype == numpy.float32:
+        return float(numpy.float32(value))
+    return float(numpy.float64(value))
+
+
+def cwipc_hip_floor_partition(pc: cwipc_pointcloud_wrapper, level: Any, flags: int, radius: Any = 0.0) -> Tuple[cwipc_pointcloud_wrapper, int]:
+    """Stable two-class partition on the GPU (include/cwipc_util_amd/hip_ext.h): (cloud, number of class A points).  The result has
+    the input's timestamp and cellsize 0, the cellsize of a cloud fresh from cwipc_from_numpy_matrix."""
+    n_first = ctypes.c_uint64(0)
+    rv = cwipc_util_dll_load().cwipc_hip_floor_partition(pc.as_cwipc_p(), _threshold(level), int(flags), _threshold(radius), ctypes.byref(n_first))
+    return _wrap_filter_result('cwipc_hip_floor_partition', rv), int(n_first.value)
+
+
+def cwipc_floor_filter(pc: cwipc_pointcloud_wrapper, level: float = 0.1, keep: bool = False) -> cwipc_pointcloud_wrapper:
+    """Remove all points that are probably on the floor (y < level); keep=True: keep only those (reference registration/util.py:146-155).
+    As in the reference the result has cellsize 0 (a cloud fresh from cwipc_from_numpy_matrix), not the input's."""
+    return cwipc_hip_floor_partition(pc, level, CWIPC_HIP_FLOOR_KEEP_FLOOR if keep else CWIPC_HIP_FLOOR_KEEP_REST)[0]
+
+
+def cwipc_randomize_floor(pc: cwipc_pointcloud_wrapper, level: float = 0.1, *, seed: Optional[int] = None) -> cwipc_pointcloud_wrapper:
+    """Randomly assign all floor points (y < level) to different tiles (reference registration/util.py:157-168): the floor points
+    first, the others behind them, the floor's tile numbers permuted among the floor points.  The permutation is the stable argsort
+    of splitmix64 keys of `seed` (None: 64 bits from os.urandom) -- reproducible from the seed, not numpy's Mersenne shuffle.
+    Cellsize 0, as in the reference."""
+    if seed is None:
+        seed = int.from_bytes(os.urandom(8), 'little')
+    rv = cwipc_util_dll_load().cwipc_hip_randomize_floor(pc.as_cwipc_p(), _threshold(level), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return _wrap_filter_result('cwipc_randomize_floor', rv)
+
+
+def cwipc_hip_tile_counts(pc: cwipc_pointcloud_wrapper, nonfloor_only: bool = False, level: Any = 0.1) -> numpy.ndarray:
+    """uint64[256]: the number of points per tile number, of all points or of those that are not floor (y < level)."""
+    counts = numpy.zeros(256, dtype=numpy.uint64)
+    rc = cwipc_util_dll_load().cwipc_hip_tile_counts(pc.as_cwipc_p(), 1 if nonfloor_only else 0, _threshold(level), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_tile_counts failed")
+    return counts
+
+
+def cwipc_compute_tile_occupancy(pc: cwipc_pointcloud_wrapper, cellsize: float = 0, filterfloor: bool = False) -> List[Tuple[int, int]]:
+    """List of (tilenum, pointcount), optionally after removing the floor and / or downsampling with cellsize, sorted by point count
+    (descending; equal counts by ascending tile number), empty tiles omitted (reference registration/util.py:184-200).  One histogram
+    kernel instead of a tile filter per tile; without cellsize no intermediate cloud is made."""
+    if cellsize != 0:
+        if filterfloor:
+            pc = cwipc_floor_filter(pc)
+        pc = cwipc_downsample(pc, cellsize)
+        filterfloor = False
+    counts = cwipc_hip_tile_counts(pc, filterfloor)
+    rv = [(t, int(counts[t])) for t in range(256) if counts[t]]
+    rv.sort(key=lambda tp: tp[1], reverse=True)   # (stable: ties stay in ascending tile order, as in the reference)
+    return rv
+
+
+def cwipc_hip_floor_radius_stats(pc: cwipc_pointcloud_wrapper, level: Any = 0.1) -> Tuple[numpy.ndarray, numpy.ndarray]:
+    """(count uint64[2], stat float32[4]) per class (0 floor, 1 not floor) on d = sqrt(x*x + z*z) in float32: stat[2c] = sorted(d)[lo],
+    stat[2c + 1] = sorted(d)[min(lo + 1, count[c] - 1)], lo = floor(float32(count[c] - 1) * float32(0.99)); NaN for an empty class."""
+    count = numpy.zeros(2, dtype=numpy.uint64)
+    stat = numpy.full(4, numpy.nan, dtype=numpy.float32)
+    rc = cwipc_util_dll_load().cwipc_hip_floor_radius_stats(pc.as_cwipc_p(), _threshold(level), count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                            stat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_floor_radius_stats failed")
+    return count, stat
+
+
+def _percentile99_from_neighbours(n: int, a: numpy.float32, b: numpy.float32) -> numpy.float32:
+    """numpy.percentile(d, 99) of n float32 values from sorted(d)[lo] and sorted(d)[min(lo + 1, n - 1)], in numpy's own arithmetic:
+    for float32 data the quantile is 99 / float32(100), the virtual index (n - 1) * q and its fractional part g are float32, and the
+    result is a + (b - a) * g, or b - (b - a) * (1 - g) where g >= 0.5."""
+    if n == 0:
+        return numpy.float32(numpy.nan)
+    virtual = numpy.float32(n - 1) * numpy.float32(0.99)
+    g = numpy.float32(virtual - numpy.floor(virtual))
+    a, b = numpy.float32(a), numpy.float32(b)
+    with numpy.errstate(invalid='ignore', over='ignore'):
+        diff = numpy.float32(b - a)
+        if g >= 0.5:
+            return numpy.float32(b - diff * numpy.float32(numpy.float32(1) - g))
+        return numpy.float32(a + diff * g)
+
+
+def cwipc_compute_radius(pc: cwipc_pointcloud_wrapper, level: float = 0.1) -> Tuple[float, float, float]:
+    """The radius in the XZ plane ignoring outliers (reference registration/util.py:202-216): (overall, not floor, floor), each the
+    99th percentile (numpy.percentile, linear) of the float32 distances from the y axis.  The two neighbouring order statistics
+    per class are selected exactly on the GPU, the interpolation between them is numpy's, on the host.  A stated departure: an empty
+    class gives nan (the reference raises IndexError) and the overall radius is then the other class's."""
+    count, stat = cwipc_hip_floor_radius_stats(pc, level)
+    floor_max = _percentile99_from_neighbours(int(count[0]), stat[0], stat[1])
+    nonfloor_max = _percentile99_from_neighbours(int(count[1]), stat[2], stat[3])
+    if count[0] == 0:
+        overall = nonfloor_max
+    elif count[1] == 0:
+        overall = floor_max
+    else:
+        overall = max(floor_max, nonfloor_max)
+    return overall, nonfloor_max, floor_max
+
+
+def cwipc_limit_floor_to_radius(pc: cwipc_pointcloud_wrapper, radius: float, level: float = 0.1) -> cwipc_pointcloud_wrapper:
+    """The cloud with the floor points (y < level) at distance >= radius from the origin removed: the remaining floor points first,
+    the others behind them (reference registration/util.py:218-229; the distance is the norm of all three coordinates, as the
+    reference computes it).  Cellsize 0, as in the reference."""
+    return cwipc_hip_floor_partition(pc, level, CWIPC_HIP_FLOOR_KEEP_FLOOR | CWIPC_HIP_FLOOR_KEEP_REST | CWIPC_HIP_FLOOR_LIMIT_RADIUS, radius)[0]
+
+
+def cwipc_hip_bounds(pc: cwipc_pointcloud_wrapper) -> numpy.ndarray:
+    """float32[6]: min x, min y, min z, max x, max y, max z, NaN skipped per coordinate (+inf / -inf for an empty cloud)."""
+    minmax = numpy.zeros(6, dtype=numpy.float32)
+    if cwipc_util_dll_load().cwipc_hip_bounds(pc.as_cwipc_p(), minmax.ctypes.data_as(ctypes.POINTER(ctypes.c_float))) != 0:
+        raise CwipcError("cwipc_hip_bounds failed")
+    return minmax
 
 
 def cwipc_transform(pc: cwipc_pointcloud_wrapper, transform: Any) -> cwipc_pointcloud_wrapper:

@@ -139,6 +139,33 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_tilefilter_masked(cwipc_pointclou
  * The reference's radius and max_nn are 0.02 and 30.  NULL on error (logged), also for radius <= 0 or not finite, max_nn < 1 or > 128. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud *pc, double dx, double dy, double dz, double threshold, float radius, int max_nn);
 
+/* ---- floor and tile helpers of the registration pipeline (reference python/cwipc/registration/util.py:146-229) ----
+ * A point is FLOOR iff (double)y < level; a NaN y is not floor.  The reference compares the float32 column with a Python scalar,
+ * which numpy rounds to float32 first: the caller passes that value (the Python wrappers do).  NULL (or -1) on error (logged):
+ * a NULL cloud, no usable GPU.  Results carry the input's timestamp and cellsize 0 -- the cellsize of a cloud fresh from
+ * cwipc_from_points / cwipc_from_numpy_matrix, which is what the reference's helpers return (they do not copy the cellsize). */
+#define CWIPC_HIP_FLOOR_KEEP_FLOOR 1     /* class A, first in the result: the floor points */
+#define CWIPC_HIP_FLOOR_KEEP_REST 2      /* class B, behind them: the points that are not floor */
+#define CWIPC_HIP_FLOOR_LIMIT_RADIUS 4   /* class A only holds floor points with (double)d < radius, d = sqrt((x*x + y*y) + z*z) in float32 */
+/* Stable two-class partition: all class A points in input order, then all class B points in input order; *n_first (may be NULL)
+ * receives the number of class A points.  cwipc_floor_filter = KEEP_REST (keep=False) or KEEP_FLOOR (keep=True);
+ * cwipc_limit_floor_to_radius = all three flags. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_floor_partition(cwipc_pointcloud *pc, double level, int flags, double radius, uint64_t *n_first);
+/* cwipc_randomize_floor: floor points first, the others behind; floor point i (in that order) has key splitmix64(seed + (i + 1) *
+ * 0x9E3779B97F4A7C15), perm is the stable ascending argsort of the keys, and position j keeps x, y, z, r, g, b and takes the tile of
+ * floor point perm[j].  (The reference shuffles with numpy's Mersenne Twister; the contract here is a uniform permutation of the
+ * floor's tiles that a seed reproduces.) */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_randomize_floor(cwipc_pointcloud *pc, double level, uint64_t seed);
+/* What cwipc_compute_radius interpolates between, per class c (0 floor, 1 not floor) on d = sqrt((x*x + 0) + z*z) in float32:
+ * count[c], stat[2 c] = sorted(d)[lo] and stat[2 c + 1] = sorted(d)[min(lo + 1, count[c] - 1)] with lo = floor((count[c] - 1) * 0.99),
+ * the product in float32 as numpy.percentile computes it for float32 data; NaN for an empty class.  Exact (radix selection). 0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_floor_radius_stats(cwipc_pointcloud *pc, double level, uint64_t count[2], float stat[4]);
+/* counts[t] = number of points with tile t, of all points or (nonfloor_only) of those that are not floor.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_tile_counts(cwipc_pointcloud *pc, int nonfloor_only, double level, uint64_t counts[256]);
+/* minmax = min x, min y, min z, max x, max y, max z; NaN is skipped per coordinate (as Python's < and > do in the reference's
+ * analyze filter); a coordinate without a value (an empty cloud) has min +inf and max -inf.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]);
+
 /* ---- the registration analyzer's arithmetic (reference python/cwipc/registration/analyze.py) ---- */
 /* Per point of `source` the SQUARED distance, in f64, to its (nth + 1)-th nearest point of `reference` among those closer than
  * max_distance (strictly; INFINITY: no bound), +inf when there are fewer: d2 = (dx*dx + dy*dy) + dz*dz with dx = (double)qx - (double)px,
