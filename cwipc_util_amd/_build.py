@@ -38,6 +38,7 @@ SOURCES = [
     "kernels_direction.hip",
     "kernels_nn.hip",
     "kernels_kde.hip",
+    "kernels_icp.hip",
     "kernels_floor.hip",
 ]
 

@@ -750,6 +750,120 @@ extern "C" int cwipc_hip_gaussian_kde(const double *samples, size_t n, double h,
 }
 
 // ---------------------------------------------------------------------------
+// reference python/cwipc/registration/fine.py (open3d registration_icp) and analyze.py's OverlapAnalyzer (evaluate_registration):
+// kernels_icp.hip
+// ---------------------------------------------------------------------------
+namespace {
+
+const double ICP_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
+// both clouds on the device, and the arguments every ICP entry point checks; false: logged
+bool icp_inputs(const char *who, cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                std::unique_ptr<cwipc_hip_pointcloud> &keep_src, std::unique_ptr<cwipc_hip_pointcloud> &keep_ref, std::shared_ptr<DeviceSoA> &src,
+                std::shared_ptr<DeviceSoA> &ref) {
+    if (source == nullptr || reference == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return false;
+    }
+    if (!(max_distance > 0.0)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_distance must be positive (inf: no bound)");
+        return false;
+    }
+    for (int i = 0; T && i < 16; i++)
+        if (!std::isfinite(T[i])) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the matrix must be finite");
+            return false;
+        }
+    src = device_input(who, source, keep_src);
+    if (!src) return false;
+    ref = source == reference ? src : device_input(who, reference, keep_ref);
+    return (bool)ref;
+}
+
+}  // namespace
+
+extern "C" int cwipc_hip_correspondences(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, uint32_t *idx,
+                                         double *dist2, size_t cap) {
+    const char *who = "cwipc_hip_correspondences";
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        const size_t n = src->npoints;
+        if (cap < n) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result arrays are too small");
+            return -1;
+        }
+        if (n == 0) return 0;
+        if (!icp_correspondences(*src, *ref, T ? T : ICP_IDENTITY, max_distance, idx, dist2)) return -1;
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+extern "C" int cwipc_hip_icp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, const double *cp,
+                                  const double *cq, uint64_t *n, double *sums) {
+    const char *who = "cwipc_hip_icp_sums";
+    if (n) *n = 0;
+    if (sums) for (int v = 0; v < 16; v++) sums[v] = 0.0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        const double zero[3] = {0, 0, 0};
+        uint64_t hn = 0;
+        double hs[16];
+        if (!icp_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, cp ? cp : zero, cq ? cq : zero, &hn, hs)) return -1;
+        if (n) *n = hn;
+        if (sums) memcpy(sums, hs, sizeof(hs));
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+extern "C" int cwipc_hip_icp_point2point(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
+                                         double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
+                                         double *inlier_rmse, int *iterations) {
+    const char *who = "cwipc_hip_icp_point2point";
+    const double *T0 = init ? init : ICP_IDENTITY;
+    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
+    if (fitness) *fitness = 0.0;
+    if (inlier_rmse) *inlier_rmse = 0.0;
+    if (iterations) *iterations = 0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
+            return -1;
+        }
+        if (src->npoints == 0 || ref->npoints == 0) return 0;
+        // the pivots, once per run: the clouds' centroids ((0, 0, 0) for a cloud with a non-finite point: any pivot is right,
+        // a near one only keeps the covariance from cancelling)
+        double cp0[3], cq[3];
+        if (!icp_centroid(*src, cp0) || !icp_centroid(*ref, cq)) return -1;
+        if (!(std::isfinite(cp0[0]) && std::isfinite(cp0[1]) && std::isfinite(cp0[2]))) cp0[0] = cp0[1] = cp0[2] = 0.0;
+        if (!(std::isfinite(cq[0]) && std::isfinite(cq[1]) && std::isfinite(cq[2]))) cq[0] = cq[1] = cq[2] = 0.0;
+        double T[16], fit = 0.0, rmse = 0.0;
+        int done = 0;
+        if (!icp_point2point(*src, *ref, max_distance, T0, relative_fitness, relative_rmse, max_iteration, cp0, cq, T, &fit, &rmse, &done)) return -1;
+        if (T_out) memcpy(T_out, T, sizeof(T));
+        if (fitness) *fitness = fit;
+        if (inlier_rmse) *inlier_rmse = rmse;
+        if (iterations) *iterations = done;
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // reference python/cwipc/registration/util.py:146-229: the floor and tile helpers (kernels_floor.hip)
 // ---------------------------------------------------------------------------
 namespace {

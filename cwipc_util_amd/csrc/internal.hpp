@@ -315,7 +315,7 @@ void count_alloc();
 void count_dealloc();
 
 // ---------------------------------------------------------------------------
-// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip;
+// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip, kernels_icp.hip;
 // the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
@@ -453,6 +453,21 @@ bool nn_distance2(const DeviceSoA &source, const DeviceSoA &reference, int nth, 
 // 1-D Gaussian kernel density estimate (kernels_kde.hip): density[j] = sum_i exp(-0.5 ((at[j] - samples[i]) / h)^2) / (n h sqrt(2 pi)),
 // all arrays device memory.  No wait inside.
 bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);
+
+// Point-to-point ICP (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All three wait
+// for their results.  False on failure (logged), also for a max_distance that is NaN or <= 0 and a matrix that is not finite.
+// Per source point the original index of its nearest reference point and the squared distance (0xFFFFFFFF / +inf: none) into host arrays, either may be nullptr.
+bool icp_correspondences(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, uint32_t *idx_host,
+                         double *d2_host);
+// One search and the fit sums over its matches: sums = sum a (3) | sum b (3) | sum a b^T (9) | sum d2, a = T p - cp, b = q - cq.
+bool icp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const double cp[3], const double cq[3],
+              uint64_t *n, double sums[16]);
+// open3d's registration_icp with the point-to-point estimate; cp0, cq: the clouds' centroids (the pivots: T cp0 and cq).
+bool icp_point2point(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], double relative_fitness,
+                     double relative_rmse, int max_iteration, const double cp0[3], const double cq[3], double T_out[16], double *fitness,
+                     double *inlier_rmse, int *iterations);
+// the mean of a cloud's points (the direction filter's centroid kernels) on the host; non-finite where a coordinate is
+bool icp_centroid(const DeviceSoA &cloud, double cen[3]);
 
 // Generic stable compaction driver used by tilefilter / crop / masked filter.
 // may_return_early: the call may come back with the scatter kernel still running (the result carries a

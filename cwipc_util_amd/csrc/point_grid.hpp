@@ -2,7 +2,8 @@
 //
 // kernels_grid.hip builds the grid (grid_and_search: a counting sort of the points into cells, three flows) and calls the
 // client's search on it; the clients are the outlier filter's k-NN (kernels_sor.hip), the direction filter's normals
-// (kernels_direction.hip) and the registration analyzer's cross-cloud distances (kernels_nn.hip).  The device helpers below are
+// (kernels_direction.hip), the registration analyzer's cross-cloud distances (kernels_nn.hip) and the ICP correspondences
+// (kernels_icp.hip).  The device helpers below are
 // the parts of a shell search that those kernels share: which slot of a device-decided grid to read, a row of cells as one range
 // of sorted points, the candidate scan, FLANN's fp32 distance, the sorted register list, the bounds that turn rows away, and the
 // walk over a shell of cells.  All of them are inlined into the kernel that uses them.

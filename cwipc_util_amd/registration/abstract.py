@@ -7,7 +7,7 @@ import numpy
 
 from ..util import cwipc_pointcloud_wrapper
 
-__all__ = ['AnalysisResults', 'AnalysisAlgorithm']
+__all__ = ['AnalysisResults', 'AnalysisAlgorithm', 'OverlapAnalysisResults']
 
 
 class AnalysisResults:
@@ -43,6 +43,20 @@ class AnalysisResults:
             if value is not None:
                 parts.append(f"{name}={value:.4f}")
         return ", ".join(parts)
+
+
+class OverlapAnalysisResults:
+    """What the overlap analyzer found out about one pair of clouds."""
+
+    def __init__(self) -> None:
+        #: matched source points / source points: higher is better
+        self.fitness: float = 0.0
+        #: root mean square of the matched points' distances: lower is better
+        self.rmse: float = 0.0
+        self.sourcePointCount: int = 0
+        self.referencePointCount: int = 0
+        self.tilemask: Optional[int] = None
+        self.referenceTilemask: Optional[int] = None
 
 
 class AnalysisAlgorithm(ABC):

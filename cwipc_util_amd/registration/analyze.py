@@ -11,7 +11,9 @@ Where it runs: the clouds stay on the device (tile mask and floor filter are dev
 reductions over them -- mean, std, median, trimmed mean, percentile, count -- are numpy on the host on purpose: the array is bit for
 bit the one the reference gets from scipy's KD-tree, so the same numpy calls give the same numbers.  scipy is not needed.
 
-Not here: OverlapAnalyzer (open3d's evaluate_registration), the reference's third analyzer.
+OverlapAnalyzer, the reference's third analyzer (open3d's evaluate_registration there), is one correspondence search and two sums
+on the device (cwipc_hip_icp_sums at the identity): the fraction of source points with a reference point within the
+correspondence, and the root mean square of their distances.
 """
 import math
 from typing import Any, List, Optional, Tuple
@@ -19,11 +21,11 @@ from typing import Any, List, Optional, Tuple
 import numpy as np
 
 from ..util import (cwipc_pointcloud_wrapper, cwipc_tilefilter_masked, cwipc_crop, cwipc_hip_nn_distance,
-                    cwipc_hip_gaussian_kde)
-from .abstract import AnalysisAlgorithm, AnalysisResults
+                    cwipc_hip_gaussian_kde, cwipc_hip_icp_sums)
+from .abstract import AnalysisAlgorithm, AnalysisResults, OverlapAnalysisResults
 
-__all__ = ['RegistrationAnalyzer', 'RegistrationAnalyzerSymmetric', 'DEFAULT_ANALYZER_ALGORITHM', 'ALL_ANALYZER_ALGORITHMS',
-           'trim_mean', 'FLOOR_Y']
+__all__ = ['RegistrationAnalyzer', 'RegistrationAnalyzerSymmetric', 'OverlapAnalyzer', 'DEFAULT_ANALYZER_ALGORITHM',
+           'ALL_ANALYZER_ALGORITHMS', 'trim_mean', 'FLOOR_Y']
 
 #: the floor filter keeps a point iff its float32 y > 0.1
 FLOOR_Y = 0.1
@@ -270,6 +272,56 @@ class RegistrationAnalyzerSymmetric(_BaseRegistrationAnalyzer):
         return True
 
 
+class OverlapAnalyzer:
+    """How much of the source cloud overlaps the reference cloud: fitness = the fraction of source points that have a reference
+    point closer than the correspondence, rmse = the root mean square of those points' distances to their nearest reference point."""
+
+    def __init__(self) -> None:
+        self._source_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self._reference_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self.source_tilemask: Optional[int] = None
+        self.reference_tilemask: Optional[int] = None
+        self.verbose = False
+        self.correspondence: float = np.inf
+        self.results: Optional[OverlapAnalysisResults] = None
+
+    def _masked(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int]) -> cwipc_pointcloud_wrapper:
+        return cwipc_tilefilter_masked(pc, tilemask) if tilemask else pc
+
+    def set_source_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
+        self._source_pointcloud = self._masked(pc, tilemask)
+        self.source_tilemask = tilemask
+
+    def set_reference_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
+        self._reference_pointcloud = self._masked(pc, tilemask)
+        self.reference_tilemask = tilemask
+
+    def set_correspondence(self, correspondence: float) -> None:
+        """The largest distance between two points that still counts as a match."""
+        self.correspondence = correspondence
+
+    def run(self) -> bool:
+        assert self._source_pointcloud is not None and self._reference_pointcloud is not None
+        source, reference = self._source_pointcloud, self._reference_pointcloud
+        count = source.count()
+        n, sums = cwipc_hip_icp_sums(source, reference, None, self.correspondence)
+        r = OverlapAnalysisResults()
+        r.fitness = n / count if count else 0.0
+        r.rmse = math.sqrt(sums[15] / n) if n else 0.0
+        r.sourcePointCount = count
+        r.referencePointCount = reference.count()
+        r.tilemask = self.source_tilemask
+        r.referenceTilemask = self.reference_tilemask
+        self.results = r
+        if self.verbose:
+            print(f"{self.__class__.__name__}: fitness={r.fitness}, rmse={r.rmse}, {n} of {count} points")
+        return True
+
+    def get_results(self) -> OverlapAnalysisResults:
+        assert self.results
+        return self.results
+
+
 DEFAULT_ANALYZER_ALGORITHM = RegistrationAnalyzerSymmetric
 
-ALL_ANALYZER_ALGORITHMS = [RegistrationAnalyzer, RegistrationAnalyzerSymmetric]
+ALL_ANALYZER_ALGORITHMS = [RegistrationAnalyzer, RegistrationAnalyzerSymmetric, OverlapAnalyzer]

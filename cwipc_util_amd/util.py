@@ -44,6 +44,7 @@ __all__ = [
     'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
+    'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point',
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
@@ -227,6 +228,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_direction_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_float, _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_estimate_normals': ([cwipc_pointcloud_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_correspondences': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_icp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_icp_point2point': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                   _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
@@ -1241,6 +1246,73 @@ def cwipc_hip_nn_distance(source: cwipc_pointcloud_wrapper, reference: cwipc_poi
     if rc != 0:
         raise CwipcError("cwipc_hip_nn_distance2 failed")
     return numpy.sqrt(out[:n])
+
+
+def _matrix4(name: str, transform: Any) -> Optional[numpy.ndarray]:
+    """None, or the 4x4 as contiguous float64 (the caller keeps it alive over the call)."""
+    if transform is None:
+        return None
+    m = numpy.ascontiguousarray(numpy.asarray(transform, dtype=numpy.float64))
+    if m.shape != (4, 4):
+        raise ValueError(f"{name}: transform must be a 4x4 matrix")
+    return m
+
+
+def _p(a: Optional[numpy.ndarray]) -> Optional[int]:
+    return None if a is None else a.ctypes.data
+
+
+def cwipc_hip_correspondences(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, transform: Any = None,
+                              max_distance: float = float('inf')) -> Tuple[numpy.ndarray, numpy.ndarray]:
+    """Per point of `source`, moved by the 4x4 `transform` (None: the identity) in f64, the index of its nearest point of `reference`
+    (uint32, 0xFFFFFFFF: none) and the squared f64 distance (inf: none), among the reference points strictly closer than
+    max_distance; among equally distant ones the smallest index.  The search of one ICP iteration, on the GPU."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_correspondences: NULL pointcloud")
+    m = _matrix4('cwipc_hip_correspondences', transform)
+    n = source.count()
+    idx = numpy.zeros(max(n, 1), dtype=numpy.uint32)
+    d2 = numpy.zeros(max(n, 1), dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_correspondences(source.as_cwipc_p(), reference.as_cwipc_p(), _p(m), float(max_distance), idx.ctypes.data, d2.ctypes.data,
+                                                         idx.size)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_correspondences failed")
+    return idx[:n], d2[:n]
+
+
+def cwipc_hip_icp_sums(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, transform: Any = None, max_distance: float = float('inf'),
+                       cp: Any = None, cq: Any = None) -> Tuple[int, numpy.ndarray]:
+    """One correspondence search and the sums of a rigid fit over the matched pairs, nothing per point leaves the device: (n, sums)
+    with sums = sum a (3) | sum b (3) | sum a b^T (9) | sum d2, a = moved source point - cp, b = matched reference point - cq
+    (None: no pivot).  With the identity, n / count(source) and sqrt(sums[15] / n) are open3d's evaluate_registration."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_sums: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_sums', transform)
+    pivots = [None if v is None else numpy.ascontiguousarray(numpy.asarray(v, dtype=numpy.float64).reshape(3)) for v in (cp, cq)]
+    n = ctypes.c_uint64(0)
+    sums = numpy.zeros(16, dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_sums(source.as_cwipc_p(), reference.as_cwipc_p(), _p(m), float(max_distance), _p(pivots[0]), _p(pivots[1]),
+                                                  ctypes.addressof(n), sums.ctypes.data)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_sums failed")
+    return int(n.value), sums
+
+
+def cwipc_hip_icp_point2point(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, max_distance: float, init: Any = None,
+                              relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_iteration: int = 30) -> Tuple[numpy.ndarray, float, float, int]:
+    """open3d's registration_icp with the point-to-point estimate, on the GPU: (transformation 4x4 float64, fitness, inlier_rmse,
+    iterations done).  The defaults are open3d's ICPConvergenceCriteria."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_point2point: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_point2point', init)
+    T = numpy.zeros((4, 4), dtype=numpy.float64)
+    fitness, rmse, iterations = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_point2point(source.as_cwipc_p(), reference.as_cwipc_p(), float(max_distance), _p(m), float(relative_fitness),
+                                                         float(relative_rmse), int(max_iteration), T.ctypes.data, ctypes.addressof(fitness),
+                                                         ctypes.addressof(rmse), ctypes.addressof(iterations))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_point2point failed")
+    return T, float(fitness.value), float(rmse.value), int(iterations.value)
 
 
 def cwipc_hip_gaussian_kde(samples: Any, at: Any, bw_method: Union[None, str, float] = None) -> numpy.ndarray:

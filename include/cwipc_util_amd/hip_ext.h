@@ -179,6 +179,35 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_nn_distance2(cwipc_pointcloud *source, cwipc_po
  * arrays: n samples, m evaluation points, m densities.  0 ok; -1 (logged) for n == 0, h not finite or <= 0, a NULL array. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_gaussian_kde(const double *samples, size_t n, double h, const double *at, size_t m, double *density);
 
+/* ---- point-to-point ICP (reference python/cwipc/registration/fine.py, and analyze.py's OverlapAnalyzer: open3d's registration_icp
+ * and evaluate_registration) ----
+ * Matrices are 16 doubles, a row-major 4x4 whose last row is taken for (0, 0, 0, 1).  A source point (x, y, z) is moved in f64:
+ * px = ((T00*x + T01*y) + T02*z) + T03 (py, pz alike), every operation rounded on its own.  Its correspondence is the reference point
+ * with the smallest d2 = (dx*dx + dy*dy) + dz*dz, dx = px - (double)qx, among those with d2 < max_distance^2 (strictly; INFINITY: no
+ * bound); among equal d2 the smallest index.  A source point with a non-finite coordinate (before or after T) has none; a reference
+ * point with a non-finite coordinate is never one.  The clouds are neither consumed nor changed.  All three return 0, or -1 (logged)
+ * for a NULL cloud, max_distance NaN or <= 0, a matrix that is not finite. */
+/* idx[i] = index of source point i's correspondence in the reference (0xFFFFFFFF: none), dist2[i] = its d2 (+inf: none); host arrays
+ * of cap >= count(source) entries, either may be NULL.  T NULL: the identity.  An empty reference gives none everywhere, an empty
+ * source writes nothing.  -1 also for a cap that is too small. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_correspondences(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                                                 uint32_t *idx, double *dist2, size_t cap);
+/* One search and the sums of a rigid fit over the source points that have a correspondence, nothing per point leaves the device:
+ * with a = p - cp (p the moved source point) and b = q - cq (q its correspondence), *n = their number and
+ * sums = sum a (3) | sum b (3) | sum a b^T (9, row-major a_i b_j) | sum d2, in f64, summed in an order fixed by count(source): the
+ * same clouds give the same bytes.  T, cp, cq NULL: the identity, (0, 0, 0).  n and sums may be NULL.  With T the identity, n / count(source)
+ * and sqrt(sums[15] / n) are the fitness and inlier_rmse of open3d's evaluate_registration. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                                          const double *cp, const double *cq, uint64_t *n, double *sums);
+/* open3d's registration_icp with TransformationEstimationPointToPoint: evaluate at T = init (NULL: the identity); without a
+ * correspondence return init, fitness 0, rmse 0; else up to max_iteration times: update = the rigid fit (umeyama without scaling) of
+ * the correspondences, T = update * T, evaluate again, stop when |fitness change| < relative_fitness and |rmse change| < relative_rmse.
+ * fitness = n / count(source), inlier_rmse = sqrt(sum d2 / n).  T is applied to the original float32 source points in every
+ * iteration (open3d moves an f64 copy of the cloud step by step).  The outputs may be NULL.  -1 also for max_iteration < 0. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_point2point(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
+                                                 double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
+                                                 double *inlier_rmse, int *iterations);
+
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
