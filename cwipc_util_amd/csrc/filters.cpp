@@ -863,6 +863,61 @@ extern "C" int cwipc_hip_icp_point2point(cwipc_pointcloud *source, cwipc_pointcl
     }
 }
 
+extern "C" int cwipc_hip_icp_plane_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, const float *normals,
+                                        float radius, int max_nn, uint64_t *n, double *sums) {
+    const char *who = "cwipc_hip_icp_plane_sums";
+    if (n) *n = 0;
+    if (sums) for (int v = 0; v < 29; v++) sums[v] = 0.0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
+        uint64_t hn = 0;
+        double hs[29];
+        if (!icp_plane_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, normals, radius, max_nn, &hn, hs)) return -1;
+        if (n) *n = hn;
+        if (sums) memcpy(sums, hs, sizeof(hs));
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+extern "C" int cwipc_hip_icp_point2plane(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init, const float *normals,
+                                         float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double *T_out,
+                                         double *fitness, double *inlier_rmse, int *iterations) {
+    const char *who = "cwipc_hip_icp_point2plane";
+    const double *T0 = init ? init : ICP_IDENTITY;
+    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
+    if (fitness) *fitness = 0.0;
+    if (inlier_rmse) *inlier_rmse = 0.0;
+    if (iterations) *iterations = 0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
+        if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
+            return -1;
+        }
+        double T[16], fit = 0.0, rmse = 0.0;
+        int done = 0;
+        if (!icp_point2plane(*src, *ref, max_distance, T0, normals, radius, max_nn, relative_fitness, relative_rmse, max_iteration, T, &fit, &rmse, &done))
+            return -1;
+        if (T_out) memcpy(T_out, T, sizeof(T));
+        if (fitness) *fitness = fit;
+        if (inlier_rmse) *inlier_rmse = rmse;
+        if (iterations) *iterations = done;
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // reference python/cwipc/registration/util.py:146-229: the floor and tile helpers (kernels_floor.hip)
 // ---------------------------------------------------------------------------

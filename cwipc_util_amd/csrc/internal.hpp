@@ -454,7 +454,7 @@ bool nn_distance2(const DeviceSoA &source, const DeviceSoA &reference, int nth, 
 // all arrays device memory.  No wait inside.
 bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);
 
-// Point-to-point ICP (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All three wait
+// Point-to-point ICP (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All of them wait
 // for their results.  False on failure (logged), also for a max_distance that is NaN or <= 0 and a matrix that is not finite.
 // Per source point the original index of its nearest reference point and the squared distance (0xFFFFFFFF / +inf: none) into host arrays, either may be nullptr.
 bool icp_correspondences(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, uint32_t *idx_host,
@@ -465,6 +465,16 @@ bool icp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double 
 // open3d's registration_icp with the point-to-point estimate; cp0, cq: the clouds' centroids (the pivots: T cp0 and cq).
 bool icp_point2point(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], double relative_fitness,
                      double relative_rmse, int max_iteration, const double cp0[3], const double cq[3], double T_out[16], double *fitness,
+                     double *inlier_rmse, int *iterations);
+// Point-to-plane ICP (the same file).  host_normals: the reference cloud's normals as three planes of reference.npoints floats (x, y,
+// z) in host memory, or nullptr: direction_normals(radius, max_nn) estimates them on the device.  False also for a caller's normal
+// that is not finite and, without caller's normals, for a radius or max_nn that direction_normals turns away.
+// sums = sum J J^T (21, upper triangle row-major) | sum J r (6) | sum r^2 | sum d2.
+bool icp_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *host_normals, float radius,
+                    int max_nn, uint64_t *n, double sums[29]);
+// open3d's registration_icp with the point-to-plane estimate (plane_fit.hpp).
+bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *host_normals,
+                     float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double T_out[16], double *fitness,
                      double *inlier_rmse, int *iterations);
 // the mean of a cloud's points (the direction filter's centroid kernels) on the host; non-finite where a coordinate is
 bool icp_centroid(const DeviceSoA &cloud, double cen[3]);

@@ -1,5 +1,5 @@
-// kernels_icp.hip -- point-to-point ICP on gfx950: correspondences, the sums of a rigid fit, the loop (registration/fine.py and
-// the overlap analyzer of registration/analyze.py).
+// kernels_icp.hip -- point-to-point and point-to-plane ICP on gfx950: correspondences, the sums of a rigid fit and of a plane fit,
+// the loops (registration/fine.py and the overlap analyzer of registration/analyze.py).
 //
 // Reference: python/cwipc/registration/fine.py and analyze.py (OverlapAnalyzer), which call open3d's registration_icp with
 // TransformationEstimationPointToPoint and evaluate_registration on the CPU.  Three layers, each with a contract of its own:
@@ -30,8 +30,31 @@
 //
 // The loop (icp_point2point) is open3d's registration_icp; it runs inside ONE GridSearch hook, so the grid over the reference is
 // built once per run.  T is applied to the ORIGINAL float32 source points on every iteration (open3d moves an f64 copy step by step).
+//
+// POINT-TO-PLANE (icp_plane_sums_partial_kernel, icp_plane_sums_final_kernel, icp_point2plane).  open3d is not on this stack, so
+// nothing is compared with it: this is a restatement of open3d's TransformationEstimationPointToPlane inside registration_icp,
+// pinned by a numpy model (tests/icp_plane_model.py).  Correspondences are exactly those above: the same kernel, the same tie
+// rule, the same strict bound.  For a matched pair, every operation rounded on its own:
+//     p = the moved source point (icp_move),  q = the matched reference point,  m = that reference point's normal
+//                                                                               (q and m: (double) of float32)
+//     e = p - q,   r = (e0*m0 + e1*m1) + e2*m2
+//     c = p x m:   c0 = p1*m2 - p2*m1,  c1 = p2*m0 - p0*m2,  c2 = p0*m1 - p1*m0
+//     J = (c0, c1, c2, m0, m1, m2)
+// No pivots: this is open3d's form.  The sums, in this order:
+//     n | sum J_i J_j for i <= j (21, the upper triangle row-major) | sum J_i r (6) | sum r^2 | sum d2          (f64)
+// 29 doubles and n; with the tag 31 of the 32 pinned 64-bit words a thread has.  They are summed by the scheme of the fit sums
+// above (the same chunks, four points per lane and step, the same trees), so two calls give the same bytes.  Negating a normal
+// negates J and r exactly and leaves every term's bits as they are: the reference's _fix_normal_direction has no effect on this
+// aligner and is not ported.
+//   The normals are float planes in pool memory (x, y, z, each count(reference) long), gathered by idx like the reference's
+// coordinates: direction_normals (kernels_direction.hip) writes them there once per run, before the grid hook -- open3d's
+// KDTreeSearchParamHybrid(radius, max_nn) estimate -- or the caller's are copied there.  Only the reference cloud has normals:
+// open3d's point-to-plane estimate never reads the source's.
+//   The loop (icp_point2plane) is the loop above with the update of plane_fit.hpp: A x = -b with A = sum J J^T, b = sum J r;
+// fitness and inlier_rmse come from n and sum d2 (the point distances, not r), and the stop rule is the same.
 #include "point_grid.hpp"
 #include "rigid_fit.hpp"
+#include "plane_fit.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -255,6 +278,85 @@ __global__ void __launch_bounds__(ICP_FINAL_THREADS) icp_sums_final_kernel(const
     }
 }
 
+// ---- the sums of a plane fit (the contract is at the top of the file) ----
+constexpr int ICP_PLANE_NSUM = 30;        // n, sum J J^T (21), sum J r (6), sum r^2, sum d2
+
+struct IcpPlaneSumArgs {
+    const float *sx, *sy, *sz;   // as IcpSumArgs
+    size_t ns;
+    const uint32_t *idx;
+    const double *d2;
+    const float *rx, *ry, *rz;   // the reference cloud's planes
+    const float *mx, *my, *mz;   // its normals' planes, in the same order
+    size_t nr;
+    double T[12];
+    size_t chunk;
+};
+
+__global__ void __launch_bounds__(GRID_BLK) icp_plane_sums_partial_kernel(IcpPlaneSumArgs A, double *__restrict__ partial /* [chunks][ICP_PLANE_NSUM] */) {
+    __shared__ double red[GRID_BLK / 64][ICP_PLANE_NSUM];
+    const size_t lo = (size_t)blockIdx.x * A.chunk, hi = lo + A.chunk < A.ns ? lo + A.chunk : A.ns;
+    double s[ICP_PLANE_NSUM];
+#pragma unroll
+    for (int v = 0; v < ICP_PLANE_NSUM; v++) s[v] = 0.0;
+    for (size_t base = lo + 4 * (size_t)threadIdx.x; base < hi; base += 4 * (size_t)GRID_BLK) {
+        const float4 x4 = *reinterpret_cast<const float4 *>(A.sx + base), y4 = *reinterpret_cast<const float4 *>(A.sy + base),
+                     z4 = *reinterpret_cast<const float4 *>(A.sz + base);
+        const uint4 i4 = *reinterpret_cast<const uint4 *>(A.idx + base);
+        const double2 da = *reinterpret_cast<const double2 *>(A.d2 + base), db = *reinterpret_cast<const double2 *>(A.d2 + base + 2);
+        const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
+        const uint32_t is[4] = {i4.x, i4.y, i4.z, i4.w};
+        const double ds[4] = {da.x, da.y, db.x, db.y};
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            // (idx is checked against the reference count before it is an address; ICP_NONE fails the test too)
+            if (base + u >= hi || (size_t)is[u] >= A.nr) continue;
+            double p[3];
+            icp_move(A.T, xs[u], ys[u], zs[u], p);
+            const double q[3] = {(double)A.rx[is[u]], (double)A.ry[is[u]], (double)A.rz[is[u]]};
+            const double m[3] = {(double)A.mx[is[u]], (double)A.my[is[u]], (double)A.mz[is[u]]};
+            const double e[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+            const double r = (e[0] * m[0] + e[1] * m[1]) + e[2] * m[2];
+            const double J[6] = {p[1] * m[2] - p[2] * m[1], p[2] * m[0] - p[0] * m[2], p[0] * m[1] - p[1] * m[0], m[0], m[1], m[2]};
+            s[0] += 1.0;   // (a count below 2^53 is exact in f64)
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = i; j < 6; j++) s[1 + (i * (11 - i)) / 2 + j] += J[i] * J[j];   // (row i of the triangle begins at i (13 - i) / 2)
+#pragma unroll
+            for (int i = 0; i < 6; i++) s[22 + i] += J[i] * r;
+            s[28] += r * r;
+            s[29] += ds[u];
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < ICP_PLANE_NSUM; v++) {
+        for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][v] = s[v];
+    }
+    __syncthreads();
+    if (threadIdx.x < ICP_PLANE_NSUM) {
+        double t = 0.0;
+        for (int w = 0; w < GRID_BLK / 64; w++) t += red[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * ICP_PLANE_NSUM + threadIdx.x] = t;
+    }
+}
+
+// out: 31 pinned 64-bit words -- n as an integer, the 29 sums, the tag
+__global__ void __launch_bounds__(ICP_FINAL_THREADS) icp_plane_sums_final_kernel(const double *__restrict__ partial, size_t nchunks,
+                                                                                unsigned long long *__restrict__ out, unsigned long long tag) {
+    const int v = threadIdx.x;
+    if (v >= ICP_PLANE_NSUM) return;
+    double acc = 0.0;
+    for (size_t c = 0; c < nchunks; c++) acc += partial[c * ICP_PLANE_NSUM + v];
+    if (v == 0) {
+        out[0] = (unsigned long long)acc;
+        out[ICP_PLANE_NSUM] = tag;
+    } else {
+        out[v] = (unsigned long long)__double_as_longlong(acc);
+    }
+}
+
 // Device memory of one search: d2 | idx | partial sums, one pool block.
 struct IcpWork {
     char *block = nullptr;
@@ -262,13 +364,13 @@ struct IcpWork {
     double *d2 = nullptr;
     double *partial = nullptr;
     size_t chunk = 0, nchunks = 0;
-    bool alloc(size_t ns) {
+    bool alloc(size_t ns, int nsum = ICP_NSUM) {   // nsum: values per chunk in `partial`
         chunk = ICP_CHUNK;
         while ((ns + chunk - 1) / chunk > ICP_MAX_CHUNKS) chunk <<= 1;
         nchunks = (ns + chunk - 1) / chunk;
         const size_t padded = (ns + 255) & ~(size_t)255;
         const size_t idx_bytes = padded * sizeof(uint32_t), d2_bytes = padded * sizeof(double);
-        block = (char *)pool_alloc(idx_bytes + d2_bytes + nchunks * ICP_NSUM * sizeof(double));
+        block = (char *)pool_alloc(idx_bytes + d2_bytes + nchunks * (size_t)nsum * sizeof(double));
         if (!block) return false;
         d2 = (double *)block;   // (both arrays start on a 1 KiB boundary of the block: 16-byte loads)
         idx = (uint32_t *)(block + d2_bytes);
@@ -471,6 +573,183 @@ bool icp_point2point(const DeviceSoA &source, const DeviceSoA &reference, double
         return true;
     };
     bool ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
+    ok = c.sync() && ok;
+    return ok && loop_ok;
+}
+
+// ---- point-to-plane: the host side ----
+namespace {
+
+void launch_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const float *normals, const double T[16], const IcpWork &w, ThreadCtx &c,
+                       uint32_t tag, hipStream_t s) {
+    IcpPlaneSumArgs S{};
+    S.sx = source.x(); S.sy = source.y(); S.sz = source.z();
+    S.ns = source.npoints;
+    S.idx = w.idx;
+    S.d2 = w.d2;
+    S.rx = reference.x(); S.ry = reference.y(); S.rz = reference.z();
+    S.nr = reference.npoints;
+    S.mx = normals; S.my = normals + S.nr; S.mz = normals + 2 * S.nr;
+    for (int i = 0; i < 12; i++) S.T[i] = T[i];
+    S.chunk = w.chunk;
+    CW_LAUNCH("icp_plane_sums_partial", icp_plane_sums_partial_kernel, dim3((unsigned)w.nchunks), dim3(GRID_BLK), 0, s, S, w.partial);
+    CW_LAUNCH("icp_plane_sums_final", icp_plane_sums_final_kernel, dim3(1), dim3(ICP_FINAL_THREADS), 0, s, w.partial, w.nchunks,
+              reinterpret_cast<unsigned long long *>(c.host_words), (unsigned long long)tag);
+}
+
+bool read_plane_sums(ThreadCtx &c, uint32_t tag, uint64_t *n, double sums[29]) {
+    const volatile unsigned long long *words = reinterpret_cast<const volatile unsigned long long *>(c.host_words);
+    if (words[ICP_PLANE_NSUM] != (unsigned long long)tag) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip_icp", "the plane sums kernel did not report");
+        return false;
+    }
+    *n = words[0];
+    for (int v = 0; v < ICP_PLANE_NSUM - 1; v++) {
+        const unsigned long long bits = words[1 + v];
+        memcpy(&sums[v], &bits, sizeof(double));
+    }
+    return true;
+}
+
+uint32_t next_plane_tag(ThreadCtx &c) {
+    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    words[ICP_PLANE_NSUM] = 0ull;
+    return ++c.tag ? c.tag : ++c.tag;
+}
+
+// The reference cloud's normals as three planes of count(reference) floats in one pool block (and, behind them, the three doubles
+// direction_normals wants for its centroid): the caller's, copied, or estimated there.  On the calling thread's stream, no wait.
+struct IcpNormals {
+    float *planes = nullptr;
+    bool make(const char *who, const DeviceSoA &reference, const float *host_normals, float radius, int max_nn, ThreadCtx &c) {
+        const size_t nr = reference.npoints;
+        const size_t cen_at = (3 * nr * sizeof(float) + 127) & ~(size_t)127;
+        planes = (float *)pool_alloc(cen_at + 3 * sizeof(double));
+        if (!planes) return false;
+        if (host_normals) {
+            for (size_t i = 0; i < 3 * nr; i++)
+                if (!std::isfinite(host_normals[i])) {
+                    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the normals must be finite");
+                    return false;
+                }
+            return hipMemcpyAsync(planes, host_normals, 3 * nr * sizeof(float), hipMemcpyHostToDevice, c.stream) == hipSuccess;
+        }
+        const double zero[3] = {0, 0, 0};
+        double *cen = reinterpret_cast<double *>(reinterpret_cast<char *>(planes) + cen_at);
+        return direction_normals(reference, radius, max_nn, zero, 0.0, nullptr, planes, nr, nullptr, cen);
+    }
+    ~IcpNormals() { pool_free(planes); }   // (the owner has waited for the stream)
+};
+
+bool plane_args_ok(const char *who, const float *host_normals, float radius, int max_nn) {
+    if (host_normals || (radius > 0.f && std::isfinite(radius) && max_nn >= 1 && max_nn <= DIRECTION_MAX_NN)) return true;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "radius must be positive and finite, max_nn between 1 and 128");
+    return false;
+}
+
+}  // namespace
+
+bool icp_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *host_normals, float radius,
+                    int max_nn, uint64_t *n, double sums[29]) {
+    const char *who = "cwipc_hip_icp_plane_sums";
+    *n = 0;
+    for (int v = 0; v < 29; v++) sums[v] = 0.0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (!icp_args_ok(who, T, max_distance) || !plane_args_ok(who, host_normals, radius, max_nn)) return false;
+    const size_t ns = source.npoints;
+    if (reference.npoints == 0) return true;
+    IcpNormals normals;
+    IcpWork w;
+    // (the caller's normals are looked at even when there is nothing to match them with: a bad array is an error either way)
+    bool ok = normals.make(who, reference, host_normals, radius, max_nn, c);
+    if (ok && ns != 0) ok = w.alloc(ns, ICP_PLANE_NSUM);
+    if (!ok || ns == 0) return c.sync() && ok;   // (a wait also on failure: kernels that write the blocks may still be in flight)
+    const IcpArgs A = correspond_args(source, T, max_distance, w);
+    const uint32_t tag = next_plane_tag(c);
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        launch_correspond(v, A, s);
+        launch_plane_sums(source, reference, normals.planes, T, w, c, tag, s);
+        return hipGetLastError() == hipSuccess;
+    };
+    ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
+    ok = c.sync() && ok;
+    return ok && read_plane_sums(c, tag, n, sums);
+}
+
+bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *host_normals,
+                     float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double T_out[16], double *fitness,
+                     double *inlier_rmse, int *iterations) {
+    const char *who = "cwipc_hip_icp_point2plane";
+    for (int i = 0; i < 16; i++) T_out[i] = init[i];
+    *fitness = 0.0;
+    *inlier_rmse = 0.0;
+    *iterations = 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (!icp_args_ok(who, init, max_distance) || !plane_args_ok(who, host_normals, radius, max_nn)) return false;
+    if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
+        return false;
+    }
+    const size_t ns = source.npoints;
+    if (reference.npoints == 0) return true;
+    IcpNormals normals;
+    IcpWork w;
+    // the normals, once per run and before the grid hook: direction_normals builds a grid of its own width
+    bool ok = normals.make(who, reference, host_normals, radius, max_nn, c);
+    if (ok && ns != 0) ok = w.alloc(ns, ICP_PLANE_NSUM);
+    if (!ok || ns == 0) return c.sync() && ok;
+    bool loop_ok = true;
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        double T[16];
+        for (int i = 0; i < 16; i++) T[i] = init[i];
+        // one evaluation: search, sums, wait, read
+        uint64_t n = 0;
+        double sums[29];
+        auto evaluate = [&]() {
+            const IcpArgs A = correspond_args(source, T, max_distance, w);
+            const uint32_t tag = next_plane_tag(c);
+            launch_correspond(v, A, s);
+            launch_plane_sums(source, reference, normals.planes, T, w, c, tag, s);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+            return read_plane_sums(c, tag, &n, sums);
+        };
+        auto measures = [&](double &fit, double &rmse) {
+            fit = n ? (double)n / (double)ns : 0.0;
+            rmse = n ? sqrt(sums[28] / (double)n) : 0.0;
+        };
+        if (!evaluate()) return loop_ok = false;
+        double fit, rmse;
+        measures(fit, rmse);
+        int done = 0;
+        if (n != 0) {
+            for (int it = 0; it < max_iteration; it++) {
+                double R[3][3], t[3];
+                plane_fit(sums, sums + 21, R, t);
+                double U[16] = {R[0][0], R[0][1], R[0][2], t[0], R[1][0], R[1][1], R[1][2], t[1], R[2][0], R[2][1], R[2][2], t[2], 0, 0, 0, 1}, N[16];
+                for (int i = 0; i < 4; i++)
+                    for (int j = 0; j < 4; j++) N[4 * i + j] = ((U[4 * i] * T[j] + U[4 * i + 1] * T[4 + j]) + U[4 * i + 2] * T[8 + j]) + U[4 * i + 3] * T[12 + j];
+                for (int i = 0; i < 16; i++) T[i] = N[i];
+                for (int i = 0; i < 16; i++)
+                    if (!std::isfinite(T[i])) {
+                        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the transformation is no longer finite");
+                        return loop_ok = false;
+                    }
+                const double fit_before = fit, rmse_before = rmse;
+                if (!evaluate()) return loop_ok = false;
+                measures(fit, rmse);
+                done = it + 1;
+                if (fabs(fit_before - fit) < relative_fitness && fabs(rmse_before - rmse) < relative_rmse) break;
+            }
+        }
+        for (int i = 0; i < 16; i++) T_out[i] = T[i];
+        *fitness = fit;
+        *inlier_rmse = rmse;
+        *iterations = done;
+        return true;
+    };
+    ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
     ok = c.sync() && ok;
     return ok && loop_ok;
 }

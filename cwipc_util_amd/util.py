@@ -44,7 +44,7 @@ __all__ = [
     'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
-    'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point',
+    'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
@@ -232,6 +232,9 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_icp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_icp_point2point': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_icp_plane_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_icp_point2plane': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_double, _c.c_double, _c.c_int,
+                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
@@ -1312,6 +1315,57 @@ def cwipc_hip_icp_point2point(source: cwipc_pointcloud_wrapper, reference: cwipc
                                                          ctypes.addressof(rmse), ctypes.addressof(iterations))
     if rc != 0:
         raise CwipcError("cwipc_hip_icp_point2point failed")
+    return T, float(fitness.value), float(rmse.value), int(iterations.value)
+
+
+def _normal_planes(name: str, normals: Any, reference: cwipc_pointcloud_wrapper) -> Optional[numpy.ndarray]:
+    """None, or the reference cloud's normals, given as (count, 3), as three contiguous float32 planes (the caller keeps them alive
+    over the call)."""
+    if normals is None:
+        return None
+    m = numpy.asarray(normals, dtype=numpy.float32)
+    if m.shape != (reference.count(), 3):
+        raise ValueError(f"{name}: normals must have the shape (count(reference), 3)")
+    return numpy.ascontiguousarray(m.T)
+
+
+def cwipc_hip_icp_plane_sums(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, transform: Any = None, max_distance: float = float('inf'),
+                             normals: Any = None, radius: float = 0.02, max_nn: int = 30) -> Tuple[int, numpy.ndarray]:
+    """One correspondence search and the sums of a point-to-plane fit over the matched pairs, nothing per point leaves the device:
+    (n, sums) with sums = sum J_i J_j for i <= j (21) | sum J_i r (6) | sum r^2 | sum d2, J = (p x m, m), r = (p - q) . m for the
+    moved source point p, its correspondence q and q's normal m.  normals: the reference cloud's, float32 (count(reference), 3) as
+    cwipc_hip_estimate_normals returns them, or None: estimated on the device with (radius, max_nn).  Their sign does not matter:
+    negating a normal leaves every term's bits unchanged (the reference's _fix_normal_direction has nothing to fix here)."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_plane_sums: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_plane_sums', transform)
+    planes = _normal_planes('cwipc_hip_icp_plane_sums', normals, reference)
+    n = ctypes.c_uint64(0)
+    sums = numpy.zeros(29, dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_plane_sums(source.as_cwipc_p(), reference.as_cwipc_p(), _p(m), float(max_distance), _p(planes), float(radius),
+                                                        int(max_nn), ctypes.addressof(n), sums.ctypes.data)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_plane_sums failed")
+    return int(n.value), sums
+
+
+def cwipc_hip_icp_point2plane(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, max_distance: float, init: Any = None,
+                              normals: Any = None, radius: float = 0.02, max_nn: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,
+                              max_iteration: int = 30) -> Tuple[numpy.ndarray, float, float, int]:
+    """open3d's registration_icp with the point-to-plane estimate, on the GPU: (transformation 4x4 float64, fitness, inlier_rmse,
+    iterations done).  normals, radius, max_nn as for cwipc_hip_icp_plane_sums: only the reference cloud has normals, estimated once
+    per run when none are given, and their orientation does not matter.  The criteria's defaults are open3d's."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_point2plane: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_point2plane', init)
+    planes = _normal_planes('cwipc_hip_icp_point2plane', normals, reference)
+    T = numpy.zeros((4, 4), dtype=numpy.float64)
+    fitness, rmse, iterations = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_point2plane(source.as_cwipc_p(), reference.as_cwipc_p(), float(max_distance), _p(m), _p(planes), float(radius),
+                                                         int(max_nn), float(relative_fitness), float(relative_rmse), int(max_iteration), T.ctypes.data,
+                                                         ctypes.addressof(fitness), ctypes.addressof(rmse), ctypes.addressof(iterations))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_point2plane failed")
     return T, float(fitness.value), float(rmse.value), int(iterations.value)
 
 

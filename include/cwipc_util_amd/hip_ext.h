@@ -208,6 +208,31 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_icp_point2point(cwipc_pointcloud *source, cwipc
                                                  double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
                                                  double *inlier_rmse, int *iterations);
 
+/* ---- point-to-plane ICP (reference python/cwipc/registration/fine.py: open3d's registration_icp with
+ * TransformationEstimationPointToPlane) ----
+ * open3d is not on this stack: the contract is a restatement of open3d's estimate, pinned by a numpy model.  Correspondences are
+ * exactly those of cwipc_hip_correspondences.  For a matched pair, every operation rounded on its own: p the moved source point,
+ * q the matched reference point, m that reference point's normal (q, m: (double) of float32), e = p - q,
+ * r = (e0*m0 + e1*m1) + e2*m2, c = p x m (c0 = p1*m2 - p2*m1, c1 = p2*m0 - p0*m2, c2 = p0*m1 - p1*m0), J = (c0, c1, c2, m0, m1, m2);
+ * no pivots.  Negating a normal leaves every term's bits unchanged: the orientation of the normals does not matter.
+ * normals: the REFERENCE cloud's, three planes of count(reference) floats, x then y then z (the layout cwipc_hip_estimate_normals
+ * writes, with cap = count(reference)), in host memory; NULL: estimated on the device as cwipc_hip_estimate_normals(radius, max_nn)
+ * does, once per call (open3d's KDTreeSearchParamHybrid; the reference uses 0.02 and 30).  The source's normals are never read.
+ * Errors as for the point-to-point entries; -1 also for a normal that is not finite and, with normals NULL, for radius <= 0 or not
+ * finite, max_nn < 1 or > 128. */
+/* One search and the sums of a plane fit: *n = the number of matched pairs,
+ * sums = sum J_i J_j for i <= j (21, the upper triangle row-major) | sum J_i r (6) | sum r^2 | sum d2, 29 doubles, summed in an order
+ * fixed by count(source): the same clouds give the same bytes.  T NULL: the identity.  n and sums may be NULL. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_plane_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                                                const float *normals, float radius, int max_nn, uint64_t *n, double *sums);
+/* cwipc_hip_icp_point2point's loop with the point-to-plane update: A x = -b with A = sum J J^T, b = sum J r, by LDL^T with diagonal
+ * pivoting in f64; the update is the identity when |det A| < 1e-6, a pivot is <= 0 or anything is not finite (open3d's check_det
+ * rule), else R = Rz(x2) Ry(x1) Rx(x0), t = (x3, x4, x5).  fitness = n / count(source), inlier_rmse = sqrt(sum d2 / n): from the
+ * point distances, not from r.  The same stop rule; T is applied to the original float32 source points in every iteration. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_point2plane(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
+                                                 const float *normals, float radius, int max_nn, double relative_fitness, double relative_rmse,
+                                                 int max_iteration, double *T_out, double *fitness, double *inlier_rmse, int *iterations);
+
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
