@@ -918,6 +918,88 @@ extern "C" int cwipc_hip_icp_point2plane(cwipc_pointcloud *source, cwipc_pointcl
     }
 }
 
+extern "C" int cwipc_hip_gicp_covariances(cwipc_pointcloud *pc, const float *normals, float radius, int max_nn, const double *direction, double epsilon,
+                                          double *cov, size_t cap) {
+    const char *who = "cwipc_hip_gicp_covariances";
+    try {
+        if (pc == nullptr) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+            return -1;
+        }
+        if (!(epsilon > 0.0) || !std::isfinite(epsilon)) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "epsilon must be positive and finite");
+            return -1;
+        }
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
+        std::unique_ptr<cwipc_hip_pointcloud> keep;
+        auto src = device_input(who, pc, keep);
+        if (!src) return -1;
+        const size_t n = src->npoints;
+        if (cap < n || (n && cov == nullptr)) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result array is too small");
+            return -1;
+        }
+        return icp_gicp_covariances(*src, normals, radius, max_nn, direction, epsilon, cov) ? 0 : -1;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+extern "C" int cwipc_hip_icp_gicp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                                       const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon, uint64_t *n,
+                                       double *sums) {
+    const char *who = "cwipc_hip_icp_gicp_sums";
+    if (n) *n = 0;
+    if (sums) for (int v = 0; v < 29; v++) sums[v] = 0.0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return -1;
+        uint64_t hn = 0;
+        double hs[29];
+        if (!icp_gicp_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, source_normals, reference_normals, radius, max_nn, epsilon, &hn, hs)) return -1;
+        if (n) *n = hn;
+        if (sums) memcpy(sums, hs, sizeof(hs));
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+extern "C" int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
+                                         const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon,
+                                         double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
+                                         double *inlier_rmse, int *iterations) {
+    const char *who = "cwipc_hip_icp_generalized";
+    const double *T0 = init ? init : ICP_IDENTITY;
+    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
+    if (fitness) *fitness = 0.0;
+    if (inlier_rmse) *inlier_rmse = 0.0;
+    if (iterations) *iterations = 0;
+    try {
+        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+        std::shared_ptr<DeviceSoA> src, ref;
+        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
+        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return -1;
+        double T[16], fit = 0.0, rmse = 0.0;
+        int done = 0;
+        if (!icp_generalized(*src, *ref, max_distance, T0, source_normals, reference_normals, radius, max_nn, epsilon, relative_fitness, relative_rmse,
+                             max_iteration, T, &fit, &rmse, &done))
+            return -1;
+        if (T_out) memcpy(T_out, T, sizeof(T));
+        if (fitness) *fitness = fit;
+        if (inlier_rmse) *inlier_rmse = rmse;
+        if (iterations) *iterations = done;
+        return 0;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // reference python/cwipc/registration/util.py:146-229: the floor and tile helpers (kernels_floor.hip)
 // ---------------------------------------------------------------------------

@@ -476,6 +476,20 @@ bool icp_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const d
 bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *host_normals,
                      float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double T_out[16], double *fitness,
                      double *inlier_rmse, int *iterations);
+// Generalized ICP (the same file; gicp_terms.hpp).  Both clouds have normals, each array as for point-to-plane (host planes, or nullptr:
+// estimated on the device); they are turned as the reference's _fix_normal_direction turns them and give each point a covariance.
+// False also for an epsilon that is not finite or <= 0.
+// The parity entry: per point of `cloud` the six values 00, 01, 02, 11, 12, 22 into cov_host (cloud.npoints rows of 6 doubles);
+// direction nullptr: the normals are not turned.
+bool icp_gicp_covariances(const DeviceSoA &cloud, const float *host_normals, float radius, int max_nn, const double *direction, double epsilon,
+                          double *cov_host);
+// sums = sum (A^T N A)_ij for i <= j (21) | sum (A^T g)_i (6) | sum e^T g | sum d2: the plane sums' layout.
+bool icp_gicp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *source_normals,
+                   const float *reference_normals, float radius, int max_nn, double epsilon, uint64_t *n, double sums[29]);
+// open3d's registration_generalized_icp: icp_point2plane's loop with these sums.
+bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *source_normals,
+                     const float *reference_normals, float radius, int max_nn, double epsilon, double relative_fitness, double relative_rmse,
+                     int max_iteration, double T_out[16], double *fitness, double *inlier_rmse, int *iterations);
 // the mean of a cloud's points (the direction filter's centroid kernels) on the host; non-finite where a coordinate is
 bool icp_centroid(const DeviceSoA &cloud, double cen[3]);
 

@@ -55,6 +55,7 @@
 #include "point_grid.hpp"
 #include "rigid_fit.hpp"
 #include "plane_fit.hpp"
+#include "gicp_terms.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -647,6 +648,68 @@ bool plane_args_ok(const char *who, const float *host_normals, float radius, int
     return false;
 }
 
+// The loop of the aligners whose update is plane_fit's (point-to-plane and generalized ICP): they differ in the sums kernel that
+// follows the search, which `launch` puts on the stream; the sums have one layout.  Inside ONE grid hook; waits for its results.
+using PlaneSumsLaunch = std::function<void(const double T[16], uint32_t tag, hipStream_t s)>;
+
+bool plane_loop(const char *who, const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], double relative_fitness,
+                double relative_rmse, int max_iteration, const IcpWork &w, ThreadCtx &c, const PlaneSumsLaunch &launch, double T_out[16],
+                double *fitness, double *inlier_rmse, int *iterations) {
+    const size_t ns = source.npoints;
+    bool loop_ok = true;
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        double T[16];
+        for (int i = 0; i < 16; i++) T[i] = init[i];
+        // one evaluation: search, sums, wait, read
+        uint64_t n = 0;
+        double sums[29];
+        auto evaluate = [&]() {
+            const IcpArgs A = correspond_args(source, T, max_distance, w);
+            const uint32_t tag = next_plane_tag(c);
+            launch_correspond(v, A, s);
+            launch(T, tag, s);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
+            return read_plane_sums(c, tag, &n, sums);
+        };
+        auto measures = [&](double &fit, double &rmse) {
+            fit = n ? (double)n / (double)ns : 0.0;
+            rmse = n ? sqrt(sums[28] / (double)n) : 0.0;
+        };
+        if (!evaluate()) return loop_ok = false;
+        double fit, rmse;
+        measures(fit, rmse);
+        int done = 0;
+        if (n != 0) {
+            for (int it = 0; it < max_iteration; it++) {
+                double R[3][3], t[3];
+                plane_fit(sums, sums + 21, R, t);
+                double U[16] = {R[0][0], R[0][1], R[0][2], t[0], R[1][0], R[1][1], R[1][2], t[1], R[2][0], R[2][1], R[2][2], t[2], 0, 0, 0, 1}, N[16];
+                for (int i = 0; i < 4; i++)
+                    for (int j = 0; j < 4; j++) N[4 * i + j] = ((U[4 * i] * T[j] + U[4 * i + 1] * T[4 + j]) + U[4 * i + 2] * T[8 + j]) + U[4 * i + 3] * T[12 + j];
+                for (int i = 0; i < 16; i++) T[i] = N[i];
+                for (int i = 0; i < 16; i++)
+                    if (!std::isfinite(T[i])) {
+                        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the transformation is no longer finite");
+                        return loop_ok = false;
+                    }
+                const double fit_before = fit, rmse_before = rmse;
+                if (!evaluate()) return loop_ok = false;
+                measures(fit, rmse);
+                done = it + 1;
+                if (fabs(fit_before - fit) < relative_fitness && fabs(rmse_before - rmse) < relative_rmse) break;
+            }
+        }
+        for (int i = 0; i < 16; i++) T_out[i] = T[i];
+        *fitness = fit;
+        *inlier_rmse = rmse;
+        *iterations = done;
+        return true;
+    };
+    bool ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
+    ok = c.sync() && ok;
+    return ok && loop_ok;
+}
+
 }  // namespace
 
 bool icp_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *host_normals, float radius,
@@ -700,58 +763,262 @@ bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double
     bool ok = normals.make(who, reference, host_normals, radius, max_nn, c);
     if (ok && ns != 0) ok = w.alloc(ns, ICP_PLANE_NSUM);
     if (!ok || ns == 0) return c.sync() && ok;
-    bool loop_ok = true;
-    const GridSearch search = [&](const GridView &v, hipStream_t s) {
-        double T[16];
-        for (int i = 0; i < 16; i++) T[i] = init[i];
-        // one evaluation: search, sums, wait, read
-        uint64_t n = 0;
-        double sums[29];
-        auto evaluate = [&]() {
-            const IcpArgs A = correspond_args(source, T, max_distance, w);
-            const uint32_t tag = next_plane_tag(c);
-            launch_correspond(v, A, s);
-            launch_plane_sums(source, reference, normals.planes, T, w, c, tag, s);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return false;
-            return read_plane_sums(c, tag, &n, sums);
-        };
-        auto measures = [&](double &fit, double &rmse) {
-            fit = n ? (double)n / (double)ns : 0.0;
-            rmse = n ? sqrt(sums[28] / (double)n) : 0.0;
-        };
-        if (!evaluate()) return loop_ok = false;
-        double fit, rmse;
-        measures(fit, rmse);
-        int done = 0;
-        if (n != 0) {
-            for (int it = 0; it < max_iteration; it++) {
-                double R[3][3], t[3];
-                plane_fit(sums, sums + 21, R, t);
-                double U[16] = {R[0][0], R[0][1], R[0][2], t[0], R[1][0], R[1][1], R[1][2], t[1], R[2][0], R[2][1], R[2][2], t[2], 0, 0, 0, 1}, N[16];
-                for (int i = 0; i < 4; i++)
-                    for (int j = 0; j < 4; j++) N[4 * i + j] = ((U[4 * i] * T[j] + U[4 * i + 1] * T[4 + j]) + U[4 * i + 2] * T[8 + j]) + U[4 * i + 3] * T[12 + j];
-                for (int i = 0; i < 16; i++) T[i] = N[i];
-                for (int i = 0; i < 16; i++)
-                    if (!std::isfinite(T[i])) {
-                        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the transformation is no longer finite");
-                        return loop_ok = false;
-                    }
-                const double fit_before = fit, rmse_before = rmse;
-                if (!evaluate()) return loop_ok = false;
-                measures(fit, rmse);
-                done = it + 1;
-                if (fabs(fit_before - fit) < relative_fitness && fabs(rmse_before - rmse) < relative_rmse) break;
-            }
+    const PlaneSumsLaunch launch = [&](const double T[16], uint32_t tag, hipStream_t s) {
+        launch_plane_sums(source, reference, normals.planes, T, w, c, tag, s);
+    };
+    return plane_loop(who, source, reference, max_distance, init, relative_fitness, relative_rmse, max_iteration, w, c, launch, T_out, fitness,
+                      inlier_rmse, iterations);
+}
+
+// ---- generalized ICP (the contract is stated in include/cwipc_util_amd/hip_ext.h; the arithmetic is gicp_terms.hpp) ----
+namespace {
+
+// Per point of a cloud the covariance of gicp_terms.hpp from its normal: value v of point i goes to cov[i * point_stride + v *
+// value_stride], which writes either layout the sums kernel reads -- six planes for the source (point_stride 1, value_stride the
+// padded count: a lane's four points are two 16-byte loads per plane, in order) and records of six doubles for the reference
+// (point_stride 6, value_stride 1: a gathered record is 48 bytes, three 16-byte loads in at most two cache lines).
+struct GicpCovArgs {
+    const float *mx, *my, *mz;   // the normals' planes
+    size_t n;
+    double dir[3];               // the cloud's direction
+    int orient;                  // 0: the normals are taken as they are
+    double eps;
+    double *cov;
+    size_t point_stride, value_stride;
+};
+
+__global__ void __launch_bounds__(GRID_BLK) gicp_covariance_kernel(GicpCovArgs A) {
+    const size_t i = (size_t)blockIdx.x * GRID_BLK + threadIdx.x;
+    if (i >= A.n) return;
+    double m[3] = {(double)A.mx[i], (double)A.my[i], (double)A.mz[i]};
+    if (A.orient) gicp_orient(m, A.dir);
+    double C[6];
+    gicp_covariance(m, A.eps, C);
+#pragma unroll
+    for (int v = 0; v < 6; v++) A.cov[i * A.point_stride + (size_t)v * A.value_stride] = C[v];
+}
+
+struct IcpGicpSumArgs {
+    const float *sx, *sy, *sz;   // as IcpSumArgs
+    size_t ns;
+    const uint32_t *idx;
+    const double *d2;
+    const float *rx, *ry, *rz;   // the reference cloud's planes
+    size_t nr;
+    const double *cs;            // the source's covariances: six planes of cs_stride doubles (cs_stride a multiple of 256)
+    size_t cs_stride;
+    const double *ct;            // the reference's: nr records of six doubles
+    double T[12];
+    size_t chunk;
+};
+
+// The shape of icp_plane_sums_partial_kernel: the same chunks, four points per lane and step in index order, the same trees.
+__global__ void __launch_bounds__(GRID_BLK) icp_gicp_sums_partial_kernel(IcpGicpSumArgs A, double *__restrict__ partial /* [chunks][GICP_NTERM] */) {
+    __shared__ double red[GRID_BLK / 64][GICP_NTERM];
+    const size_t lo = (size_t)blockIdx.x * A.chunk, hi = lo + A.chunk < A.ns ? lo + A.chunk : A.ns;
+    const double R[9] = {A.T[0], A.T[1], A.T[2], A.T[4], A.T[5], A.T[6], A.T[8], A.T[9], A.T[10]};
+    double s[GICP_NTERM];
+#pragma unroll
+    for (int v = 0; v < GICP_NTERM; v++) s[v] = 0.0;
+    for (size_t base = lo + 4 * (size_t)threadIdx.x; base < hi; base += 4 * (size_t)GRID_BLK) {
+        const float4 x4 = *reinterpret_cast<const float4 *>(A.sx + base), y4 = *reinterpret_cast<const float4 *>(A.sy + base),
+                     z4 = *reinterpret_cast<const float4 *>(A.sz + base);
+        const uint4 i4 = *reinterpret_cast<const uint4 *>(A.idx + base);
+        const double2 da = *reinterpret_cast<const double2 *>(A.d2 + base), db = *reinterpret_cast<const double2 *>(A.d2 + base + 2);
+        const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
+        const uint32_t is[4] = {i4.x, i4.y, i4.z, i4.w};
+        const double ds[4] = {da.x, da.y, db.x, db.y};
+        double cs[4][6];
+#pragma unroll
+        for (int v = 0; v < 6; v++) {
+            const double2 ca = *reinterpret_cast<const double2 *>(A.cs + (size_t)v * A.cs_stride + base),
+                          cb = *reinterpret_cast<const double2 *>(A.cs + (size_t)v * A.cs_stride + base + 2);
+            cs[0][v] = ca.x; cs[1][v] = ca.y; cs[2][v] = cb.x; cs[3][v] = cb.y;
         }
-        for (int i = 0; i < 16; i++) T_out[i] = T[i];
-        *fitness = fit;
-        *inlier_rmse = rmse;
-        *iterations = done;
-        return true;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            // (idx is checked against the reference count before it is an address; ICP_NONE fails the test too)
+            if (base + u >= hi || (size_t)is[u] >= A.nr) continue;
+            double p[3];
+            icp_move(A.T, xs[u], ys[u], zs[u], p);
+            const double q[3] = {(double)A.rx[is[u]], (double)A.ry[is[u]], (double)A.rz[is[u]]};
+            const double2 *rec = reinterpret_cast<const double2 *>(A.ct + 6 * (size_t)is[u]);
+            const double2 c0 = rec[0], c1 = rec[1], c2 = rec[2];
+            const double ct[6] = {c0.x, c0.y, c1.x, c1.y, c2.x, c2.y};
+            double t[GICP_NTERM];
+            gicp_pair_terms(p, q, cs[u], ct, R, ds[u], t);
+#pragma unroll
+            for (int v = 0; v < GICP_NTERM; v++) s[v] += t[v];   // (t[0] is 1: a count below 2^53 is exact in f64)
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < GICP_NTERM; v++) {
+        for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][v] = s[v];
+    }
+    __syncthreads();
+    if (threadIdx.x < GICP_NTERM) {
+        double t = 0.0;
+        for (int w = 0; w < GRID_BLK / 64; w++) t += red[w][threadIdx.x];
+        partial[(size_t)blockIdx.x * GICP_NTERM + threadIdx.x] = t;
+    }
+}
+static_assert(GICP_NTERM == ICP_PLANE_NSUM, "the generalized sums go through the plane sums' final kernel and pinned words");
+
+// A cloud's covariances in one pool block, in either layout of gicp_covariance_kernel.  On the calling thread's stream, no wait.
+struct GicpCov {
+    double *values = nullptr;
+    size_t stride = 0;   // planes: the padded count
+    bool make(const DeviceSoA &cloud, const float *normal_planes, const double *direction, double eps, bool records, ThreadCtx &c) {
+        const size_t n = cloud.npoints;
+        stride = (n + 255) & ~(size_t)255;
+        values = (double *)pool_alloc(6 * (records ? n : stride) * sizeof(double));
+        if (!values) return false;
+        GicpCovArgs A{};
+        A.mx = normal_planes; A.my = normal_planes + n; A.mz = normal_planes + 2 * n;
+        A.n = n;
+        A.orient = direction != nullptr;
+        for (int a = 0; a < 3; a++) A.dir[a] = direction ? direction[a] : 0.0;
+        A.eps = eps;
+        A.cov = values;
+        A.point_stride = records ? 6 : 1;
+        A.value_stride = records ? 1 : stride;
+        CW_LAUNCH("gicp_covariance", gicp_covariance_kernel, dim3((unsigned)((n + GRID_BLK - 1) / GRID_BLK)), dim3(GRID_BLK), 0, c.stream, A);
+        return hipGetLastError() == hipSuccess;
+    }
+    ~GicpCov() { pool_free(values); }   // (the owner has waited for the stream)
+};
+
+void launch_gicp_sums(const DeviceSoA &source, const DeviceSoA &reference, const GicpCov &cs, const GicpCov &ct, const double T[16], const IcpWork &w,
+                      ThreadCtx &c, uint32_t tag, hipStream_t s) {
+    IcpGicpSumArgs S{};
+    S.sx = source.x(); S.sy = source.y(); S.sz = source.z();
+    S.ns = source.npoints;
+    S.idx = w.idx;
+    S.d2 = w.d2;
+    S.rx = reference.x(); S.ry = reference.y(); S.rz = reference.z();
+    S.nr = reference.npoints;
+    S.cs = cs.values;
+    S.cs_stride = cs.stride;
+    S.ct = ct.values;
+    for (int i = 0; i < 12; i++) S.T[i] = T[i];
+    S.chunk = w.chunk;
+    CW_LAUNCH("icp_gicp_sums_partial", icp_gicp_sums_partial_kernel, dim3((unsigned)w.nchunks), dim3(GRID_BLK), 0, s, S, w.partial);
+    CW_LAUNCH("icp_plane_sums_final", icp_plane_sums_final_kernel, dim3(1), dim3(ICP_FINAL_THREADS), 0, s, w.partial, w.nchunks,
+              reinterpret_cast<unsigned long long *>(c.host_words), (unsigned long long)tag);
+}
+
+bool gicp_args_ok(const char *who, const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon) {
+    if (!(epsilon > 0.0) || !std::isfinite(epsilon)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "epsilon must be positive and finite");
+        return false;
+    }
+    // (radius and max_nn matter when either cloud's normals are to be estimated)
+    return plane_args_ok(who, source_normals && reference_normals ? source_normals : nullptr, radius, max_nn);
+}
+
+bool normals_finite(const char *who, const float *host_normals, size_t n) {
+    for (size_t i = 0; host_normals && i < 3 * n; i++)
+        if (!std::isfinite(host_normals[i])) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the normals must be finite");
+            return false;
+        }
+    return true;
+}
+
+// What both clouds need before the first search, once per run and before the grid hook: the two directions (the reference's
+// _fix_normal_direction: from the midpoint of the two centroids towards each cloud's own), the normals, the covariances.
+struct GicpClouds {
+    IcpNormals source_normals, reference_normals;
+    GicpCov cs, ct;
+    bool make(const char *who, const DeviceSoA &source, const DeviceSoA &reference, const float *host_source_normals, const float *host_reference_normals,
+              float radius, int max_nn, double epsilon, ThreadCtx &c) {
+        double cen_s[3], cen_t[3], ds[3], dt[3];
+        if (!icp_centroid(source, cen_s) || !icp_centroid(reference, cen_t)) return false;
+        for (int a = 0; a < 3; a++) {
+            const double o = (cen_s[a] + cen_t[a]) / 2;
+            ds[a] = cen_s[a] - o;
+            dt[a] = cen_t[a] - o;
+        }
+        // (the source's normals are those of the original source cloud: T never reaches them, its rotation reaches the covariances)
+        return source_normals.make(who, source, host_source_normals, radius, max_nn, c) &&
+               reference_normals.make(who, reference, host_reference_normals, radius, max_nn, c) &&
+               cs.make(source, source_normals.planes, ds, epsilon, false, c) && ct.make(reference, reference_normals.planes, dt, epsilon, true, c);
+    }
+};
+
+}  // namespace
+
+bool icp_gicp_covariances(const DeviceSoA &cloud, const float *host_normals, float radius, int max_nn, const double *direction, double epsilon,
+                          double *cov_host) {
+    const char *who = "cwipc_hip_gicp_covariances";
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (!gicp_args_ok(who, host_normals, host_normals, radius, max_nn, epsilon)) return false;
+    const size_t n = cloud.npoints;
+    if (n == 0) return true;
+    IcpNormals normals;
+    GicpCov cov;
+    bool ok = normals.make(who, cloud, host_normals, radius, max_nn, c) && cov.make(cloud, normals.planes, direction, epsilon, true, c);
+    ok = ok && hipMemcpyAsync(cov_host, cov.values, 6 * n * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    return c.sync() && ok;   // (a wait also on failure: kernels that write the blocks may still be in flight)
+}
+
+bool icp_gicp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *source_normals,
+                   const float *reference_normals, float radius, int max_nn, double epsilon, uint64_t *n, double sums[29]) {
+    const char *who = "cwipc_hip_icp_gicp_sums";
+    *n = 0;
+    for (int v = 0; v < 29; v++) sums[v] = 0.0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (!icp_args_ok(who, T, max_distance) || !gicp_args_ok(who, source_normals, reference_normals, radius, max_nn, epsilon)) return false;
+    const size_t ns = source.npoints;
+    // (the caller's normals are looked at even when there is nothing to match them with: a bad array is an error either way)
+    if (!normals_finite(who, source_normals, ns) || !normals_finite(who, reference_normals, reference.npoints)) return false;
+    if (ns == 0 || reference.npoints == 0) return true;
+    GicpClouds clouds;
+    IcpWork w;
+    bool ok = clouds.make(who, source, reference, source_normals, reference_normals, radius, max_nn, epsilon, c) && w.alloc(ns, GICP_NTERM);
+    if (!ok) return c.sync() && ok;   // (a wait also on failure: kernels that write the blocks may still be in flight)
+    const IcpArgs A = correspond_args(source, T, max_distance, w);
+    const uint32_t tag = next_plane_tag(c);
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        launch_correspond(v, A, s);
+        launch_gicp_sums(source, reference, clouds.cs, clouds.ct, T, w, c, tag, s);
+        return hipGetLastError() == hipSuccess;
     };
     ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
     ok = c.sync() && ok;
-    return ok && loop_ok;
+    return ok && read_plane_sums(c, tag, n, sums);
+}
+
+bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *source_normals,
+                     const float *reference_normals, float radius, int max_nn, double epsilon, double relative_fitness, double relative_rmse,
+                     int max_iteration, double T_out[16], double *fitness, double *inlier_rmse, int *iterations) {
+    const char *who = "cwipc_hip_icp_generalized";
+    for (int i = 0; i < 16; i++) T_out[i] = init[i];
+    *fitness = 0.0;
+    *inlier_rmse = 0.0;
+    *iterations = 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (!icp_args_ok(who, init, max_distance) || !gicp_args_ok(who, source_normals, reference_normals, radius, max_nn, epsilon)) return false;
+    if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
+        return false;
+    }
+    const size_t ns = source.npoints;
+    if (!normals_finite(who, source_normals, ns) || !normals_finite(who, reference_normals, reference.npoints)) return false;
+    if (ns == 0 || reference.npoints == 0) return true;
+    GicpClouds clouds;
+    IcpWork w;
+    const bool ok = clouds.make(who, source, reference, source_normals, reference_normals, radius, max_nn, epsilon, c) && w.alloc(ns, GICP_NTERM);
+    if (!ok) return c.sync() && ok;
+    const PlaneSumsLaunch launch = [&](const double T[16], uint32_t tag, hipStream_t s) {
+        launch_gicp_sums(source, reference, clouds.cs, clouds.ct, T, w, c, tag, s);
+    };
+    return plane_loop(who, source, reference, max_distance, init, relative_fitness, relative_rmse, max_iteration, w, c, launch, T_out, fitness,
+                      inlier_rmse, iterations);
 }
 
 // the mean of the cloud's points (the direction filter's centroid kernels), on the host; non-finite where a point is

@@ -1,7 +1,7 @@
 """Fine alignment of one cloud onto another (reference python/cwipc/registration/fine.py: the aligner that every camera's step of
 registration/multicamera.py runs between its two analyses).
 
-Here: the base class, which finds nothing and returns the identity, point-to-point ICP and point-to-plane ICP.  The reference runs
+Here: the base class, which finds nothing and returns the identity, point-to-point ICP, point-to-plane ICP and generalized ICP.  The reference runs
 open3d's registration_icp on the CPU, on numpy copies of both clouds; here the clouds stay on the device, the loop is
 cwipc_hip_icp_point2point (correspondence search on the point grid over the reference cloud, sums of the rigid fit, a 3x3 solve on
 the host per iteration) or cwipc_hip_icp_point2plane (the same search, the sums of the plane fit, a 6x6 solve on the host per
@@ -13,18 +13,24 @@ turns the normals round with _fix_normal_direction; negating a normal leaves eve
 bit, so that step has no effect here and is not ported.  The source cloud's normals are never read by open3d's point-to-plane
 estimate and are not computed.
 
-Not provided: the reference's default aligner, generalized ICP (it needs per-point covariances on both clouds and another
-linearisation).  DEFAULT_FINE_ALIGNMENT_ALGORITHM is therefore the point-to-point class.
+Generalized ICP, the reference's default aligner, is cwipc_hip_icp_generalized: the same search and the same 6x6 solve, with sums
+that weigh every pair by the inverse of Ct + R Cs R^T, the two points' covariances.  It needs normals on both clouds (estimated on the
+device as above, the source's on the source cloud as given) and, unlike point-to-plane, their orientation: the sign of a normal
+reaches the covariance, so the reference's _fix_normal_direction is ported for this aligner (each cloud's normals face away from
+the midpoint of the two centroids).
+
+DEFAULT_FINE_ALIGNMENT_ALGORITHM is still the point-to-point class (see the comment at the end of the file); a script that wants
+the reference's default asks for RegistrationComputer_ICP_Generalized by name.
 """
 from typing import Callable, List, Optional
 
 import numpy as np
 
 from ..util import (cwipc_pointcloud_wrapper, cwipc_tilefilter_masked, cwipc_transform, cwipc_join, cwipc_center,
-                    cwipc_hip_icp_point2point, cwipc_hip_icp_point2plane)
+                    cwipc_hip_icp_point2point, cwipc_hip_icp_point2plane, cwipc_hip_icp_generalized)
 
 __all__ = ['RegistrationComputer', 'RegistrationComputer_ICP_Point2Point', 'RegistrationComputer_ICP_Point2Plane',
-           'DEFAULT_FINE_ALIGNMENT_ALGORITHM', 'ALL_FINE_ALIGNMENT_ALGORITHMS']
+           'RegistrationComputer_ICP_Generalized', 'DEFAULT_FINE_ALIGNMENT_ALGORITHM', 'ALL_FINE_ALIGNMENT_ALGORITHMS']
 
 PointCloudFilter = Callable[[cwipc_pointcloud_wrapper], cwipc_pointcloud_wrapper]
 
@@ -179,9 +185,25 @@ class RegistrationComputer_ICP_Point2Plane(_RegistrationComputer_ICP):
         return True
 
 
-#: (the reference's default is generalized ICP, which is not provided)
+class RegistrationComputer_ICP_Generalized(RegistrationComputer_ICP_Point2Plane):
+    """Generalized ICP on geometry alone (the reference's default aligner), with the reference's criteria and normal parameters,
+    which are the point-to-plane class's, and open3d's epsilon: the variance along a point's normal, against 1 in its plane.  Both
+    clouds' normals are estimated on the device and turned as the reference's _fix_normal_direction turns them."""
+
+    epsilon = 1e-3
+
+    def run(self) -> bool:
+        self._prepare()
+        self.transformation, self.fitness, self.inlier_rmse, self.iterations = cwipc_hip_icp_generalized(
+            self.get_filtered_source_pointcloud(), self.get_filtered_reference_pointcloud(), self.correspondence, None, None, None,
+            self.normal_radius, self.normal_max_nn, self.epsilon, self.relative_fitness, self.relative_rmse, self.max_iteration)
+        return True
+
+
+#: (the reference's default is generalized ICP, RegistrationComputer_ICP_Generalized here; see below for why this one stays)
 DEFAULT_FINE_ALIGNMENT_ALGORITHM = RegistrationComputer_ICP_Point2Point
 
-# (the point-to-plane class is not in this list: tests/test_gpu_icp.py asserts the list and the default as they were when
-# point-to-point went in, and existing tests are not edited; it is exported and used by name)
+# (the point-to-plane and the generalized class are not in this list, and the default is not the generalized class:
+# tests/test_gpu_icp.py asserts the list and the default as they were when point-to-point went in, and existing tests are not
+# edited; both classes are exported and used by name)
 ALL_FINE_ALIGNMENT_ALGORITHMS: List[type] = [RegistrationComputer, RegistrationComputer_ICP_Point2Point]

@@ -45,6 +45,7 @@ __all__ = [
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
+    'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
@@ -235,6 +236,11 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_icp_plane_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_icp_point2plane': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_double, _c.c_double, _c.c_int,
                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_gicp_covariances': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_icp_gicp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_double,
+                                 _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_icp_generalized': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_double,
+                                   _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
@@ -1319,13 +1325,13 @@ def cwipc_hip_icp_point2point(source: cwipc_pointcloud_wrapper, reference: cwipc
 
 
 def _normal_planes(name: str, normals: Any, reference: cwipc_pointcloud_wrapper) -> Optional[numpy.ndarray]:
-    """None, or the reference cloud's normals, given as (count, 3), as three contiguous float32 planes (the caller keeps them alive
-    over the call)."""
+    """None, or a cloud's normals (the reference's for point-to-plane, either cloud's for generalized ICP), given as (count, 3), as
+    three contiguous float32 planes (the caller keeps them alive over the call)."""
     if normals is None:
         return None
     m = numpy.asarray(normals, dtype=numpy.float32)
     if m.shape != (reference.count(), 3):
-        raise ValueError(f"{name}: normals must have the shape (count(reference), 3)")
+        raise ValueError(f"{name}: normals must have the shape (count, 3) of their cloud")
     return numpy.ascontiguousarray(m.T)
 
 
@@ -1366,6 +1372,68 @@ def cwipc_hip_icp_point2plane(source: cwipc_pointcloud_wrapper, reference: cwipc
                                                          ctypes.addressof(fitness), ctypes.addressof(rmse), ctypes.addressof(iterations))
     if rc != 0:
         raise CwipcError("cwipc_hip_icp_point2plane failed")
+    return T, float(fitness.value), float(rmse.value), int(iterations.value)
+
+
+def cwipc_hip_gicp_covariances(pc: cwipc_pointcloud_wrapper, normals: Any = None, radius: float = 0.02, max_nn: int = 30, direction: Any = None,
+                               epsilon: float = 1e-3) -> numpy.ndarray:
+    """Intermediate result of generalized ICP: per point the covariance Rx diag(epsilon, 1, 1) Rx^T of its normal, as the six values
+    00, 01, 02, 11, 12, 22, float64 (count, 6).  normals: float32 (count, 3), or None: estimated on the device with (radius, max_nn).
+    direction: three numbers the normals are turned to face first (a zero normal becomes the direction), or None: no turning.
+    For parity tests."""
+    if pc is None:
+        raise CwipcError("cwipc_hip_gicp_covariances: NULL pointcloud")
+    planes = _normal_planes('cwipc_hip_gicp_covariances', normals, pc)
+    d = None if direction is None else numpy.ascontiguousarray(numpy.asarray(direction, dtype=numpy.float64).reshape(3))
+    n = pc.count()
+    cov = numpy.zeros((max(n, 1), 6), dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_gicp_covariances(pc.as_cwipc_p(), _p(planes), float(radius), int(max_nn), _p(d), float(epsilon), cov.ctypes.data,
+                                                          len(cov))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_gicp_covariances failed")
+    return cov[:n]
+
+
+def cwipc_hip_icp_gicp_sums(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, transform: Any = None, max_distance: float = float('inf'),
+                            source_normals: Any = None, reference_normals: Any = None, radius: float = 0.02, max_nn: int = 30,
+                            epsilon: float = 1e-3) -> Tuple[int, numpy.ndarray]:
+    """One correspondence search and the sums of a generalized ICP fit over the matched pairs, nothing per point leaves the device:
+    (n, sums) with sums = sum (A^T N A)_ij for i <= j (21) | sum (A^T g)_i (6) | sum e^T g | sum d2, where A = [-skew(p) | I],
+    N = (Ct + R Cs R^T)^-1, e = p - q, g = N e for the moved source point p, its correspondence q and their covariances Cs, Ct.
+    Each cloud's normals: float32 (count, 3), or None: estimated on the device with (radius, max_nn).  They are turned as the
+    reference's _fix_normal_direction turns them before the covariances are taken."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_gicp_sums: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_gicp_sums', transform)
+    ps = _normal_planes('cwipc_hip_icp_gicp_sums', source_normals, source)
+    pr = _normal_planes('cwipc_hip_icp_gicp_sums', reference_normals, reference)
+    n = ctypes.c_uint64(0)
+    sums = numpy.zeros(29, dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_gicp_sums(source.as_cwipc_p(), reference.as_cwipc_p(), _p(m), float(max_distance), _p(ps), _p(pr), float(radius),
+                                                       int(max_nn), float(epsilon), ctypes.addressof(n), sums.ctypes.data)
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_gicp_sums failed")
+    return int(n.value), sums
+
+
+def cwipc_hip_icp_generalized(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, max_distance: float, init: Any = None,
+                              source_normals: Any = None, reference_normals: Any = None, radius: float = 0.02, max_nn: int = 30, epsilon: float = 1e-3,
+                              relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, max_iteration: int = 30) -> Tuple[numpy.ndarray, float, float, int]:
+    """open3d's registration_generalized_icp, on the GPU: (transformation 4x4 float64, fitness, inlier_rmse, iterations done).
+    The normals, radius, max_nn and epsilon as for cwipc_hip_icp_gicp_sums: both clouds have normals, estimated once per run when
+    none are given.  The criteria's defaults are open3d's."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_icp_generalized: NULL pointcloud")
+    m = _matrix4('cwipc_hip_icp_generalized', init)
+    ps = _normal_planes('cwipc_hip_icp_generalized', source_normals, source)
+    pr = _normal_planes('cwipc_hip_icp_generalized', reference_normals, reference)
+    T = numpy.zeros((4, 4), dtype=numpy.float64)
+    fitness, rmse, iterations = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+    rc = cwipc_util_dll_load().cwipc_hip_icp_generalized(source.as_cwipc_p(), reference.as_cwipc_p(), float(max_distance), _p(m), _p(ps), _p(pr), float(radius),
+                                                         int(max_nn), float(epsilon), float(relative_fitness), float(relative_rmse), int(max_iteration),
+                                                         T.ctypes.data, ctypes.addressof(fitness), ctypes.addressof(rmse), ctypes.addressof(iterations))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_icp_generalized failed")
     return T, float(fitness.value), float(rmse.value), int(iterations.value)
 
 

@@ -233,6 +233,56 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_icp_point2plane(cwipc_pointcloud *source, cwipc
                                                  const float *normals, float radius, int max_nn, double relative_fitness, double relative_rmse,
                                                  int max_iteration, double *T_out, double *fitness, double *inlier_rmse, int *iterations);
 
+/* ---- generalized ICP (reference python/cwipc/registration/fine.py, its default aligner: open3d's registration_generalized_icp with
+ * TransformationEstimationForGeneralizedICP, epsilon 1e-3, L2 loss) ----
+ * open3d is not on this stack: the contract is a restatement of the published algorithm, pinned by a numpy model.  Every operation is
+ * rounded on its own, in f64.
+ * NORMALS.  Both clouds have normals: the caller's (three planes of count floats, x then y then z, the layout
+ * cwipc_hip_estimate_normals writes with cap = count) or, for NULL, estimated on the device as cwipc_hip_estimate_normals(radius,
+ * max_nn) does, once per call and on the cloud as given (the source's on the original source cloud, not on the moved one).
+ * ORIENTATION (the reference's _fix_normal_direction; open3d's OrientNormalsToAlignWithDirection).  cs, ct: the f64 means of the
+ * source and the reference, o = (cs + ct) / 2; the source's direction is d = cs - o, the reference's d = ct - o.  Per normal m
+ * ((double) of float32): all three components 0: m = d; else if (m0*d0 + m1*d1) + m2*d2 < 0: m = -m.  A comparison with NaN is
+ * false, so a NaN direction never flips a normal.
+ * COVARIANCE (open3d's GetRotationFromE1ToX and Rx diag(eps, 1, 1) Rx^T), per point, once per call, from the oriented normal:
+ * c = m0; if c < -0.99, Rx = I (open3d's rule as published: the covariance is diag(eps, 1, 1) for every normal within about 8
+ * degrees of -x); otherwise, with f = 1 / (1 + c),
+ *     Rx = [[1 - f*(m1*m1 + m2*m2),  -m1,            -m2          ],
+ *           [m1,                     1 - f*(m1*m1),  -(f*(m1*m2)) ],
+ *           [m2,                     -(f*(m1*m2)),   1 - f*(m2*m2)]]
+ * and C_ij = ((eps*Rx_i0)*Rx_j0 + Rx_i1*Rx_j1) + Rx_i2*Rx_j2 for i <= j: six values, in the order 00, 01, 02, 11, 12, 22.
+ * PER MATCHED PAIR.  Correspondences are exactly those of cwipc_hip_correspondences.  p the moved source point, q the matched
+ * reference point ((double) of float32), R the 3x3 block of T, Cs the source point's covariance, Ct the reference point's:
+ *     B = R Cs:  B_ij = (R_i0*Cs_0j + R_i1*Cs_1j) + R_i2*Cs_2j;   S_ij = (B_i0*R_j0 + B_i1*R_j1) + B_i2*R_j2;   M_ij = Ct_ij + S_ij   (i <= j)
+ *     k00 = M11*M22 - M12*M12,  k01 = M02*M12 - M01*M22,  k02 = M01*M12 - M02*M11,
+ *     k11 = M00*M22 - M02*M02,  k12 = M01*M02 - M00*M12,  k22 = M00*M11 - M01*M01,
+ *     det = (M00*k00 + M01*k01) + M02*k02,  N_ij = k_ij / det                                   (N = M^-1, symmetric)
+ *     e = p - q,  g_i = (N_i0*e0 + N_i1*e1) + N_i2*e2
+ *     A = [-skew(p) | I]: the rows (0, p2, -p1, 1, 0, 0), (-p2, 0, p0, 0, 1, 0), (p1, -p0, 0, 0, 0, 1)
+ *     H = N A:  H_ij = (N_i0*A_0j + N_i1*A_1j) + N_i2*A_2j;   (A^T H)_ij = (A_0i*H_0j + A_1i*H_1j) + A_2i*H_2j   (i <= j)
+ *     (A^T g)_i = (A_0i*g0 + A_1i*g1) + A_2i*g2,   e^T g = (e0*g0 + e1*g1) + e2*g2
+ * open3d writes W = (M^-1)^(1/2), J = W A, r = W e; W is symmetric, so J^T J = A^T N A, J^T r = A^T g, r^T r = e^T g.
+ * Errors as for the point-to-plane entries (either normals array NULL: radius and max_nn are checked); -1 also for an epsilon that
+ * is not finite or <= 0. */
+/* The covariances of one cloud, for parity tests: cov = count rows of the six values, host memory of cap >= count rows.  direction: 3
+ * doubles, or NULL: no orientation step.  -1 also for a cap that is too small. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_gicp_covariances(cwipc_pointcloud *pc, const float *normals, float radius, int max_nn, const double *direction,
+                                                  double epsilon, double *cov, size_t cap);
+/* One search and the sums of a generalized fit, in the layout of the plane sums: *n = the number of matched pairs,
+ * sums = sum (A^T N A)_ij for i <= j (21, the upper triangle row-major) | sum (A^T g)_i (6) | sum e^T g | sum d2, 29 doubles, summed
+ * as the plane sums are: the same clouds give the same bytes.  Both directions come from the two clouds.  T NULL: the identity.  n
+ * and sums may be NULL. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_gicp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
+                                               const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon,
+                                               uint64_t *n, double *sums);
+/* cwipc_hip_icp_point2plane's loop with these sums: the same 6x6 solve and check_det rule, R = Rz Ry Rx, fitness = n / count(source),
+ * inlier_rmse = sqrt(sum d2 / n), the same stop rule.  T is applied to the original float32 source points, and its rotation to the
+ * original source covariances, in every iteration (open3d moves an f64 copy of both step by step). */
+_CWIPC_UTIL_EXPORT int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
+                                                 const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon,
+                                                 double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
+                                                 double *inlier_rmse, int *iterations);
+
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
