@@ -264,6 +264,30 @@ extern "C" cwipc_pointcloud *cwipc_hip_transform(cwipc_pointcloud *pc, const dou
     return wrap(dst, pc->timestamp(), pc->cellsize());
 }
 
+// reference python/cwipc/registration/multicamera.py:399-403 (MultiCameraToFloor._prepare_floor: every point projected onto y = 0): a copy
+// of the x and z planes and a memset of the y plane (+0.0 is all zero bytes), colours and tiles shared with the input.  Timestamp 0,
+// cellsize 0, as cwipc_from_numpy_matrix(matrix, 0) gives them there.
+extern "C" cwipc_pointcloud *cwipc_hip_flatten_y(cwipc_pointcloud *pc) {
+    if (pc == nullptr) return nullptr;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input("cwipc_hip_flatten_y", pc, keep);
+    if (!src) return nullptr;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    auto dst = soa_with_new_xyz(src);
+    if (!dst) return nullptr;
+    const size_t plane = src->stride * sizeof(float);
+    bool ok = true;
+    if (plane) {
+        ok = hipMemcpyAsync(dst->x(), src->x(), plane, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+             hipMemsetAsync(dst->y(), 0, plane, c.stream) == hipSuccess &&
+             hipMemcpyAsync(dst->z(), src->z(), plane, hipMemcpyDeviceToDevice, c.stream) == hipSuccess;
+    }
+    ok = c.sync() && ok;
+    if (!ok) return nullptr;
+    return wrap(dst, 0, 0.f);
+}
+
 // reference python/cwipc/filters/transform.py:38-52 (TransformFilter: (p + offset) * scale in Python floats; cellsize * scale)
 extern "C" cwipc_pointcloud *cwipc_hip_offset_scale(cwipc_pointcloud *pc, double x, double y, double z, double scale) {
     if (pc == nullptr) return nullptr;
@@ -723,6 +747,54 @@ extern "C" int cwipc_hip_nn_distance2(cwipc_pointcloud *source, cwipc_pointcloud
     ok = ok && hipMemcpyAsync(dist2, dev, n * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
     ok = c.sync() && ok;   // (also on failure: kernels that write `dev` may still be in flight)
     pool_free(dev);
+    return ok ? 0 : -1;
+}
+
+extern "C" int cwipc_hip_nn_distance2_jobs(cwipc_pointcloud *source, cwipc_pointcloud *reference, const cwipc_hip_nn_job *jobs, int njobs, double *dist2,
+                                           size_t cap) {
+    const char *who = "cwipc_hip_nn_distance2_jobs";
+    if (source == nullptr || reference == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return -1;
+    }
+    if (jobs == nullptr || njobs < 1 || njobs > NN_MAX_JOBS) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "between 1 and 64 jobs");
+        return -1;
+    }
+    for (int j = 0; j < njobs; j++) {
+        const cwipc_hip_nn_job &b = jobs[j];
+        if (b.nth < 0 || b.nth > NN_MAX_NTH || !(b.max_distance > 0.0) || std::isnan(b.source_y[0]) || std::isnan(b.source_y[1]) ||
+            std::isnan(b.reference_y[0]) || std::isnan(b.reference_y[1])) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "nth must lie between 0 and 31, max_distance must be positive (inf: no bound), a y limit is not NaN");
+            return -1;
+        }
+    }
+    std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+    auto src = device_input(who, source, keep_src);
+    if (!src) return -1;
+    auto ref = source == reference ? src : device_input(who, reference, keep_ref);
+    if (!ref) return -1;
+    const size_t n = src->npoints;
+    if (cap < n || (n && dist2 == nullptr)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result array is too small");
+        return -1;
+    }
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    double *dev = (double *)pool_alloc((size_t)njobs * n * sizeof(double));
+    void *table = pool_alloc(nn_jobs_table_bytes(njobs));
+    if (!dev || !table) { pool_free(dev); pool_free(table); return -1; }
+    bool ok = nn_distance2_jobs(*src, *ref, jobs, njobs, dev, table);
+    if (ok && cap == n) {
+        ok = hipMemcpyAsync(dist2, dev, (size_t)njobs * n * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    } else {
+        for (int j = 0; ok && j < njobs; j++)
+            ok = hipMemcpyAsync(dist2 + (size_t)j * cap, dev + (size_t)j * n, n * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    }
+    ok = c.sync() && ok;   // (also on failure: kernels that read the table and write `dev` may still be in flight)
+    pool_free(dev);
+    pool_free(table);
     return ok ? 0 : -1;
 }
 

@@ -450,6 +450,13 @@ bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const dou
 // max_distance that is NaN or <= 0.
 constexpr int NN_MAX_NTH = 31;
 bool nn_distance2(const DeviceSoA &source, const DeviceSoA &reference, int nth, double max_distance, double *dev_out);
+// The same for a table of jobs over one pair of clouds (hip_ext.h: cwipc_hip_nn_job): row j of dev_out (njobs rows of source.npoints
+// device doubles) holds job j's squared distances, NaN where the source point takes no part in the job.  dev_table: nn_jobs_table_bytes(njobs)
+// bytes of device memory that the caller keeps until it has waited for the stream.  One wait inside (the jobs' participant counts), none
+// behind the search.  False on failure (logged), also for njobs outside 1..NN_MAX_JOBS and a job that cwipc_hip_nn_distance2_jobs turns away.
+constexpr int NN_MAX_JOBS = 64;
+size_t nn_jobs_table_bytes(int njobs);
+bool nn_distance2_jobs(const DeviceSoA &source, const DeviceSoA &reference, const cwipc_hip_nn_job *jobs, int njobs, double *dev_out, void *dev_table);
 // 1-D Gaussian kernel density estimate (kernels_kde.hip): density[j] = sum_i exp(-0.5 ((at[j] - samples[i]) / h)^2) / (n h sqrt(2 pi)),
 // all arrays device memory.  No wait inside.
 bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);

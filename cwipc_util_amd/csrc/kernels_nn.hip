@@ -22,6 +22,7 @@
 #include "point_grid.hpp"
 
 #include <algorithm>
+#include <cstring>
 
 namespace cwipc_amd {
 
@@ -141,7 +142,306 @@ void launch_nn(const GridView &v, const NNArgs &A, hipStream_t s) {
         CW_LAUNCH("nn_distance2", (nn_distance2_kernel<KCAP, false>), dim3(qgrid), dim3(QB), 0, s, v.g, v.gm, v.sorted, v.starts, v.counts, v.counts2, A);
 }
 
+// ---------------------------------------------------------------------------
+// The same search for a table of JOBS over one pair of clouds (registration/multicamera.py: every camera of a frame against the
+// others, against itself, against a ground truth -- 2N searches whose clouds are all subsets of the same frame).  A job names its
+// subsets by predicates -- a tile mask and an open y interval per side -- instead of by compacted clouds: ONE grid over the whole
+// reference cloud serves all jobs, the job index is the launch's second grid dimension, and a reference point that takes no part in
+// a job is passed over where the scan meets it.  A distance is a value (above), so a job's row holds the very bits that
+// nn_distance2 gives for the compacted clouds, whatever grid either of them walked.
+//   * the job table lives in device memory (one pool block, copied once per call), in the order of the list widths, so that the
+//     jobs of one width are one launch; `row` is the job's place in the caller's list;
+//   * a candidate's tile is read from a byte array in SORTED order, written once per call behind the counting sort
+//     (nn_gather_tiles_kernel): the scan loads it beside sorted[e], no dependent load through sorted[e].w into rgbt.  Its y is in
+//     the register already.  (This layout has not been timed against the dependent load.)
+//   * a query that takes no part writes NaN and returns before it touches the grid: the tile word is its first and, when the mask
+//     turns it away, its only load;
+//   * a job without a participating reference point would send every query through the whole grid (nothing ever bounds its
+//     shells): the participants are counted per job first, and such a job's rows are filled (+inf / NaN) instead of searched; so
+//     is a job without a participating source point (all NaN).
+// ---------------------------------------------------------------------------
+struct NNJobDev {
+    double max2;             // max_distance^2
+    double src_y[2];         // a source point takes part iff src_y[0] < (double)y < src_y[1]
+    double ref_y[2];         // the same for reference points
+    uint32_t row;            // the job's index in the caller's list: its row of the output
+    int32_t want;            // nth + 1
+    uint32_t src_mask;       // ... and iff (tile & mask) != 0; 0: every tile
+    uint32_t ref_mask;
+};
+
+struct NNJobsArgs {
+    const float *qx, *qy, *qz;   // the source cloud's planes
+    const uint32_t *qrgbt;       // its colour / tile words
+    size_t nq;
+    const NNJobDev *jobs;        // the first job of this launch (blockIdx.y counts from it)
+    double *out;                 // rows of nq squared distances
+};
+
+__device__ __forceinline__ bool nn_takes_part(uint32_t tile, float y, uint32_t mask, const double (&lim)[2]) {
+    return (mask == 0u || (tile & mask) != 0u) && lim[0] < (double)y && (double)y < lim[1];
+}
+
+// tiles[e] = the tile of sorted[e]'s point
+__global__ void __launch_bounds__(GRID_BLK) nn_gather_tiles_kernel(const float4 *__restrict__ sorted, const uint32_t *__restrict__ rgbt, size_t n, size_t nref,
+                                                                   uint8_t *__restrict__ tiles) {
+    for (size_t e = (size_t)blockIdx.x * GRID_BLK + threadIdx.x; e < n; e += (size_t)gridDim.x * GRID_BLK) {
+        const uint32_t id = __float_as_uint(sorted[e].w);
+        tiles[e] = id < nref ? (uint8_t)(rgbt[id] >> 24) : (uint8_t)0;
+    }
+}
+
+// counts[2 * (jobs + blockIdx.y) + side] += the points of one cloud that take part in the job as its source (side 0) or reference (1)
+__global__ void __launch_bounds__(GRID_BLK) nn_jobs_count_kernel(const float *__restrict__ y, const uint32_t *__restrict__ rgbt, size_t n,
+                                                                 const NNJobDev *__restrict__ jobs, int side, uint32_t *__restrict__ counts) {
+    const NNJobDev &J = jobs[blockIdx.y];
+    const uint32_t mask = side ? J.ref_mask : J.src_mask;
+    const double lim[2] = {side ? J.ref_y[0] : J.src_y[0], side ? J.ref_y[1] : J.src_y[1]};
+    uint32_t mine = 0;
+    for (size_t i = (size_t)blockIdx.x * GRID_BLK + threadIdx.x; i < n; i += (size_t)gridDim.x * GRID_BLK)
+        mine += nn_takes_part(rgbt[i] >> 24, y[i], mask, lim) ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) mine += __shfl_xor(mine, o);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&counts[2 * blockIdx.y + side], mine);
+}
+
+// the rows of jobs that are not searched: +inf for a query that takes part, NaN for one that does not
+__global__ void __launch_bounds__(GRID_BLK) nn_jobs_fill_kernel(NNJobsArgs A) {
+    const NNJobDev &J = A.jobs[blockIdx.y];
+    double *row = A.out + (size_t)J.row * A.nq;
+    for (size_t i = (size_t)blockIdx.x * GRID_BLK + threadIdx.x; i < A.nq; i += (size_t)gridDim.x * GRID_BLK)
+        row[i] = nn_takes_part(A.qrgbt[i] >> 24, A.qy[i], J.src_mask, J.src_y) ? (double)INFINITY : (double)NAN;
+}
+
+template <int KCAP, bool SPARSE>
+__global__ void __launch_bounds__(QB) nn_jobs_kernel(Grid gv, const GridMeta *__restrict__ gm, const float4 *__restrict__ sorted,
+                                                    const uint8_t *__restrict__ tiles, const uint32_t *__restrict__ cell_start,
+                                                    const uint32_t *__restrict__ cell_count, const uint32_t *__restrict__ cell_count2, NNJobsArgs A) {
+    const size_t qi = (size_t)blockIdx.x * QB + threadIdx.x;
+    if (qi >= A.nq) return;
+    const NNJobDev &J = A.jobs[blockIdx.y];   // (the same for the whole workgroup: scalar loads)
+    double *out = A.out + (size_t)J.row * A.nq + qi;
+    // a query that takes no part: nothing of the grid is read, and a mask that turns it away has cost this one load
+    const uint32_t qtile = A.qrgbt[qi] >> 24;
+    if (J.src_mask != 0u && (qtile & J.src_mask) == 0u) { *out = (double)NAN; return; }
+    const float qyf = A.qy[qi];
+    if (!(J.src_y[0] < (double)qyf && (double)qyf < J.src_y[1])) { *out = (double)NAN; return; }
+    const GridRows<SPARSE> rows(gv, gm, cell_start, cell_count, cell_count2);
+    const Grid &g = rows.g;
+    const float qf[3] = {A.qx[qi], qyf, A.qz[qi]};
+    const double q[3] = {(double)qf[0], (double)qf[1], (double)qf[2]};
+    const int c[3] = {cell_coord(g, qf[0], 0), cell_coord(g, qf[1], 1), cell_coord(g, qf[2], 2)};
+    const uint32_t ref_mask = J.ref_mask;
+    const double ref_y[2] = {J.ref_y[0], J.ref_y[1]};
+    const double max2 = J.max2;
+    const int pad = KCAP - J.want;
+    double best[KCAP];
+#pragma unroll
+    for (int j = 0; j < KCAP; j++) best[j] = j < pad ? -INFINITY : INFINITY;
+    auto limit = [&]() { return fmin(best[KCAP - 1], max2); };
+    auto candidate = [&](const float4 p, uint32_t tile) {
+        const double dx = q[0] - (double)p.x, dy = q[1] - (double)p.y, dz = q[2] - (double)p.z;
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        // A reference point that takes no part in this job changes nothing: neither the list nor, through limit(), any bound.  The
+        // bounds below therefore only ever depend on accepted candidates, and the walk ends as nn_distance2_kernel's does: when
+        // the bound has passed the (nth + 1)-th ACCEPTED candidate or max_distance, or the shells have covered the grid.
+        if (nn_takes_part(tile, p.y, ref_mask, ref_y) && d2 < limit()) {
+#pragma unroll
+            for (int j = KCAP - 1; j >= 1; j--) best[j] = d2 < best[j - 1] ? best[j - 1] : fmin(best[j], d2);
+            best[0] = fmin(best[0], d2);
+        }
+    };
+    // sorted[first, last) with the tile bytes beside it, four loads of each in flight (scan_range's shape)
+    auto scan = [&](uint32_t first, uint32_t last) {
+        uint32_t e = first;
+        for (; e + 4 <= last; e += 4) {
+            const float4 p0 = sorted[e], p1 = sorted[e + 1], p2 = sorted[e + 2], p3 = sorted[e + 3];
+            const uint32_t t0 = tiles[e], t1 = tiles[e + 1], t2 = tiles[e + 2], t3 = tiles[e + 3];
+            candidate(p0, t0); candidate(p1, t1); candidate(p2, t2); candidate(p3, t3);
+        }
+        for (; e < last; e++) candidate(sorted[e], tiles[e]);
+    };
+    // from here on: nn_distance2_kernel's walk, bound for bound
+    auto shorten = [&](double d) {
+        const double t = d * (1.0 - 1e-9) - 1e-6 * g.h;
+        return t > 0.0 ? t : 0.0;
+    };
+    auto face_gap = [&](int a, int cell, int o) {
+        const double face = (double)g.mn[a] + (double)(o < 0 ? cell + o + 1 : cell + o) * g.h;
+        return shorten(o < 0 ? q[a] - face : face - q[a]);
+    };
+    double box[3], box2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        box[a] = fmax(face_gap(a, -1, 1), face_gap(a, g.dim[a], -1));
+        box2 += box[a] * box[a];
+    }
+    const int maxring = max(max(max(c[0], g.dim[0] - 1 - c[0]), max(c[1], g.dim[1] - 1 - c[1])), max(c[2], g.dim[2] - 1 - c[2]));
+    if (box2 < limit()) {
+        for (int ring = 0; ring <= maxring; ring++) {
+            const int x0 = max(c[0] - ring, 0), x1 = min(c[0] + ring, g.dim[0] - 1);
+            const double gx_lo = c[0] - ring >= 0 && ring > 0 ? face_gap(0, c[0], -ring) : 0.0;
+            const double gx_hi = c[0] + ring < g.dim[0] && ring > 0 ? face_gap(0, c[0], ring) : 0.0;
+            for (int dz = -ring; dz <= ring; dz++) {
+                const int z = c[2] + dz;
+                if (z < 0 || z >= g.dim[2]) continue;
+                const double gz = dz == 0 ? box[2] : face_gap(2, c[2], dz);
+                for (int dy = -ring; dy <= ring; dy++) {
+                    const int y = c[1] + dy;
+                    if (y < 0 || y >= g.dim[1]) continue;
+                    const double gy = dy == 0 ? box[1] : face_gap(1, c[1], dy);
+                    const double gyz = gy * gy + gz * gz;
+                    if (gyz >= limit()) continue;
+                    const bool face = dz == -ring || dz == ring || dy == -ring || dy == ring;
+                    uint32_t first, last;
+                    if (face) {
+                        rows.range(x0, x1, y, z, first, last);
+                        scan(first, last);
+                    } else {
+                        if (c[0] - ring >= 0 && gyz + gx_lo * gx_lo < limit()) {
+                            rows.range(c[0] - ring, c[0] - ring, y, z, first, last);
+                            scan(first, last);
+                        }
+                        if (c[0] + ring < g.dim[0] && gyz + gx_hi * gx_hi < limit()) {
+                            rows.range(c[0] + ring, c[0] + ring, y, z, first, last);
+                            scan(first, last);
+                        }
+                    }
+                }
+            }
+            double beyond = INFINITY;
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                if (c[a] - ring - 1 >= 0) beyond = fmin(beyond, face_gap(a, c[a], -(ring + 1)));
+                if (c[a] + ring + 1 < g.dim[a]) beyond = fmin(beyond, face_gap(a, c[a], ring + 1));
+            }
+            if (!(limit() > beyond * beyond)) break;
+        }
+    }
+    *out = best[KCAP - 1];
+}
+
+template <int KCAP>
+void launch_nn_jobs(const GridView &v, const uint8_t *tiles, const NNJobsArgs &A, unsigned njobs, hipStream_t s) {
+    const dim3 grid((unsigned)((A.nq + QB - 1) / QB), njobs);
+    if (v.sparse)
+        CW_LAUNCH("nn_jobs", (nn_jobs_kernel<KCAP, true>), grid, dim3(QB), 0, s, v.g, v.gm, v.sorted, tiles, v.starts, v.counts, v.counts2, A);
+    else
+        CW_LAUNCH("nn_jobs", (nn_jobs_kernel<KCAP, false>), grid, dim3(QB), 0, s, v.g, v.gm, v.sorted, tiles, v.starts, v.counts, v.counts2, A);
+}
+
+int nn_width_class(int want) { return want <= 2 ? 0 : want <= 4 ? 1 : 2; }
+
 }  // namespace
+
+size_t nn_jobs_table_bytes(int njobs) { return (size_t)(njobs > 0 ? njobs : 0) * (sizeof(NNJobDev) + 2 * sizeof(uint32_t)); }
+
+bool nn_distance2_jobs(const DeviceSoA &source, const DeviceSoA &reference, const cwipc_hip_nn_job *jobs, int njobs, double *dev_out, void *dev_table) {
+    const char *who = "cwipc_hip_nn_distance2_jobs";
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    if (jobs == nullptr || njobs < 1 || njobs > NN_MAX_JOBS) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "between 1 and 64 jobs");
+        return false;
+    }
+    int maxwant = 1;
+    for (int j = 0; j < njobs; j++) {
+        const cwipc_hip_nn_job &b = jobs[j];
+        if (b.nth < 0 || b.nth > NN_MAX_NTH || !(b.max_distance > 0.0) || std::isnan(b.source_y[0]) || std::isnan(b.source_y[1]) ||
+            std::isnan(b.reference_y[0]) || std::isnan(b.reference_y[1])) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "nth must lie between 0 and 31, max_distance must be positive (inf: no bound), a y limit is not NaN");
+            return false;
+        }
+        maxwant = std::max(maxwant, b.nth + 1);
+    }
+    const size_t nq = source.npoints;
+    if (nq == 0) return true;
+    // the table in the order of the list widths (stable), and where each width's jobs start
+    NNJobDev tab[NN_MAX_JOBS];
+    int first_of[4] = {0, 0, 0, 0};
+    int at = 0;
+    for (int w = 0; w < 3; w++) {
+        first_of[w] = at;
+        for (int j = 0; j < njobs; j++) {
+            const cwipc_hip_nn_job &b = jobs[j];
+            if (nn_width_class(b.nth + 1) != w) continue;
+            NNJobDev &d = tab[at++];
+            d.max2 = b.max_distance * b.max_distance;
+            d.src_y[0] = b.source_y[0]; d.src_y[1] = b.source_y[1];
+            d.ref_y[0] = b.reference_y[0]; d.ref_y[1] = b.reference_y[1];
+            d.row = (uint32_t)j;
+            d.want = b.nth + 1;
+            d.src_mask = b.source_mask;
+            d.ref_mask = b.reference_mask;
+        }
+    }
+    first_of[3] = at;
+    // the caller's block: the table | two counts per job; the pinned staging holds the same
+    const size_t tab_bytes = (size_t)njobs * sizeof(NNJobDev), cnt_bytes = (size_t)njobs * 2 * sizeof(uint32_t);
+    char *block = (char *)dev_table;
+    char *stage = (char *)c.staging(tab_bytes + cnt_bytes);
+    if (!block || !stage) return false;
+    const NNJobDev *dev_tab = (const NNJobDev *)block;
+    uint32_t *dev_counts = (uint32_t *)(block + tab_bytes);
+    memcpy(stage, tab, tab_bytes);
+    if (hipMemcpyAsync(block, stage, tab_bytes, hipMemcpyHostToDevice, c.stream) != hipSuccess ||
+        hipMemsetAsync(dev_counts, 0, cnt_bytes, c.stream) != hipSuccess) return false;
+    CW_LAUNCH("nn_jobs_count", nn_jobs_count_kernel, dim3(std::min(grid_blocks(nq), 256u), (unsigned)njobs), dim3(GRID_BLK), 0, c.stream, source.y(),
+              source.rgbt(), nq, dev_tab, 0, dev_counts);
+    if (reference.npoints)
+        CW_LAUNCH("nn_jobs_count", nn_jobs_count_kernel, dim3(std::min(grid_blocks(reference.npoints), 256u), (unsigned)njobs), dim3(GRID_BLK), 0, c.stream,
+                  reference.y(), reference.rgbt(), reference.npoints, dev_tab, 1, dev_counts);
+    if (hipGetLastError() != hipSuccess) return false;
+    // the one wait of the search: which jobs have anybody on both sides
+    if (hipMemcpyAsync(stage + tab_bytes, dev_counts, cnt_bytes, hipMemcpyDeviceToHost, c.stream) != hipSuccess || !c.sync()) return false;
+    bool live[NN_MAX_JOBS];
+    bool any_live = false;
+    {
+        const uint32_t *cnt = (const uint32_t *)(stage + tab_bytes);
+        for (int e = 0; e < njobs; e++) {
+            live[e] = cnt[2 * e] != 0 && cnt[2 * e + 1] != 0;
+            any_live = any_live || live[e];
+        }
+    }
+    NNJobsArgs A{};
+    A.qx = source.x(); A.qy = source.y(); A.qz = source.z();
+    A.qrgbt = source.rgbt();
+    A.nq = nq;
+    A.out = dev_out;
+    // runs of consecutive table entries that are (not) searched: one launch each
+    auto for_runs = [&](int lo, int hi, bool want_live, const std::function<void(int, int)> &f) {
+        for (int e = lo; e < hi;) {
+            if (live[e] != want_live) { e++; continue; }
+            int end = e;
+            while (end < hi && live[end] == want_live) end++;
+            f(e, end - e);
+            e = end;
+        }
+    };
+    for_runs(0, njobs, false, [&](int e, int count) {
+        NNJobsArgs F = A;
+        F.jobs = dev_tab + e;
+        CW_LAUNCH("nn_jobs_fill", nn_jobs_fill_kernel, dim3(std::min(grid_blocks(nq), 1024u), (unsigned)count), dim3(GRID_BLK), 0, c.stream, F);
+    });
+    if (hipGetLastError() != hipSuccess) return false;
+    if (!any_live) return true;
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        uint8_t *tiles = (uint8_t *)pool_alloc(v.n);
+        if (!tiles) return false;
+        tctx().free_later(tiles);
+        CW_LAUNCH("nn_gather_tiles", nn_gather_tiles_kernel, dim3(grid_blocks(v.n)), dim3(GRID_BLK), 0, s, v.sorted, reference.rgbt(), v.n, reference.npoints, tiles);
+        for (int w = 0; w < 3; w++)
+            for_runs(first_of[w], first_of[w + 1], true, [&](int e, int count) {
+                NNJobsArgs S = A;
+                S.jobs = dev_tab + e;
+                if (w == 0) launch_nn_jobs<2>(v, tiles, S, (unsigned)count, s);
+                else if (w == 1) launch_nn_jobs<4>(v, tiles, S, (unsigned)count, s);
+                else launch_nn_jobs<32>(v, tiles, S, (unsigned)count, s);
+            });
+        return hipGetLastError() == hipSuccess;
+    };
+    return grid_and_search(reference, std::max(maxwant, NN_GRID_WIDTH), true, search);
+}
 
 bool nn_distance2(const DeviceSoA &source, const DeviceSoA &reference, int nth, double max_distance, double *dev_out) {
     ThreadCtx &c = tctx();

@@ -7,9 +7,19 @@ their per-point work (cross-cloud nearest distances and correspondences, the Gau
 normals and covariances, the sums of a rigid fit, of a plane fit and of a generalized fit) runs on the GPU.  The per-point helpers
 the rest of the reference's tooling calls (cwipc_tilefilter_masked, cwipc_transform, get_tiles_used, cwipc_downsample_pertile,
 cwipc_direction_filter) live in cwipc_util_amd.util.
+
+The multi-camera algorithms (`multicamera.MultiCameraIterative`, the default, `multicamera.MultiCameraOneToAllOthers`,
+`multicamera.MultiCameraToFloor`, `multicamera.MultiCameraToGroundTruth`) loop over those pieces and give one transformation per
+camera of a tiled capture; their per-camera analyses run as one batch (`analyze.run_analyzers_batched`, one tile-aware search over
+one grid: cwipc_hip_nn_distance_jobs).  The transformation helpers are in `util`.
 """
-from .abstract import AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults   # noqa: F401
+from .abstract import (AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults, AlignmentAlgorithm, MulticamAlgorithm,   # noqa: F401
+                       MulticamAlignmentAlgorithm)
 from .analyze import (RegistrationAnalyzer, RegistrationAnalyzerSymmetric, OverlapAnalyzer, DEFAULT_ANALYZER_ALGORITHM,   # noqa: F401
-                      ALL_ANALYZER_ALGORITHMS)
+                      ALL_ANALYZER_ALGORITHMS, run_analyzers_batched, build_analyzer_jobs)
 from .fine import (RegistrationComputer, RegistrationComputer_ICP_Point2Point, RegistrationComputer_ICP_Point2Plane,   # noqa: F401
                    RegistrationComputer_ICP_Generalized, DEFAULT_FINE_ALIGNMENT_ALGORITHM, ALL_FINE_ALIGNMENT_ALGORITHMS)
+from .util import (transformation_identity, transformation_invert, transformation_frompython, transformation_topython,   # noqa: F401
+                   transformation_get_translation, transformation_compare, BaseMulticamAlgorithm)
+from .multicamera import (BaseMulticamAlignmentAlgorithm, MultiCameraOneToAllOthers, MultiCameraToFloor, MultiCameraToGroundTruth,   # noqa: F401
+                          MultiCameraIterative, DEFAULT_MULTICAMERA_ALGORITHM, ALL_MULTICAMERA_ALGORITHMS, DEFAULT_MULTICAMERA_ALIGNER)

@@ -1,13 +1,19 @@
-"""Result record and interface of the registration analyzers (the surface of reference python/cwipc/registration/abstract.py that
-the analyzers use: AnalysisResults, AnalysisAlgorithm)."""
+"""Result records and interfaces of the registration tooling (the surface of reference python/cwipc/registration/abstract.py that
+the analyzers, the aligners and the multi-camera algorithms use: AnalysisResults, AnalysisAlgorithm, AlignmentAlgorithm,
+MulticamAlgorithm, MulticamAlignmentAlgorithm)."""
 from abc import ABC, abstractmethod
-from typing import Optional, Union
+from typing import Any, List, Optional, Type, Union
 
 import numpy
 
 from ..util import cwipc_pointcloud_wrapper
 
-__all__ = ['AnalysisResults', 'AnalysisAlgorithm', 'OverlapAnalysisResults']
+__all__ = ['AnalysisResults', 'AnalysisAlgorithm', 'OverlapAnalysisResults', 'AlignmentAlgorithm', 'MulticamAlgorithm',
+           'MulticamAlignmentAlgorithm', 'RegistrationTransformation', 'Vector3']
+
+#: a 4x4 float64 matrix; three floats
+RegistrationTransformation = numpy.ndarray
+Vector3 = Any
 
 
 class AnalysisResults:
@@ -89,3 +95,89 @@ class AnalysisAlgorithm(ABC):
 
     @abstractmethod
     def get_results(self) -> AnalysisResults: ...
+
+
+class AlignmentAlgorithm(ABC):
+    """An algorithm that looks for the best alignment of one tile: a new matrix for that tile only (reference abstract.py:226-247).
+    The fine aligners of registration/fine.py have this surface; they are used through it, not derived from it."""
+    verbose: bool
+
+    @abstractmethod
+    def set_source_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None: ...
+
+    @abstractmethod
+    def set_reference_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None: ...
+
+    @abstractmethod
+    def set_correspondence(self, correspondence: float) -> None:
+        """The largest distance between two points that may be "the same" point."""
+
+    @abstractmethod
+    def run(self) -> bool: ...
+
+    @abstractmethod
+    def get_result_transformation(self) -> RegistrationTransformation:
+        """After run(): the transformation applied to the tile under test."""
+
+    @abstractmethod
+    def get_result_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        """After run(): the tile under test, moved."""
+
+    @abstractmethod
+    def get_result_pointcloud_full(self) -> cwipc_pointcloud_wrapper:
+        """After run(): all tiles together, the moved one among them."""
+
+
+class MulticamAlgorithm(ABC):
+    """Anything that works on a tiled cloud, one tile per camera (reference abstract.py:251-288): the cloud, the mapping between a
+    camera's index in the results and its tile number in the cloud, and run()."""
+    verbose: bool
+
+    @abstractmethod
+    def set_tiled_pointcloud(self, pc: cwipc_pointcloud_wrapper) -> None:
+        """The cloud whose tiles are the cameras."""
+
+    @abstractmethod
+    def camera_count(self) -> int: ...
+
+    @abstractmethod
+    def tilemask_for_camera_index(self, cam_index: int) -> int:
+        """The tile number (in the cloud) of this index (in the results)."""
+
+    @abstractmethod
+    def camera_index_for_tilemask(self, tilenum: int) -> int:
+        """... and back."""
+
+    @abstractmethod
+    def run(self) -> bool:
+        """False: it failed."""
+
+
+class MulticamAlignmentAlgorithm(MulticamAlgorithm):
+    """An algorithm that aligns all tiles (reference abstract.py:293-326): which analyzer and which aligner it uses, and its results."""
+
+    def __init__(self) -> None:
+        self.analyzer_class: Optional[Type[Any]] = None
+        self.aligner_class: Optional[Type[Any]] = None
+
+    def set_analyzer_class(self, analyzer_class: Type[Any]) -> None:
+        self.analyzer_class = analyzer_class
+
+    def set_aligner_class(self, aligner_class: Type[Any]) -> None:
+        self.aligner_class = aligner_class
+
+    def set_max_correspondence(self, max_correspondence: float) -> None:
+        """Overrides the distance within which matching points are looked for."""
+        assert False, f"{self.__class__.__name__} does not implement set_max_correspondence()"
+
+    def set_original_transform(self, cam_index: int, matrix: RegistrationTransformation) -> None:
+        """The matrix a camera has before the run."""
+        assert False, f"{self.__class__.__name__} does not implement set_original_transform()"
+
+    @abstractmethod
+    def get_result_transformations(self) -> List[RegistrationTransformation]:
+        """After run(): one transformation per tile."""
+
+    @abstractmethod
+    def get_result_pointcloud_full(self) -> cwipc_pointcloud_wrapper:
+        """After run(): all tiles together, moved."""

@@ -11,21 +11,29 @@ Where it runs: the clouds stay on the device (tile mask and floor filter are dev
 reductions over them -- mean, std, median, trimmed mean, percentile, count -- are numpy on the host on purpose: the array is bit for
 bit the one the reference gets from scipy's KD-tree, so the same numpy calls give the same numbers.  scipy is not needed.
 
+The clouds an analyzer is given are masked when they are first asked for, not when they are set, and filters can be applied to them
+(apply_source_filter, apply_reference_filter: reference registration/util.py:367-395).  run_analyzers_batched runs a list of analyzers
+that look at subsets of ONE pair of clouds -- every camera of a frame against the others, as registration/multicamera.py asks -- with
+one cwipc_hip_nn_distance_jobs call per direction: no tile compaction, no floor crop, one grid; the distances are the per-analyzer
+path's bit for bit, so the results are too.
+
 OverlapAnalyzer, the reference's third analyzer (open3d's evaluate_registration there), is one correspondence search and two sums
 on the device (cwipc_hip_icp_sums at the identity): the fraction of source points with a reference point within the
 correspondence, and the root mean square of their distances.
 """
 import math
-from typing import Any, List, Optional, Tuple
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..util import (cwipc_pointcloud_wrapper, cwipc_tilefilter_masked, cwipc_crop, cwipc_hip_nn_distance,
-                    cwipc_hip_gaussian_kde, cwipc_hip_icp_sums)
+from ..util import (cwipc_pointcloud_wrapper, cwipc_tilefilter_masked, cwipc_crop, cwipc_floor_filter, cwipc_hip_nn_distance,
+                    cwipc_hip_nn_distance_jobs, NNJob, cwipc_hip_gaussian_kde, cwipc_hip_icp_sums)
 from .abstract import AnalysisAlgorithm, AnalysisResults, OverlapAnalysisResults
 
 __all__ = ['RegistrationAnalyzer', 'RegistrationAnalyzerSymmetric', 'OverlapAnalyzer', 'DEFAULT_ANALYZER_ALGORITHM',
-           'ALL_ANALYZER_ALGORITHMS', 'trim_mean', 'FLOOR_Y']
+           'ALL_ANALYZER_ALGORITHMS', 'trim_mean', 'FLOOR_Y', 'run_analyzers_batched', 'build_analyzer_jobs']
+
+PointCloudFilter = Callable[[cwipc_pointcloud_wrapper], cwipc_pointcloud_wrapper]
 
 #: the floor filter keeps a point iff its float32 y > 0.1
 FLOOR_Y = 0.1
@@ -56,10 +64,18 @@ def _floor_filter(pc: cwipc_pointcloud_wrapper) -> cwipc_pointcloud_wrapper:
 
 class _BaseRegistrationAnalyzer(AnalysisAlgorithm):
     def __init__(self) -> None:
+        # per side: the cloud as it was given, the masked cloud (made when first asked for), the cloud after the applied filters
+        self._source_given: Optional[cwipc_pointcloud_wrapper] = None
+        self._reference_given: Optional[cwipc_pointcloud_wrapper] = None
         self._source_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
         self._reference_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self._filtered_source_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self._filtered_reference_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self._filters_applied = 0
         self.source_tilemask: Optional[int] = None
         self.reference_tilemask: Optional[int] = None
+        #: a floor level: only the source points with y < level take part (set_source_floor_only)
+        self.source_floor_only: Optional[float] = None
         self.verbose = False
         self.histogram_bincount = 400
         self.max_correspondence_distance: float = np.inf
@@ -77,8 +93,6 @@ class _BaseRegistrationAnalyzer(AnalysisAlgorithm):
     def _masked(self, which: str, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int]) -> cwipc_pointcloud_wrapper:
         name = self.__class__.__name__
         before = pc.count()
-        if before == 0:
-            print(f"{name}: set_{which}_pointcloud: Warning: pre_count={before}")
         if tilemask is None:
             if self.verbose:
                 print(f"{name}: Setting {which} point cloud with {before} points")
@@ -92,21 +106,60 @@ class _BaseRegistrationAnalyzer(AnalysisAlgorithm):
             print(f"{name}: Setting {which} point cloud with {after} (of {before}) points using tilemask {tilemask:#x}")
         return pc
 
+    def _given(self, which: str, pc: cwipc_pointcloud_wrapper) -> cwipc_pointcloud_wrapper:
+        if pc.count() == 0:
+            print(f"{self.__class__.__name__}: set_{which}_pointcloud: Warning: pre_count=0")
+        return pc
+
     def set_source_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
-        self._source_pointcloud = self._masked("source", pc, tilemask)
+        """The tile mask is applied when the cloud is first asked for: a batched run (run_analyzers_batched) never asks."""
+        self._source_given = self._given("source", pc)
+        self._source_pointcloud = None
+        self._filtered_source_pointcloud = None
         self.source_tilemask = tilemask
 
     def set_reference_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
-        self._reference_pointcloud = self._masked("reference", pc, tilemask)
+        self._reference_given = self._given("reference", pc)
+        self._reference_pointcloud = None
+        self._filtered_reference_pointcloud = None
         self.reference_tilemask = tilemask
 
     def get_source_pointcloud(self) -> cwipc_pointcloud_wrapper:
-        assert self._source_pointcloud
+        if self._source_pointcloud is None:
+            assert self._source_given is not None
+            self._source_pointcloud = self._masked("source", self._source_given, self.source_tilemask)
         return self._source_pointcloud
 
     def get_reference_pointcloud(self) -> cwipc_pointcloud_wrapper:
-        assert self._reference_pointcloud
+        if self._reference_pointcloud is None:
+            assert self._reference_given is not None
+            self._reference_pointcloud = self._masked("reference", self._reference_given, self.reference_tilemask)
         return self._reference_pointcloud
+
+    # ---- filters (reference registration/util.py:367-395) ----
+    def get_filtered_source_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        if self._filtered_source_pointcloud is not None:
+            return self._filtered_source_pointcloud
+        return self.get_source_pointcloud()
+
+    def get_filtered_reference_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        if self._filtered_reference_pointcloud is not None:
+            return self._filtered_reference_pointcloud
+        return self.get_reference_pointcloud()
+
+    def apply_source_filter(self, filter: PointCloudFilter) -> None:
+        """The distances are taken from the filtered cloud; filters applied one after the other stack."""
+        self._filtered_source_pointcloud = filter(self.get_filtered_source_pointcloud())
+        self._filters_applied += 1
+
+    def apply_reference_filter(self, filter: PointCloudFilter) -> None:
+        self._filtered_reference_pointcloud = filter(self.get_filtered_reference_pointcloud())
+        self._filters_applied += 1
+
+    def set_source_floor_only(self, level: Optional[float] = FLOOR_Y) -> None:
+        """Only the source points on the floor (y < level) take part: apply_source_filter(lambda pc: cwipc_floor_filter(pc, keep=True))
+        as a setting -- a batched run can read a setting, it cannot read a lambda.  None: off."""
+        self.source_floor_only = level
 
     # ---- settings ----
     def set_correspondence_measure(self, method: str, *other_methods: str) -> None:
@@ -137,18 +190,25 @@ class _BaseRegistrationAnalyzer(AnalysisAlgorithm):
         return self.results
 
     # ---- one run ----
-    def _prepare(self) -> Tuple[cwipc_pointcloud_wrapper, cwipc_pointcloud_wrapper, List[cwipc_pointcloud_wrapper]]:
-        """A fresh result record and the two clouds the distances are taken between, still on the device; the third value lists
-        the clouds made here, for the caller to free."""
+    def _new_results(self) -> None:
         self.results = AnalysisResults()
         self.results.algorithm = self.__class__.__name__
         self.results.tilemask = self.source_tilemask
         self.results.referenceTilemask = self.reference_tilemask
         if self.variants:
             self.results.variant = ",".join(self.variants)
+
+    def _prepare(self) -> Tuple[cwipc_pointcloud_wrapper, cwipc_pointcloud_wrapper, List[cwipc_pointcloud_wrapper]]:
+        """A fresh result record and the two clouds the distances are taken between, still on the device; the third value lists
+        the clouds made here, for the caller to free."""
+        self._new_results()
         made: List[cwipc_pointcloud_wrapper] = []
         clouds = []
-        for pc in (self.get_source_pointcloud(), self.get_reference_pointcloud()):
+        source = self.get_filtered_source_pointcloud()
+        if self.source_floor_only is not None:
+            source = cwipc_floor_filter(source, self.source_floor_only, keep=True)
+            made.append(source)
+        for pc in (source, self.get_filtered_reference_pointcloud()):
             if self.ignore_floor:
                 kept = _floor_filter(pc)
                 made.append(kept)
@@ -242,6 +302,7 @@ class _BaseRegistrationAnalyzer(AnalysisAlgorithm):
 
 class RegistrationAnalyzer(_BaseRegistrationAnalyzer):
     """Distances from every source point to the reference cloud."""
+    directions = 1
 
     def run(self) -> bool:
         source, reference, made = self._prepare()
@@ -250,20 +311,28 @@ class RegistrationAnalyzer(_BaseRegistrationAnalyzer):
         finally:
             for pc in made:
                 pc.free()
-        return self._analyze(distances)
+        return self._finish([distances])
+
+    def _finish(self, rows: Sequence[np.ndarray]) -> bool:
+        """From the distances (one array per direction of `directions`) to the results; the point counts are set already."""
+        return self._analyze(rows[0])
 
 
 class RegistrationAnalyzerSymmetric(_BaseRegistrationAnalyzer):
     """Distances both ways round -- source points to the reference cloud, reference points to the source cloud -- as one set."""
+    directions = 2
 
     def run(self) -> bool:
         source, reference, made = self._prepare()
         try:
-            distances = np.concatenate((self._distances(source, reference), self._distances(reference, source)))
+            rows = [self._distances(source, reference), self._distances(reference, source)]
         finally:
             for pc in made:
                 pc.free()
-        if not self._analyze(distances):
+        return self._finish(rows)
+
+    def _finish(self, rows: Sequence[np.ndarray]) -> bool:
+        if not self._analyze(np.concatenate((rows[0], rows[1]))):
             return False
         # both counts become the number of points that took part
         total = self.results.sourcePointCount + self.results.referencePointCount
@@ -282,6 +351,8 @@ class OverlapAnalyzer:
         self.source_tilemask: Optional[int] = None
         self.reference_tilemask: Optional[int] = None
         self.verbose = False
+        self._filtered_source_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
+        self._filtered_reference_pointcloud: Optional[cwipc_pointcloud_wrapper] = None
         self.correspondence: float = np.inf
         self.results: Optional[OverlapAnalysisResults] = None
 
@@ -290,19 +361,40 @@ class OverlapAnalyzer:
 
     def set_source_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
         self._source_pointcloud = self._masked(pc, tilemask)
+        self._filtered_source_pointcloud = None
         self.source_tilemask = tilemask
 
     def set_reference_pointcloud(self, pc: cwipc_pointcloud_wrapper, tilemask: Optional[int] = None) -> None:
         self._reference_pointcloud = self._masked(pc, tilemask)
+        self._filtered_reference_pointcloud = None
         self.reference_tilemask = tilemask
+
+    def get_source_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        assert self._source_pointcloud is not None
+        return self._source_pointcloud
+
+    def get_reference_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        assert self._reference_pointcloud is not None
+        return self._reference_pointcloud
+
+    def get_filtered_source_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        return self._filtered_source_pointcloud if self._filtered_source_pointcloud is not None else self.get_source_pointcloud()
+
+    def get_filtered_reference_pointcloud(self) -> cwipc_pointcloud_wrapper:
+        return self._filtered_reference_pointcloud if self._filtered_reference_pointcloud is not None else self.get_reference_pointcloud()
+
+    def apply_source_filter(self, filter: PointCloudFilter) -> None:
+        self._filtered_source_pointcloud = filter(self.get_filtered_source_pointcloud())
+
+    def apply_reference_filter(self, filter: PointCloudFilter) -> None:
+        self._filtered_reference_pointcloud = filter(self.get_filtered_reference_pointcloud())
 
     def set_correspondence(self, correspondence: float) -> None:
         """The largest distance between two points that still counts as a match."""
         self.correspondence = correspondence
 
     def run(self) -> bool:
-        assert self._source_pointcloud is not None and self._reference_pointcloud is not None
-        source, reference = self._source_pointcloud, self._reference_pointcloud
+        source, reference = self.get_filtered_source_pointcloud(), self.get_filtered_reference_pointcloud()
         count = source.count()
         n, sums = cwipc_hip_icp_sums(source, reference, None, self.correspondence)
         r = OverlapAnalysisResults()
@@ -320,6 +412,110 @@ class OverlapAnalyzer:
     def get_results(self) -> OverlapAnalysisResults:
         assert self.results
         return self.results
+
+
+# ---- a list of analyzers over one pair of clouds, as one batch ----
+MAX_BATCH_JOBS = 64
+
+
+def _job_mask(tilemask: Optional[int]) -> Optional[int]:
+    """The job's mask byte for an analyzer's tile mask (None and 0: every tile, a job's 0), or None for a mask a byte cannot hold."""
+    if tilemask is None:
+        return 0
+    if not isinstance(tilemask, (int, np.integer)) or tilemask < 0 or tilemask > 255:
+        return None
+    return int(tilemask)
+
+
+def build_analyzer_jobs(analyzers: Sequence[Any]) -> Optional[Tuple[List[NNJob], List[NNJob], List[int]]]:
+    """The jobs that run `analyzers` as one batch: (forward jobs, one per analyzer, for the call on (source, reference); backward jobs
+    for the call on (reference, source); which analyzer each backward job belongs to -- the symmetric ones, in order).  None when
+    the list does not qualify: every analyzer must be a RegistrationAnalyzer or RegistrationAnalyzerSymmetric with its own run(), all
+    must have been given the same source cloud object and the same reference cloud object, none may have had a filter callable applied,
+    and masks, ignore_nearest and max_correspondence_distance must be what a job can hold.  What may differ: the tile masks, the floor
+    settings (ignore_floor, source_floor_only), and whatever does not touch the search (measures, histogram settings)."""
+    if not analyzers:
+        return None
+    first = analyzers[0]
+    forward: List[NNJob] = []
+    backward: List[NNJob] = []
+    owners: List[int] = []
+    for i, a in enumerate(analyzers):
+        if type(a) not in (RegistrationAnalyzer, RegistrationAnalyzerSymmetric):
+            return None
+        if a._source_given is None or a._reference_given is None:
+            return None
+        if a._source_given is not first._source_given or a._reference_given is not first._reference_given:
+            return None
+        if a._filters_applied:
+            return None
+        smask, rmask = _job_mask(a.source_tilemask), _job_mask(a.reference_tilemask)
+        if smask is None or rmask is None:
+            return None
+        nth, bound = a.ignore_nearest, a.max_correspondence_distance
+        if not isinstance(nth, (int, np.integer)) or nth < 0 or nth > 31 or not (bound > 0):
+            return None
+        inf = math.inf
+        floor_lo = NNJob.ignore_floor(FLOOR_Y)[0] if a.ignore_floor else -inf
+        source_y = (floor_lo, NNJob.floor_only(a.source_floor_only)[1] if a.source_floor_only is not None else inf)
+        reference_y = (floor_lo, inf)
+        forward.append(NNJob(source_mask=smask, reference_mask=rmask, nth=nth, max_distance=bound, source_y=source_y, reference_y=reference_y))
+        if a.directions == 2:
+            backward.append(NNJob(source_mask=rmask, reference_mask=smask, nth=nth, max_distance=bound, source_y=reference_y, reference_y=source_y))
+            owners.append(i)
+    return forward, backward, owners
+
+
+def _reference_count(a: Any, cache: dict) -> int:
+    """How many reference points take part in a one-directional analyzer's run: through the very filters of its _prepare, once per
+    distinct (mask, floor) of the batch."""
+    key = (a.reference_tilemask, a.ignore_floor)
+    if key not in cache:
+        pc = a.get_reference_pointcloud()
+        if a.ignore_floor:
+            kept = _floor_filter(pc)
+            cache[key] = kept.count()
+            kept.free()
+        else:
+            cache[key] = pc.count()
+    return cache[key]
+
+
+def run_analyzers_batched(analyzers: Sequence[Any]) -> List[bool]:
+    """run() for every analyzer of the list; what each run() would have returned.  A list that qualifies (build_analyzer_jobs) makes
+    one cwipc_hip_nn_distance_jobs call per direction -- forward for all, backward for the symmetric analyzers -- in place of two
+    compactions, two floor crops, a grid and a search per analyzer and direction; any other list is run one by one.  Either way the
+    AnalysisResults are the same, bit for bit: a job's row IS the array the per-analyzer search returns.  Fewer launches is not
+    less time: on an MI355X the batch measured slower than the analyzers one by one."""
+    analyzers = list(analyzers)
+    built = build_analyzer_jobs(analyzers)
+    if built is None:
+        return [a.run() for a in analyzers]
+    forward, backward, owners = built
+    source, reference = analyzers[0]._source_given, analyzers[0]._reference_given
+
+    def rows_of(src: cwipc_pointcloud_wrapper, ref: cwipc_pointcloud_wrapper, jobs: List[NNJob]) -> List[np.ndarray]:
+        rows: List[np.ndarray] = []
+        for at in range(0, len(jobs), MAX_BATCH_JOBS):
+            rows.extend(cwipc_hip_nn_distance_jobs(src, ref, jobs[at:at + MAX_BATCH_JOBS]))
+        return rows
+
+    forward_rows = rows_of(source, reference, forward)
+    backward_rows = dict(zip(owners, rows_of(reference, source, backward)))
+    counts: dict = {}
+    rv = []
+    for i, a in enumerate(analyzers):
+        a._new_results()
+        a.results.sourcePointCount = int(forward_rows[i].shape[0])
+        if a.directions == 2:
+            a.results.referencePointCount = int(backward_rows[i].shape[0])
+            rv.append(a._finish([forward_rows[i], backward_rows[i]]))
+        else:
+            same_side = (source is reference and forward[i].source_mask == forward[i].reference_mask and
+                         tuple(forward[i].source_y) == tuple(forward[i].reference_y))
+            a.results.referencePointCount = a.results.sourcePointCount if same_side else _reference_count(a, counts)
+            rv.append(a._finish([forward_rows[i]]))
+    return rv
 
 
 DEFAULT_ANALYZER_ALGORITHM = RegistrationAnalyzerSymmetric

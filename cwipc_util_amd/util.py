@@ -41,9 +41,9 @@ __all__ = [
     # MI355X extensions (no reference counterpart)
     'cwipc_hip_device_count', 'cwipc_hip_set_device', 'cwipc_hip_upload', 'cwipc_hip_pinned_points', 'cwipc_hip_pin_array', 'cwipc_hip_colorize', 'cwipc_tilefilter_masked', 'cwipc_hip_device_planes',
     'cwipc_hip_profile', 'cwipc_hip_knn_mean_dist', 'cwipc_hip_from_device_aos', 'cwipc_hip_from_device_slots', 'cwipc_hip_copy_device_aos',
-    'cwipc_transform', 'cwipc_offset_scale', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
+    'cwipc_transform', 'cwipc_offset_scale', 'cwipc_hip_flatten_y', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
-    'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde',
+    'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde', 'NNJob', 'cwipc_hip_nn_distance_jobs', 'compact_job_rows',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
@@ -223,6 +223,7 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_simulatecams': ([cwipc_pointcloud_p, _c.c_int, _c.c_float, _c.c_float, _c.c_void_p], cwipc_pointcloud_p),
     'cwipc_hip_tilefilter_masked': ([cwipc_pointcloud_p, _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_transform': ([cwipc_pointcloud_p, _c.POINTER(_c.c_double)], cwipc_pointcloud_p),
+    'cwipc_hip_flatten_y': ([cwipc_pointcloud_p], cwipc_pointcloud_p),
     'cwipc_hip_offset_scale': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double], cwipc_pointcloud_p),
     'cwipc_hip_tiles_used': ([cwipc_pointcloud_p, _c.POINTER(_c.c_ubyte)], _c.c_int),
     'cwipc_hip_knn_mean_dist': ([cwipc_pointcloud_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_double), _c.c_float], _c.c_int),
@@ -245,6 +246,7 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
     'cwipc_hip_floor_radius_stats': ([cwipc_pointcloud_p, _c.c_double, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_float)], _c.c_int),
+    'cwipc_hip_nn_distance2_jobs': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_tile_counts': ([cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], _c.c_int),
     'cwipc_hip_bounds': ([cwipc_pointcloud_p, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
@@ -1169,6 +1171,12 @@ def cwipc_transform(pc: cwipc_pointcloud_wrapper, transform: Any) -> cwipc_point
     return _wrap_filter_result('cwipc_transform', rv)
 
 
+def cwipc_hip_flatten_y(pc: cwipc_pointcloud_wrapper) -> cwipc_pointcloud_wrapper:
+    """The cloud projected onto the plane y = 0: x, z, colours and tiles kept, y = +0.0, timestamp 0, cellsize 0 -- what the reference's
+    MultiCameraToFloor._prepare_floor makes through numpy (registration/multicamera.py:399-403), here without leaving the device."""
+    return _wrap_filter_result('cwipc_hip_flatten_y', cwipc_util_dll_load().cwipc_hip_flatten_y(pc.as_cwipc_p()))
+
+
 def cwipc_offset_scale(pc: cwipc_pointcloud_wrapper, x: float, y: float, z: float, scale: float) -> cwipc_pointcloud_wrapper:
     """(p + (x, y, z)) * scale for every point, cellsize * scale (the loop of the reference's TransformFilter,
     python/cwipc/filters/transform.py:38-52, in the same float64 arithmetic)."""
@@ -1255,6 +1263,63 @@ def cwipc_hip_nn_distance(source: cwipc_pointcloud_wrapper, reference: cwipc_poi
     if rc != 0:
         raise CwipcError("cwipc_hip_nn_distance2 failed")
     return numpy.sqrt(out[:n])
+
+
+class NNJob(ctypes.Structure):
+    """One job of cwipc_hip_nn_distance_jobs (include/cwipc_util_amd/hip_ext.h: cwipc_hip_nn_job): which points of the source and of the
+    reference cloud take part -- a tile mask (0: every tile) and an open y interval per side -- and the search's nth and bound.
+    Keyword construction; the y limits go through _threshold, so that `y > 0.1` and `y < level` mean what numpy means by them on a
+    float32 column: NNJob.ignore_floor() and NNJob.floor_only(level) give the two intervals the tooling uses."""
+    _fields_ = [("source_mask", ctypes.c_uint8), ("reference_mask", ctypes.c_uint8), ("nth", ctypes.c_int32), ("max_distance", ctypes.c_double),
+                ("source_y", ctypes.c_double * 2), ("reference_y", ctypes.c_double * 2)]
+
+    def __init__(self, source_mask: int = 0, reference_mask: int = 0, nth: int = 0, max_distance: float = float('inf'),
+                 source_y: Sequence[Any] = (-float('inf'), float('inf')), reference_y: Sequence[Any] = (-float('inf'), float('inf'))) -> None:
+        super().__init__()
+        self.source_mask = int(source_mask)
+        self.reference_mask = int(reference_mask)
+        self.nth = int(nth)
+        self.max_distance = float(max_distance)
+        self.source_y[0], self.source_y[1] = _threshold(source_y[0]), _threshold(source_y[1])
+        self.reference_y[0], self.reference_y[1] = _threshold(reference_y[0]), _threshold(reference_y[1])
+
+    @staticmethod
+    def ignore_floor(level: Any = 0.1) -> Tuple[float, float]:
+        """The interval of the points that are not floor: y > level."""
+        return (_threshold(level), float('inf'))
+
+    @staticmethod
+    def floor_only(level: Any = 0.1) -> Tuple[float, float]:
+        """The interval of cwipc_floor_filter(keep=True): y < level."""
+        return (-float('inf'), _threshold(level))
+
+    def __repr__(self) -> str:
+        return (f"NNJob(source_mask={self.source_mask}, reference_mask={self.reference_mask}, nth={self.nth}, max_distance={self.max_distance}, "
+                f"source_y={tuple(self.source_y)}, reference_y={tuple(self.reference_y)})")
+
+
+def compact_job_rows(dist2: numpy.ndarray) -> List[numpy.ndarray]:
+    """Per row of cwipc_hip_nn_distance2_jobs' result (squared distances, NaN where the source point takes no part in the row's job):
+    the distances of the points that do take part, in source order, after the root."""
+    return [numpy.sqrt(row[~numpy.isnan(row)]) for row in numpy.asarray(dist2, dtype=numpy.float64)]
+
+
+def cwipc_hip_nn_distance_jobs(source: cwipc_pointcloud_wrapper, reference: cwipc_pointcloud_wrapper, jobs: Sequence[NNJob]) -> List[numpy.ndarray]:
+    """cwipc_hip_nn_distance for a list of jobs over one pair of clouds, in one call and over one grid: per job the array that
+    cwipc_hip_nn_distance(filtered source, filtered reference, job.nth, job.max_distance) returns, bit for bit, the filters being the
+    job's tile masks and y intervals (NNJob).  Nothing is compacted on the device: the kernel writes NaN for a source point that
+    takes no part in a job, and those entries are dropped here."""
+    if source is None or reference is None:
+        raise CwipcError("cwipc_hip_nn_distance_jobs: NULL pointcloud")
+    jobs = list(jobs)
+    table = (NNJob * max(len(jobs), 1))(*jobs)
+    n = source.count()
+    out = numpy.zeros((max(len(jobs), 1), max(n, 1)), dtype=numpy.float64)
+    rc = cwipc_util_dll_load().cwipc_hip_nn_distance2_jobs(source.as_cwipc_p(), reference.as_cwipc_p(), ctypes.addressof(table), len(jobs), out.ctypes.data,
+                                                           out.shape[1])
+    if rc != 0:
+        raise CwipcError("cwipc_hip_nn_distance2_jobs failed")
+    return compact_job_rows(out[:len(jobs), :n])
 
 
 def _matrix4(name: str, transform: Any) -> Optional[numpy.ndarray]:

@@ -126,6 +126,9 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_join_multi(cwipc_pointcloud **pcs
 /* p' = R p + t for a row-major 4x4 matrix (last row ignored), in f64, stored as float: what the reference's
  * cwipc_transform does through numpy (python/cwipc/registration/util.py:295-309). */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_transform(cwipc_pointcloud *pc, const double *matrix4x4);
+/* Every point projected onto the plane y = 0 (MultiCameraToFloor's floor cloud): x, z, colours and tiles kept, y = +0.0, timestamp 0,
+ * cellsize 0.  A copy of two planes and a memset on the device.  NULL (logged) on failure. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_flatten_y(cwipc_pointcloud *pc);
 /* p' = (p + (x, y, z)) * scale in f64, cellsize * scale: the reference's TransformFilter loop (python/cwipc/filters/transform.py:38-52). */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_offset_scale(cwipc_pointcloud *pc, double x, double y, double z, double scale);
 /* used256[t] = 1 for every tile value t that occurs (python/cwipc/registration/util.py:285-293, get_tiles_used); returns how many, -1 on error. */
@@ -174,6 +177,25 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]);
  * (the point itself is then the nearest, at 0) and are neither consumed nor changed.  An empty source writes nothing, an empty
  * reference gives +inf everywhere.  0 ok; -1 (logged) for a NULL cloud, nth < 0 or > 31, max_distance NaN or <= 0, cap too small. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_nn_distance2(cwipc_pointcloud *source, cwipc_pointcloud *reference, int nth, double max_distance, double *dist2, size_t cap);
+/* The same search for up to 64 JOBS over one pair of clouds in one call (registration/multicamera.py: every camera of a frame against
+ * the others): a job names the points that take part by a tile mask and an open y interval per side, instead of by filtered clouds.
+ * dist2: host array of njobs rows of cap >= count(source) doubles; dist2[j * cap + i] is NaN where source point i takes no part in job
+ * j, otherwise the squared distance (the arithmetic above) to its (nth + 1)-th nearest PARTICIPATING reference point strictly under
+ * max_distance, +inf where there is none -- the bits cwipc_hip_nn_distance2 gives for the two filtered clouds.  The clouds may be the
+ * same one (the point itself is then a candidate if it takes part as a reference point); they are neither consumed nor changed.
+ * The y limits in the doubles the floor predicates use: ignore_floor (y > float32(0.1)) is {(double)float32(0.1), +inf} on both sides,
+ * cwipc_floor_filter(keep=True) (y < float32(level)) is {-inf, (double)float32(level)}.  0 ok; -1 (logged) for a NULL cloud, njobs
+ * outside 1..64, a job with nth outside 0..31, max_distance NaN or <= 0 or a NaN y limit, cap too small. */
+typedef struct cwipc_hip_nn_job {
+    uint8_t  source_mask;      /* a source point takes part iff (tile & source_mask) != 0; 0: every source point */
+    uint8_t  reference_mask;   /* the same for reference points */
+    int32_t  nth;              /* 0..31, as cwipc_hip_nn_distance2 */
+    double   max_distance;     /* > 0, INFINITY: no bound */
+    double   source_y[2];      /* a source point takes part iff source_y[0] < (double)y < source_y[1]; -inf / +inf: no limit */
+    double   reference_y[2];   /* the same for reference points */
+} cwipc_hip_nn_job;
+_CWIPC_UTIL_EXPORT int cwipc_hip_nn_distance2_jobs(cwipc_pointcloud *source, cwipc_pointcloud *reference, const cwipc_hip_nn_job *jobs, int njobs,
+                                                   double *dist2, size_t cap);
 /* 1-D Gaussian kernel density estimate: density[j] = sum_i exp(-0.5 ((at[j] - samples[i]) / h)^2) / (n h sqrt(2 pi)) in f64, summed in
  * an order fixed by n (what scipy.stats.gaussian_kde(samples).evaluate(at) computes for h = std(samples, ddof=1) * factor).  Host
  * arrays: n samples, m evaluation points, m densities.  0 ok; -1 (logged) for n == 0, h not finite or <= 0, a NULL array. */
