@@ -40,6 +40,7 @@ SOURCES = [
     "kernels_kde.hip",
     "kernels_icp.hip",
     "kernels_floor.hip",
+    "kernels_render.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -49,6 +49,11 @@ bool hip_failed(hipError_t err, const char *what, const char *file, int line) {
     return false;
 }
 
+void note_error(const char *who, const std::string &message) {
+    t_last_error = std::string(who) + ": " + message;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, message);
+}
+
 int current_device() {
     int d = g_device.load();
     if (d == -2) {

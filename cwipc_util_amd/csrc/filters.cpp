@@ -1235,3 +1235,83 @@ extern "C" int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]) {
         }
     return 0;
 }
+
+// ---------------------------------------------------------------------------
+// reference python/cwipc/registration/multicoarse.py:333-360 (the open3d window's colour and depth capture of one camera's tile)
+// ---------------------------------------------------------------------------
+extern "C" long cwipc_hip_render(cwipc_pointcloud *pc, const cwipc_hip_view *view, int point_size, int tilemask, const uint8_t background[3], uint8_t *rgb,
+                                 float *depth, int32_t *index) {
+    const char *who = "cwipc_hip_render";
+    if (pc == nullptr || view == nullptr || background == nullptr || rgb == nullptr || depth == nullptr) {
+        note_error(who, "NULL argument");
+        return -1;
+    }
+    if (view->width < 1 || view->height < 1 || (int64_t)view->width * (int64_t)view->height > ((int64_t)1 << 24)) {
+        note_error(who, "width and height must be at least 1 and width * height at most 2^24");
+        return -1;
+    }
+    if (point_size < 1 || point_size > 15 || (point_size & 1) == 0) {
+        note_error(who, "point_size must be odd and between 1 and 15");
+        return -1;
+    }
+    bool finite = std::isfinite(view->fx) && std::isfinite(view->fy) && std::isfinite(view->cx) && std::isfinite(view->cy);
+    for (int i = 0; i < 16; i++) finite = finite && std::isfinite(view->extrinsic[i]);
+    if (!finite) {
+        note_error(who, "the intrinsics and the extrinsic matrix must be finite");
+        return -1;
+    }
+    if (!(view->near > 0.0) || !(view->far > view->near)) {
+        note_error(who, "near must be positive and far greater than near (inf: no far plane)");
+        return -1;
+    }
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input(who, pc, keep);
+    if (!src) {
+        if (!*cwipc_hip_last_error()) note_error(who, "the argument has no point data");
+        return -1;
+    }
+    if (src->npoints >= 0xFFFFFFFFull) {   // (the key's low word; a cloud's count is an int anyway)
+        note_error(who, "too many points");
+        return -1;
+    }
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const size_t npix = (size_t)view->width * (size_t)view->height;
+    // one block for what goes back: the count | depth | rgb | index, each part on a 16-byte boundary
+    const size_t plane = (npix * 4 + 15) & ~(size_t)15, rgb_bytes = (npix * 3 + 15) & ~(size_t)15;
+    const size_t off_depth = 16, off_rgb = off_depth + plane, off_index = off_rgb + rgb_bytes;
+    const size_t back_bytes = index ? off_index + plane : off_index;
+    unsigned long long *keys = (unsigned long long *)pool_alloc(npix * sizeof(unsigned long long));
+    uint8_t *dev = (uint8_t *)pool_alloc(back_bytes);
+    uint8_t *host = (uint8_t *)c.staging(back_bytes);
+    if (!keys || !dev || !host) {
+        pool_free(keys);
+        pool_free(dev);
+        note_error(who, "out of memory");
+        return -1;
+    }
+    k::RenderArgs a;
+    a.width = view->width; a.height = view->height; a.half = (point_size - 1) / 2; a.tilemask = tilemask;
+    a.fx = view->fx; a.fy = view->fy; a.cx = view->cx; a.cy = view->cy; a.near_z = view->near; a.far_z = view->far;
+    for (int i = 0; i < 12; i++) a.e[i] = view->extrinsic[i];
+    const uint32_t bg = (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16);
+    k::render_fill(keys, npix, (uint32_t *)dev, c.stream);
+    k::render_splat(*src, a, keys, c.stream);
+    k::render_resolve(keys, src->npoints ? src->rgbt() : nullptr, npix, bg, (float *)(dev + off_depth), dev + off_rgb,
+                      index ? (int32_t *)(dev + off_index) : nullptr, (uint32_t *)dev, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(host, dev, back_bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;   // (also on failure: kernels that write the blocks may still be in flight)
+    pool_free(keys);
+    pool_free(dev);
+    if (!ok) {
+        if (!*cwipc_hip_last_error()) note_error(who, "a kernel or a copy failed");
+        return -1;
+    }
+    parallel_memcpy(depth, host + off_depth, npix * sizeof(float));
+    parallel_memcpy(rgb, host + off_rgb, npix * 3);
+    if (index) parallel_memcpy(index, host + off_index, npix * sizeof(int32_t));
+    uint32_t covered;
+    memcpy(&covered, host, sizeof(covered));
+    return (long)covered;
+}

@@ -46,6 +46,8 @@ bool api_version_rejected(const char *fname, uint64_t apiVersion, char **errorMe
 
 // Record a HIP failure: thread-local text + cwipc_log(ERROR).  Returns false.
 bool hip_failed(hipError_t err, const char *what, const char *file, int line);
+// The same for a call that was turned away before it reached the device (bad arguments): the text cwipc_hip_last_error() returns.
+void note_error(const char *who, const std::string &message);
 #define CW_HIP_OK(expr) ((expr) == hipSuccess ? true : ::cwipc_amd::hip_failed(hipGetLastError(), #expr, __FILE__, __LINE__))
 #define CW_HIP_TRY(expr)                                                            \
     do {                                                                            \
@@ -315,7 +317,8 @@ void count_alloc();
 void count_dealloc();
 
 // ---------------------------------------------------------------------------
-// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip, kernels_icp.hip;
+// kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip, kernels_icp.hip,
+// kernels_floor.hip, kernels_render.hip;
 // the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
@@ -413,6 +416,22 @@ void tile_histogram(const DeviceSoA &src, int nonfloor_only, double level, unsig
 // per workgroup min x, y, z, max x, y, z (NaN skipped per coordinate; +inf / -inf where there is nothing): bounds_blocks(n) x 6 floats
 unsigned bounds_blocks(size_t n);
 void bounds_partial(const DeviceSoA &src, float *partial, hipStream_t s);
+
+// ---- kernels_render.hip: cwipc_hip_render (the contract is at the top of that file and in hip_ext.h) ----
+struct RenderArgs {
+    int width, height;
+    int half;        // (point_size - 1) / 2
+    int tilemask;
+    double fx, fy, cx, cy, near_z, far_z;
+    double e[12];    // rows 0-2 of the world -> camera matrix
+};
+// keys: width * height 64-bit words (float_bits(depth) << 32 | index, all ones: nothing).  fill also zeroes *covered, which resolve
+// counts the covered pixels into.  resolve writes depth (npix floats), rgb (3 npix bytes, 16-byte aligned) and index (npix words,
+// or nullptr); rgbt is only read for covered pixels.
+void render_fill(unsigned long long *keys, size_t npix, uint32_t *covered, hipStream_t s);
+void render_splat(const DeviceSoA &src, const RenderArgs &a, unsigned long long *keys, hipStream_t s);
+void render_resolve(const unsigned long long *keys, const uint32_t *rgbt, size_t npix, uint32_t background, float *depth, uint8_t *rgb, int32_t *index,
+                    uint32_t *covered, hipStream_t s);
 
 }  // namespace k
 

@@ -12,6 +12,11 @@ The multi-camera algorithms (`multicamera.MultiCameraIterative`, the default, `m
 `multicamera.MultiCameraToFloor`, `multicamera.MultiCameraToGroundTruth`) loop over those pieces and give one transformation per
 camera of a tiled capture; their per-camera analyses run as one batch (`analyze.run_analyzers_batched`, one tile-aware search over
 one grid: cwipc_hip_nn_distance_jobs).  The transformation helpers are in `util`.
+
+The step in front of them, from cameras that each have their own coordinates to a rough alignment, is `multicoarse.MultiCameraCoarse`
+and `multicoarse.MultiCameraCoarseAruco`: markers with known corners, found in an image of each camera's tile.  The image comes from
+`render` (`PinholeView`, `render_pointcloud`: a colour, depth and point-index image of a cloud on the GPU, cwipc_hip_render, where the
+reference opens a window), and `deproject` takes image corners back to 3D.
 """
 from .abstract import (AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults, AlignmentAlgorithm, MulticamAlgorithm,   # noqa: F401
                        MulticamAlignmentAlgorithm)
@@ -23,3 +28,5 @@ from .util import (transformation_identity, transformation_invert, transformatio
                    transformation_get_translation, transformation_compare, BaseMulticamAlgorithm)
 from .multicamera import (BaseMulticamAlignmentAlgorithm, MultiCameraOneToAllOthers, MultiCameraToFloor, MultiCameraToGroundTruth,   # noqa: F401
                           MultiCameraIterative, DEFAULT_MULTICAMERA_ALGORITHM, ALL_MULTICAMERA_ALGORITHMS, DEFAULT_MULTICAMERA_ALIGNER)
+from .render import PinholeView, default_view, look_at, render_pointcloud, deproject, mean_depth   # noqa: F401
+from .multicoarse import MultiCameraCoarse, MultiCameraCoarseAruco, MarkerPosition, MarkerPositions   # noqa: F401

@@ -49,6 +49,7 @@ __all__ = [
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
+    'cwipc_hip_view', 'cwipc_hip_render',
 ]
 
 # reference util.py:86, 346, 348
@@ -249,6 +250,7 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_nn_distance2_jobs': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_tile_counts': ([cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], _c.c_int),
     'cwipc_hip_bounds': ([cwipc_pointcloud_p, _c.POINTER(_c.c_float)], _c.c_int),
+    'cwipc_hip_render': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_long),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1159,6 +1161,38 @@ def cwipc_hip_bounds(pc: cwipc_pointcloud_wrapper) -> numpy.ndarray:
     if cwipc_util_dll_load().cwipc_hip_bounds(pc.as_cwipc_p(), minmax.ctypes.data_as(ctypes.POINTER(ctypes.c_float))) != 0:
         raise CwipcError("cwipc_hip_bounds failed")
     return minmax
+
+
+class cwipc_hip_view(ctypes.Structure):
+    """A pinhole view (include/cwipc_util_amd/hip_ext.h: cwipc_hip_view): the image size, the intrinsics, the depth range and the
+    world -> camera matrix (row-major).  The camera looks along +z, image x runs right, image y down."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double),
+                ("cy", ctypes.c_double), ("near", ctypes.c_double), ("far", ctypes.c_double), ("extrinsic", ctypes.c_double * 16)]
+
+
+def cwipc_hip_render(pc: cwipc_pointcloud_wrapper, view: cwipc_hip_view, point_size: int = 5, tilemask: int = 0,
+                     background: Sequence[int] = (255, 255, 255), want_index: bool = True) -> Tuple[numpy.ndarray, numpy.ndarray, Optional[numpy.ndarray]]:
+    """The cloud seen through a pinhole camera, every point a square of point_size x point_size pixels in a z-buffer on the GPU:
+    (rgb uint8[H, W, 3], depth float32[H, W], index int32[H, W]).  A pixel no point covers has depth 0, the background colour and
+    index -1; index is the winning point's position in `pc` (None with want_index=False).  tilemask != 0: only points with
+    (tile & tilemask) != 0 are drawn.  Point size 5 and the white background are open3d's defaults, which the reference's
+    MultiCameraCoarseAruco sees.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    if pc is None or view is None:
+        raise CwipcError("cwipc_hip_render: NULL argument")
+    h, w = max(int(view.height), 0), max(int(view.width), 0)
+    if h * w > (1 << 24):
+        h = w = 0   # (the library turns the call away; no arrays of that size are made for it)
+    rgb = numpy.zeros((h, w, 3), dtype=numpy.uint8)
+    depth = numpy.zeros((h, w), dtype=numpy.float32)
+    index = numpy.zeros((h, w), dtype=numpy.int32) if want_index else None
+    bg = (ctypes.c_uint8 * 3)(*[int(v) for v in background])
+    dll = cwipc_util_dll_load()
+    # (a dummy address for empty arrays: the library checks the sizes before it looks at them)
+    rc = dll.cwipc_hip_render(pc.as_cwipc_p(), ctypes.addressof(view), int(point_size), int(tilemask), ctypes.addressof(bg), rgb.ctypes.data or 1,
+                              depth.ctypes.data or 1, index.ctypes.data or 1 if index is not None else None)
+    if rc < 0:
+        raise CwipcError("cwipc_hip_render failed: " + dll.cwipc_hip_last_error().decode('utf8'))
+    return rgb, depth, index
 
 
 def cwipc_transform(pc: cwipc_pointcloud_wrapper, transform: Any) -> cwipc_pointcloud_wrapper:

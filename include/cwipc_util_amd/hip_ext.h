@@ -305,6 +305,36 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc
                                                  double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
                                                  double *inlier_rmse, int *iterations);
 
+/* ---- a cloud seen through a pinhole camera (reference python/cwipc/registration/multicoarse.py:333-360: MultiCameraCoarseAruco looks at
+ * a camera's tile from the origin in an open3d window and grabs the window's colour and depth buffers) ----
+ * Camera space looks along +z, image x runs right and image y down: the conventions of the reference's _deproject
+ * (multicoarse.py:426-428, x = (u - cx) * z / fx, y = (v - cy) * z / fy).  extrinsic: world -> camera, a row-major 4x4 whose last row is
+ * not read. */
+typedef struct cwipc_hip_view {
+    int32_t width, height;
+    double fx, fy, cx, cy, near, far;
+    double extrinsic[16];
+} cwipc_hip_view;
+/* Every point is drawn as a square of point_size x point_size pixels into a z-buffer.  Every operation is rounded on its own, in this
+ * order, E = extrinsic, h = (point_size - 1) / 2:
+ *  1. A point takes part iff (tilemask == 0 || (tile & tilemask) != 0) and x, y, z are finite.
+ *  2. In f64 from the float32 coordinates: xc = ((E00*x + E01*y) + E02*z) + E03, yc and zc alike from rows 1 and 2.
+ *  3. The point is dropped unless near < zc && zc < far.
+ *  4. u = fx*(xc/zc) + cx, v = fy*(yc/zc) + cy.
+ *  5. col = floor(u), row = floor(v); the point is dropped unless -(h+1) < floor(u) < width+h and -(h+1) < floor(v) < height+h, decided in
+ *     f64 (a u or v that is not finite fails): no value is converted to an integer before it is known to fit.
+ *  6. Its splat is every pixel (c, r) of the image with |c - col| <= h and |r - row| <= h.
+ *  7. Its depth is (float)zc.  A pixel goes to the smallest depth, compared as float32; among equal depths to the smallest point index.
+ *  8. Per pixel: depth = the winner's depth, rgb = its r, g, b, index = its position in the cloud (the unfiltered one, whatever the
+ *     tilemask); a pixel no splat covers has depth 0.0f (what open3d's depth capture gives for the background), the background colour
+ *     and index -1.
+ * A pure function of its input: two calls give the same bytes.  rgb: height*width*3 bytes, depth: height*width floats, index:
+ * height*width words or NULL, all row-major host arrays.  Returns the number of covered pixels; an empty cloud is all background and
+ * returns 0.  -1 (cwipc_hip_last_error() has the text) for a NULL argument, width or height < 1, width*height > 2^24, a point_size that
+ * is even or outside 1..15, near not > 0, far not > near, an intrinsic or extrinsic entry that is not finite (far may be INFINITY). */
+_CWIPC_UTIL_EXPORT long cwipc_hip_render(cwipc_pointcloud *pc, const cwipc_hip_view *view, int point_size, int tilemask, const uint8_t background[3],
+                                         uint8_t *rgb, float *depth, int32_t *index);
+
 /* ---- intermediate results for parity tests ---- */
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
