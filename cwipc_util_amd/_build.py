@@ -41,6 +41,7 @@ SOURCES = [
     "kernels_icp.hip",
     "kernels_floor.hip",
     "kernels_render.hip",
+    "kernels_markers.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -318,7 +318,7 @@ void count_dealloc();
 
 // ---------------------------------------------------------------------------
 // kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip, kernels_icp.hip,
-// kernels_floor.hip, kernels_render.hip;
+// kernels_floor.hip, kernels_render.hip, kernels_markers.hip;
 // the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
@@ -432,6 +432,31 @@ void render_fill(unsigned long long *keys, size_t npix, uint32_t *covered, hipSt
 void render_splat(const DeviceSoA &src, const RenderArgs &a, unsigned long long *keys, hipStream_t s);
 void render_resolve(const unsigned long long *keys, const uint32_t *rgbt, size_t npix, uint32_t background, float *depth, uint8_t *rgb, int32_t *index,
                     uint32_t *covered, hipStream_t s);
+
+// ---- kernels_markers.hip: cwipc_hip_detect_markers (the contract is at the top of that file and in hip_ext.h) ----
+constexpr int MARKER_MAX_SIDE = 8192;   // (derived at the top of kernels_markers.hip)
+// What the decode kernel leaves per candidate: id -1 when it is no marker; the corners in output order, the depth image's value at them
+struct MarkerRecord {
+    int32_t id;
+    uint32_t area, label;
+    int32_t x[4], y[4];
+    float depth[4];
+    uint32_t pad;
+};
+struct MarkerWorkspace {
+    bool ok = false;
+    const uint32_t *ncand = nullptr;       // the number of candidates (device)
+    const MarkerRecord *records = nullptr; // that many records (device), in no particular order
+    const uint32_t *label = nullptr;       // per pixel its component's label, 0xFFFFFFFF for a light pixel (device)
+    uint32_t cap = 0;                      // the bound on the number of candidates
+};
+size_t marker_workspace_bytes(size_t npix, int min_side, int nmarkers);
+// All of the detector's kernels on stream s, nothing waited for.  dev_rgb: the image on the device; dict_staged: the dictionary in
+// pinned host memory that stays as it is until the stream has been waited for; dev_depth: a depth image for the records, or nullptr;
+// workspace: marker_workspace_bytes() of device memory.  The parameters have been checked.
+MarkerWorkspace marker_launch(const uint8_t *dev_rgb, int width, int height, const uint32_t *dict_staged, int nmarkers, const cwipc_hip_marker_params &p,
+                              const float *dev_depth, void *workspace, hipStream_t s);
+void marker_labels_out(const uint32_t *label, size_t npix, int32_t *out, hipStream_t s);
 
 }  // namespace k
 

@@ -16,7 +16,10 @@ one grid: cwipc_hip_nn_distance_jobs).  The transformation helpers are in `util`
 The step in front of them, from cameras that each have their own coordinates to a rough alignment, is `multicoarse.MultiCameraCoarse`
 and `multicoarse.MultiCameraCoarseAruco`: markers with known corners, found in an image of each camera's tile.  The image comes from
 `render` (`PinholeView`, `render_pointcloud`: a colour, depth and point-index image of a cloud on the GPU, cwipc_hip_render, where the
-reference opens a window), and `deproject` takes image corners back to 3D.
+reference opens a window), and `deproject` takes image corners back to 3D.  The markers themselves are found by `markers`
+(`MarkerDictionary`, `detect_markers`, `gpu_marker_detector`: square 5 x 5 binary fiducials on the GPU, cwipc_hip_detect_markers, where the
+reference calls cv2.aruco); with `MultiCameraCoarseAruco.set_marker_dictionary` render and detection are one call and no image leaves the
+GPU (cwipc_hip_render_detect_markers).  The user supplies the dictionary's bit patterns.
 """
 from .abstract import (AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults, AlignmentAlgorithm, MulticamAlgorithm,   # noqa: F401
                        MulticamAlignmentAlgorithm)
@@ -28,5 +31,6 @@ from .util import (transformation_identity, transformation_invert, transformatio
                    transformation_get_translation, transformation_compare, BaseMulticamAlgorithm)
 from .multicamera import (BaseMulticamAlignmentAlgorithm, MultiCameraOneToAllOthers, MultiCameraToFloor, MultiCameraToGroundTruth,   # noqa: F401
                           MultiCameraIterative, DEFAULT_MULTICAMERA_ALGORITHM, ALL_MULTICAMERA_ALGORITHMS, DEFAULT_MULTICAMERA_ALIGNER)
-from .render import PinholeView, default_view, look_at, render_pointcloud, deproject, mean_depth   # noqa: F401
+from .render import PinholeView, default_view, look_at, render_pointcloud, deproject, deproject_depth, mean_depth   # noqa: F401
+from .markers import MarkerDictionary, detect_markers, gpu_marker_detector   # noqa: F401
 from .multicoarse import MultiCameraCoarse, MultiCameraCoarseAruco, MarkerPosition, MarkerPositions   # noqa: F401

@@ -10,7 +10,9 @@ cwipc_tilefilter when it is needed.
 `MultiCameraCoarseAruco` finds the markers the way the reference does, without the reference's windows: the camera's tile is
 rendered on the GPU through a pinhole view (render.py; by default the view from the origin, the reference's `from000`, which is the
 physical camera's view of a tile that has not been registered), a detector finds marker corners in the colour image, and the depth
-image takes them back to 3D.  The detector is a plug-in (`set_marker_detector`); the default one needs cv2.aruco.
+image takes them back to 3D.  The detector is a plug-in (`set_marker_detector`).  With a marker dictionary instead
+(`set_marker_dictionary`, markers.py) the GPU finds the markers in the image where the renderer left it, and only the corners and their
+depths come back (cwipc_hip_render_detect_markers).  With neither, cv2.aruco is asked for, as in the reference.
 
 Out of scope, and not here: the interactive `MultiCameraCoarseColorTarget` (a person picks the corners in a window) and
 `MultiCameraCoarseArucoRgb` (the capturer's own RGB and depth images from the cloud's metadata, mapped with the capturer's
@@ -22,7 +24,9 @@ import numpy as np
 
 from ..util import cwipc_pointcloud_wrapper, cwipc_tilefilter, cwipc_join, cwipc_transform, get_tiles_used
 from .abstract import MulticamAlignmentAlgorithm, RegistrationTransformation
-from .render import PinholeView, default_view, render_pointcloud, deproject
+from ..util import cwipc_hip_render_detect_markers, cwipc_hip_marker_params
+from .render import PinholeView, default_view, render_pointcloud, deproject, deproject_depth
+from .markers import MarkerDictionary
 from .util import transformation_identity
 
 __all__ = ['MarkerPosition', 'MarkerPositions', 'MarkerDetector', 'MultiCameraCoarse', 'MultiCameraCoarseAruco']
@@ -222,7 +226,8 @@ def _cv2_aruco_detector() -> MarkerDetector:
         import cv2
         import cv2.aruco
     except ImportError:
-        raise RuntimeError("MultiCameraCoarseAruco: cv2.aruco is not available: a marker detector must be set with set_marker_detector()") from None
+        raise RuntimeError("MultiCameraCoarseAruco: cv2.aruco is not available: a marker detector must be set with set_marker_detector(), "
+                           "or a marker dictionary with set_marker_dictionary()") from None
     detector = cv2.aruco.ArucoDetector(cv2.aruco.getPredefinedDictionary(cv2.aruco.DICT_5X5_50), cv2.aruco.DetectorParameters())
 
     def detect(img: np.ndarray) -> Tuple[List[List[List[float]]], List[int]]:
@@ -258,6 +263,8 @@ class MultiCameraCoarseAruco(MultiCameraCoarse):
         self.default_view: PinholeView = default_view()
         self.per_camera_view: Dict[int, PinholeView] = {}
         self.marker_detector: Optional[MarkerDetector] = None
+        self.marker_dictionary: Optional[MarkerDictionary] = None
+        self.marker_params: Dict[str, int] = {}
 
     def set_view(self, camindex: Optional[int], view: PinholeView) -> None:
         """The view one camera's tile is rendered through, or (None) every camera's that has none of its own."""
@@ -273,8 +280,32 @@ class MultiCameraCoarseAruco(MultiCameraCoarse):
         """detector(rgb image) -> (per marker its four (u, v) corners, the markers' ids); None: cv2.aruco."""
         self.marker_detector = detector
 
+    def set_marker_dictionary(self, dictionary: Optional[MarkerDictionary], **params: int) -> None:
+        """The markers to look for on the GPU when no detector is set (params: the fields of cwipc_hip_marker_params); None: none."""
+        cwipc_hip_marker_params(**params)   # (a wrong name fails here)
+        self.marker_dictionary = dictionary
+        self.marker_params = dict(params)
+
+    def _find_markers_on_device(self, camindex: int) -> MarkerPositions:
+        """Render and detect in one call; the corners' depths come back with them."""
+        assert self.marker_dictionary is not None
+        view = self.view_for_camera_index(camindex)
+        tile_pc = self.get_pointcloud_for_tilemask(self.per_camera_tilenum[camindex])
+        ids, corners, corner_depth, _found = cwipc_hip_render_detect_markers(tile_pc, view.as_struct(), self.marker_dictionary.words, self.point_size,
+                                                                             params=cwipc_hip_marker_params(**self.marker_params))
+        rv: MarkerPositions = {}
+        for id, area_2d, depths in zip(ids, corners, corner_depth):
+            if self.debug:
+                print(f"cwipc_register: camera {camindex}: find_markers: marker {id}: 2d-area={area_2d.tolist()}")
+            corners_3d = [deproject_depth(view, int(uv[0]), int(uv[1]), d) for uv, d in zip(area_2d, depths)]
+            rv[int(id)] = [c for c in corners_3d if c is not None]
+        return rv
+
     def _find_markers(self, passnum: int, camindex: int) -> MarkerPositions:
-        """Render this camera's tile, find the markers in the colour image, take their corners to 3D through the depth image."""
+        """Render this camera's tile, find the markers in the colour image, take their corners to 3D through the depth image.  An
+        explicit detector comes first, then a dictionary (all on the GPU), then cv2.aruco."""
+        if self.marker_detector is None and self.marker_dictionary is not None:
+            return self._find_markers_on_device(camindex)
         detector = self.marker_detector if self.marker_detector is not None else _cv2_aruco_detector()
         view = self.view_for_camera_index(camindex)
         tile_pc = self.get_pointcloud_for_tilemask(self.per_camera_tilenum[camindex])

@@ -15,7 +15,7 @@ import numpy as np
 from ..util import cwipc_pointcloud_wrapper, cwipc_hip_view, cwipc_hip_render
 from .util import transformation_identity, transformation_invert
 
-__all__ = ['PinholeView', 'default_view', 'look_at', 'render_pointcloud', 'deproject', 'mean_depth']
+__all__ = ['PinholeView', 'default_view', 'look_at', 'render_pointcloud', 'deproject', 'deproject_depth', 'mean_depth']
 
 
 @dataclass
@@ -90,6 +90,20 @@ def deproject(view: PinholeView, depth: np.ndarray, uv: Sequence[float]) -> Opti
     if u < 0 or u >= width or v < 0 or v >= height:
         return None
     d = float(depth[v, u])
+    if d == 0:
+        return None
+    z = d
+    x = (u - view.cx) * z / view.fx
+    y = (v - view.cy) * z / view.fy
+    transform = transformation_invert(np.asarray(view.extrinsic, dtype=np.float64))
+    p = transform @ np.array([x, y, z, 1.0])
+    return float(p[0]), float(p[1]), float(p[2])
+
+
+def deproject_depth(view: PinholeView, u: int, v: int, d: float) -> Optional[Tuple[float, float, float]]:
+    """`deproject`'s arithmetic for a pixel (u, v) whose depth d is known already (cwipc_hip_render_detect_markers hands the corners'
+    depths over without the image): None for depth 0, the background."""
+    d = float(d)
     if d == 0:
         return None
     z = d

@@ -50,6 +50,7 @@ __all__ = [
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
     'cwipc_hip_view', 'cwipc_hip_render',
+    'cwipc_hip_marker_params', 'cwipc_hip_detect_markers', 'cwipc_hip_render_detect_markers', 'cwipc_hip_marker_labels',
 ]
 
 # reference util.py:86, 346, 348
@@ -251,6 +252,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_tile_counts': ([cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], _c.c_int),
     'cwipc_hip_bounds': ([cwipc_pointcloud_p, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_render': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_long),
+    'cwipc_hip_detect_markers': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_long),
+    'cwipc_hip_render_detect_markers': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_long),
+    'cwipc_hip_marker_labels': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1193,6 +1198,77 @@ def cwipc_hip_render(pc: cwipc_pointcloud_wrapper, view: cwipc_hip_view, point_s
     if rc < 0:
         raise CwipcError("cwipc_hip_render failed: " + dll.cwipc_hip_last_error().decode('utf8'))
     return rgb, depth, index
+
+
+class cwipc_hip_marker_params(ctypes.Structure):
+    """The marker detector's parameters (include/cwipc_util_amd/hip_ext.h: cwipc_hip_marker_params); the defaults are the library's."""
+    _fields_ = [("window_half", ctypes.c_int32), ("threshold_offset", ctypes.c_int32), ("min_side", ctypes.c_int32),
+                ("max_border_errors", ctypes.c_int32), ("max_bit_errors", ctypes.c_int32)]
+
+    def __init__(self, window_half: int = 40, threshold_offset: int = 7, min_side: int = 14, max_border_errors: int = 2, max_bit_errors: int = 0) -> None:
+        ctypes.Structure.__init__(self, int(window_half), int(threshold_offset), int(min_side), int(max_border_errors), int(max_bit_errors))
+
+
+def _marker_arguments(dictionary: Any, params: Optional[cwipc_hip_marker_params], cap: Optional[int]) -> Tuple[numpy.ndarray, int, int, numpy.ndarray, numpy.ndarray]:
+    words = numpy.ascontiguousarray(numpy.asarray(dictionary, dtype=numpy.uint32).reshape(-1))
+    if cap is None:
+        cap = len(words)   # (every id comes out once at most)
+    cap = max(int(cap), 0)
+    return words, (ctypes.addressof(params) if params is not None else 0), cap, numpy.zeros(cap, dtype=numpy.int32), numpy.zeros((cap, 4, 2), dtype=numpy.float32)
+
+
+def cwipc_hip_detect_markers(rgb: numpy.ndarray, dictionary: Any, params: Optional[cwipc_hip_marker_params] = None,
+                             cap: Optional[int] = None) -> Tuple[numpy.ndarray, numpy.ndarray, int]:
+    """The square binary markers (5 x 5 payload, one-cell black border) in an rgb image (uint8[H, W, 3]), found on the GPU:
+    (ids int32[n], corners float32[n, 4, 2] as (u, v): the marker's top-left, top-right, bottom-right, bottom-left, number found).
+    dictionary: one payload word per id (bit 24 - (5*row + col), set = white).  n = min(number found, cap); cap None: the size of
+    the dictionary.  Sorted by id.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    img = numpy.ascontiguousarray(rgb, dtype=numpy.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise CwipcError("cwipc_hip_detect_markers: rgb must be uint8[H, W, 3]")
+    words, pp, cap, ids, corners = _marker_arguments(dictionary, params, cap)
+    dll = cwipc_util_dll_load()
+    # (a dummy address for empty arrays: the library checks the sizes before it looks at them)
+    rc = dll.cwipc_hip_detect_markers(img.ctypes.data or 1, img.shape[1], img.shape[0], words.ctypes.data or 1, len(words), pp, ids.ctypes.data or None,
+                                      corners.ctypes.data or None, cap)
+    if rc < 0:
+        raise CwipcError("cwipc_hip_detect_markers failed: " + dll.cwipc_hip_last_error().decode('utf8'))
+    n = min(int(rc), cap)
+    return ids[:n], corners[:n], int(rc)
+
+
+def cwipc_hip_render_detect_markers(pc: cwipc_pointcloud_wrapper, view: cwipc_hip_view, dictionary: Any, point_size: int = 5, tilemask: int = 0,
+                                    background: Sequence[int] = (255, 255, 255), params: Optional[cwipc_hip_marker_params] = None,
+                                    cap: Optional[int] = None) -> Tuple[numpy.ndarray, numpy.ndarray, numpy.ndarray, int]:
+    """cwipc_hip_render and cwipc_hip_detect_markers in one call, the image never leaving the GPU: (ids, corners, corner_depth
+    float32[n, 4]: the depth image's value at each corner pixel, number found).  Equal to the two calls one after the other."""
+    if pc is None or view is None:
+        raise CwipcError("cwipc_hip_render_detect_markers: NULL argument")
+    words, pp, cap, ids, corners = _marker_arguments(dictionary, params, cap)
+    corner_depth = numpy.zeros((cap, 4), dtype=numpy.float32)
+    bg = (ctypes.c_uint8 * 3)(*[int(v) for v in background])
+    dll = cwipc_util_dll_load()
+    rc = dll.cwipc_hip_render_detect_markers(pc.as_cwipc_p(), ctypes.addressof(view), int(point_size), int(tilemask), ctypes.addressof(bg),
+                                             words.ctypes.data or 1, len(words), pp, ids.ctypes.data or None, corners.ctypes.data or None,
+                                             corner_depth.ctypes.data or None, cap)
+    if rc < 0:
+        raise CwipcError("cwipc_hip_render_detect_markers failed: " + dll.cwipc_hip_last_error().decode('utf8'))
+    n = min(int(rc), cap)
+    return ids[:n], corners[:n], corner_depth[:n], int(rc)
+
+
+def cwipc_hip_marker_labels(rgb: numpy.ndarray, params: Optional[cwipc_hip_marker_params] = None) -> numpy.ndarray:
+    """For parity tests: int32[H, W], per dark pixel of the detector's mask the smallest linear index of its 4-connected component,
+    -1 for a light pixel."""
+    img = numpy.ascontiguousarray(rgb, dtype=numpy.uint8)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise CwipcError("cwipc_hip_marker_labels: rgb must be uint8[H, W, 3]")
+    labels = numpy.zeros(img.shape[:2], dtype=numpy.int32)
+    dll = cwipc_util_dll_load()
+    if dll.cwipc_hip_marker_labels(img.ctypes.data or 1, img.shape[1], img.shape[0], ctypes.addressof(params) if params is not None else 0,
+                                   labels.ctypes.data or 1) != 0:
+        raise CwipcError("cwipc_hip_marker_labels failed: " + dll.cwipc_hip_last_error().decode('utf8'))
+    return labels
 
 
 def cwipc_transform(pc: cwipc_pointcloud_wrapper, transform: Any) -> cwipc_pointcloud_wrapper:

@@ -335,7 +335,68 @@ typedef struct cwipc_hip_view {
 _CWIPC_UTIL_EXPORT long cwipc_hip_render(cwipc_pointcloud *pc, const cwipc_hip_view *view, int point_size, int tilemask, const uint8_t background[3],
                                          uint8_t *rgb, float *depth, int32_t *index);
 
+/* ---- square binary fiducials in an image (the reference finds them with cv2.aruco, python/cwipc/registration/multicoarse.py:492-527;
+ * cv2 is no dependency of this project) ----
+ * The markers have a 5 x 5 payload inside a one-cell black border, a 7 x 7 grid: the family of the reference's printable targets,
+ * data/src/5x5_1000-N.svg.  dictionary[i] holds marker i's payload: bit 24 - (5*row + col) is the cell at row `row`, column `col`, a set
+ * bit is a white cell; bits 25-31 are not looked at.  The package ships no bit patterns: the caller supplies them.
+ * Every step is integer arithmetic; tests/marker_model.py restates it in numpy.  r = row, c = column, linear index = r*width + c: */
+typedef struct cwipc_hip_marker_params {
+    int32_t window_half;        /* default 40; 1..8192 */
+    int32_t threshold_offset;   /* default 7;  0..255 */
+    int32_t min_side;           /* default 14; 2..8192 */
+    int32_t max_border_errors;  /* default 2;  0..24 */
+    int32_t max_bit_errors;     /* default 0;  0..25 */
+} cwipc_hip_marker_params;
+/*  1. Grey.  Y = (77*R + 150*G + 29*B + 128) >> 8.
+ *  2. Dark mask.  S = the sum of Y over the window [r-w, r+w] x [c-w, c+w], w = window_half, clipped to the image; n = the number of
+ *     pixels in that clipped window.  A pixel is dark iff Y*n + threshold_offset*n < S.  S comes from a summed-area table in uint32
+ *     (255 * 2^24 fits; width*height <= 2^24 as for the renderer).  The window is wide on purpose: every black pixel of a marker whose
+ *     cells are narrower than w has white inside its window, so the whole border ring with every black cell 4-connected to it comes out
+ *     as one blob.
+ *  3. Components.  A component is a 4-connected set of dark pixels; its label is its smallest linear index.
+ *  4. Candidate.  The component's bounding box touches no image edge and is at least min_side wide and high.
+ *  5. Corners.  P0 = the label's pixel.  A = the component pixel farthest from P0 by squared distance, C = the one farthest from A.
+ *     k(p) = (px-Ax)*(Cy-Ay) - (py-Ay)*(Cx-Ax) for every component pixel p; B = the pixel with the largest k, D = the one with the
+ *     smallest.  Every tie goes to the smallest linear index.  Rejected unless k(B) > 0 > k(D), and unless A, B, C, D is strictly convex
+ *     (the cross products of consecutive edges are all positive or all negative).  Of the two cycles A, B, C, D and A, D, C, B the one
+ *     whose shoelace sum, sum(x_i*y_(i+1) - x_(i+1)*y_i), is positive is Q0..Q3, Q0 = A: clockwise on screen, because y runs down.
+ *     Limit: this finds the corners of a quadrilateral whose diagonals are longer than its sides (a marker seen at any angle a camera
+ *     can decode it from), not of a sliver whose longest chord is a side.
+ *  6. Sampling.  The projective map that takes the square (0,0), (7,0), (7,7), (0,7) onto Q0..Q3, in Heckbert's closed form for
+ *     square-to-quad: with dx1 = x1-x2, dx2 = x3-x2, sx = x0-x1+x2-x3 (dy1, dy2, sy alike), Dn = dx1*dy2 - dx2*dy1,
+ *     G = sx*dy2 - dx2*sy, H = dx1*sy - sx*dy1, and U = 4*j + a, V = 4*i + b for the sample (j + a/4, i + b/4) of cell (i, j), a, b in
+ *     {1, 2, 3}:
+ *        numx = ((x1-x0)*Dn + G*x1)*U + ((x3-x0)*Dn + H*x3)*V + 28*x0*Dn   (numy alike),   den = G*U + H*V + 28*Dn;
+ *     if den < 0 all three change sign; the sample's pixel is (floor((2*numx + den) / (2*den)), floor((2*numy + den) / (2*den))),
+ *     i.e. floor(num/den + 1/2), by exact integer division.  A sample outside the image, or with den = 0, is not dark.  A cell is black
+ *     iff at least 5 of its 9 sampled pixels are dark.
+ *     Magnitudes, L = the larger side: |2*num + den| < 760 L^3 + 272 L^2, which int64 holds for L <= 2^17; the squared distances and
+ *     k of step 5, < 2 L^2, are kept in 32 bits, which holds for L <= 2^14.  A side above 8192 is refused.
+ *  7. Decode.  Rejected if more than max_border_errors of the 24 border cells are white.  The 25 inner cells form a code (white = 1).
+ *     Rotation k means that the marker's canonical top-left corner is Q_k: the canonical cell (r, c) is the sampled inner cell (r, c),
+ *     (c, 4-r), (4-r, 4-c), (4-c, r) for k = 0, 1, 2, 3.  The (id, k) of smallest Hamming distance to the dictionary is taken, ties to
+ *     the smallest id, then the smallest k; accepted iff that distance is at most max_bit_errors.  The output corners are Q_k, Q_(k+1),
+ *     Q_(k+2), Q_(k+3): cv2's order, top-left, top-right, bottom-right, bottom-left of the marker.  A mirrored marker does not decode.
+ *  8. Output.  When an id is found more than once the candidate with the largest component area stays, ties to the smallest label.
+ *     Sorted by id.  ids: cap words; corners: cap*4*2 floats, u then v, the integer pixel coordinates as floats.
+ * Returns the number found; the first cap are written.  A pure function of the image.  -1 (cwipc_hip_last_error() has the text) for a
+ * NULL argument (params may be NULL: the defaults; ids and corners may be NULL when cap is 0), width or height < 1 or > 8192,
+ * width*height > 2^24, nmarkers < 1, a parameter outside the range given above. */
+_CWIPC_UTIL_EXPORT long cwipc_hip_detect_markers(const uint8_t *rgb, int width, int height, const uint32_t *dictionary, int nmarkers,
+                                                 const cwipc_hip_marker_params *params, int32_t *ids, float *corners, size_t cap);
+/* cwipc_hip_render's kernels and the detector's on one stream; no image goes to the host.  corner_depth (cap*4 floats, may be NULL): the
+ * depth image's value at each corner pixel.  ids, corners and corner_depth are, byte for byte, what cwipc_hip_render followed by
+ * cwipc_hip_detect_markers on the host copy of its rgb image gives.  Errors: those of both calls. */
+_CWIPC_UTIL_EXPORT long cwipc_hip_render_detect_markers(cwipc_pointcloud *pc, const cwipc_hip_view *view, int point_size, int tilemask,
+                                                        const uint8_t background[3], const uint32_t *dictionary, int nmarkers,
+                                                        const cwipc_hip_marker_params *params, int32_t *ids, float *corners, float *corner_depth,
+                                                        size_t cap);
+
 /* ---- intermediate results for parity tests ---- */
+/* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
+ * pixel; 0 ok, -1 error (the image and parameter checks of cwipc_hip_detect_markers). */
+_CWIPC_UTIL_EXPORT int cwipc_hip_marker_labels(const uint8_t *rgb, int width, int height, const cwipc_hip_marker_params *params, int32_t *labels);
 /* Mean k-NN distance d_i of every point (the quantity pcl::StatisticalOutlierRemoval thresholds) into host memory; 0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_knn_mean_dist(cwipc_pointcloud *pc, int kNeighbors, float *mean_dist, size_t cap, double *threshold, float stddevMulThresh);
 /* The direction filter's normals, in their final orientation, as three planes of cap floats (x then y then z), the size of every
