@@ -829,10 +829,15 @@ namespace {
 
 const double ICP_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
-// both clouds on the device, and the arguments every ICP entry point checks; false: logged
-bool icp_inputs(const char *who, cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
-                std::unique_ptr<cwipc_hip_pointcloud> &keep_src, std::unique_ptr<cwipc_hip_pointcloud> &keep_ref, std::shared_ptr<DeviceSoA> &src,
-                std::shared_ptr<DeviceSoA> &ref) {
+// The scalar arguments of the ICP entry points are checked HERE, once (kernels_icp.hip takes them as checked), in the order of the
+// helpers below; false: logged.
+struct IcpClouds {
+    std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
+    std::shared_ptr<DeviceSoA> src, ref;
+};
+
+// both clouds on the device, and the arguments every ICP entry point has
+bool icp_inputs(const char *who, cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, IcpClouds &in) {
     if (source == nullptr || reference == nullptr) {
         cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
         return false;
@@ -846,10 +851,52 @@ bool icp_inputs(const char *who, cwipc_pointcloud *source, cwipc_pointcloud *ref
             cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the matrix must be finite");
             return false;
         }
-    src = device_input(who, source, keep_src);
-    if (!src) return false;
-    ref = source == reference ? src : device_input(who, reference, keep_ref);
-    return (bool)ref;
+    in.src = device_input(who, source, in.keep_src);
+    if (!in.src) return false;
+    in.ref = source == reference ? in.src : device_input(who, reference, in.keep_ref);
+    return (bool)in.ref;
+}
+
+bool icp_criteria_ok(const char *who, const IcpCriteria &k) {
+    if (k.max_iteration >= 0 && !std::isnan(k.relative_fitness) && !std::isnan(k.relative_rmse)) return true;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
+    return false;
+}
+
+bool gicp_epsilon_ok(const char *who, double epsilon) {
+    if (epsilon > 0.0 && std::isfinite(epsilon)) return true;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "epsilon must be positive and finite");
+    return false;
+}
+
+// an entry point's body between the C caller and C++: 0 / -1, no exception leaves
+template <class Body>
+int icp_entry(const char *who, Body &&body) {
+    try {
+        return body() ? 0 : -1;
+    } catch (...) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
+        return -1;
+    }
+}
+
+// What an aligner starts from, which is also what its caller gets when it fails; and a result into the caller's optional pointers.
+IcpResult icp_start(const double *init) {
+    IcpResult r{};
+    memcpy(r.T, init ? init : ICP_IDENTITY, sizeof(r.T));
+    return r;
+}
+
+void icp_result_out(const IcpResult &r, double *T_out, double *fitness, double *inlier_rmse, int *iterations) {
+    if (T_out) memcpy(T_out, r.T, sizeof(r.T));
+    if (fitness) *fitness = r.fitness;
+    if (inlier_rmse) *inlier_rmse = r.inlier_rmse;
+    if (iterations) *iterations = r.iterations;
+}
+
+void icp_sums_out(uint64_t hn, const double *hs, int count, uint64_t *n, double *sums) {
+    if (n) *n = hn;
+    if (sums) memcpy(sums, hs, (size_t)count * sizeof(double));
 }
 
 }  // namespace
@@ -857,188 +904,129 @@ bool icp_inputs(const char *who, cwipc_pointcloud *source, cwipc_pointcloud *ref
 extern "C" int cwipc_hip_correspondences(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, uint32_t *idx,
                                          double *dist2, size_t cap) {
     const char *who = "cwipc_hip_correspondences";
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        const size_t n = src->npoints;
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        if (!icp_inputs(who, source, reference, T, max_distance, in)) return false;
+        const size_t n = in.src->npoints;
         if (cap < n) {
             cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result arrays are too small");
-            return -1;
+            return false;
         }
-        if (n == 0) return 0;
-        if (!icp_correspondences(*src, *ref, T ? T : ICP_IDENTITY, max_distance, idx, dist2)) return -1;
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+        return n == 0 || icp_correspondences(*in.src, *in.ref, T ? T : ICP_IDENTITY, max_distance, idx, dist2);
+    });
 }
 
 extern "C" int cwipc_hip_icp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, const double *cp,
                                   const double *cq, uint64_t *n, double *sums) {
     const char *who = "cwipc_hip_icp_sums";
-    if (n) *n = 0;
-    if (sums) for (int v = 0; v < 16; v++) sums[v] = 0.0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
+    uint64_t hn = 0;
+    double hs[16] = {};
+    icp_sums_out(hn, hs, 16, n, sums);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        if (!icp_inputs(who, source, reference, T, max_distance, in)) return false;
         const double zero[3] = {0, 0, 0};
-        uint64_t hn = 0;
-        double hs[16];
-        if (!icp_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, cp ? cp : zero, cq ? cq : zero, &hn, hs)) return -1;
-        if (n) *n = hn;
-        if (sums) memcpy(sums, hs, sizeof(hs));
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+        if (!icp_sums(*in.src, *in.ref, T ? T : ICP_IDENTITY, max_distance, cp ? cp : zero, cq ? cq : zero, &hn, hs)) return false;
+        icp_sums_out(hn, hs, 16, n, sums);
+        return true;
+    });
 }
 
 extern "C" int cwipc_hip_icp_point2point(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
                                          double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
                                          double *inlier_rmse, int *iterations) {
     const char *who = "cwipc_hip_icp_point2point";
-    const double *T0 = init ? init : ICP_IDENTITY;
-    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
-    if (fitness) *fitness = 0.0;
-    if (inlier_rmse) *inlier_rmse = 0.0;
-    if (iterations) *iterations = 0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
-            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
-            return -1;
-        }
-        if (src->npoints == 0 || ref->npoints == 0) return 0;
+    IcpResult res = icp_start(init);
+    icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        const IcpCriteria k{relative_fitness, relative_rmse, max_iteration};
+        if (!icp_inputs(who, source, reference, init, max_distance, in) || !icp_criteria_ok(who, k)) return false;
+        if (in.src->npoints == 0 || in.ref->npoints == 0) return true;
         // the pivots, once per run: the clouds' centroids ((0, 0, 0) for a cloud with a non-finite point: any pivot is right,
         // a near one only keeps the covariance from cancelling)
         double cp0[3], cq[3];
-        if (!icp_centroid(*src, cp0) || !icp_centroid(*ref, cq)) return -1;
+        if (!icp_centroid(*in.src, cp0) || !icp_centroid(*in.ref, cq)) return false;
         if (!(std::isfinite(cp0[0]) && std::isfinite(cp0[1]) && std::isfinite(cp0[2]))) cp0[0] = cp0[1] = cp0[2] = 0.0;
         if (!(std::isfinite(cq[0]) && std::isfinite(cq[1]) && std::isfinite(cq[2]))) cq[0] = cq[1] = cq[2] = 0.0;
-        double T[16], fit = 0.0, rmse = 0.0;
-        int done = 0;
-        if (!icp_point2point(*src, *ref, max_distance, T0, relative_fitness, relative_rmse, max_iteration, cp0, cq, T, &fit, &rmse, &done)) return -1;
-        if (T_out) memcpy(T_out, T, sizeof(T));
-        if (fitness) *fitness = fit;
-        if (inlier_rmse) *inlier_rmse = rmse;
-        if (iterations) *iterations = done;
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+        if (!icp_point2point(*in.src, *in.ref, max_distance, k, cp0, cq, res)) return false;
+        icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+        return true;
+    });
 }
 
 extern "C" int cwipc_hip_icp_plane_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance, const float *normals,
                                         float radius, int max_nn, uint64_t *n, double *sums) {
     const char *who = "cwipc_hip_icp_plane_sums";
-    if (n) *n = 0;
-    if (sums) for (int v = 0; v < 29; v++) sums[v] = 0.0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
-        uint64_t hn = 0;
-        double hs[29];
-        if (!icp_plane_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, normals, radius, max_nn, &hn, hs)) return -1;
-        if (n) *n = hn;
-        if (sums) memcpy(sums, hs, sizeof(hs));
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+    uint64_t hn = 0;
+    double hs[29] = {};
+    icp_sums_out(hn, hs, 29, n, sums);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        if (!icp_inputs(who, source, reference, T, max_distance, in)) return false;
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return false;
+        if (!icp_plane_sums(*in.src, *in.ref, T ? T : ICP_IDENTITY, max_distance, normals, radius, max_nn, &hn, hs)) return false;
+        icp_sums_out(hn, hs, 29, n, sums);
+        return true;
+    });
 }
 
 extern "C" int cwipc_hip_icp_point2plane(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init, const float *normals,
                                          float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double *T_out,
                                          double *fitness, double *inlier_rmse, int *iterations) {
     const char *who = "cwipc_hip_icp_point2plane";
-    const double *T0 = init ? init : ICP_IDENTITY;
-    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
-    if (fitness) *fitness = 0.0;
-    if (inlier_rmse) *inlier_rmse = 0.0;
-    if (iterations) *iterations = 0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
-        if (max_iteration < 0 || std::isnan(relative_fitness) || std::isnan(relative_rmse)) {
-            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_iteration must not be negative, the criteria not NaN");
-            return -1;
-        }
-        double T[16], fit = 0.0, rmse = 0.0;
-        int done = 0;
-        if (!icp_point2plane(*src, *ref, max_distance, T0, normals, radius, max_nn, relative_fitness, relative_rmse, max_iteration, T, &fit, &rmse, &done))
-            return -1;
-        if (T_out) memcpy(T_out, T, sizeof(T));
-        if (fitness) *fitness = fit;
-        if (inlier_rmse) *inlier_rmse = rmse;
-        if (iterations) *iterations = done;
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+    IcpResult res = icp_start(init);
+    icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        const IcpCriteria k{relative_fitness, relative_rmse, max_iteration};
+        if (!icp_inputs(who, source, reference, init, max_distance, in)) return false;
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return false;
+        if (!icp_criteria_ok(who, k)) return false;
+        if (!icp_point2plane(*in.src, *in.ref, max_distance, normals, radius, max_nn, k, res)) return false;
+        icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+        return true;
+    });
 }
 
 extern "C" int cwipc_hip_gicp_covariances(cwipc_pointcloud *pc, const float *normals, float radius, int max_nn, const double *direction, double epsilon,
                                           double *cov, size_t cap) {
     const char *who = "cwipc_hip_gicp_covariances";
-    try {
+    return icp_entry(who, [&] {
         if (pc == nullptr) {
             cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
-            return -1;
+            return false;
         }
-        if (!(epsilon > 0.0) || !std::isfinite(epsilon)) {
-            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "epsilon must be positive and finite");
-            return -1;
-        }
-        if (!normals && !direction_args_ok(who, radius, max_nn)) return -1;
+        if (!gicp_epsilon_ok(who, epsilon)) return false;
+        if (!normals && !direction_args_ok(who, radius, max_nn)) return false;
         std::unique_ptr<cwipc_hip_pointcloud> keep;
         auto src = device_input(who, pc, keep);
-        if (!src) return -1;
+        if (!src) return false;
         const size_t n = src->npoints;
         if (cap < n || (n && cov == nullptr)) {
             cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the result array is too small");
-            return -1;
+            return false;
         }
-        return icp_gicp_covariances(*src, normals, radius, max_nn, direction, epsilon, cov) ? 0 : -1;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+        return icp_gicp_covariances(*src, normals, radius, max_nn, direction, epsilon, cov);
+    });
 }
 
 extern "C" int cwipc_hip_icp_gicp_sums(cwipc_pointcloud *source, cwipc_pointcloud *reference, const double *T, double max_distance,
                                        const float *source_normals, const float *reference_normals, float radius, int max_nn, double epsilon, uint64_t *n,
                                        double *sums) {
     const char *who = "cwipc_hip_icp_gicp_sums";
-    if (n) *n = 0;
-    if (sums) for (int v = 0; v < 29; v++) sums[v] = 0.0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, T, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return -1;
-        uint64_t hn = 0;
-        double hs[29];
-        if (!icp_gicp_sums(*src, *ref, T ? T : ICP_IDENTITY, max_distance, source_normals, reference_normals, radius, max_nn, epsilon, &hn, hs)) return -1;
-        if (n) *n = hn;
-        if (sums) memcpy(sums, hs, sizeof(hs));
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+    uint64_t hn = 0;
+    double hs[29] = {};
+    icp_sums_out(hn, hs, 29, n, sums);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        if (!icp_inputs(who, source, reference, T, max_distance, in)) return false;
+        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return false;
+        if (!gicp_epsilon_ok(who, epsilon)) return false;
+        if (!icp_gicp_sums(*in.src, *in.ref, T ? T : ICP_IDENTITY, max_distance, source_normals, reference_normals, radius, max_nn, epsilon, &hn, hs)) return false;
+        icp_sums_out(hn, hs, 29, n, sums);
+        return true;
+    });
 }
 
 extern "C" int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc_pointcloud *reference, double max_distance, const double *init,
@@ -1046,30 +1034,18 @@ extern "C" int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc_pointcl
                                          double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
                                          double *inlier_rmse, int *iterations) {
     const char *who = "cwipc_hip_icp_generalized";
-    const double *T0 = init ? init : ICP_IDENTITY;
-    if (T_out) memcpy(T_out, T0, 16 * sizeof(double));
-    if (fitness) *fitness = 0.0;
-    if (inlier_rmse) *inlier_rmse = 0.0;
-    if (iterations) *iterations = 0;
-    try {
-        std::unique_ptr<cwipc_hip_pointcloud> keep_src, keep_ref;
-        std::shared_ptr<DeviceSoA> src, ref;
-        if (!icp_inputs(who, source, reference, init, max_distance, keep_src, keep_ref, src, ref)) return -1;
-        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return -1;
-        double T[16], fit = 0.0, rmse = 0.0;
-        int done = 0;
-        if (!icp_generalized(*src, *ref, max_distance, T0, source_normals, reference_normals, radius, max_nn, epsilon, relative_fitness, relative_rmse,
-                             max_iteration, T, &fit, &rmse, &done))
-            return -1;
-        if (T_out) memcpy(T_out, T, sizeof(T));
-        if (fitness) *fitness = fit;
-        if (inlier_rmse) *inlier_rmse = rmse;
-        if (iterations) *iterations = done;
-        return 0;
-    } catch (...) {
-        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "exception");
-        return -1;
-    }
+    IcpResult res = icp_start(init);
+    icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+    return icp_entry(who, [&] {
+        IcpClouds in;
+        const IcpCriteria k{relative_fitness, relative_rmse, max_iteration};
+        if (!icp_inputs(who, source, reference, init, max_distance, in)) return false;
+        if (!(source_normals && reference_normals) && !direction_args_ok(who, radius, max_nn)) return false;
+        if (!gicp_epsilon_ok(who, epsilon) || !icp_criteria_ok(who, k)) return false;
+        if (!icp_generalized(*in.src, *in.ref, max_distance, source_normals, reference_normals, radius, max_nn, epsilon, k, res)) return false;
+        icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+        return true;
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -505,31 +505,34 @@ bool nn_distance2_jobs(const DeviceSoA &source, const DeviceSoA &reference, cons
 // all arrays device memory.  No wait inside.
 bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);
 
-// Point-to-point ICP (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All of them wait
-// for their results.  False on failure (logged), also for a max_distance that is NaN or <= 0 and a matrix that is not finite.
+// ICP fine alignment (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All of them wait
+// for their results.  False on failure (logged).  THE CALLER HAS CHECKED the scalar arguments (filters.cpp, once for both layers):
+// max_distance > 0 (not NaN), a finite matrix, the criteria, radius and max_nn where normals are estimated, epsilon; what depends
+// on a cloud's size is checked here: false also for a caller's normal that is not finite.
+struct IcpCriteria { double relative_fitness, relative_rmse; int max_iteration; };   // open3d's ICPConvergenceCriteria
+// An aligner's answer.  The caller sets T to the initial matrix and the rest to 0; an aligner that has nothing to do (an empty
+// cloud) or fails leaves it so.
+struct IcpResult { double T[16]; double fitness, inlier_rmse; int iterations; };
 // Per source point the original index of its nearest reference point and the squared distance (0xFFFFFFFF / +inf: none) into host arrays, either may be nullptr.
 bool icp_correspondences(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, uint32_t *idx_host,
                          double *d2_host);
 // One search and the fit sums over its matches: sums = sum a (3) | sum b (3) | sum a b^T (9) | sum d2, a = T p - cp, b = q - cq.
+// False also for a pivot that is not finite.
 bool icp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const double cp[3], const double cq[3],
               uint64_t *n, double sums[16]);
 // open3d's registration_icp with the point-to-point estimate; cp0, cq: the clouds' centroids (the pivots: T cp0 and cq).
-bool icp_point2point(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], double relative_fitness,
-                     double relative_rmse, int max_iteration, const double cp0[3], const double cq[3], double T_out[16], double *fitness,
-                     double *inlier_rmse, int *iterations);
-// Point-to-plane ICP (the same file).  host_normals: the reference cloud's normals as three planes of reference.npoints floats (x, y,
-// z) in host memory, or nullptr: direction_normals(radius, max_nn) estimates them on the device.  False also for a caller's normal
-// that is not finite and, without caller's normals, for a radius or max_nn that direction_normals turns away.
+bool icp_point2point(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const IcpCriteria &k, const double cp0[3],
+                     const double cq[3], IcpResult &res);
+// Point-to-plane ICP.  host_normals: the reference cloud's normals as three planes of reference.npoints floats (x, y, z) in host
+// memory, or nullptr: direction_normals(radius, max_nn) estimates them on the device.
 // sums = sum J J^T (21, upper triangle row-major) | sum J r (6) | sum r^2 | sum d2.
 bool icp_plane_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *host_normals, float radius,
                     int max_nn, uint64_t *n, double sums[29]);
 // open3d's registration_icp with the point-to-plane estimate (plane_fit.hpp).
-bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *host_normals,
-                     float radius, int max_nn, double relative_fitness, double relative_rmse, int max_iteration, double T_out[16], double *fitness,
-                     double *inlier_rmse, int *iterations);
-// Generalized ICP (the same file; gicp_terms.hpp).  Both clouds have normals, each array as for point-to-plane (host planes, or nullptr:
-// estimated on the device); they are turned as the reference's _fix_normal_direction turns them and give each point a covariance.
-// False also for an epsilon that is not finite or <= 0.
+bool icp_point2plane(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const float *host_normals, float radius, int max_nn,
+                     const IcpCriteria &k, IcpResult &res);
+// Generalized ICP (gicp_terms.hpp).  Both clouds have normals, each array as for point-to-plane (host planes, or nullptr: estimated
+// on the device); they are turned as the reference's _fix_normal_direction turns them and give each point a covariance.
 // The parity entry: per point of `cloud` the six values 00, 01, 02, 11, 12, 22 into cov_host (cloud.npoints rows of 6 doubles);
 // direction nullptr: the normals are not turned.
 bool icp_gicp_covariances(const DeviceSoA &cloud, const float *host_normals, float radius, int max_nn, const double *direction, double epsilon,
@@ -537,10 +540,9 @@ bool icp_gicp_covariances(const DeviceSoA &cloud, const float *host_normals, flo
 // sums = sum (A^T N A)_ij for i <= j (21) | sum (A^T g)_i (6) | sum e^T g | sum d2: the plane sums' layout.
 bool icp_gicp_sums(const DeviceSoA &source, const DeviceSoA &reference, const double T[16], double max_distance, const float *source_normals,
                    const float *reference_normals, float radius, int max_nn, double epsilon, uint64_t *n, double sums[29]);
-// open3d's registration_generalized_icp: icp_point2plane's loop with these sums.
-bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const double init[16], const float *source_normals,
-                     const float *reference_normals, float radius, int max_nn, double epsilon, double relative_fitness, double relative_rmse,
-                     int max_iteration, double T_out[16], double *fitness, double *inlier_rmse, int *iterations);
+// open3d's registration_generalized_icp: the same loop with these sums and the point-to-plane update.
+bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const float *source_normals,
+                     const float *reference_normals, float radius, int max_nn, double epsilon, const IcpCriteria &k, IcpResult &res);
 // the mean of a cloud's points (the direction filter's centroid kernels) on the host; non-finite where a coordinate is
 bool icp_centroid(const DeviceSoA &cloud, double cen[3]);
 

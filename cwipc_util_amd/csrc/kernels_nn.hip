@@ -7,16 +7,13 @@
 //
 // The grid is the point grid built over the reference cloud (grid_and_search, any of its three flows); the queries are the
 // points of another cloud, one lane each, in the caller's order, wherever they lie:
-//   * the search starts from the query's cell CLAMPED to the grid and walks growing cubic shells of cells around it;
+//   * the search starts from the query's cell CLAMPED to the grid and is the exact walk of point_grid.hpp (walk_exact: the shells,
+//     the short f64 bounds, the stop rule -- stated there, once, for this file's two kernels and the ICP correspondences), with
+//     the (nth + 1)-th candidate so far and max_distance as its limit.  A query far from every reference point with no
+//     max_distance therefore scans the whole grid: correct, and as slow as it sounds;
 //   * the candidate list is kept in f64 (KCAP = 2, 4 or 32 sorted registers), so the selection is made on the very values that are
 //     returned -- an fp32 search with a margin and a second pass would read every candidate's coordinates twice to save registers
-//     that this kernel has to spare (at the tooling's nth of 0 or 1 the list is two registers pairs);
-//   * lower bounds on the distance to what has not been looked at -- the box as a whole, a row of cells, everything beyond shell r --
-//     come from the cells' faces in f64, the query's distance to the box included when it lies outside, each taken short by
-//     1e-9 of itself and 1e-6 of a cell (a point's cell is floor((v - mn) / h) in f64: it may sit a rounding error beyond its cell's
-//     face, some 1e-13 of a cell); a bound only ever turns away cells that cannot hold an answer, so the result does not depend on it;
-//   * the search ends when the bound has passed the (nth + 1)-th candidate or max_distance, or the shells have covered the grid.  A
-//     query far from every reference point with no max_distance therefore scans the whole grid: correct, and as slow as it sounds.
+//     that this kernel has to spare (at the tooling's nth of 0 or 1 the list is two registers pairs).
 // A distance is a value: which of two equally distant points is kept, and the order the counting sort left a cell's points in,
 // cannot change it -- two calls give the same bits.
 #include "point_grid.hpp"
@@ -70,65 +67,14 @@ __global__ void __launch_bounds__(QB) nn_distance2_kernel(Grid gv, const GridMet
         }
     };
     auto scan = [&](uint32_t first, uint32_t last) { scan_range<1>(sorted, first, last, candidate); };
-    // a distance along axis a that no point of the cells on the far side of `face` undercuts, taken short
-    auto shorten = [&](double d) {
-        const double t = d * (1.0 - 1e-9) - 1e-6 * g.h;
-        return t > 0.0 ? t : 0.0;
-    };
-    // ... to the cells `o` cells away from `cell` (o != 0)
-    auto face_gap = [&](int a, int cell, int o) {
-        const double face = (double)g.mn[a] + (double)(o < 0 ? cell + o + 1 : cell + o) * g.h;
-        return shorten(o < 0 ? q[a] - face : face - q[a]);
-    };
-    // ... to the grid's box: 0 for a query between its faces
-    double box[3], box2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        box[a] = fmax(face_gap(a, -1, 1), face_gap(a, g.dim[a], -1));
-        box2 += box[a] * box[a];
-    }
-    const int maxring = max(max(max(c[0], g.dim[0] - 1 - c[0]), max(c[1], g.dim[1] - 1 - c[1])), max(c[2], g.dim[2] - 1 - c[2]));
-    if (box2 < limit()) {   // (a query further from the box than max_distance has no answer)
-        for (int ring = 0; ring <= maxring; ring++) {
-            const int x0 = max(c[0] - ring, 0), x1 = min(c[0] + ring, g.dim[0] - 1);
-            const double gx_lo = c[0] - ring >= 0 && ring > 0 ? face_gap(0, c[0], -ring) : 0.0;
-            const double gx_hi = c[0] + ring < g.dim[0] && ring > 0 ? face_gap(0, c[0], ring) : 0.0;
-            for (int dz = -ring; dz <= ring; dz++) {
-                const int z = c[2] + dz;
-                if (z < 0 || z >= g.dim[2]) continue;
-                const double gz = dz == 0 ? box[2] : face_gap(2, c[2], dz);
-                for (int dy = -ring; dy <= ring; dy++) {
-                    const int y = c[1] + dy;
-                    if (y < 0 || y >= g.dim[1]) continue;
-                    const double gy = dy == 0 ? box[1] : face_gap(1, c[1], dy);
-                    const double gyz = gy * gy + gz * gz;
-                    if (gyz >= limit()) continue;
-                    const bool face = dz == -ring || dz == ring || dy == -ring || dy == ring;
-                    uint32_t first, last;
-                    if (face) {   // the whole row belongs to the shell
-                        rows.range(x0, x1, y, z, first, last);
-                        scan(first, last);
-                    } else {      // only its two end cells do
-                        if (c[0] - ring >= 0 && gyz + gx_lo * gx_lo < limit()) {
-                            rows.range(c[0] - ring, c[0] - ring, y, z, first, last);
-                            scan(first, last);
-                        }
-                        if (c[0] + ring < g.dim[0] && gyz + gx_hi * gx_hi < limit()) {
-                            rows.range(c[0] + ring, c[0] + ring, y, z, first, last);
-                            scan(first, last);
-                        }
-                    }
-                }
-            }
-            // everything not looked at yet lies at least one more cell away along some axis
-            double beyond = INFINITY;
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                if (c[a] - ring - 1 >= 0) beyond = fmin(beyond, face_gap(a, c[a], -(ring + 1)));
-                if (c[a] + ring + 1 < g.dim[a]) beyond = fmin(beyond, face_gap(a, c[a], ring + 1));
-            }
-            if (!(limit() > beyond * beyond)) break;
-        }
+    if constexpr (KCAP > 4) {
+        // The list of 32: the scan stays a function call and the list lives in scratch, as the compiler has always built this
+        // instantiation (profiles/grid_split_resources.txt, icp_nn_refactor_resources.txt): four or five waves per SIMD.  Inlined
+        // into the walk it takes 200 VGPRs, two waves, no scratch -- which of the two is faster has not been timed.
+        auto scan_call = [&](uint32_t first, uint32_t last) __attribute__((noinline)) { scan(first, last); };
+        walk_exact(rows, q, c, limit, scan_call);
+    } else {
+        walk_exact(rows, q, c, limit, scan);
     }
     A.out[qi] = best[KCAP - 1];
 }
@@ -261,63 +207,7 @@ __global__ void __launch_bounds__(QB) nn_jobs_kernel(Grid gv, const GridMeta *__
         }
         for (; e < last; e++) candidate(sorted[e], tiles[e]);
     };
-    // from here on: nn_distance2_kernel's walk, bound for bound
-    auto shorten = [&](double d) {
-        const double t = d * (1.0 - 1e-9) - 1e-6 * g.h;
-        return t > 0.0 ? t : 0.0;
-    };
-    auto face_gap = [&](int a, int cell, int o) {
-        const double face = (double)g.mn[a] + (double)(o < 0 ? cell + o + 1 : cell + o) * g.h;
-        return shorten(o < 0 ? q[a] - face : face - q[a]);
-    };
-    double box[3], box2 = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        box[a] = fmax(face_gap(a, -1, 1), face_gap(a, g.dim[a], -1));
-        box2 += box[a] * box[a];
-    }
-    const int maxring = max(max(max(c[0], g.dim[0] - 1 - c[0]), max(c[1], g.dim[1] - 1 - c[1])), max(c[2], g.dim[2] - 1 - c[2]));
-    if (box2 < limit()) {
-        for (int ring = 0; ring <= maxring; ring++) {
-            const int x0 = max(c[0] - ring, 0), x1 = min(c[0] + ring, g.dim[0] - 1);
-            const double gx_lo = c[0] - ring >= 0 && ring > 0 ? face_gap(0, c[0], -ring) : 0.0;
-            const double gx_hi = c[0] + ring < g.dim[0] && ring > 0 ? face_gap(0, c[0], ring) : 0.0;
-            for (int dz = -ring; dz <= ring; dz++) {
-                const int z = c[2] + dz;
-                if (z < 0 || z >= g.dim[2]) continue;
-                const double gz = dz == 0 ? box[2] : face_gap(2, c[2], dz);
-                for (int dy = -ring; dy <= ring; dy++) {
-                    const int y = c[1] + dy;
-                    if (y < 0 || y >= g.dim[1]) continue;
-                    const double gy = dy == 0 ? box[1] : face_gap(1, c[1], dy);
-                    const double gyz = gy * gy + gz * gz;
-                    if (gyz >= limit()) continue;
-                    const bool face = dz == -ring || dz == ring || dy == -ring || dy == ring;
-                    uint32_t first, last;
-                    if (face) {
-                        rows.range(x0, x1, y, z, first, last);
-                        scan(first, last);
-                    } else {
-                        if (c[0] - ring >= 0 && gyz + gx_lo * gx_lo < limit()) {
-                            rows.range(c[0] - ring, c[0] - ring, y, z, first, last);
-                            scan(first, last);
-                        }
-                        if (c[0] + ring < g.dim[0] && gyz + gx_hi * gx_hi < limit()) {
-                            rows.range(c[0] + ring, c[0] + ring, y, z, first, last);
-                            scan(first, last);
-                        }
-                    }
-                }
-            }
-            double beyond = INFINITY;
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                if (c[a] - ring - 1 >= 0) beyond = fmin(beyond, face_gap(a, c[a], -(ring + 1)));
-                if (c[a] + ring + 1 < g.dim[a]) beyond = fmin(beyond, face_gap(a, c[a], ring + 1));
-            }
-            if (!(limit() > beyond * beyond)) break;
-        }
-    }
+    walk_exact(rows, q, c, limit, scan);
     *out = best[KCAP - 1];
 }
 

@@ -1,4 +1,4 @@
-"""Generalized ICP on the GPU (kernels_icp.hip: gicp_covariance_kernel, icp_gicp_sums_partial_kernel, icp_generalized;
+"""Generalized ICP on the GPU (kernels_icp.hip: gicp_covariance_kernel, icp_sums_partial_kernel<GicpPair>, icp_generalized;
 gicp_terms.hpp; registration/fine.py) against the numpy model of its contracts (tests/icp_gicp_model.py, checked on the CPU by
 tests/test_icp_gicp_model.py and, bit for bit against the header, by tests/test_gicp_terms_host.py).  open3d is not available: the
 model restates the published algorithm, nothing here is compared with open3d's output.  Unless a test says otherwise the model's
