@@ -10,7 +10,7 @@
 // 1. CORRESPONDENCES (icp_correspond_kernel), the same for every aligner.  One lane per SOURCE point, in the caller's order.  The
 // query is the source point moved by the 4x4 matrix T (row-major f64), computed in f64 from the float32 coordinates (icp_move):
 //     px = ((T00*x + T01*y) + T02*z) + T03        (py, pz alike; every operation rounded on its own, -ffp-contract=off)
-// and searched in the point grid over the REFERENCE cloud by the exact walk of point_grid.hpp (walk_exact: what nn_distance2_kernel
+// and searched in the point grid over the REFERENCE cloud by the exact walk of exact_walk.hpp (walk_exact: what nn_distance2_kernel
 // of kernels_nn.hip walks, by construction), from the cell floor((p - mn) * inv_h) of the f64 value, clamped.  Per source point:
 // idx = the ORIGINAL index (sorted[].w) of the nearest reference point, d2 = (dx*dx + dy*dy) + dz*dz with dx = px - (double)qx;
 // only candidates with d2 < max_distance^2 (strictly) count; 0xFFFFFFFF and +inf when there is none, also for a source point with

@@ -7,7 +7,7 @@
 //
 // The grid is the point grid built over the reference cloud (grid_and_search, any of its three flows); the queries are the
 // points of another cloud, one lane each, in the caller's order, wherever they lie:
-//   * the search starts from the query's cell CLAMPED to the grid and is the exact walk of point_grid.hpp (walk_exact: the shells,
+//   * the search starts from the query's cell CLAMPED to the grid and is the exact walk of exact_walk.hpp (walk_exact: the shells,
 //     the short f64 bounds, the stop rule -- stated there, once, for this file's two kernels and the ICP correspondences), with
 //     the (nth + 1)-th candidate so far and max_distance as its limit.  A query far from every reference point with no
 //     max_distance therefore scans the whole grid: correct, and as slow as it sounds;

@@ -196,21 +196,30 @@ def test_ties_go_to_the_smallest_index(gpu):
 # ---------------------------------------------------------------------------
 # sums
 # ---------------------------------------------------------------------------
-def test_sums_are_exact_on_lattice_clouds(gpu):
+@pytest.mark.parametrize("nsrc", [16875, 1024 * 1024 + 1])
+def test_sums_are_exact_on_lattice_clouds(gpu, nsrc):
+    """16875: every midpoint once.  1024 * 1024 + 1: the first source count whose chunk doubles (ICP_CHUNK << 1 in IcpWork::alloc), the
+    midpoints over and over -- a source point's correspondence and terms do not depend on the others, so the model's answer for
+    the midpoints is repeated in the same way; every sum is still exact (integers in units of 2^-14 far below 2^53)."""
     lat = lattice()
-    q = np.concatenate([v for v in midpoints(lat).values()]).astype(np.float32)
+    once = np.concatenate([v for v in midpoints(lat).values()]).astype(np.float32)
+    assert len(once) == 16875
+    q = np.resize(once, (nsrc, 3))
     T = im.rigid(0.0, (0, 1, 0), (2 / 64, -1 / 64, 3 / 64))
     cp, cq = np.array([1.125, 0.625, -0.875]), np.array([1.0 + 7 / 64, 0.5 + 9 / 64, -1.0 + 5 / 64])
     src, ref = cloud(gpu, q), cloud(gpu, lat)
     for maxd in (np.inf, 1 / 64):
         n, s = gpu.cwipc_hip_icp_sums(src, ref, T, maxd, cp, cq)
-        idx, d2 = im.correspondences(q, lat, T, maxd)
+        idx, d2 = im.correspondences(once, lat, T, maxd)
+        idx, d2 = np.resize(idx, nsrc), np.resize(d2, nsrc)
         terms = im.sum_terms(q, lat, T, idx, d2, cp, cq)
         wn, ws = im.sums(terms, exact=True)
         assert np.array_equal(ws, terms.sum(axis=0))   # (exact: every order gives this)
         assert n == wn and 0 < n and np.array_equal(s, ws), (maxd, n, wn)
         if np.isfinite(maxd):
             assert n < len(q)
+    src.free()
+    ref.free()
 
 
 @pytest.mark.parametrize("nsrc", [1, 1000, 1024, 1025, 5000, 36000])
