@@ -351,6 +351,43 @@ extern "C" cwipc_pointcloud *cwipc_hip_simulatecams(cwipc_pointcloud *pc, int nc
     return wrap(dst, pc->timestamp(), pc->cellsize());
 }
 
+// reference python/cwipc/filters/simulatecams.py:60-69 (hard = False); the random stream is the library's (hip_ext.h), not numpy's
+extern "C" cwipc_pointcloud *cwipc_hip_simulatecams_soft(cwipc_pointcloud *pc, int ncamera, float centroid_x, float centroid_z, const double *camera_dirs,
+                                                         double skew, uint64_t seed) {
+    if (pc == nullptr || camera_dirs == nullptr) return nullptr;
+    if (ncamera < 2 || ncamera > 32) {
+        // (the reference raises IndexError for one camera: there is no second one to draw against)
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip_simulatecams_soft", "the soft rule needs between 2 and 32 cameras");
+        return nullptr;
+    }
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input("cwipc_hip_simulatecams_soft", pc, keep);
+    if (!src) return nullptr;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    auto dst = soa_with_new_rgbt(src);   // the coordinates do not change: the result holds the very same planes
+    if (!dst) return nullptr;
+    k::map_cameras_soft(*src, *dst, ncamera, centroid_x, centroid_z, camera_dirs, skew, seed, c.stream);
+    if (!c.sync()) return nullptr;
+    inherit_first(*dst, *src);
+    return wrap(dst, pc->timestamp(), pc->cellsize());
+}
+
+// reference python/cwipc/filters/noise.py:31-50; the random stream is the library's (hip_ext.h), not numpy's
+extern "C" cwipc_pointcloud *cwipc_hip_noise(cwipc_pointcloud *pc, double distance, uint64_t seed) {
+    if (pc == nullptr) return nullptr;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input("cwipc_hip_noise", pc, keep);
+    if (!src) return nullptr;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    auto dst = soa_with_new_xyz(src);   // colours and tiles do not change: the result holds the very same words
+    if (!dst) return nullptr;
+    k::map_noise(*src, *dst, distance, seed, c.stream);
+    if (!c.sync()) return nullptr;
+    return wrap(dst, pc->timestamp(), pc->cellsize());
+}
+
 // reference python/cwipc/filters/colorize.py:100-119
 extern "C" cwipc_pointcloud *cwipc_hip_colorize(cwipc_pointcloud *pc, double weight, const double *lut, const uint8_t *valid) {
     if (pc == nullptr || lut == nullptr || valid == nullptr) return nullptr;

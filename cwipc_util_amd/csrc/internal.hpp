@@ -371,6 +371,11 @@ void synthetic_fill(const DeviceSoA &dst, int hsteps, int asteps, float m_angle,
                     const float *angle, const double *sin_a, const double *cos_a, hipStream_t s);
 // simulatecams (hard): tile = 1 << index of the camera direction (dirs: cos, sin per camera) nearest to the centred position
 void map_cameras(const DeviceSoA &src, const DeviceSoA &dst, int ncam, float cen_x, float cen_z, const double *dirs, hipStream_t s);
+// simulatecams (soft): the nearest or the second nearest direction, by one draw per point of the stream of `seed` (counter_rng.hpp); ncam >= 2
+void map_cameras_soft(const DeviceSoA &src, const DeviceSoA &dst, int ncam, float cen_x, float cen_z, const double *dirs, double skew, uint64_t seed,
+                      hipStream_t s);
+// the noise filter: p' = p + a random vector of length up to `distance`, four draws per point of the stream of `seed` (counter_rng.hpp)
+void map_noise(const DeviceSoA &src, const DeviceSoA &dst, double distance, uint64_t seed, hipStream_t s);
 // ORs the set of tile values that occur into 8 device words
 void tiles_used(const DeviceSoA &src, uint32_t *dev_bits8, hipStream_t s);
 // first256[t] = index of the first point with tile value t, 0xffffffff if there is none (256 device words)

@@ -9,6 +9,7 @@
 //   tilemap     src/cwipc_filters.cpp:322-325      colormap  :376-380
 //   join        src/cwipc_filters.cpp:403-409      colorize  python/cwipc/filters/colorize.py:100-119
 #include "internal.hpp"
+#include "counter_rng.hpp"
 
 namespace cwipc_amd {
 namespace k {
@@ -685,6 +686,48 @@ void map_affine(const DeviceSoA &src, const DeviceSoA &dst, const double m[12], 
               dst.rgbt(), n);
 }
 
+// The noise filter (reference python/cwipc/filters/noise.py:31-50): every point moved along a random vector of length up to
+// `distance`.  The arithmetic and the draws are counter_rng.hpp's (noise_point_at: four draws per point, keyed by the point's
+// index, f64, every operation rounded once).  A streaming map, 12 B in and 12 B out per point: four points per lane, one
+// 16-byte access per plane (the planes start on 1 KiB boundaries), the ragged tail by one lane.  The grid is capped at eight
+// workgroups per CU; lanes stride over the rest.
+static constexpr unsigned NOISE_MAX_BLOCKS = 2048;
+
+__global__ void __launch_bounds__(BLOCK) noise_kernel(unsigned long long base, double distance, const float *__restrict__ x, const float *__restrict__ y,
+                                                     const float *__restrict__ z, float *__restrict__ ox, float *__restrict__ oy, float *__restrict__ oz,
+                                                     size_t n) {
+    const size_t nvec = n / 4;
+    const size_t stride = (size_t)gridDim.x * BLOCK;
+    for (size_t v = (size_t)blockIdx.x * BLOCK + threadIdx.x; v < nvec + 1; v += stride) {
+        if (v < nvec) {
+            const float4 px = ((const float4 *)x)[v], py = ((const float4 *)y)[v], pz = ((const float4 *)z)[v];
+            const float in[4][3] = {{px.x, py.x, pz.x}, {px.y, py.y, pz.y}, {px.z, py.z, pz.z}, {px.w, py.w, pz.w}};
+            float out[4][3];
+#pragma unroll
+            for (int j = 0; j < 4; j++) noise_point_at(base, (unsigned long long)(4 * v + j), distance, in[j], out[j]);
+            ((float4 *)ox)[v] = make_float4(out[0][0], out[1][0], out[2][0], out[3][0]);
+            ((float4 *)oy)[v] = make_float4(out[0][1], out[1][1], out[2][1], out[3][1]);
+            ((float4 *)oz)[v] = make_float4(out[0][2], out[1][2], out[2][2], out[3][2]);
+        } else {
+            for (size_t i = nvec * 4; i < n; i++) {   // ragged tail, handled by one lane
+                const float in[3] = {x[i], y[i], z[i]};
+                float out[3];
+                noise_point_at(base, (unsigned long long)i, distance, in, out);
+                ox[i] = out[0]; oy[i] = out[1]; oz[i] = out[2];
+            }
+        }
+    }
+}
+
+void map_noise(const DeviceSoA &src, const DeviceSoA &dst, double distance, uint64_t seed, hipStream_t s) {
+    const size_t n = src.npoints;
+    if (!n) return;
+    unsigned grid = grid_for(n / 4 + 1, BLOCK);
+    if (grid > NOISE_MAX_BLOCKS) grid = NOISE_MAX_BLOCKS;
+    CW_LAUNCH("map_noise", noise_kernel, dim3(grid), dim3(BLOCK), 0, s, rng_base(seed, RNG_TAG_NOISE), distance, src.x(), src.y(), src.z(), dst.x(), dst.y(),
+              dst.z(), n);
+}
+
 // The synthetic source's points, generated where they are going to be used (reference src/cwipc_synthetic.cpp:182-222).
 // Per point the reference takes one product per coordinate of a per-row value (the radius) and a per-column value (sin /
 // cos of the angle): those two tables come from the host, made with the host's libm exactly as the reference makes
@@ -772,6 +815,31 @@ void map_cameras(const DeviceSoA &src, const DeviceSoA &dst, int ncam, float cen
     a.cen_z = cen_z;
     for (int i = 0; i < 2 * ncam; i++) a.dir[i] = dirs[i];
     CW_LAUNCH("map_cameras", camera_assign_kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, a, src.x(), src.z(), src.rgbt(), dst.rgbt(), n);
+}
+
+// simulated cameras, soft assignment (reference python/cwipc/filters/simulatecams.py:60-69): the camera with the largest dot
+// product or the one with the second largest, by one draw per point keyed by the point's index (counter_rng.hpp: soft_camera).
+// The tile byte is written as the hard kernel writes it.
+__global__ void __launch_bounds__(BLOCK) camera_soft_kernel(CameraArgs a, double skew, unsigned long long base, const float *__restrict__ x,
+                                                           const float *__restrict__ z, const uint32_t *__restrict__ rgbt, uint32_t *__restrict__ ow, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) {
+        const double vx = (double)__fsub_rn(x[i], a.cen_x), vz = (double)__fsub_rn(z[i], a.cen_z);
+        const int cam = soft_camera(a.ncam, vx, vz, a.dir, skew, rng_u01(rng_draw(base, (unsigned long long)i)));
+        ow[i] = (rgbt[i] & 0x00ffffffu) | (((1u << cam) & 0xffu) << 24);
+    }
+}
+
+void map_cameras_soft(const DeviceSoA &src, const DeviceSoA &dst, int ncam, float cen_x, float cen_z, const double *dirs, double skew, uint64_t seed,
+                      hipStream_t s) {
+    const size_t n = src.npoints;
+    if (!n) return;
+    CameraArgs a;
+    a.ncam = ncam;
+    a.cen_x = cen_x;
+    a.cen_z = cen_z;
+    for (int i = 0; i < 2 * ncam; i++) a.dir[i] = dirs[i];
+    CW_LAUNCH("map_cameras_soft", camera_soft_kernel, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, a, skew, rng_base(seed, RNG_TAG_CAMS), src.x(), src.z(),
+              src.rgbt(), dst.rgbt(), n);
 }
 
 // which tile values occur: 256-bit set (8 words)

@@ -8,6 +8,7 @@
 // A point is FLOOR iff (double)y < level -- numpy's `column < scalar` on a float32 column, the scalar's conversion being
 // the caller's (util.py: _threshold); a NaN y is therefore not floor.
 #include "internal.hpp"
+#include "counter_rng.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -203,13 +204,7 @@ void floor_scatter(const DeviceSoA &src, const FloorArgs &a, const uint32_t *off
 // ---------------------------------------------------------------------------
 // b. tile shuffle within the first n_first points
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
+// (splitmix64: counter_rng.hpp)
 __global__ void __launch_bounds__(FBLOCK) shuffle_keys_kernel(unsigned long long seed, size_t n_first, unsigned long long *__restrict__ keys,
                                                              uint32_t *__restrict__ index) {
     for (size_t i = (size_t)blockIdx.x * FBLOCK + threadIdx.x; i < n_first; i += (size_t)gridDim.x * FBLOCK) {

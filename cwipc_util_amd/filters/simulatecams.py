@@ -4,7 +4,7 @@ from typing import Optional
 import numpy
 
 from .abstract import _TimedFilter
-from ..util import cwipc_from_numpy_matrix, cwipc_hip_simulatecams, cwipc_pointcloud_wrapper
+from ..util import cwipc_hip_simulatecams, cwipc_hip_simulatecams_soft, cwipc_pointcloud_wrapper
 
 
 class SimulatecamsFilter(_TimedFilter):
@@ -16,10 +16,12 @@ class SimulatecamsFilter(_TimedFilter):
                   or the second highest dot product, with a probability proportional to the dot products.
                   If True, each point is assigned to the camera with the highest dot product.
             skew: If hard=False a skew > 1 will skew the distribution to the closest camera.
+            seed: If hard=False, the seed of the draws (an extension: the reference takes numpy's global generator). Frame f of this
+                  filter uses seed + f. Default: a fresh one per frame.
     """
     filtername = "simulatecams"
 
-    def __init__(self, ncamera: int, hard: Optional[bool] = False, skew: Optional[float] = 1.0):
+    def __init__(self, ncamera: int, hard: Optional[bool] = False, skew: Optional[float] = 1.0, seed: Optional[int] = None):
         super().__init__()
         self.ncamera = ncamera
         self.camera_vectors = numpy.zeros((ncamera, 3), dtype=float)
@@ -29,8 +31,12 @@ class SimulatecamsFilter(_TimedFilter):
             self.camera_vectors[i, 2] = numpy.sin(angle)
         self.hard = hard
         self.skew = skew
+        self.seed = seed
 
     def filter(self, pc: cwipc_pointcloud_wrapper) -> cwipc_pointcloud_wrapper:
+        if not self.hard and self.ncamera < 2:
+            # (the reference raises IndexError here: there is no second camera to draw against)
+            raise ValueError("simulatecams: hard=False needs at least two cameras")
         return self._run(pc, self._assign)
 
     def _assign(self, pc: cwipc_pointcloud_wrapper) -> cwipc_pointcloud_wrapper:
@@ -41,22 +47,10 @@ class SimulatecamsFilter(_TimedFilter):
         if self.hard:
             # the per-point loop (:47-58, :70) is one kernel: tile = 1 << camera with the largest dot product
             return cwipc_hip_simulatecams(pc, self.camera_vectors, centroid)
-        # hard = False draws from numpy.random for every point (:60-69): the same rule, vectorised on the host -- same
-        # distribution, not the same random stream as the reference's per-point calls
-        flat = point_matrix[:, :3].copy()
-        flat[:, 1] = 0.0
-        flat -= centroid
-        dots = flat.astype(float) @ self.camera_vectors.T
-        order = numpy.argsort(dots, axis=1, kind="stable")[:, ::-1]
-        first, second = order[:, 0], order[:, 1]
-        rows = numpy.arange(len(flat))
-        w0, w1 = dots[rows, first] ** self.skew, dots[rows, second] ** self.skew
-        chance = numpy.random.uniform(-w0, w1)
-        camera = numpy.where(chance < 0, first, second)
-        point_matrix[:, 6] = (1 << camera).astype(numpy.float32)
-        out = cwipc_from_numpy_matrix(point_matrix, pc.timestamp())
-        out._set_cellsize(pc.cellsize())
-        return out
+        # hard = False (:60-69) is a kernel too: the same rule on the library's seeded draws -- the same distribution, not the random
+        # stream of the reference's numpy.random calls.  (self.count is already this frame's number + 1.)
+        seed = None if self.seed is None else self.seed + self.count - 1
+        return cwipc_hip_simulatecams_soft(pc, self.camera_vectors, centroid, self.skew, seed=seed)
 
 
 CustomFilter = SimulatecamsFilter

@@ -49,6 +49,7 @@ __all__ = [
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
+    'cwipc_hip_noise', 'cwipc_hip_simulatecams_soft',
     'cwipc_hip_view', 'cwipc_hip_render',
     'cwipc_hip_marker_params', 'cwipc_hip_detect_markers', 'cwipc_hip_render_detect_markers', 'cwipc_hip_marker_labels',
 ]
@@ -223,6 +224,8 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_colorize': ([cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_void_p], cwipc_pointcloud_p),
     'cwipc_hip_join_multi': ([_c.POINTER(cwipc_pointcloud_p), _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_simulatecams': ([cwipc_pointcloud_p, _c.c_int, _c.c_float, _c.c_float, _c.c_void_p], cwipc_pointcloud_p),
+    'cwipc_hip_simulatecams_soft': ([cwipc_pointcloud_p, _c.c_int, _c.c_float, _c.c_float, _c.c_void_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
+    'cwipc_hip_noise': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
     'cwipc_hip_tilefilter_masked': ([cwipc_pointcloud_p, _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_transform': ([cwipc_pointcloud_p, _c.POINTER(_c.c_double)], cwipc_pointcloud_p),
     'cwipc_hip_flatten_y': ([cwipc_pointcloud_p], cwipc_pointcloud_p),
@@ -988,6 +991,34 @@ def cwipc_hip_simulatecams(pc: cwipc_pointcloud_wrapper, camera_vectors: numpy.n
     rv = cwipc_util_dll_load().cwipc_hip_simulatecams(pc.as_cwipc_p(), int(cams.shape[0]), float(numpy.float32(centroid[0])), float(numpy.float32(centroid[2])),
                                                       cams.ctypes.data)
     return _wrap_filter_result("cwipc_hip_simulatecams", rv)
+
+
+def _seed64(seed: Optional[int]) -> int:
+    """The 64-bit seed of a random filter: the caller's, modulo 2^64, or (None) 64 bits from os.urandom."""
+    if seed is None:
+        return int.from_bytes(os.urandom(8), 'little')
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def cwipc_hip_simulatecams_soft(pc: cwipc_pointcloud_wrapper, camera_vectors: numpy.ndarray, centroid: numpy.ndarray, skew: float = 1.0, *,
+                                seed: Optional[int] = None) -> cwipc_pointcloud_wrapper:
+    """Soft camera assignment of SimulatecamsFilter on the GPU: the nearest camera or the second nearest, with a chance in proportion to
+    their dot products ** skew, by one draw per point of the stream of `seed` (None: 64 bits from os.urandom; the draws are stated in
+    include/cwipc_util_amd/hip_ext.h).  Arguments as cwipc_hip_simulatecams; at least two cameras."""
+    cams = numpy.ascontiguousarray(numpy.asarray(camera_vectors, dtype=numpy.float64)[:, [0, 2]])
+    if cams.shape[0] < 2:
+        raise ValueError("cwipc_hip_simulatecams_soft: the soft rule needs at least two cameras")
+    rv = cwipc_util_dll_load().cwipc_hip_simulatecams_soft(pc.as_cwipc_p(), int(cams.shape[0]), float(numpy.float32(centroid[0])), float(numpy.float32(centroid[2])),
+                                                           cams.ctypes.data, float(skew), _seed64(seed))
+    return _wrap_filter_result("cwipc_hip_simulatecams_soft", rv)
+
+
+def cwipc_hip_noise(pc: cwipc_pointcloud_wrapper, distance: float, seed: Optional[int] = None) -> cwipc_pointcloud_wrapper:
+    """Every point moved along a random vector of length up to `distance` (reference python/cwipc/filters/noise.py:31-50), on the GPU:
+    the reference's f64 arithmetic on four draws per point of the stream of `seed` (None: 64 bits from os.urandom; the draws are
+    stated in include/cwipc_util_amd/hip_ext.h).  Colours, tiles, timestamp and cellsize are kept; the result stays on the device."""
+    rv = cwipc_util_dll_load().cwipc_hip_noise(pc.as_cwipc_p(), float(distance), _seed64(seed))
+    return _wrap_filter_result("cwipc_hip_noise", rv)
 
 
 CWIPC_HIP_COMM_ID_BYTES = 128

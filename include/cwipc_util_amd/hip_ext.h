@@ -121,6 +121,32 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_colorize(cwipc_pointcloud *pc, do
  * (camera_dirs: cos, sin of 2 pi c / ncamera, as doubles) with the largest dot product with the point's position minus the
  * centroid, y ignored.  The centroid (numpy.mean of the float32 coordinates) is computed by the caller, as the reference does. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_simulatecams(cwipc_pointcloud *pc, int ncamera, float centroid_x, float centroid_z, const double *camera_dirs);
+/* ---- the seeded random filters ----
+ * Their draws are stateless, keyed by a 64-bit seed, a tag per filter and a counter (csrc/counter_rng.hpp; tests/scene_model.py is
+ * the numpy statement):
+ *   GOLDEN          = 0x9E3779B97F4A7C15
+ *   mix(z)          = the splitmix64 output function (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31)
+ *   base(seed, tag) = mix((seed + tag) mod 2^64)         tag = 0x6e6f697365 ("noise") or 0x63616d73 ("cams")
+ *   draw(b, k)      = mix((b + (k + 1) * GOLDEN) mod 2^64)       k = 0, 1, 2, ...
+ *   u01(x)          = (double)(x >> 11) * 2^-53           in [0, 1)
+ * Reproducible from the seed; not numpy's Mersenne stream, which the reference draws from.
+ *
+ * SimulatecamsFilter, soft assignment (reference python/cwipc/filters/simulatecams.py:60-69): the dot products are those of
+ * cwipc_hip_simulatecams; `first` and `second` are the top two of the descending order by (value, camera index), of equal dot
+ * products the higher index first.  With u = u01(draw(base(seed, cams), i)) for point i: w0 = d_first ** skew, w1 = d_second ** skew
+ * (the dot products themselves when skew == 1.0), chance = -w0 + (w1 + w0) * u in f64, every step rounded; tile = 1 << first if
+ * chance < 0, else 1 << second (so a NaN chance takes `second`, as in the reference).  The coordinate planes are shared with the
+ * input.  NULL (logged) for ncamera < 2 -- the reference raises IndexError -- or > 32. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_simulatecams_soft(cwipc_pointcloud *pc, int ncamera, float centroid_x, float centroid_z,
+                                                                 const double *camera_dirs, double skew, uint64_t seed);
+/* NoiseFilter (reference python/cwipc/filters/noise.py:31-50): every point moved along a random vector of length up to `distance`.  For
+ * point i, with b = base(seed, noise) and u_j = u01(draw(b, 4 i + j)), in f64, every operation rounded once, in this order:
+ *   v_c = -1.0 + 2.0 * u_c  (c = 0, 1, 2);  s = (v_0*v_0 + v_1*v_1) + v_2*v_2;  scale = sqrt(s) / u_3;  n_c = (v_c / scale) * distance;
+ *   out_c = (float)((double)p_c + n_c)
+ * -- numpy's uniform(-1, 1), linalg.norm(axis=1), rnd_vec / (norm / unif) * distance and `float32 += float64`.  IEEE at the edges:
+ * u_3 == 0 gives an infinite scale and no noise, s == 0 gives NaN, non-finite coordinates propagate.  Colours and tiles are the
+ * input's very words (shared, not copied); timestamp and cellsize are kept; an empty cloud gives an empty cloud. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_noise(cwipc_pointcloud *pc, double distance, uint64_t seed);
 /* cwipc_join_multi (reference python/cwipc/util.py:1330-1332): same result as the left fold of cwipc_join, one pass. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_join_multi(cwipc_pointcloud **pcs, int npc);
 /* p' = R p + t for a row-major 4x4 matrix (last row ignored), in f64, stored as float: what the reference's
