@@ -30,6 +30,7 @@ SOURCES = [
     "stubs.cpp",
     "ply.cpp",
     "filters.cpp",
+    "rgbd.cpp",
     "exchange.cpp",
     "kernels_basic.hip",
     "kernels_voxel.hip",
@@ -42,6 +43,7 @@ SOURCES = [
     "kernels_floor.hip",
     "kernels_render.hip",
     "kernels_markers.hip",
+    "kernels_rgbd.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -7,6 +7,7 @@
 //   synthetic.cpp   cwipc_synthetic source          (reference src/cwipc_synthetic.cpp)
 //   stubs.cpp       out-of-scope constructors that fail loudly
 //   filters.cpp     C entry points of the hot path, host orchestration
+//   rgbd.cpp        cwipc_hip_from_rgbd: the RGB-D source end (images in, device-resident cloud out)
 //   kernels_*.hip   the HIP kernels (gfx950)
 #pragma once
 
@@ -24,6 +25,7 @@
 
 #include "cwipc_util/api.h"
 #include "cwipc_util_amd/hip_ext.h"
+#include "rgbd_terms.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -462,6 +464,26 @@ size_t marker_workspace_bytes(size_t npix, int min_side, int nmarkers);
 MarkerWorkspace marker_launch(const uint8_t *dev_rgb, int width, int height, const uint32_t *dict_staged, int nmarkers, const cwipc_hip_marker_params &p,
                               const float *dev_depth, void *workspace, hipStream_t s);
 void marker_labels_out(const uint32_t *label, size_t npix, int32_t *out, hipStream_t s);
+
+// ---- kernels_rgbd.hip: cwipc_hip_from_rgbd (the contract is in rgbd_terms.hpp and hip_ext.h) ----
+// One camera of a frame as the kernels see it; the cameras' pixels are numbered through, camera after camera, row-major: `first` is
+// the number of this camera's pixel (0, 0).  depth and colour are device memory; colour is 4-byte aligned with at least 8 readable
+// bytes behind its last pixel.
+struct RgbdCamDev {
+    RgbdCamTerms t;
+    const uint16_t *depth;
+    const uint8_t *colour;
+    uint32_t width, bpp, tile, first;
+};
+size_t rgbd_blocks(uint32_t total_pixels);
+// Pass 1: per workgroup the number of pixels that give a point, then the exclusive scan of those: counts (rgbd_blocks() + 1 device
+// words) ends up holding offsets and the total, which also goes to *total_host (pinned) below `tag`.  Frames of up to 256 k pixels:
+// one launch, the last workgroup scans (ticket: a zeroed device word, left zeroed); larger ones: the count kernel, then compact_scan.
+void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
+                unsigned long long *total_host, uint32_t tag, hipStream_t s);
+// Pass 2: the points, in pixel order, into dst (room for total_pixels points).
+void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
+                  hipStream_t s);
 
 }  // namespace k
 

@@ -19,7 +19,8 @@ and `multicoarse.MultiCameraCoarseAruco`: markers with known corners, found in a
 reference opens a window), and `deproject` takes image corners back to 3D.  The markers themselves are found by `markers`
 (`MarkerDictionary`, `detect_markers`, `gpu_marker_detector`: square 5 x 5 binary fiducials on the GPU, cwipc_hip_detect_markers, where the
 reference calls cv2.aruco); with `MultiCameraCoarseAruco.set_marker_dictionary` render and detection are one call and no image leaves the
-GPU (cwipc_hip_render_detect_markers).  The user supplies the dictionary's bit patterns.
+GPU (cwipc_hip_render_detect_markers).  The user supplies the dictionary's bit patterns.  `multicoarse.MultiCameraCoarseArucoRgb` looks for
+the markers in the cameras' own colour and depth images instead, which a grabber (`cwipc_util_amd.rgbd.RgbdSource`) attaches to the cloud.
 """
 from .abstract import (AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults, AlignmentAlgorithm, MulticamAlgorithm,   # noqa: F401
                        MulticamAlignmentAlgorithm)
@@ -33,4 +34,4 @@ from .multicamera import (BaseMulticamAlignmentAlgorithm, MultiCameraOneToAllOth
                           MultiCameraIterative, DEFAULT_MULTICAMERA_ALGORITHM, ALL_MULTICAMERA_ALGORITHMS, DEFAULT_MULTICAMERA_ALIGNER)
 from .render import PinholeView, default_view, look_at, render_pointcloud, deproject, deproject_depth, mean_depth   # noqa: F401
 from .markers import MarkerDictionary, detect_markers, gpu_marker_detector   # noqa: F401
-from .multicoarse import MultiCameraCoarse, MultiCameraCoarseAruco, MarkerPosition, MarkerPositions   # noqa: F401
+from .multicoarse import MultiCameraCoarse, MultiCameraCoarseAruco, MultiCameraCoarseArucoRgb, MarkerPosition, MarkerPositions   # noqa: F401

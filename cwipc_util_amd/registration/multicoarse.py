@@ -14,10 +14,14 @@ image takes them back to 3D.  The detector is a plug-in (`set_marker_detector`).
 (`set_marker_dictionary`, markers.py) the GPU finds the markers in the image where the renderer left it, and only the corners and their
 depths come back (cwipc_hip_render_detect_markers).  With neither, cv2.aruco is asked for, as in the reference.
 
-Out of scope, and not here: the interactive `MultiCameraCoarseColorTarget` (a person picks the corners in a window) and
-`MultiCameraCoarseArucoRgb` (the capturer's own RGB and depth images from the cloud's metadata, mapped with the capturer's
-auxiliary operations).
+`MultiCameraCoarseArucoRgb` finds them in the cameras' own images instead of in a rendering: the colour and depth image a grabber
+attached to the cloud's metadata (rgbd.RgbdSource does, when asked), by the camera's serial number; every corner goes through the
+grabber's auxiliary operations "mapcolordepth" and "map2d3d", its depth being the mean of the 7 x 7 depths around it.  It is the class
+the reference's cwipc_register picks when a capturer is present.  A camera without images falls back to the rendered path.
+
+Out of scope, and not here: the interactive `MultiCameraCoarseColorTarget` (a person picks the corners in a window).
 """
+import struct
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -25,11 +29,11 @@ import numpy as np
 from ..util import cwipc_pointcloud_wrapper, cwipc_tilefilter, cwipc_join, cwipc_transform, get_tiles_used
 from .abstract import MulticamAlignmentAlgorithm, RegistrationTransformation
 from ..util import cwipc_hip_render_detect_markers, cwipc_hip_marker_params
-from .render import PinholeView, default_view, render_pointcloud, deproject, deproject_depth
-from .markers import MarkerDictionary
+from .render import PinholeView, default_view, render_pointcloud, deproject, deproject_depth, mean_depth
+from .markers import MarkerDictionary, detect_markers
 from .util import transformation_identity
 
-__all__ = ['MarkerPosition', 'MarkerPositions', 'MarkerDetector', 'MultiCameraCoarse', 'MultiCameraCoarseAruco']
+__all__ = ['MarkerPosition', 'MarkerPositions', 'MarkerDetector', 'MultiCameraCoarse', 'MultiCameraCoarseAruco', 'MultiCameraCoarseArucoRgb']
 
 #: the outline of a marker in 3D; marker id -> outline
 MarkerPosition = List[Tuple[float, float, float]]
@@ -322,3 +326,113 @@ class MultiCameraCoarseAruco(MultiCameraCoarse):
             corners_3d = [deproject(view, depth, corner_2d) for corner_2d in area_2d]
             rv[int(id)] = [c for c in corners_3d if c is not None]
         return rv
+
+
+class MultiCameraCoarseArucoRgb(MultiCameraCoarseAruco):
+    """Coarse alignment from Aruco markers found in the cameras' own colour images (reference multicoarse.py:529-655): the images come
+    from the cloud's metadata, the grabber maps a colour pixel to its depth pixel and a pixel with its depth to 3D."""
+
+    def __init__(self) -> None:
+        MultiCameraCoarseAruco.__init__(self)
+        self.grabber: Any = None
+
+    def set_grabber(self, grabber: Any) -> None:
+        """The source the cloud came from: it answers auxiliary_operation("map2d3d" / "mapcolordepth") and, when it has a
+        serial_dict() and no serial numbers have been set, says which serial number each tile has."""
+        self.grabber = grabber
+        if not self.serial_for_tilenum and hasattr(grabber, "serial_dict"):
+            self.set_serial_dict(grabber.serial_dict())
+
+    def _detect_in_image(self, rgb: np.ndarray) -> Tuple[Sequence[Sequence[Sequence[float]]], Sequence[int]]:
+        """The parent's order: an explicit detector, then a dictionary (the GPU detector on the image), then cv2.aruco."""
+        if self.marker_detector is not None:
+            areas_2d, ids = self.marker_detector(rgb)
+        elif self.marker_dictionary is not None:
+            areas_2d, ids = detect_markers(rgb, self.marker_dictionary, **self.marker_params)
+        else:
+            areas_2d, ids = _cv2_aruco_detector()(rgb)
+        return (areas_2d, ids) if ids is not None else ([], [])
+
+    def _find_markers(self, passnum: int, camindex: int) -> MarkerPositions:
+        tilenum = self.per_camera_tilenum[camindex]
+        np_rgb_image, np_depth_image = self._get_rgb_depth_images(camindex)
+        if np_rgb_image is None or np_depth_image is None:
+            print(f"cwipc_register: camera {camindex}: Warning: RGB or Depth image not captured. Revert to the rendered image.")
+            return MultiCameraCoarseAruco._find_markers(self, passnum, camindex)
+        areas_2d, ids = self._detect_in_image(np_rgb_image)
+        rv: MarkerPositions = {}
+        if self.verbose:
+            print(f"cwipc_register: camera {camindex}: _find_markers: Auruco-IDs: {ids}, 2D-Areas: {areas_2d}")
+        for i in range(len(ids)):
+            marker_id = int(ids[i])
+            area_2d = areas_2d[i]
+            assert len(area_2d) == 4
+            area_3d: MarkerPosition = []
+            for corner_2d_idx, corner_2d in enumerate(area_2d):
+                u, v = int(corner_2d[0]), int(corner_2d[1])
+                du, dv = self._map_color_to_depth(tilenum, u, v)
+                d = self._get_depth_value(camindex, np_depth_image, du, dv)
+                if d <= 0:
+                    break   # (the marker keeps fewer than four corners: run() skips it)
+                # (map2d3d wants the colour image's coordinates)
+                corner_3d = self._map_2d_to_3d(tilenum, u, v, d)
+                if self.verbose:
+                    print(f"cwipc_register: camera {camindex}: find_markers: marker {i}, corner {corner_2d_idx}: u,v,d={(u, v, d)} 3d-point={corner_3d}")
+                area_3d.append(corner_3d)
+            if marker_id not in rv:
+                rv[marker_id] = area_3d
+            else:
+                # A second marker with this id in view (one lying around, say): the one whose first corner is nearer the origin stays.
+                # (One without a first corner is as far away as can be; the reference would fail on it.)
+                old_area_3d = rv[marker_id]
+                new_distance = float(np.linalg.norm(area_3d[0])) if area_3d else float('inf')
+                old_distance = float(np.linalg.norm(old_area_3d[0])) if old_area_3d else float('inf')
+                if new_distance < old_distance:
+                    print(f"cwipc_register: camera {camindex}: Warning: duplicate marker {marker_id}. Use new at distance {new_distance}, old was at {old_distance}")
+                    rv[marker_id] = area_3d
+                else:
+                    print(f"cwipc_register: camera {camindex}: Warning: duplicate marker {marker_id}. Keep old at distance {old_distance}, new was at {new_distance}")
+        return rv
+
+    def _map_2d_to_3d(self, tilenum: int, u: int, v: int, d: int) -> Tuple[float, float, float]:
+        assert self.grabber
+        inargs = struct.pack("ffff", float(tilenum), float(u), float(v), float(d))
+        outargs = bytearray(12)
+        if not self.grabber.auxiliary_operation("map2d3d", inargs, outargs):
+            raise RuntimeError(f"MultiCameraCoarseArucoRgb: camera {tilenum}: map2d3d failed")
+        rv_x, rv_y, rv_z = struct.unpack("fff", outargs)
+        return rv_x, rv_y, rv_z
+
+    def _map_color_to_depth(self, tilenum: int, cu: int, cv: int) -> Tuple[int, int]:
+        assert self.grabber
+        inargs = struct.pack("iii", tilenum, cu, cv)
+        outargs = bytearray(8)
+        if not self.grabber.auxiliary_operation("mapcolordepth", inargs, outargs):
+            print(f"cwipc_register: Warning: camera {tilenum}: mapcolordepth failed")
+            return cu, cv
+        du, dv = struct.unpack("ii", outargs)
+        return du, dv
+
+    def _get_depth_value(self, camindex: int, np_depth_image: np.ndarray, x: int, y: int) -> int:
+        """The depth at (x, y): the mean of the depths there are in the 7 x 7 pixels around it, 0 when there are fewer than 10."""
+        return int(mean_depth(np_depth_image, x, y, 3, 10))
+
+    def _get_rgb_depth_images(self, camindex: int) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+        """This camera's colour image (uint8[H, W, 3], R, G, B: what a MarkerDetector takes) and depth image (uint16[H, W]) from the
+        cloud's metadata; (None, None) when the tile has no serial number or the cloud carries no images of it."""
+        tilenum = self.per_camera_tilenum[camindex]
+        serial = self.serial_for_tilenum.get(tilenum)
+        if not serial:
+            print(f"cwipc_register: camera {camindex}: get_rgb_depth_images: Unknown tilenum {tilenum}, no serial number known")
+            return None, None
+        assert self.original_pointcloud
+        metadata = self.original_pointcloud.access_metadata()
+        if not metadata or metadata.count() == 0:
+            print(f"cwipc_register: camera {camindex}: get_rgb_depth_images: tilenum {tilenum}: no metadata")
+            return None, None
+        image_dict = metadata.get_all_images(serial)
+        depth_image, bgr_image = image_dict.get("depth."), image_dict.get("rgb.")
+        if depth_image is None or bgr_image is None:
+            return None, None
+        # (get_all_images hands colour out as B, G, R, which is what cv2 works on; this project's detectors take R, G, B)
+        return np.ascontiguousarray(bgr_image[:, :, ::-1]), depth_image

@@ -1,0 +1,225 @@
+"""The RGB-D source end: a capture box sends one depth image and one colour image per camera, and cwipc_hip_from_rgbd turns a frame
+of them into a tiled, device-resident cloud on the GPU (include/cwipc_util_amd/hip_ext.h has the contract; the per-point filters are
+those every camera plug-in of the reference applies, reference include/cwipc_util/internal/capturers.hpp:208-275).
+
+`RgbdCamera` and `RgbdFilter` describe the cameras and the filters; `RgbdSource` is the grabber: it is fed frames, hands out clouds,
+attaches the images as metadata when asked (request_metadata("rgb" / "depth")), and answers the two auxiliary operations the
+registration tooling asks a grabber for, "map2d3d" and "mapcolordepth", with the struct layouts of the reference
+(python/cwipc/registration/multicoarse.py:592-612)."""
+from __future__ import annotations
+
+import struct
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
+
+import numpy
+
+from . import util
+from .abstract import cwipc_activesource_abstract, cwipc_tileinfo_dict
+
+__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd"]
+
+#: one frame: per camera its (depth uint16[H, W], colour uint8[H, W, bpp]) images, the colour image aligned to the depth image
+Frame = Sequence[Tuple[numpy.ndarray, numpy.ndarray]]
+
+
+def _identity() -> numpy.ndarray:
+    return numpy.identity(4, dtype=numpy.float64)
+
+
+@dataclass
+class RgbdCamera:
+    """Image size, intrinsics, metres per depth unit, camera -> world matrix (4x4, float64), tile number, serial number and the colour
+    format (bpp 3: R, G, B bytes; 4: B, G, R, A bytes) of one camera."""
+    width: int
+    height: int
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    depth_scale: float = 0.001
+    trafo: numpy.ndarray = field(default_factory=_identity)
+    tile: int = 1
+    serial: str = ""
+    bpp: int = 3
+
+    def as_struct(self, depth: Optional[numpy.ndarray] = None, colour: Optional[numpy.ndarray] = None) -> util.cwipc_hip_rgbd_camera:
+        """The camera as the C structure, pointing at the two images (none: only good for the mappings).  The structure keeps the
+        arrays it points at alive."""
+        m = numpy.ascontiguousarray(numpy.asarray(self.trafo, dtype=numpy.float64))
+        if m.shape != (4, 4):
+            raise ValueError("RgbdCamera: trafo must be a 4x4 matrix")
+        if not 0 <= int(self.tile) <= 255:
+            raise ValueError("RgbdCamera: tile must be between 0 and 255")
+        rv = util.cwipc_hip_rgbd_camera()
+        rv.width, rv.height, rv.bpp, rv.tile = int(self.width), int(self.height), int(self.bpp), int(self.tile)
+        rv.fx, rv.fy, rv.cx, rv.cy, rv.depth_scale = float(self.fx), float(self.fy), float(self.cx), float(self.cy), float(self.depth_scale)
+        rv.trafo[:] = m.reshape(16).tolist()
+        rv.serial = self.serial.encode('utf8')
+        if depth is not None or colour is not None:
+            if depth is None or colour is None:
+                raise ValueError("RgbdCamera: a depth and a colour image, or neither")
+            if depth.dtype != numpy.uint16 or depth.shape != (rv.height, rv.width) or not depth.flags['C_CONTIGUOUS']:
+                raise ValueError("RgbdCamera: depth must be a contiguous uint16[height, width] array")
+            if colour.dtype != numpy.uint8 or colour.shape != (rv.height, rv.width, rv.bpp) or not colour.flags['C_CONTIGUOUS']:
+                raise ValueError("RgbdCamera: colour must be a contiguous uint8[height, width, bpp] array")
+            rv.depth, rv.colour = depth.ctypes.data, colour.ctypes.data
+            rv._images = (depth, colour)
+        return rv
+
+
+@dataclass
+class RgbdFilter:
+    """The per-point filters, in the order they run; the defaults are "off".  threshold_near / threshold_far: the depth range in metres
+    along the camera's axis (off when far <= near); height_min / height_max: the world y range (off when equal); radius: the distance
+    from the world's y axis (off when <= 0); greenscreen: drop green points."""
+    threshold_near: float = 0.0
+    threshold_far: float = 0.0
+    height_min: float = 0.0
+    height_max: float = 0.0
+    radius: float = 0.0
+    greenscreen: bool = False
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_filter:
+        return util.cwipc_hip_rgbd_filter(float(self.threshold_near), float(self.threshold_far), float(self.height_min), float(self.height_max),
+                                          float(self.radius), 1 if self.greenscreen else 0)
+
+
+def from_rgbd(cameras: Sequence[RgbdCamera], frame: Frame, filter: Optional[RgbdFilter] = None, timestamp: int = 0, cellsize: float = 0.0,
+              attach_flags: int = 0) -> util.cwipc_pointcloud_wrapper:
+    """cwipc_hip_from_rgbd on dataclasses and arrays."""
+    if len(cameras) != len(frame):
+        raise ValueError("from_rgbd: one (depth, colour) pair per camera")
+    structs = [cam.as_struct(depth, colour) for cam, (depth, colour) in zip(cameras, frame)]
+    return util.cwipc_hip_from_rgbd(structs, filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
+
+
+class RgbdSource(cwipc_activesource_abstract):
+    """A grabber over frames of camera images.  `frames`: an iterable of frames, or a callable that returns the next frame (None: the
+    end).  Cloud i gets the timestamp first_timestamp + i."""
+
+    def __init__(self, cameras: Sequence[RgbdCamera], frames: Union[Iterable[Frame], Callable[[], Optional[Frame]]], filter: Optional[RgbdFilter] = None,
+                 cellsize: float = 0.0, first_timestamp: int = 0) -> None:
+        self.cameras: List[RgbdCamera] = list(cameras)
+        if not self.cameras:
+            raise ValueError("RgbdSource: no cameras")
+        self.filter = filter
+        self.cellsize = cellsize
+        self._next: Callable[[], Optional[Frame]]
+        if callable(frames):
+            self._next = frames
+        else:
+            it: Iterator[Frame] = iter(frames)
+            self._next = lambda: next(it, None)
+        self._pending: Optional[Frame] = None
+        self._eof = False
+        self._count = 0
+        self._first_timestamp = int(first_timestamp)
+        self._requested: set = set()
+        self._mapping_structs: Dict[int, util.cwipc_hip_rgbd_camera] = {}
+
+    # ---- cwipc_source_abstract ----
+    def free(self) -> None:
+        self._eof = True
+        self._pending = None
+
+    def eof(self) -> bool:
+        return self._eof and self._pending is None
+
+    def available(self, wait: bool) -> bool:
+        if self._pending is None and not self._eof:
+            self._pending = self._next()
+            if self._pending is None:
+                self._eof = True
+        return self._pending is not None
+
+    def get(self) -> Optional[util.cwipc_pointcloud_wrapper]:
+        if not self.available(True):
+            return None
+        frame, self._pending = self._pending, None
+        flags = (util.CWIPC_HIP_RGBD_ATTACH_RGB if "rgb" in self._requested else 0) | (util.CWIPC_HIP_RGBD_ATTACH_DEPTH if "depth" in self._requested else 0)
+        assert frame is not None
+        pc = from_rgbd(self.cameras, frame, self.filter, self._first_timestamp + self._count, self.cellsize, flags)
+        self._count += 1
+        return pc
+
+    def statistics(self) -> None:
+        print(f"RgbdSource: {self._count} frames")
+
+    # ---- cwipc_activesource_abstract ----
+    def start(self) -> bool:
+        return True
+
+    def stop(self) -> None:
+        pass
+
+    def reload_config(self, config: Union[str, bytes, None]) -> Any:
+        return False   # (cameraconfig.json is not read: the cameras are given to the constructor)
+
+    def get_config(self) -> bytes:
+        return b""
+
+    def seek(self, timestamp: int) -> bool:
+        return False
+
+    def maxtile(self) -> int:
+        """The reference's numbering: tile 0 is every camera together, tile i + 1 is camera i."""
+        return len(self.cameras) + 1
+
+    def get_tileinfo_dict(self, tilenum: int) -> cwipc_tileinfo_dict:
+        if tilenum == 0:
+            mask = 0
+            for cam in self.cameras:
+                mask |= cam.tile
+            return {"normal": {"x": 0.0, "y": 0.0, "z": 0.0}, "cameraName": None, "ncamera": len(self.cameras), "cameraMask": mask}
+        cam = self.cameras[tilenum - 1]
+        # the camera looks along +z: the tile's normal points back at it, the world direction of the camera's -z axis
+        m = numpy.asarray(cam.trafo, dtype=numpy.float64)
+        return {"normal": {"x": float(-m[0, 2]), "y": float(-m[1, 2]), "z": float(-m[2, 2])}, "cameraName": cam.serial.encode('utf8'), "ncamera": 1,
+                "cameraMask": cam.tile}
+
+    def request_metadata(self, name: str) -> None:
+        self._requested.add(name)
+
+    def is_metadata_requested(self, name: str) -> bool:
+        return name in self._requested
+
+    def serial_dict(self) -> Dict[int, str]:
+        """tile number -> serial number, what MultiCameraCoarse.set_serial_dict takes."""
+        return {cam.tile: cam.serial for cam in self.cameras}
+
+    def _camera_struct(self, tilenum: int) -> Optional[util.cwipc_hip_rgbd_camera]:
+        if tilenum not in self._mapping_structs:
+            for cam in self.cameras:
+                if cam.tile == tilenum:
+                    self._mapping_structs[tilenum] = cam.as_struct()
+                    break
+            else:
+                return None
+        return self._mapping_structs[tilenum]
+
+    def auxiliary_operation(self, op: str, inbuf: bytes, outbuf: bytearray) -> bool:
+        """"map2d3d": "ffff" (tile, u, v, depth in depth units) -> "fff" (the world point); "mapcolordepth": "iii" (tile, u, v of the
+        colour image) -> "ii" (u, v of the depth image).  False for another operation, a buffer of the wrong size, an unknown tile, and
+        where the library says false (no depth; outside the image)."""
+        if op == "map2d3d":
+            if len(inbuf) != 16 or len(outbuf) != 12:
+                return False
+            tile, u, v, d = struct.unpack("ffff", inbuf)
+            cam = self._camera_struct(int(tile)) if tile == int(tile) else None
+            point = util.cwipc_hip_rgbd_map2d3d(cam, int(u), int(v), int(d)) if cam is not None else None
+            if point is None:
+                return False
+            outbuf[:] = struct.pack("fff", *point)
+            return True
+        if op == "mapcolordepth":
+            if len(inbuf) != 12 or len(outbuf) != 8:
+                return False
+            tile, u, v = struct.unpack("iii", inbuf)
+            cam = self._camera_struct(tile)
+            pixel = util.cwipc_hip_rgbd_mapcolordepth(cam, u, v) if cam is not None else None
+            if pixel is None:
+                return False
+            outbuf[:] = struct.pack("ii", *pixel)
+            return True
+        return False

@@ -52,6 +52,8 @@ __all__ = [
     'cwipc_hip_noise', 'cwipc_hip_simulatecams_soft',
     'cwipc_hip_view', 'cwipc_hip_render',
     'cwipc_hip_marker_params', 'cwipc_hip_detect_markers', 'cwipc_hip_render_detect_markers', 'cwipc_hip_marker_labels',
+    'cwipc_hip_rgbd_camera', 'cwipc_hip_rgbd_filter', 'CWIPC_HIP_RGBD_ATTACH_RGB', 'CWIPC_HIP_RGBD_ATTACH_DEPTH', 'cwipc_hip_from_rgbd',
+    'cwipc_hip_rgbd_map2d3d', 'cwipc_hip_rgbd_mapcolordepth',
 ]
 
 # reference util.py:86, 346, 348
@@ -259,6 +261,9 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_render_detect_markers': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_long),
     'cwipc_hip_marker_labels': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_from_rgbd': ([_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR], cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
+    'cwipc_hip_rgbd_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -613,7 +618,8 @@ class cwipc_sink_wrapper:
 
 
 class cwipc_metadata:
-    """Additional data attached to a point cloud (reference util.py:950-1083; image helpers omitted: capture is out of scope)."""
+    """Additional data attached to a point cloud (reference util.py:946-1082), the image helpers included: a source that is asked for
+    "rgb" or "depth" metadata attaches its cameras' images as "rgb.<serial>" and "depth.<serial>" (RgbdSource does)."""
 
     def __init__(self, _cwipc_metadata: Optional[cwipc_metadata_p] = None):
         if _cwipc_metadata is not None:
@@ -642,6 +648,62 @@ class cwipc_metadata:
     def data(self, idx: int) -> bytes:
         size = self.size(idx)
         return bytearray((ctypes.c_ubyte * size).from_address(self.pointer(idx)))
+
+    # the images among the items (reference util.py:993-1082)
+    def _parse_aux_description(self, description: str) -> Dict[str, Any]:
+        """"k=v,k=v,..." as a dictionary; a value that reads as an integer becomes one."""
+        rv: Dict[str, Any] = {}
+        for f in description.split(','):
+            k, v = f.split('=')
+            try:
+                rv[k] = int(v)
+            except ValueError:
+                rv[k] = v
+        return rv
+
+    def get_image_description(self, idx: int) -> Dict[str, Any]:
+        """Item idx's description as an image description, with "image_format" (and "bpp", where a "format" gives it) added."""
+        desc = self._parse_aux_description(self.description(idx))
+        if "bpp" in desc:
+            by_bpp = {2: "Z16", 3: "RGB8", 4: "RGBA"}
+            if desc["bpp"] in by_bpp:
+                desc["image_format"] = by_bpp[desc["bpp"]]
+        if "format" in desc:
+            image_format = desc["format"]
+            by_format = {2: (3, "RGB8"), 3: (4, "BGRA"), 4: (2, "Z16")}
+            if image_format in by_format:
+                desc["bpp"], desc["image_format"] = by_format[image_format]
+            else:
+                desc["image_format"] = image_format   # a format given by name (it overrides what bpp suggested)
+        return desc
+
+    def get_image(self, idx: int) -> numpy.typing.NDArray[Any]:
+        """Item idx, an image, as an array: a colour image as uint8[height, width, 3] B, G, R, a depth image as uint16[height, width]."""
+        descr = self.get_image_description(idx)
+        image_format = descr["image_format"]
+        image_data = self.data(idx)
+        if image_format == "Z16":
+            return numpy.reshape(numpy.frombuffer(image_data, numpy.uint16), (descr["height"], descr["width"]))
+        if image_format == "RGB8":
+            return numpy.reshape(numpy.frombuffer(image_data, numpy.uint8), (descr["height"], descr["width"], descr["bpp"]))[:, :, [2, 1, 0]]
+        if image_format == "BGRA":
+            return numpy.reshape(numpy.frombuffer(image_data, numpy.uint8), (descr["height"], descr["width"], descr["bpp"]))[:, :, [0, 1, 2]]
+        raise CwipcError(f"Unknown auxiliary data image format: {repr(image_format)}")
+
+    def get_all_images(self, pattern: str = "") -> Dict[str, numpy.typing.NDArray[Any]]:
+        """The items named "rgb.*" and "depth.*" as arrays (get_image), by name.  With a pattern only those whose name contains it, and
+        the pattern is taken out of the name: ".12345" gives "rgb" and "depth" of that serial number, "rgb." the serial numbers."""
+        rv = {}
+        for idx in range(self.count()):
+            name = self.name(idx)
+            if not name.startswith("rgb.") and not name.startswith("depth."):
+                continue
+            if pattern:
+                if pattern not in name:
+                    continue
+                name = name.replace(pattern, '')
+            rv[name] = self.get_image(idx)
+        return rv
 
 
 # ---------------------------------------------------------------------------
@@ -1300,6 +1362,59 @@ def cwipc_hip_marker_labels(rgb: numpy.ndarray, params: Optional[cwipc_hip_marke
                                    labels.ctypes.data or 1) != 0:
         raise CwipcError("cwipc_hip_marker_labels failed: " + dll.cwipc_hip_last_error().decode('utf8'))
     return labels
+
+
+class cwipc_hip_rgbd_camera(ctypes.Structure):
+    """One camera of a frame (include/cwipc_util_amd/hip_ext.h: cwipc_hip_rgbd_camera): the image size, the addresses of its Z16 depth
+    image and of the colour image aligned to it (bpp 3: R, G, B; 4: B, G, R, A), the tile, the intrinsics, metres per depth unit, the
+    camera -> world matrix (row-major) and the serial number that names the attached images."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("depth", ctypes.c_void_p), ("colour", ctypes.c_void_p), ("bpp", ctypes.c_int32),
+                ("tile", ctypes.c_uint8), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+                ("depth_scale", ctypes.c_double), ("trafo", ctypes.c_double * 16), ("serial", ctypes.c_char_p)]
+
+
+class cwipc_hip_rgbd_filter(ctypes.Structure):
+    """The per-point filters of cwipc_hip_from_rgbd (include/cwipc_util_amd/hip_ext.h: cwipc_hip_rgbd_filter); all zero: all off."""
+    _fields_ = [("threshold_near", ctypes.c_double), ("threshold_far", ctypes.c_double), ("height_min", ctypes.c_double), ("height_max", ctypes.c_double),
+                ("radius", ctypes.c_float), ("greenscreen", ctypes.c_int32)]
+
+
+CWIPC_HIP_RGBD_ATTACH_RGB = 1
+CWIPC_HIP_RGBD_ATTACH_DEPTH = 2
+
+
+def cwipc_hip_from_rgbd(cameras: Sequence[cwipc_hip_rgbd_camera], filter: Optional[cwipc_hip_rgbd_filter] = None, timestamp: int = 0, cellsize: float = 0.0,
+                        attach_flags: int = 0) -> cwipc_pointcloud_wrapper:
+    """One device-resident cloud from the cameras' depth and colour images, built on the GPU: the cameras in the order given, each
+    camera's surviving pixels in row-major order, every point with its pixel's colour and its camera's tile.  The images the
+    structures point at must stay alive during the call (rgbd.RgbdCamera.as_struct keeps them).  attach_flags
+    (CWIPC_HIP_RGBD_ATTACH_*): the images go into the cloud's metadata.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    n = len(cameras)
+    array = (cwipc_hip_rgbd_camera * max(n, 1))(*cameras)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_from_rgbd(ctypes.addressof(array), n, ctypes.addressof(filter) if filter is not None else None, int(timestamp),
+                                                   float(cellsize), int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError("cwipc_hip_from_rgbd: no pointcloud created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_map2d3d(camera: cwipc_hip_rgbd_camera, u: int, v: int, d: int) -> Optional[Tuple[float, float, float]]:
+    """The world point of the camera's pixel (u, v) at depth d (in depth units), in the arithmetic of cwipc_hip_from_rgbd, as three
+    float32 values; None where the library says false (d <= 0, a camera it would refuse)."""
+    out = (ctypes.c_float * 3)()
+    if not cwipc_util_dll_load().cwipc_hip_rgbd_map2d3d(ctypes.addressof(camera), int(u), int(v), int(d), out):
+        return None
+    return out[0], out[1], out[2]
+
+
+def cwipc_hip_rgbd_mapcolordepth(camera: cwipc_hip_rgbd_camera, u: int, v: int) -> Optional[Tuple[int, int]]:
+    """The depth pixel of colour pixel (u, v): the same pixel, the images being aligned; None outside the image."""
+    out = (ctypes.c_int * 2)()
+    if not cwipc_util_dll_load().cwipc_hip_rgbd_mapcolordepth(ctypes.addressof(camera), int(u), int(v), out):
+        return None
+    return out[0], out[1]
 
 
 def cwipc_transform(pc: cwipc_pointcloud_wrapper, transform: Any) -> cwipc_pointcloud_wrapper:

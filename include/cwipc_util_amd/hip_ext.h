@@ -419,6 +419,54 @@ _CWIPC_UTIL_EXPORT long cwipc_hip_render_detect_markers(cwipc_pointcloud *pc, co
                                                         const cwipc_hip_marker_params *params, int32_t *ids, float *corners, float *corner_depth,
                                                         size_t cap);
 
+/* ---- the RGB-D source: a cloud from the cameras' own depth and colour images (the step a capturer plug-in of the reference does on
+ * the host; its shared per-point filters: reference include/cwipc_util/internal/capturers.hpp:208-275) ---- */
+typedef struct cwipc_hip_rgbd_camera {
+    int32_t width, height;
+    const uint16_t *depth;      /* Z16, row-major, 0: no depth */
+    const uint8_t *colour;      /* ALIGNED to the depth image, the same size, rows tightly packed */
+    int32_t bpp;                /* 3: R, G, B bytes; 4: B, G, R, A bytes */
+    uint8_t tile;
+    double fx, fy, cx, cy;
+    double depth_scale;         /* metres per depth unit */
+    double trafo[16];           /* camera -> world, row-major */
+    const char *serial;         /* names the attached images; may be NULL when attach_flags is 0 */
+} cwipc_hip_rgbd_camera;
+typedef struct cwipc_hip_rgbd_filter {
+    double threshold_near, threshold_far;   /* off when threshold_far <= threshold_near */
+    double height_min, height_max;          /* off when height_min == height_max */
+    float radius;                           /* off when radius <= 0 */
+    int32_t greenscreen;                    /* off when 0 */
+} cwipc_hip_rgbd_filter;
+#define CWIPC_HIP_RGBD_ATTACH_RGB 1
+#define CWIPC_HIP_RGBD_ATTACH_DEPTH 2
+/* One device-resident cloud from ncam cameras' images.  All arithmetic is float64, every operation rounded on its own
+ * (csrc/rgbd_terms.hpp is the one statement of it, tests/rgbd_model.py its numpy restatement).  Pixel (u, v) with depth d != 0:
+ *    z  = (double)d * depth_scale;  xc = ((double)u - cx) * z / fx;  yc = ((double)v - cy) * z / fy      (left to right)
+ *    X  = ((m00*xc + m01*yc) + m02*z) + m03, Y and Z alike, m = trafo;  the point is (float)X, (float)Y, (float)Z with the pixel's
+ *    r, g, b and the camera's tile.
+ * Filters, in this order (filter may be NULL: all off):
+ *    depth range: dropped if z < threshold_near || z > threshold_far;
+ *    height:      dropped if y < height_min || y > height_max, y the float32 world y;
+ *    radius:      kept iff (float)((double)x*(double)x + (double)z*(double)z) < radius*radius (float32 product), x and z the float32
+ *                 world coordinates: the reference's isPointInRadius;
+ *    greenscreen: dropped iff the reference's integer hue (rgbToHsv) is in 60..130: what its isNotGreen comes to.
+ * Output order: the cameras in argument order, within a camera the kept pixels in row-major order.  The images may be ordinary or
+ * page-locked host memory (cwipc_hip_host_alloc / _register: then they are copied from where they lie); they go up with asynchronous
+ * copies on the calling thread's stream and are free again when the call returns.  A frame in which nothing survives is a valid
+ * empty cloud.  The cloud knows the tiles it can hold.  attach_flags (CWIPC_HIP_RGBD_ATTACH_*) copies the given images into the cloud's
+ * metadata as "rgb.<serial>" ("width=W,height=H,bpp=3|4") and "depth.<serial>" ("width=W,height=H,bpp=2"), per camera in that order.
+ * NULL (errorMessage, if given, and cwipc_hip_last_error() have the text) for a NULL pointer, ncam <= 0, a width or height < 1, more than
+ * 2^31 - 1 pixels in all, bpp not 3 or 4, an intrinsic, depth_scale or matrix entry that is not finite, fx or fy zero. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_camera *cams, int ncam, const cwipc_hip_rgbd_filter *filter, uint64_t timestamp,
+                                                         float cellsize, int attach_flags, char **errorMessage);
+/* The two mappings a grabber answers for the registration tooling (auxiliary operations "map2d3d" and "mapcolordepth"), on the host,
+ * with the arithmetic above.  map2d3d: the world point of colour pixel (u, v) at depth d (any u, v; d > 0); 1, or 0 for a NULL
+ * argument, d <= 0, or a camera cwipc_hip_from_rgbd would refuse.  mapcolordepth: the depth pixel of colour pixel (u, v) -- the same
+ * pixel, the images being aligned; 1 inside the image, 0 outside it or for a NULL argument. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_map2d3d(const cwipc_hip_rgbd_camera *cam, int u, int v, int d, float out[3]);
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_mapcolordepth(const cwipc_hip_rgbd_camera *cam, int u, int v, int out[2]);
+
 /* ---- intermediate results for parity tests ---- */
 /* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
  * pixel; 0 ok, -1 error (the image and parameter checks of cwipc_hip_detect_markers). */
