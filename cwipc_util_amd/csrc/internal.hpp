@@ -7,7 +7,7 @@
 //   synthetic.cpp   cwipc_synthetic source          (reference src/cwipc_synthetic.cpp)
 //   stubs.cpp       out-of-scope constructors that fail loudly
 //   filters.cpp     C entry points of the hot path, host orchestration
-//   rgbd.cpp        cwipc_hip_from_rgbd: the RGB-D source end (images in, device-resident cloud out)
+//   rgbd.cpp        cwipc_hip_from_rgbd, cwipc_hip_rgbd_rig_*: the RGB-D source end (images in, device-resident cloud out)
 //   kernels_*.hip   the HIP kernels (gfx950)
 #pragma once
 
@@ -26,6 +26,7 @@
 #include "cwipc_util/api.h"
 #include "cwipc_util_amd/hip_ext.h"
 #include "rgbd_terms.hpp"
+#include "rgbd_lens.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -484,6 +485,28 @@ void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const R
 // Pass 2: the points, in pixel order, into dst (room for total_pixels points).
 void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
                   hipStream_t s);
+// ---- the raw entry, cwipc_hip_rgbd_rig_grab (the contract is in rgbd_lens.hpp and hip_ext.h) ----
+// One camera of a rig.  The RgbdCamDev part is the camera as count and scatter see it once the registration has run: depth is the
+// (eroded, cleared) depth image, colour the REGISTERED image on the depth grid, bpp 3.  depth_rw and registered are those two again,
+// to write through.  rays: the ray table (2 doubles per depth pixel), nullptr for a sensor without depth lens coefficients.
+// raw_colour: the colour image as the camera sent it (raw_bpp bytes per pixel, ct.width x ct.height, 4-byte aligned, 8 readable
+// bytes behind it).  The validity words of the erosion: wpr words per row, this camera's first is number wfirst.
+struct RgbdRawCamDev : RgbdCamDev {
+    uint16_t *depth_rw;
+    uint8_t *registered;
+    const double *rays;
+    const uint8_t *raw_colour;
+    RgbdColourTerms ct;
+    uint32_t raw_bpp, height, wpr, wfirst;
+};
+void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
+                unsigned long long *total_host, uint32_t tag, hipStream_t s);
+void rgbd_scatter(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
+                  hipStream_t s);
+// Box erosion of every camera's depth image in place, 0 <= ex, ey <= 32: two launches over the word grid (total_words words).
+void rgbd_erode(const RgbdRawCamDev *cams, int ncam, uint32_t total_words, int ex, int ey, unsigned long long *words, hipStream_t s);
+// Every depth pixel's registered colour; the depth of a pixel without one is cleared.
+void rgbd_register(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, hipStream_t s);
 
 }  // namespace k
 

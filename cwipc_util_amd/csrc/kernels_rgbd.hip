@@ -8,8 +8,16 @@
 // per wave.  A 3-byte colour pixel is NOT read as three byte loads: a lane reads the two aligned dwords that hold its bytes (the
 // second is the next lane's first or in the same 64-byte line) and shifts the pixel out of the 64-bit pair -- two dword loads of
 // 192 contiguous bytes per wave.  The host leaves 8 readable bytes behind every colour image for the last pixel's pair.
+//
+// The raw entry (cwipc_hip_rgbd_rig_grab, rgbd_lens.hpp) runs up to three kernels in front of the same count -> scan -> scatter: the
+// depth erosion as two passes over one 1-bit validity plane (a wave's 64 pixels of a row are one ballot word), and the registration,
+// which gives every depth pixel the colour pixel its point projects to and clears the depth of those that have none.  After it the
+// frame is a depth image with an aligned RGB8 image again; count and scatter are the kernels above instantiated for a camera type
+// that also knows its ray table (Cam = RgbdRawCamDev), the existing instantiation (Cam = RgbdCamDev) computing what it always did.
 #include "internal.hpp"
 #include "block_scan.hpp"
+
+#include <type_traits>
 
 namespace cwipc_amd {
 namespace k {
@@ -35,7 +43,8 @@ __device__ __forceinline__ uint32_t load_colour(const uint8_t *__restrict__ colo
 }
 
 // the camera of pixel number g, searched upwards from k0 (the camera of the workgroup's first pixel)
-__device__ __forceinline__ int camera_of(const RgbdCamDev *__restrict__ cams, int ncam, int k0, uint32_t g) {
+template <class Cam>
+__device__ __forceinline__ int camera_of(const Cam *__restrict__ cams, int ncam, int k0, uint32_t g) {
     int k = k0;
     while (k + 1 < ncam && g >= cams[k + 1].first) k++;
     return k;
@@ -49,11 +58,12 @@ struct Pixel {
 };
 
 // does pixel number g give a point?  px: what the scatter pass needs of it
-__device__ __forceinline__ bool pixel_keep(const RgbdCamDev *__restrict__ cams, int ncam, int k0, uint32_t g, uint32_t total, const RgbdFilterTerms &f,
+template <class Cam>
+__device__ __forceinline__ bool pixel_keep(const Cam *__restrict__ cams, int ncam, int k0, uint32_t g, uint32_t total, const RgbdFilterTerms &f,
                                            unsigned active, Pixel &px) {
     if (g >= total) return false;
     px.cam = camera_of(cams, ncam, k0, g);
-    const RgbdCamDev &c = cams[px.cam];
+    const Cam &c = cams[px.cam];
     px.p = g - c.first;
     px.d = c.depth[px.p];
     if (px.d == 0u) return false;
@@ -61,11 +71,15 @@ __device__ __forceinline__ bool pixel_keep(const RgbdCamDev *__restrict__ cams, 
     px.u = (int)(px.p - (uint32_t)px.v * c.width);
     const uint8_t *colour = c.colour;
     const uint32_t p = px.p, bpp = c.bpp;
+    if constexpr (std::is_same<Cam, RgbdRawCamDev>::value) {
+        if (c.rays) return rgbd_keep_ray(c.t, f, active, c.rays + 2 * (size_t)p, px.d, [=]() { return load_colour(colour, p, bpp); });
+    }
     return rgbd_keep(c.t, f, active, px.u, px.v, px.d, [=]() { return load_colour(colour, p, bpp); });
 }
 
 // the workgroup's count (thread 0's return value)
-__device__ __forceinline__ uint32_t count_tile(const RgbdCamDev *__restrict__ cams, int ncam, uint32_t total, const RgbdFilterTerms &f, unsigned active,
+template <class Cam>
+__device__ __forceinline__ uint32_t count_tile(const Cam *__restrict__ cams, int ncam, uint32_t total, const RgbdFilterTerms &f, unsigned active,
                                                uint32_t *wave_sum) {
     const uint32_t tile0 = blockIdx.x * (uint32_t)TILE;
     const int k0 = camera_of(cams, ncam, 0, tile0);
@@ -84,7 +98,8 @@ __device__ __forceinline__ uint32_t count_tile(const RgbdCamDev *__restrict__ ca
     return t;
 }
 
-__global__ void __launch_bounds__(BLOCK) rgbd_count_kernel(const RgbdCamDev *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f, unsigned active,
+template <class Cam>
+__global__ void __launch_bounds__(BLOCK) rgbd_count_kernel(const Cam *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f, unsigned active,
                                                           uint32_t *__restrict__ counts) {
     __shared__ uint32_t wave_sum[WAVES];
     const uint32_t t = count_tile(cams, ncam, total, f, active, wave_sum);
@@ -92,7 +107,8 @@ __global__ void __launch_bounds__(BLOCK) rgbd_count_kernel(const RgbdCamDev *__r
 }
 
 // count and scan in one launch: compact_count_scan_kernel's ticket (kernels_basic.hip)
-__global__ void __launch_bounds__(BLOCK) rgbd_count_scan_kernel(const RgbdCamDev *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f,
+template <class Cam>
+__global__ void __launch_bounds__(BLOCK) rgbd_count_scan_kernel(const Cam *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f,
                                                                unsigned active, uint32_t *__restrict__ counts, uint32_t *__restrict__ ticket,
                                                                unsigned long long *__restrict__ total_host, uint32_t tag) {
     __shared__ uint32_t wave_sum[WAVES];
@@ -112,7 +128,8 @@ __global__ void __launch_bounds__(BLOCK) rgbd_count_scan_kernel(const RgbdCamDev
 
 // offsets: the scanned counts.  A kept pixel's rank inside the tile: the kept pixels of the steps before its own, of the waves before
 // its own in its step, and of the lanes before its own in its wave -- pixel order.
-__global__ void __launch_bounds__(BLOCK) rgbd_scatter_kernel(const RgbdCamDev *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f, unsigned active,
+template <class Cam>
+__global__ void __launch_bounds__(BLOCK) rgbd_scatter_kernel(const Cam *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f, unsigned active,
                                                             const uint32_t *__restrict__ offsets, float *__restrict__ ox, float *__restrict__ oy,
                                                             float *__restrict__ oz, uint32_t *__restrict__ ow) {
     __shared__ uint32_t wave_sum[STEPS][WAVES];
@@ -142,9 +159,12 @@ __global__ void __launch_bounds__(BLOCK) rgbd_scatter_kernel(const RgbdCamDev *_
         }
         if (keep[s]) {
             const uint32_t idx = at + before_wave + before_lane[s];
-            const RgbdCamDev &c = cams[px[s].cam];
+            const Cam &c = cams[px[s].cam];
             float pt[3];
-            rgbd_point(c.t, px[s].u, px[s].v, px[s].d, pt);
+            if constexpr (std::is_same<Cam, RgbdRawCamDev>::value)
+                rgbd_raw_point(c.t, c.rays ? c.rays + 2 * (size_t)px[s].p : nullptr, px[s].u, px[s].v, px[s].d, pt);
+            else
+                rgbd_point(c.t, px[s].u, px[s].v, px[s].d, pt);
             const uint32_t w = load_colour(c.colour, px[s].p, c.bpp) | (c.tile << 24);
             if (idx < total) {   // (always, the two passes seeing the same images; no store past the planes whatever happens)
                 ox[idx] = pt[0]; oy[idx] = pt[1]; oz[idx] = pt[2]; ow[idx] = w;
@@ -158,23 +178,128 @@ __global__ void __launch_bounds__(BLOCK) rgbd_scatter_kernel(const RgbdCamDev *_
 
 size_t rgbd_blocks(uint32_t total_pixels) { return ((size_t)total_pixels + TILE - 1) / TILE; }
 
-void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
-                unsigned long long *total_host, uint32_t tag, hipStream_t s) {
+namespace {
+
+template <class Cam>
+void count_launch(const Cam *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
+                  unsigned long long *total_host, uint32_t tag, hipStream_t s) {
     const size_t nb = rgbd_blocks(total_pixels);
     const unsigned active = rgbd_active(f);
     if (total_pixels <= SMALL_FRAME && ticket) {
-        CW_LAUNCH("rgbd_count", rgbd_count_scan_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f, active, counts, ticket, total_host,
-                  tag);
+        CW_LAUNCH("rgbd_count", rgbd_count_scan_kernel<Cam>, dim3((unsigned)nb), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f, active, counts, ticket,
+                  total_host, tag);
     } else {
-        CW_LAUNCH("rgbd_count", rgbd_count_kernel, dim3((unsigned)nb), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f, active, counts);
+        CW_LAUNCH("rgbd_count", rgbd_count_kernel<Cam>, dim3((unsigned)nb), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f, active, counts);
         compact_scan(counts, nb, total_host, tag, s);
     }
 }
 
+template <class Cam>
+void scatter_launch(const Cam *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s) {
+    CW_LAUNCH("rgbd_scatter", rgbd_scatter_kernel<Cam>, dim3((unsigned)rgbd_blocks(total_pixels)), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f,
+              rgbd_active(f), offsets, dst.x(), dst.y(), dst.z(), dst.rgbt());
+}
+
+// ---- the raw entry's own kernels ----
+
+// the camera of validity word g
+__device__ __forceinline__ int camera_of_word(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t g) {
+    int k = 0;
+    while (k + 1 < ncam && g >= cams[k + 1].wfirst) k++;
+    return k;
+}
+
+// Erosion, the row pass.  Wave g owns word g of the word grid: camera after camera, row after row, ceil(width / 64) words per row.
+// Its 64 pixels' validity is one ballot; so is either neighbour's (all ones where the row ends: outside the image nothing erodes).
+__global__ void __launch_bounds__(BLOCK) rgbd_erode_rows_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total_words, int ex,
+                                                               unsigned long long *__restrict__ words) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x * (uint32_t)WAVES + (threadIdx.x >> 6);
+    if (g >= total_words) return;   // (the whole wave)
+    const RgbdRawCamDev &c = cams[camera_of_word(cams, ncam, g)];
+    const uint32_t local = g - c.wfirst, row = local / c.wpr, wi = local - row * c.wpr;
+    const uint16_t *__restrict__ line = c.depth + (size_t)row * c.width;
+    const uint32_t u = wi * 64u + (uint32_t)lane;
+    const unsigned long long own = __ballot(u >= c.width || line[u] != 0);
+    unsigned long long left = ~0ull, right = ~0ull;
+    if (ex > 0) {
+        if (wi > 0) left = __ballot(line[u - 64u] != 0);   // (a whole word: all its pixels are in the row)
+        if (wi + 1 < c.wpr) right = __ballot(u + 64u >= c.width || line[u + 64u] != 0);
+    }
+    const unsigned long long acc = rgbd_erode_word(left, own, right, ex);
+    if (lane == 0) words[g] = acc;
+}
+
+// Erosion, the column pass: the AND of the 2 ey + 1 row-eroded words above and below (those inside the image) says which of the
+// wave's 64 pixels keep their depth; the others' depth is cleared in place.
+__global__ void __launch_bounds__(BLOCK) rgbd_erode_cols_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total_words, int ey,
+                                                               const unsigned long long *__restrict__ words) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t g = blockIdx.x * (uint32_t)WAVES + (threadIdx.x >> 6);
+    if (g >= total_words) return;
+    const RgbdRawCamDev &c = cams[camera_of_word(cams, ncam, g)];
+    const uint32_t local = g - c.wfirst, row = local / c.wpr, wi = local - row * c.wpr;
+    const uint32_t lo = row > (uint32_t)ey ? row - (uint32_t)ey : 0u, hi = row + (uint32_t)ey < c.height ? row + (uint32_t)ey : c.height - 1u;
+    unsigned long long acc = ~0ull;
+    for (uint32_t r = lo; r <= hi; r++) acc &= words[(size_t)c.wfirst + (size_t)r * c.wpr + wi];
+    const uint32_t u = wi * 64u + (uint32_t)lane;
+    if (u < c.width && !((acc >> lane) & 1ull)) c.depth_rw[(size_t)row * c.width + u] = 0;
+}
+
+// Registration: one lane per depth pixel of the frame.  A pixel with depth takes the colour of the colour pixel its point projects to
+// (rgbd_colour_pixel: evaluated here and nowhere else) or, having none, loses its depth; every pixel's registered colour is written,
+// black where there is none.  The colour index is in range by rgbd_colour_pixel's test on the doubles; p < the camera's pixel count.
+__global__ void __launch_bounds__(BLOCK) rgbd_register_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total) {
+    const uint32_t g = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
+    if (g >= total) return;
+    const RgbdRawCamDev &c = cams[camera_of(cams, ncam, 0, g)];
+    const uint32_t p = g - c.first;
+    const unsigned d = c.depth[p];
+    uint32_t rgb = 0;
+    if (d != 0u) {
+        const int v = (int)(p / c.width), u = (int)(p - (uint32_t)v * c.width);
+        const double z = rgbd_z(d, c.t.depth_scale);
+        double xc, yc;
+        rgbd_raw_xy(c.t, c.rays ? c.rays + 2 * (size_t)p : nullptr, u, v, z, xc, yc);
+        int at[2];
+        if (rgbd_colour_pixel(c.ct, xc, yc, z, at)) rgb = load_colour(c.raw_colour, (uint32_t)at[1] * (uint32_t)c.ct.width + (uint32_t)at[0], c.raw_bpp);
+        else c.depth_rw[p] = 0;
+    }
+    uint8_t *out = c.registered + (size_t)p * 3u;
+    out[0] = (uint8_t)rgb; out[1] = (uint8_t)(rgb >> 8); out[2] = (uint8_t)(rgb >> 16);
+}
+
+}  // namespace
+
+void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
+                unsigned long long *total_host, uint32_t tag, hipStream_t s) {
+    count_launch(cams, ncam, total_pixels, f, counts, ticket, total_host, tag, s);
+}
+
 void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
                   hipStream_t s) {
-    CW_LAUNCH("rgbd_scatter", rgbd_scatter_kernel, dim3((unsigned)rgbd_blocks(total_pixels)), dim3(BLOCK), 0, s, cams, ncam, total_pixels, f, rgbd_active(f),
-              offsets, dst.x(), dst.y(), dst.z(), dst.rgbt());
+    scatter_launch(cams, ncam, total_pixels, f, offsets, dst, s);
+}
+
+void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
+                unsigned long long *total_host, uint32_t tag, hipStream_t s) {
+    count_launch(cams, ncam, total_pixels, f, counts, ticket, total_host, tag, s);
+}
+
+void rgbd_scatter(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
+                  hipStream_t s) {
+    scatter_launch(cams, ncam, total_pixels, f, offsets, dst, s);
+}
+
+void rgbd_erode(const RgbdRawCamDev *cams, int ncam, uint32_t total_words, int ex, int ey, unsigned long long *words, hipStream_t s) {
+    const dim3 grid((unsigned)(((size_t)total_words + WAVES - 1) / WAVES));
+    CW_LAUNCH("rgbd_erode_rows", rgbd_erode_rows_kernel, grid, dim3(BLOCK), 0, s, cams, ncam, total_words, ex, words);
+    CW_LAUNCH("rgbd_erode_cols", rgbd_erode_cols_kernel, grid, dim3(BLOCK), 0, s, cams, ncam, total_words, ey, (const unsigned long long *)words);
+}
+
+void rgbd_register(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, hipStream_t s) {
+    CW_LAUNCH("rgbd_register", rgbd_register_kernel, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams, ncam,
+              total_pixels);
 }
 
 }  // namespace k

@@ -5,10 +5,16 @@
 // holds them in page-locked memory, through the thread's pinned staging buffer otherwise) together with one small table of cameras;
 // the point count comes back in a pinned word.  The two mappings a grabber answers for the registration tooling are here too, on the
 // host.  There is NO CPU fallback for the cloud: without a usable GPU the call logs an ERROR and returns NULL.
+//
+// The raw entry (cwipc_hip_rgbd_rig_*, rgbd_lens.hpp) keeps what is constant per camera in a rig: the camera table, the ray tables
+// (computed here at creation) and the frame's device buffers, so that a grab uploads the images and nothing else.
 #include "internal.hpp"
 
 #include <cmath>
 #include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
 
 using namespace cwipc_amd;
 
@@ -52,6 +58,39 @@ void attach_image(cwipc_metadata *meta, const std::string &name, const cwipc_hip
     if (!copy) return;
     memcpy(copy, data, bytes);
     meta->_add(name, "width=" + std::to_string(cam.width) + ",height=" + std::to_string(cam.height) + ",bpp=" + std::to_string(bpp), copy, bytes, ::free);
+}
+
+// After the stream has been waited for (ok: everything until then went well): the cloud of the `kept` points the scan published under
+// `tag`, in dst's planes (room for total points) or, when few survive, in planes of their own.  nullptr: the error has been noted.
+cwipc_hip_pointcloud *finish_cloud(const char *who, ThreadCtx &c, bool ok, uint32_t tag, size_t total, std::shared_ptr<DeviceSoA> dst, const uint32_t tiles[8],
+                                   uint64_t timestamp, float cellsize) {
+    volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    const size_t kept = (uint32_t)*word;
+    if (!ok || (uint32_t)(*word >> 32) != tag || kept > total) {
+        if (ok) note_error(who, "inconsistent point count");
+        else if (!*cwipc_hip_last_error()) note_error(who, "a kernel or a copy failed");
+        else cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, cwipc_hip_last_error());
+        return nullptr;
+    }
+    if (kept * 16 >= total) {
+        dst->npoints = kept;   // the planes keep their spacing, only the count shrinks (as a compaction's result)
+    } else {
+        auto small = soa_alloc(kept);
+        if (!small) return nullptr;
+        if (kept) {
+            bool copied = hipMemcpyAsync(small->x(), dst->x(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                          hipMemcpyAsync(small->y(), dst->y(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                          hipMemcpyAsync(small->z(), dst->z(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                          hipMemcpyAsync(small->rgbt(), dst->rgbt(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess;
+            copied = c.sync() && copied;
+            if (!copied) { hip_failed(hipGetLastError(), who, __FILE__, __LINE__); return nullptr; }
+        }
+        dst = small;
+    }
+    dst->set_tiles(tiles);
+    auto *rv = new cwipc_hip_pointcloud();
+    rv->adopt_device(dst, timestamp, cellsize);
+    return rv;
 }
 
 }  // namespace
@@ -140,31 +179,8 @@ extern "C" cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_camera *ca
     }
     ok = c.sync() && ok;   // (also on failure: copies that read the staging buffer and kernels that write the planes may be in flight)
     pool_free(dev);
-    const size_t kept = (uint32_t)*word;
-    if (!ok || (uint32_t)(*word >> 32) != tag || kept > total) {
-        if (ok) note_error(who, "inconsistent point count");
-        else if (!*cwipc_hip_last_error()) note_error(who, "a kernel or a copy failed");
-        else cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, cwipc_hip_last_error());
-        return nullptr;
-    }
-    if (kept * 16 >= total) {
-        dst->npoints = kept;   // the planes keep their spacing, only the count shrinks (as a compaction's result)
-    } else {
-        auto small = soa_alloc(kept);
-        if (!small) return nullptr;
-        if (kept) {
-            bool copied = hipMemcpyAsync(small->x(), dst->x(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->y(), dst->y(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->z(), dst->z(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->rgbt(), dst->rgbt(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess;
-            copied = c.sync() && copied;
-            if (!copied) { hip_failed(hipGetLastError(), "cwipc_hip_from_rgbd", __FILE__, __LINE__); return nullptr; }
-        }
-        dst = small;
-    }
-    dst->set_tiles(tiles);
-    auto *rv = new cwipc_hip_pointcloud();
-    rv->adopt_device(dst, timestamp, cellsize);
+    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, (size_t)total, dst, tiles, timestamp, cellsize);
+    if (!rv) return nullptr;
     if (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) {
         cwipc_metadata *meta = rv->access_metadata();
         for (int k = 0; k < ncam; k++) {
@@ -183,6 +199,295 @@ extern "C" int cwipc_hip_rgbd_map2d3d(const cwipc_hip_rgbd_camera *cam, int u, i
 
 extern "C" int cwipc_hip_rgbd_mapcolordepth(const cwipc_hip_rgbd_camera *cam, int u, int v, int out[2]) {
     if (cam == nullptr || out == nullptr || u < 0 || v < 0 || u >= cam->width || v >= cam->height) return 0;
+    out[0] = u;
+    out[1] = v;
+    return 1;
+}
+
+// ---------------------------------------------------------------------------
+// the raw entry: a rig of sensors (hip_ext.h: cwipc_hip_rgbd_rig_*)
+// ---------------------------------------------------------------------------
+
+struct cwipc_hip_rgbd_rig {
+    int device = -1;
+    std::vector<cwipc_hip_rgbd_sensor> sensors;
+    std::vector<std::string> serials;            // copies; has_serial says which sensors had one
+    std::vector<bool> has_serial;
+    std::vector<std::vector<double>> rays;       // per camera 2 * W * H doubles
+    std::vector<k::RgbdRawCamDev> table;         // the host copy of the device table
+    uint8_t *dev = nullptr;                      // one pool block: the table | per camera its ray table, depth, colour and registered image | the words
+    unsigned long long *words = nullptr;
+    uint32_t total = 0, total_words = 0;
+    uint32_t tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::mutex lock;                             // one grab at a time: the frame's device buffers are the rig's
+};
+
+namespace {
+
+RgbdLens lens_of(const double k[8]) {
+    RgbdLens l;
+    l.k1 = k[0]; l.k2 = k[1]; l.p1 = k[2]; l.p2 = k[3]; l.k3 = k[4]; l.k4 = k[5]; l.k5 = k[6]; l.k6 = k[7];
+    return l;
+}
+
+const char *sensor_problem(const cwipc_hip_rgbd_sensor &s) {
+    if (s.width < 1 || s.height < 1 || s.colour_width < 1 || s.colour_height < 1) return "width and height must be at least 1";
+    if ((uint64_t)s.colour_width * (uint64_t)s.colour_height > 0x7fffffffull) return "more than 2^31 - 1 pixels";
+    if (s.colour_bpp != 3 && s.colour_bpp != 4) return "colour_bpp must be 3 (R, G, B) or 4 (B, G, R, A)";
+    bool finite = std::isfinite(s.fx) && std::isfinite(s.fy) && std::isfinite(s.cx) && std::isfinite(s.cy) && std::isfinite(s.depth_scale) &&
+                  std::isfinite(s.colour_fx) && std::isfinite(s.colour_fy) && std::isfinite(s.colour_cx) && std::isfinite(s.colour_cy);
+    for (int i = 0; i < 8; i++) finite = finite && std::isfinite(s.coeffs[i]) && std::isfinite(s.colour_coeffs[i]);
+    for (int i = 0; i < 16; i++) finite = finite && std::isfinite(s.trafo[i]) && std::isfinite(s.depth_to_colour[i]);
+    if (!finite) return "the intrinsics, the lens coefficients, depth_scale and the matrices must be finite";
+    if (s.fx == 0.0 || s.fy == 0.0 || s.colour_fx == 0.0 || s.colour_fy == 0.0) return "fx and fy must not be zero";
+    return nullptr;
+}
+
+RgbdCamTerms sensor_terms(const cwipc_hip_rgbd_sensor &s) {
+    RgbdCamTerms t;
+    t.fx = s.fx; t.fy = s.fy; t.cx = s.cx; t.cy = s.cy; t.depth_scale = s.depth_scale;
+    for (int i = 0; i < 12; i++) t.m[i] = s.trafo[i];
+    return t;
+}
+
+RgbdColourTerms colour_terms(const cwipc_hip_rgbd_sensor &s) {
+    RgbdColourTerms t;
+    t.fx = s.colour_fx; t.fy = s.colour_fy; t.cx = s.colour_cx; t.cy = s.colour_cy;
+    t.lens = lens_of(s.colour_coeffs);
+    for (int i = 0; i < 12; i++) t.m[i] = s.depth_to_colour[i];
+    t.width = s.colour_width; t.height = s.colour_height;
+    return t;
+}
+
+bool rig_camera_ok(const cwipc_hip_rgbd_rig *rig, int cam) { return rig != nullptr && cam >= 0 && (size_t)cam < rig->sensors.size(); }
+
+}  // namespace
+
+extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage) {
+    const char *who = "cwipc_hip_rgbd_rig_create";
+    cwipc_log_set_errorbuf(errorMessage);
+    struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
+    if (sensors == nullptr || ncam <= 0) {
+        note_error(who, sensors == nullptr ? "NULL argument" : "ncam must be at least 1");
+        return nullptr;
+    }
+    uint64_t total = 0, total_words = 0;
+    for (int k = 0; k < ncam; k++) {
+        if (const char *problem = sensor_problem(sensors[k])) {
+            note_error(who, "camera " + std::to_string(k) + ": " + problem);
+            return nullptr;
+        }
+        total += (uint64_t)sensors[k].width * (uint64_t)sensors[k].height;
+        total_words += (uint64_t)sensors[k].height * (((uint64_t)sensors[k].width + 63) / 64);
+        if (total > 0x7fffffffull) {
+            note_error(who, "more than 2^31 - 1 pixels");
+            return nullptr;
+        }
+    }
+    if (!device_available(who)) return nullptr;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+
+    std::unique_ptr<cwipc_hip_rgbd_rig> rig(new cwipc_hip_rgbd_rig());
+    rig->device = current_device();
+    rig->sensors.assign(sensors, sensors + ncam);
+    rig->total = (uint32_t)total;
+    rig->total_words = (uint32_t)total_words;
+    rig->table.resize((size_t)ncam);
+    rig->rays.resize((size_t)ncam);
+    const size_t table_bytes = round256((size_t)ncam * sizeof(k::RgbdRawCamDev));
+    size_t bytes = table_bytes;
+    for (int k = 0; k < ncam; k++) {
+        cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        rig->has_serial.push_back(s.serial != nullptr);
+        rig->serials.push_back(s.serial ? s.serial : "");
+        s.serial = nullptr;   // (the caller's string is not kept)
+        const size_t npix = (size_t)s.width * (size_t)s.height, ncol = (size_t)s.colour_width * (size_t)s.colour_height;
+        const RgbdCamTerms t = sensor_terms(s);
+        const RgbdLens lens = lens_of(s.coeffs);
+        std::vector<double> &rays = rig->rays[(size_t)k];
+        rays.resize(2 * npix);
+        for (int v = 0; v < s.height; v++)
+            for (int u = 0; u < s.width; u++) rgbd_ray(t, lens, u, v, &rays[2 * ((size_t)v * (size_t)s.width + (size_t)u)]);
+        if (!rgbd_lens_is_pinhole(lens)) bytes += round256(npix * 16);
+        bytes += round256(npix * 2) + round256(ncol * (size_t)s.colour_bpp + 8) + round256(npix * 3 + 8);
+        rig->tiles[s.tile >> 5] |= 1u << (s.tile & 31u);
+    }
+    bytes += round256((size_t)total_words * 8);
+    rig->dev = (uint8_t *)pool_alloc(bytes);
+    if (!rig->dev) {
+        note_error(who, "out of memory");
+        return nullptr;
+    }
+    uint8_t *at = rig->dev + table_bytes;
+    uint32_t first = 0, wfirst = 0;
+    bool ok = true;
+    for (int k = 0; k < ncam; k++) {
+        const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        const size_t npix = (size_t)s.width * (size_t)s.height, ncol = (size_t)s.colour_width * (size_t)s.colour_height;
+        k::RgbdRawCamDev &t = rig->table[(size_t)k];
+        t.t = sensor_terms(s);
+        t.ct = colour_terms(s);
+        t.rays = nullptr;
+        if (!rgbd_lens_is_pinhole(lens_of(s.coeffs))) {
+            t.rays = (const double *)at;
+            ok = ok && hipMemcpyAsync(at, rig->rays[(size_t)k].data(), npix * 16, hipMemcpyHostToDevice, c.stream) == hipSuccess;
+            at += round256(npix * 16);
+        }
+        t.depth_rw = (uint16_t *)at; t.depth = t.depth_rw;
+        at += round256(npix * 2);
+        t.raw_colour = at;
+        at += round256(ncol * (size_t)s.colour_bpp + 8);
+        t.registered = at; t.colour = t.registered;
+        at += round256(npix * 3 + 8);
+        t.width = (uint32_t)s.width; t.height = (uint32_t)s.height; t.bpp = 3u; t.raw_bpp = (uint32_t)s.colour_bpp; t.tile = s.tile;
+        t.first = first; t.wpr = (uint32_t)(((uint64_t)s.width + 63) / 64); t.wfirst = wfirst;
+        first += (uint32_t)npix;
+        wfirst += t.height * t.wpr;
+    }
+    rig->words = (unsigned long long *)at;
+    ok = ok && hipMemcpyAsync(rig->dev, rig->table.data(), (size_t)ncam * sizeof(k::RgbdRawCamDev), hipMemcpyHostToDevice, c.stream) == hipSuccess;
+    ok = c.sync() && ok;   // (the copies read the rig's vectors: they stay, but the next call may come from another thread)
+    if (!ok) {
+        if (!*cwipc_hip_last_error()) note_error(who, "a copy failed");
+        else cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, cwipc_hip_last_error());
+        pool_free(rig->dev);
+        return nullptr;
+    }
+    return rig.release();
+}
+
+extern "C" void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig) {
+    if (rig == nullptr) return;
+    pool_free(rig->dev);
+    delete rig;
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
+                                                     const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
+                                                     char **errorMessage) {
+    const char *who = "cwipc_hip_rgbd_rig_grab";
+    cwipc_log_set_errorbuf(errorMessage);
+    struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
+    if (rig == nullptr || frames == nullptr) {
+        note_error(who, "NULL argument");
+        return nullptr;
+    }
+    const int ncam = (int)rig->sensors.size();
+    const int ex = prep ? prep->depth_x_erosion : 0, ey = prep ? prep->depth_y_erosion : 0;
+    if (ex < 0 || ex > RGBD_MAX_EROSION || ey < 0 || ey > RGBD_MAX_EROSION) {
+        note_error(who, "depth_x_erosion and depth_y_erosion must be between 0 and 32");
+        return nullptr;
+    }
+    const bool attach = (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) != 0;
+    size_t staged_bytes = 0;
+    for (int k = 0; k < ncam; k++) {
+        const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        if (frames[k].depth == nullptr || frames[k].colour == nullptr || (attach_flags != 0 && !rig->has_serial[(size_t)k])) {
+            note_error(who, "camera " + std::to_string(k) + ": NULL argument");
+            return nullptr;
+        }
+        const size_t depth_bytes = (size_t)s.width * (size_t)s.height * 2, colour_bytes = (size_t)s.colour_width * (size_t)s.colour_height * (size_t)s.colour_bpp;
+        if (!host_range_device_alias(frames[k].depth, depth_bytes)) staged_bytes += round256(depth_bytes);
+        if (!host_range_device_alias(frames[k].colour, colour_bytes)) staged_bytes += round256(colour_bytes);
+    }
+    if (!device_available(who)) return nullptr;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    if (current_device() != rig->device) {
+        note_error(who, "the rig was made on another device");
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> guard(rig->lock);
+
+    RgbdFilterTerms f{};
+    if (filter) {
+        f.near_z = filter->threshold_near; f.far_z = filter->threshold_far;
+        f.height_min = filter->height_min; f.height_max = filter->height_max;
+        f.radius = filter->radius; f.green = filter->greenscreen;
+    }
+    const uint32_t total = rig->total;
+    const size_t nb = k::rgbd_blocks(total);
+    uint8_t *stage = (uint8_t *)c.staging(staged_bytes ? staged_bytes : 256);
+    uint32_t *counts = (uint32_t *)c.device_scratch((nb + 1) * sizeof(uint32_t));
+    auto dst = soa_alloc((size_t)total);
+    if (!stage || !counts || !dst) {
+        note_error(who, "out of memory");
+        return nullptr;
+    }
+    // the attached images come back into memory of their own, which the metadata then own
+    std::vector<void *> images;
+    struct FreeImages { std::vector<void *> &v; ~FreeImages() { for (void *p : v) ::free(p); } } free_images{images};
+    if (attach)
+        for (int k = 0; k < ncam; k++) {
+            const size_t npix = (size_t)rig->sensors[(size_t)k].width * (size_t)rig->sensors[(size_t)k].height;
+            images.push_back((attach_flags & CWIPC_HIP_RGBD_ATTACH_RGB) ? malloc(npix * 3) : nullptr);
+            images.push_back((attach_flags & CWIPC_HIP_RGBD_ATTACH_DEPTH) ? malloc(npix * 2) : nullptr);
+            if (((attach_flags & CWIPC_HIP_RGBD_ATTACH_RGB) && !images[images.size() - 2]) || ((attach_flags & CWIPC_HIP_RGBD_ATTACH_DEPTH) && !images.back())) {
+                note_error(who, "out of memory");
+                return nullptr;
+            }
+        }
+    const k::RgbdRawCamDev *table = (const k::RgbdRawCamDev *)rig->dev;
+    bool ok = true;
+    for (int k = 0; k < ncam && ok; k++) {
+        const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        const k::RgbdRawCamDev &t = rig->table[(size_t)k];
+        ok = upload(frames[k].depth, (size_t)s.width * (size_t)s.height * 2, (uint8_t *)t.depth_rw, &stage, c.stream) &&
+             upload(frames[k].colour, (size_t)s.colour_width * (size_t)s.colour_height * (size_t)s.colour_bpp, (uint8_t *)t.raw_colour, &stage, c.stream);
+    }
+    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
+    volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    *word = 0ull;
+    if (ok) {
+        if (ex > 0 || ey > 0) k::rgbd_erode(table, ncam, rig->total_words, ex, ey, rig->words, c.stream);
+        k::rgbd_register(table, ncam, total, c.stream);
+        k::rgbd_count(table, ncam, total, f, counts, c.tickets, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        k::rgbd_scatter(table, ncam, total, f, counts, *dst, c.stream);
+        ok = hipGetLastError() == hipSuccess;
+        for (int k = 0; k < ncam && ok && attach; k++) {
+            const k::RgbdRawCamDev &t = rig->table[(size_t)k];
+            const size_t npix = (size_t)t.width * (size_t)t.height;
+            if (images[2 * (size_t)k]) ok = hipMemcpyAsync(images[2 * (size_t)k], t.registered, npix * 3, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+            if (ok && images[2 * (size_t)k + 1])
+                ok = hipMemcpyAsync(images[2 * (size_t)k + 1], t.depth_rw, npix * 2, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        }
+    }
+    ok = c.sync() && ok;   // (also on failure: copies that read the staging buffer and kernels that write the planes may be in flight)
+    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, (size_t)total, dst, rig->tiles, timestamp, cellsize);
+    if (!rv) return nullptr;
+    if (attach) {
+        cwipc_metadata *meta = rv->access_metadata();
+        for (int k = 0; k < ncam; k++) {
+            const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+            const std::string size = "width=" + std::to_string(s.width) + ",height=" + std::to_string(s.height);
+            const size_t npix = (size_t)s.width * (size_t)s.height;
+            if (images[2 * (size_t)k]) meta->_add("rgb." + rig->serials[(size_t)k], size + ",bpp=3", images[2 * (size_t)k], npix * 3, ::free);
+            if (images[2 * (size_t)k + 1]) meta->_add("depth." + rig->serials[(size_t)k], size + ",bpp=2", images[2 * (size_t)k + 1], npix * 2, ::free);
+        }
+        images.clear();   // (the metadata own them now)
+    }
+    return rv;
+}
+
+extern "C" const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam) {
+    return rig_camera_ok(rig, cam) ? rig->rays[(size_t)cam].data() : nullptr;
+}
+
+extern "C" int cwipc_hip_rgbd_rig_map2d3d(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int d, float out[3]) {
+    if (!rig_camera_ok(rig, cam) || out == nullptr || d <= 0) return 0;
+    const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)cam];
+    if (u < 0 || v < 0 || u >= s.width || v >= s.height) return 0;
+    const double *ray = &rig->rays[(size_t)cam][2 * ((size_t)v * (size_t)s.width + (size_t)u)];
+    if (ray[0] != ray[0] || ray[1] != ray[1]) return 0;
+    rgbd_raw_point(rig->table[(size_t)cam].t, rig->table[(size_t)cam].rays ? ray : nullptr, u, v, (unsigned)d, out);
+    return 1;
+}
+
+extern "C" int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int out[2]) {
+    if (!rig_camera_ok(rig, cam) || out == nullptr) return 0;
+    const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)cam];
+    if (u < 0 || v < 0 || u >= s.width || v >= s.height) return 0;
     out[0] = u;
     out[1] = v;
     return 1;

@@ -5,7 +5,12 @@ those every camera plug-in of the reference applies, reference include/cwipc_uti
 `RgbdCamera` and `RgbdFilter` describe the cameras and the filters; `RgbdSource` is the grabber: it is fed frames, hands out clouds,
 attaches the images as metadata when asked (request_metadata("rgb" / "depth")), and answers the two auxiliary operations the
 registration tooling asks a grabber for, "map2d3d" and "mapcolordepth", with the struct layouts of the reference
-(python/cwipc/registration/multicoarse.py:592-612)."""
+(python/cwipc/registration/multicoarse.py:592-612).
+
+`RgbdSensor`, `RgbdPrep`, `RgbdRig` and `RgbdRigSource` are the same for RAW sensor pairs (cwipc_hip_rgbd_rig_grab): a depth image that
+is eroded first, a colour image of another size from a second sensor beside the depth sensor, both behind rational-model lenses.  The
+rig holds what is constant per camera; the images it attaches are the depth image the cloud was made from and the colour image
+registered onto the depth grid, so the registration tooling works on them as it does on aligned ones."""
 from __future__ import annotations
 
 import struct
@@ -17,7 +22,7 @@ import numpy
 from . import util
 from .abstract import cwipc_activesource_abstract, cwipc_tileinfo_dict
 
-__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd"]
+__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdRig", "RgbdRigSource"]
 
 #: one frame: per camera its (depth uint16[H, W], colour uint8[H, W, bpp]) images, the colour image aligned to the depth image
 Frame = Sequence[Tuple[numpy.ndarray, numpy.ndarray]]
@@ -218,6 +223,188 @@ class RgbdSource(cwipc_activesource_abstract):
             tile, u, v = struct.unpack("iii", inbuf)
             cam = self._camera_struct(tile)
             pixel = util.cwipc_hip_rgbd_mapcolordepth(cam, u, v) if cam is not None else None
+            if pixel is None:
+                return False
+            outbuf[:] = struct.pack("ii", *pixel)
+            return True
+        return False
+
+
+def _zeros8() -> Tuple[float, ...]:
+    return (0.0,) * 8
+
+
+@dataclass
+class RgbdSensor:
+    """One camera of a raw rig.  The depth side: image size, intrinsics, the eight lens coefficients k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's
+    rational model; all zero: pinhole), metres per depth unit.  The colour side: its own size, bpp (3: R, G, B bytes; 4: B, G, R, A
+    bytes), intrinsics and coefficients.  depth_to_colour: depth-camera -> colour-camera coordinates, trafo: camera -> world (4x4,
+    float64).  Tile number and serial number."""
+    width: int
+    height: int
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    colour_width: int
+    colour_height: int
+    colour_fx: float
+    colour_fy: float
+    colour_cx: float
+    colour_cy: float
+    coeffs: Sequence[float] = field(default_factory=_zeros8)
+    colour_coeffs: Sequence[float] = field(default_factory=_zeros8)
+    depth_to_colour: numpy.ndarray = field(default_factory=_identity)
+    depth_scale: float = 0.001
+    trafo: numpy.ndarray = field(default_factory=_identity)
+    tile: int = 1
+    serial: str = ""
+    bpp: int = 3
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_sensor:
+        m = numpy.ascontiguousarray(numpy.asarray(self.trafo, dtype=numpy.float64))
+        d2c = numpy.ascontiguousarray(numpy.asarray(self.depth_to_colour, dtype=numpy.float64))
+        if m.shape != (4, 4) or d2c.shape != (4, 4):
+            raise ValueError("RgbdSensor: trafo and depth_to_colour must be 4x4 matrices")
+        if len(self.coeffs) != 8 or len(self.colour_coeffs) != 8:
+            raise ValueError("RgbdSensor: eight lens coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+        if not 0 <= int(self.tile) <= 255:
+            raise ValueError("RgbdSensor: tile must be between 0 and 255")
+        rv = util.cwipc_hip_rgbd_sensor()
+        rv.width, rv.height, rv.tile = int(self.width), int(self.height), int(self.tile)
+        rv.fx, rv.fy, rv.cx, rv.cy, rv.depth_scale = float(self.fx), float(self.fy), float(self.cx), float(self.cy), float(self.depth_scale)
+        rv.coeffs[:] = [float(c) for c in self.coeffs]
+        rv.colour_width, rv.colour_height, rv.colour_bpp = int(self.colour_width), int(self.colour_height), int(self.bpp)
+        rv.colour_fx, rv.colour_fy, rv.colour_cx, rv.colour_cy = float(self.colour_fx), float(self.colour_fy), float(self.colour_cx), float(self.colour_cy)
+        rv.colour_coeffs[:] = [float(c) for c in self.colour_coeffs]
+        rv.depth_to_colour[:] = d2c.reshape(16).tolist()
+        rv.trafo[:] = m.reshape(16).tolist()
+        rv.serial = self.serial.encode('utf8')
+        return rv
+
+
+@dataclass
+class RgbdPrep:
+    """What is done to the raw depth images before anything else: box erosion of the validity mask by depth_x_erosion pixels to either
+    side and depth_y_erosion up and down (0 .. 32, 0: off), which takes away the rim of a subject where background colours leak."""
+    depth_x_erosion: int = 0
+    depth_y_erosion: int = 0
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_prep:
+        return util.cwipc_hip_rgbd_prep(int(self.depth_x_erosion), int(self.depth_y_erosion))
+
+
+class RgbdRig:
+    """cwipc_hip_rgbd_rig_* on dataclasses and arrays: what is constant per camera, made once.  A context manager; free() gives the
+    device memory back."""
+
+    def __init__(self, sensors: Sequence[RgbdSensor]) -> None:
+        self.sensors: List[RgbdSensor] = list(sensors)
+        self._rig: Optional[int] = util.cwipc_hip_rgbd_rig_create([s.as_struct() for s in self.sensors])
+
+    def __enter__(self) -> "RgbdRig":
+        return self
+
+    def __exit__(self, *exc: Any) -> None:
+        self.free()
+
+    def __del__(self) -> None:
+        try:
+            self.free()
+        except Exception:   # (interpreter shutdown: the library may be gone already)
+            pass
+
+    def free(self) -> None:
+        if getattr(self, "_rig", None):
+            util.cwipc_hip_rgbd_rig_free(self._rig)
+        self._rig = None
+
+    def _handle(self) -> int:
+        if not self._rig:
+            raise util.CwipcError("RgbdRig: used after free()")
+        return self._rig
+
+    def grab(self, frame: Frame, filter: Optional[RgbdFilter] = None, prep: Optional[RgbdPrep] = None, timestamp: int = 0, cellsize: float = 0.0,
+             attach_flags: int = 0) -> util.cwipc_pointcloud_wrapper:
+        """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images."""
+        if len(frame) != len(self.sensors):
+            raise ValueError("RgbdRig: one (depth, colour) pair per sensor")
+        structs = []
+        for s, (depth, colour) in zip(self.sensors, frame):
+            if depth.dtype != numpy.uint16 or depth.shape != (s.height, s.width) or not depth.flags['C_CONTIGUOUS']:
+                raise ValueError("RgbdRig: depth must be a contiguous uint16[height, width] array")
+            if colour.dtype != numpy.uint8 or colour.shape != (s.colour_height, s.colour_width, s.bpp) or not colour.flags['C_CONTIGUOUS']:
+                raise ValueError("RgbdRig: colour must be a contiguous uint8[colour_height, colour_width, bpp] array")
+            structs.append(util.cwipc_hip_rgbd_frame(depth.ctypes.data, colour.ctypes.data))
+        return util.cwipc_hip_rgbd_rig_grab(self._handle(), structs, prep.as_struct() if prep is not None else None,
+                                            filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
+
+    def ray_table(self, i: int) -> numpy.ndarray:
+        """Sensor i's ray table, float64[height, width, 2]: the undistorted normalised (x, y) of every depth pixel, NaN where the
+        lens model has none."""
+        if not 0 <= i < len(self.sensors):
+            raise IndexError("RgbdRig: no such sensor")
+        return util.cwipc_hip_rgbd_rig_ray_table(self._handle(), i, self.sensors[i].width, self.sensors[i].height)
+
+    def map2d3d(self, i: int, u: int, v: int, d: int) -> Optional[Tuple[float, float, float]]:
+        return util.cwipc_hip_rgbd_rig_map2d3d(self._handle(), i, u, v, d)
+
+    def mapcolordepth(self, i: int, u: int, v: int) -> Optional[Tuple[int, int]]:
+        return util.cwipc_hip_rgbd_rig_mapcolordepth(self._handle(), i, u, v)
+
+
+class RgbdRigSource(RgbdSource):
+    """RgbdSource for raw sensor pairs: the same surface -- get, request_metadata, auxiliary_operation("map2d3d" / "mapcolordepth"),
+    serial_dict -- over an RgbdRig, which it makes and frees.  The attached "rgb." image lies on the depth grid, so both mappings
+    take depth-grid coordinates."""
+
+    def __init__(self, sensors: Sequence[RgbdSensor], frames: Union[Iterable[Frame], Callable[[], Optional[Frame]]], filter: Optional[RgbdFilter] = None,
+                 prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0) -> None:
+        super().__init__(sensors, frames, filter, cellsize, first_timestamp)   # type: ignore[arg-type]  # (tile, serial, trafo: all it reads)
+        self.prep = prep
+        self.rig = RgbdRig(sensors)
+
+    def free(self) -> None:
+        super().free()
+        self.rig.free()
+
+    def get(self) -> Optional[util.cwipc_pointcloud_wrapper]:
+        if not self.available(True):
+            return None
+        frame, self._pending = self._pending, None
+        flags = (util.CWIPC_HIP_RGBD_ATTACH_RGB if "rgb" in self._requested else 0) | (util.CWIPC_HIP_RGBD_ATTACH_DEPTH if "depth" in self._requested else 0)
+        assert frame is not None
+        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags)
+        self._count += 1
+        return pc
+
+    def statistics(self) -> None:
+        print(f"RgbdRigSource: {self._count} frames")
+
+    def _sensor_index(self, tilenum: int) -> Optional[int]:
+        for i, s in enumerate(self.cameras):
+            if s.tile == tilenum:
+                return i
+        return None
+
+    def auxiliary_operation(self, op: str, inbuf: bytes, outbuf: bytearray) -> bool:
+        """As RgbdSource.auxiliary_operation, with (u, v) on the depth grid for both operations."""
+        if op == "map2d3d":
+            if len(inbuf) != 16 or len(outbuf) != 12:
+                return False
+            tile, u, v, d = struct.unpack("ffff", inbuf)
+            i = self._sensor_index(int(tile)) if tile == int(tile) else None
+            point = self.rig.map2d3d(i, int(u), int(v), int(d)) if i is not None else None
+            if point is None:
+                return False
+            outbuf[:] = struct.pack("fff", *point)
+            return True
+        if op == "mapcolordepth":
+            if len(inbuf) != 12 or len(outbuf) != 8:
+                return False
+            tile, u, v = struct.unpack("iii", inbuf)
+            i = self._sensor_index(tile)
+            pixel = self.rig.mapcolordepth(i, u, v) if i is not None else None
             if pixel is None:
                 return False
             outbuf[:] = struct.pack("ii", *pixel)

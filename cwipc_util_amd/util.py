@@ -54,6 +54,8 @@ __all__ = [
     'cwipc_hip_marker_params', 'cwipc_hip_detect_markers', 'cwipc_hip_render_detect_markers', 'cwipc_hip_marker_labels',
     'cwipc_hip_rgbd_camera', 'cwipc_hip_rgbd_filter', 'CWIPC_HIP_RGBD_ATTACH_RGB', 'CWIPC_HIP_RGBD_ATTACH_DEPTH', 'cwipc_hip_from_rgbd',
     'cwipc_hip_rgbd_map2d3d', 'cwipc_hip_rgbd_mapcolordepth',
+    'cwipc_hip_rgbd_sensor', 'cwipc_hip_rgbd_frame', 'cwipc_hip_rgbd_prep', 'cwipc_hip_rgbd_rig_create', 'cwipc_hip_rgbd_rig_free',
+    'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
 ]
 
 # reference util.py:86, 346, 348
@@ -264,6 +266,12 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_from_rgbd': ([_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR], cwipc_pointcloud_p),
     'cwipc_hip_rgbd_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_rgbd_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
+    'cwipc_hip_rgbd_rig_create': ([_c.c_void_p, _c.c_int, _ERR], _c.c_void_p),
+    'cwipc_hip_rgbd_rig_free': ([_c.c_void_p], None),
+    'cwipc_hip_rgbd_rig_grab': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR], cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_rig_ray_table': ([_c.c_void_p, _c.c_int], _c.POINTER(_c.c_double)),
+    'cwipc_hip_rgbd_rig_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
+    'cwipc_hip_rgbd_rig_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1413,6 +1421,86 @@ def cwipc_hip_rgbd_mapcolordepth(camera: cwipc_hip_rgbd_camera, u: int, v: int) 
     """The depth pixel of colour pixel (u, v): the same pixel, the images being aligned; None outside the image."""
     out = (ctypes.c_int * 2)()
     if not cwipc_util_dll_load().cwipc_hip_rgbd_mapcolordepth(ctypes.addressof(camera), int(u), int(v), out):
+        return None
+    return out[0], out[1]
+
+
+class cwipc_hip_rgbd_sensor(ctypes.Structure):
+    """One camera of a raw rig (include/cwipc_util_amd/hip_ext.h: cwipc_hip_rgbd_sensor): the depth side (size, intrinsics, the eight
+    lens coefficients k1 k2 p1 p2 k3 k4 k5 k6, metres per depth unit), the colour side (its own size, bpp, intrinsics and
+    coefficients), the depth-camera -> colour-camera and camera -> world matrices (row-major), the tile and the serial number."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double),
+                ("cy", ctypes.c_double), ("coeffs", ctypes.c_double * 8), ("depth_scale", ctypes.c_double), ("colour_width", ctypes.c_int32),
+                ("colour_height", ctypes.c_int32), ("colour_bpp", ctypes.c_int32), ("colour_fx", ctypes.c_double), ("colour_fy", ctypes.c_double),
+                ("colour_cx", ctypes.c_double), ("colour_cy", ctypes.c_double), ("colour_coeffs", ctypes.c_double * 8),
+                ("depth_to_colour", ctypes.c_double * 16), ("trafo", ctypes.c_double * 16), ("tile", ctypes.c_uint8), ("serial", ctypes.c_char_p)]
+
+
+class cwipc_hip_rgbd_frame(ctypes.Structure):
+    """One camera's images of one frame: the addresses of its Z16 depth image and of its colour image."""
+    _fields_ = [("depth", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
+
+
+class cwipc_hip_rgbd_prep(ctypes.Structure):
+    """What happens to the depth images before anything else: the box erosion's half widths, 0 .. 32, 0: off."""
+    _fields_ = [("depth_x_erosion", ctypes.c_int32), ("depth_y_erosion", ctypes.c_int32)]
+
+
+def cwipc_hip_rgbd_rig_create(sensors: Sequence[cwipc_hip_rgbd_sensor]) -> int:
+    """The rig of these sensors (an opaque handle for the calls below; cwipc_hip_rgbd_rig_free gives it back): the sensor table and the
+    depth cameras' ray tables, computed and uploaded once."""
+    n = len(sensors)
+    array = (cwipc_hip_rgbd_sensor * max(n, 1))(*sensors)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_create(ctypes.addressof(array), n, ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return rv
+    raise CwipcError("cwipc_hip_rgbd_rig_create: no rig created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_free(rig: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_rgbd_rig_free(rig)
+
+
+def cwipc_hip_rgbd_rig_grab(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], prep: Optional[cwipc_hip_rgbd_prep] = None,
+                            filter: Optional[cwipc_hip_rgbd_filter] = None, timestamp: int = 0, cellsize: float = 0.0,
+                            attach_flags: int = 0) -> cwipc_pointcloud_wrapper:
+    """One device-resident cloud from one frame of raw sensor images, built on the GPU: depth erosion, the ray tables, registration of
+    the colour image onto the depth grid, then cwipc_hip_from_rgbd's filters and order.  frames: one entry per sensor of the rig, in
+    their order; the images must stay alive during the call.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab(rig, ctypes.addressof(array) if len(frames) else None, ctypes.addressof(prep) if prep is not None else None,
+                                                       ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
+                                                       int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError("cwipc_hip_rgbd_rig_grab: no pointcloud created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_ray_table(rig: int, cam: int, width: int, height: int) -> numpy.ndarray:
+    """A copy of camera cam's ray table as float64[height, width, 2] (width and height: that camera's depth image)."""
+    ptr = cwipc_util_dll_load().cwipc_hip_rgbd_rig_ray_table(rig, int(cam))
+    if not ptr:
+        raise CwipcError("cwipc_hip_rgbd_rig_ray_table: no such camera")
+    return numpy.ctypeslib.as_array(ptr, shape=(int(height), int(width), 2)).copy()
+
+
+def cwipc_hip_rgbd_rig_map2d3d(rig: int, cam: int, u: int, v: int, d: int) -> Optional[Tuple[float, float, float]]:
+    """The world point of depth-grid pixel (u, v) of camera cam at depth d (in depth units), in the arithmetic of
+    cwipc_hip_rgbd_rig_grab; None where the library says false (outside the image, d <= 0, a pixel without a ray)."""
+    out = (ctypes.c_float * 3)()
+    if not cwipc_util_dll_load().cwipc_hip_rgbd_rig_map2d3d(rig, int(cam), int(u), int(v), int(d), out):
+        return None
+    return out[0], out[1], out[2]
+
+
+def cwipc_hip_rgbd_rig_mapcolordepth(rig: int, cam: int, u: int, v: int) -> Optional[Tuple[int, int]]:
+    """The depth pixel of pixel (u, v) of the attached (registered) colour image: the same pixel; None outside the depth image."""
+    out = (ctypes.c_int * 2)()
+    if not cwipc_util_dll_load().cwipc_hip_rgbd_rig_mapcolordepth(rig, int(cam), int(u), int(v), out):
         return None
     return out[0], out[1]
 

@@ -467,6 +467,74 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_ca
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_map2d3d(const cwipc_hip_rgbd_camera *cam, int u, int v, int d, float out[3]);
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_mapcolordepth(const cwipc_hip_rgbd_camera *cam, int u, int v, int out[2]);
 
+/* ---- the RGB-D source's RAW entry: sensor pairs as a camera delivers them -- a depth image to be eroded, a colour image of another
+ * size from a second sensor beside the first, both behind rational-model lenses.  The rules below are this project's own
+ * definition (the camera plug-ins that hold the reference's versions are not in the reference tree); csrc/rgbd_lens.hpp is the one
+ * statement of the arithmetic, tests/rgbd_lens_model.py its numpy restatement.  Float64, every operation rounded on its own. ---- */
+typedef struct cwipc_hip_rgbd_sensor {
+    int32_t width, height;              /* the depth image */
+    double fx, fy, cx, cy;
+    double coeffs[8];                   /* k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's rational model; all zero: pinhole */
+    double depth_scale;                 /* metres per depth unit */
+    int32_t colour_width, colour_height;
+    int32_t colour_bpp;                 /* 3: R, G, B bytes; 4: B, G, R, A bytes */
+    double colour_fx, colour_fy, colour_cx, colour_cy;
+    double colour_coeffs[8];
+    double depth_to_colour[16];         /* row-major, depth-camera to colour-camera coordinates; taken as given, not judged */
+    double trafo[16];                   /* camera -> world, row-major */
+    uint8_t tile;
+    const char *serial;                 /* names the attached images (copied by rig_create); may be NULL when nothing is ever attached */
+} cwipc_hip_rgbd_sensor;
+typedef struct cwipc_hip_rgbd_frame {
+    const uint16_t *depth;              /* Z16, width x height, row-major, 0: no depth */
+    const uint8_t *colour;              /* colour_width x colour_height x colour_bpp, rows tightly packed */
+} cwipc_hip_rgbd_frame;
+typedef struct cwipc_hip_rgbd_prep {
+    int32_t depth_x_erosion, depth_y_erosion;   /* 0 .. 32 pixels, 0: off */
+} cwipc_hip_rgbd_prep;
+typedef struct cwipc_hip_rgbd_rig cwipc_hip_rgbd_rig;
+/* What is constant per camera: the sensor table and every depth camera's ray table, computed here on the host and uploaded once (a
+ * host copy stays for the mappings), and the device memory a frame needs.  Per grab only the images go up and the count comes back.
+ * The ray table, entry (u, v):  xd = (u - cx) / fx;  yd = (v - cy) / fy;  all eight coefficients zero: (xd, yd); otherwise Newton's
+ * method on distort(x, y) = (xd, yd) with the analytic Jacobian, from (xd, yd), at most 20 steps, accepted when |ex| < 1e-12 and
+ * |ey| < 1e-12 and the Jacobian's determinant there is positive; anything else: (NaN, NaN), the pixel has no ray and gives no point.
+ *    distort(x, y):  xx = x*x;  yy = y*y;  r2 = xx + yy
+ *                    rad = (1 + r2*(k1 + r2*(k2 + r2*k3))) / (1 + r2*(k4 + r2*(k5 + r2*k6)))
+ *                    a1 = (2*x)*y;  a2 = r2 + 2*xx;  a3 = r2 + 2*yy
+ *                    x' = (x*rad + p1*a1) + p2*a2;   y' = (y*rad + p1*a3) + p2*a1
+ * NULL (errorMessage, if given, and cwipc_hip_last_error() have the text) for a NULL pointer, ncam <= 0, a width or height < 1 (either
+ * image), more than 2^31 - 1 depth pixels in all or colour pixels in one image, colour_bpp not 3 or 4, an intrinsic, coefficient,
+ * depth_scale or matrix entry that is not finite, a focal length that is zero.  One grab at a time per rig (calls are serialised). */
+_CWIPC_UTIL_EXPORT cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage);
+_CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig);
+/* One device-resident cloud from one frame (frames: ncam entries, in the sensors' order).  Per camera:
+ *  1. Erosion of the depth image (prep may be NULL: none): a pixel keeps its depth iff no pixel (u + du, v + dv) with |du| <=
+ *     depth_x_erosion, |dv| <= depth_y_erosion that lies inside the image has depth 0.  Pixels outside the image do not erode.
+ *  2. The point of pixel (u, v), depth d != 0:  z = (double)d * depth_scale;  xc = xn*z;  yc = yn*z, (xn, yn) the ray table's entry;
+ *     X = ((m00*xc + m01*yc) + m02*z) + m03, Y and Z alike, m = trafo, as cwipc_hip_from_rgbd.  EXCEPTION: a sensor whose eight depth
+ *     coefficients are all zero takes xc and yc as cwipc_hip_from_rgbd does: ((u - cx) * z) / fx.
+ *  3. Its colour:  P = depth_to_colour . (xc, yc, z), each row ((r0*xc + r1*yc) + r2*z) + r3.  Pz <= 0 or not finite: none.
+ *     (x', y') = distort(Px / Pz, Py / Pz) with colour_coeffs;  uc = floor((colour_fx*x' + colour_cx) + 0.5), vc alike; outside
+ *     [0, colour_width) x [0, colour_height), tested on the doubles, or NaN: none.  Otherwise the colour of that pixel: the nearest
+ *     one.  Occlusion between the two sensors is NOT modelled.  A depth pixel without a ray or without a colour gives no point.
+ *  4. The four filters of cwipc_hip_from_rgbd, unchanged, in their order, on the point and that colour; then stable compaction: the
+ *     cameras in argument order, the pixels row-major.
+ * attach_flags: "depth.<serial>" is the depth image the cloud was made from -- eroded, and 0 where the pixel has no ray or no colour --
+ * ("width=W,height=H,bpp=2"), "rgb.<serial>" the colour image REGISTERED onto the depth grid, R, G, B bytes, black where there is
+ * none ("width=W,height=H,bpp=3"); per camera rgb then depth.  The images may be ordinary or page-locked memory and are free again on
+ * return.  NULL, and nothing left behind, for a NULL rig or frames or image, an erosion outside 0 .. 32, attach_flags with a sensor
+ * that has no serial, a rig made on another device than the calling thread's. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
+                                                             const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
+                                                             char **errorMessage);
+/* Camera cam's ray table: 2 * width * height doubles (x then y per pixel, row-major), the rig's own host copy; NULL for a bad argument. */
+_CWIPC_UTIL_EXPORT const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam);
+/* The two mappings for a rig's clouds.  The attached colour image lies on the depth grid, so mapcolordepth is the identity inside the
+ * depth image (0 outside) and map2d3d takes depth-grid coordinates: the world point of pixel (u, v) at depth d by rule 2, through the
+ * ray table; 0 for a bad argument, (u, v) outside the image, d <= 0, a pixel without a ray. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_map2d3d(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int d, float out[3]);
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int out[2]);
+
 /* ---- intermediate results for parity tests ---- */
 /* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
  * pixel; 0 ok, -1 error (the image and parameter checks of cwipc_hip_detect_markers). */
