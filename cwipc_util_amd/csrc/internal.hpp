@@ -490,7 +490,8 @@ void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const
 // (eroded, cleared) depth image, colour the REGISTERED image on the depth grid, bpp 3.  depth_rw and registered are those two again,
 // to write through.  rays: the ray table (2 doubles per depth pixel), nullptr for a sensor without depth lens coefficients.
 // raw_colour: the colour image as the camera sent it (raw_bpp bytes per pixel, ct.width x ct.height, 4-byte aligned, 8 readable
-// bytes behind it).  The validity words of the erosion: wpr words per row, this camera's first is number wfirst.
+// bytes behind it).  The validity words of the erosion: wpr words per row, this camera's first is number wfirst.  The occlusion
+// test's z-buffer: one word per colour pixel, row-major, this camera's first is number zfirst.
 struct RgbdRawCamDev : RgbdCamDev {
     uint16_t *depth_rw;
     uint8_t *registered;
@@ -498,6 +499,7 @@ struct RgbdRawCamDev : RgbdCamDev {
     const uint8_t *raw_colour;
     RgbdColourTerms ct;
     uint32_t raw_bpp, height, wpr, wfirst;
+    size_t zfirst;
 };
 void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
                 unsigned long long *total_host, uint32_t tag, hipStream_t s);
@@ -507,6 +509,13 @@ void rgbd_scatter(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, co
 void rgbd_erode(const RgbdRawCamDev *cams, int ncam, uint32_t total_words, int ex, int ey, unsigned long long *words, hipStream_t s);
 // Every depth pixel's registered colour; the depth of a pixel without one is cleared.
 void rgbd_register(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, hipStream_t s);
+// The occlusion test (rgbd_lens.hpp), between erosion and count in place of rgbd_register.  zbuf: one word per colour pixel of every
+// camera, all ones.  rgbd_zsplat: every candidate's key goes, by atomic minimum, to the cell of its own colour pixel.
+// rgbd_register_occluded: rgbd_register, with Zmin at a candidate's colour pixel taken as the smallest word of its (2 splat + 1)^2
+// square inside the colour image, an occluded candidate being a pixel without a colour.
+void rgbd_zsplat(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, unsigned long long *zbuf, hipStream_t s);
+void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const unsigned long long *zbuf, int splat, double margin,
+                            hipStream_t s);
 
 }  // namespace k
 

@@ -11,7 +11,8 @@
 //
 // The raw entry (cwipc_hip_rgbd_rig_grab, rgbd_lens.hpp) runs up to three kernels in front of the same count -> scan -> scatter: the
 // depth erosion as two passes over one 1-bit validity plane (a wave's 64 pixels of a row are one ballot word), and the registration,
-// which gives every depth pixel the colour pixel its point projects to and clears the depth of those that have none.  After it the
+// which gives every depth pixel the colour pixel its point projects to and clears the depth of those that have none (on request also
+// of those the colour camera cannot see: a z-buffer of the colour grid, filled by rgbd_zsplat in front of it).  After it the
 // frame is a depth image with an aligned RGB8 image again; count and scatter are the kernels above instantiated for a camera type
 // that also knows its ray table (Cam = RgbdRawCamDev), the existing instantiation (Cam = RgbdCamDev) computing what it always did.
 #include "internal.hpp"
@@ -246,10 +247,44 @@ __global__ void __launch_bounds__(BLOCK) rgbd_erode_cols_kernel(const RgbdRawCam
     if (u < c.width && !((acc >> lane) & 1ull)) c.depth_rw[(size_t)row * c.width + u] = 0;
 }
 
+// What the z-splat and the registration both ask of depth pixel p of camera c: is it a candidate (depth after erosion, a colour pixel),
+// and then its colour pixel and its depth along the colour camera's axis.  The one evaluation both kernels share, so their bits agree.
+__device__ __forceinline__ bool colour_of(const RgbdRawCamDev &c, uint32_t p, unsigned d, int at[2], double &pz) {
+    const int v = (int)(p / c.width), u = (int)(p - (uint32_t)v * c.width);
+    const double z = rgbd_z(d, c.t.depth_scale);
+    double xc, yc;
+    rgbd_raw_xy(c.t, c.rays ? c.rays + 2 * (size_t)p : nullptr, u, v, z, xc, yc);
+    return rgbd_colour_pixel_depth(c.ct, xc, yc, z, at, pz);
+}
+
+// The z-buffer of the colour grids: one lane per depth pixel of the frame.  A candidate's key goes, by atomic minimum, to the cell of
+// its own colour pixel: (uc, vc) is in range by rgbd_colour_pixel_depth's test on the doubles, so the cell is one of this camera's
+// Wc * Hc words behind zfirst.  The square of the rule is NOT written here -- with (2 splat + 1)^2 atomics per candidate the grab's
+// kernels took 3.7 (splat 1) to 8 (splat 2) times the plain grab's, DESIGN 3.19 -- but read by the registration: the minimum over a
+// candidate's square of these words is the minimum over the candidates whose squares reach its pixel, the same set.
+__global__ void __launch_bounds__(BLOCK) rgbd_zsplat_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total,
+                                                           unsigned long long *__restrict__ zbuf) {
+    const uint32_t g = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
+    if (g >= total) return;
+    const RgbdRawCamDev &c = cams[camera_of(cams, ncam, 0, g)];
+    const uint32_t p = g - c.first;
+    const unsigned d = c.depth[p];
+    if (d == 0u) return;
+    int at[2];
+    double pz;
+    if (!colour_of(c, p, d, at, pz)) return;
+    (void)__hip_atomic_fetch_min(zbuf + c.zfirst + (size_t)at[1] * (size_t)c.ct.width + (size_t)at[0], rgbd_depth_key(pz), __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Registration: one lane per depth pixel of the frame.  A pixel with depth takes the colour of the colour pixel its point projects to
-// (rgbd_colour_pixel: evaluated here and nowhere else) or, having none, loses its depth; every pixel's registered colour is written,
-// black where there is none.  The colour index is in range by rgbd_colour_pixel's test on the doubles; p < the camera's pixel count.
-__global__ void __launch_bounds__(BLOCK) rgbd_register_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total) {
+// (rgbd_colour_pixel) or, having none, loses its depth; every pixel's registered colour is written, black where there is none.  The
+// colour index is in range by rgbd_colour_pixel's test on the doubles; p < the camera's pixel count.  OCCLUSION: Zmin at a candidate's
+// colour pixel is the smallest z-buffer word of its square, clipped to the colour image before an index is formed (rgbd_splat_box:
+// plain loads, the neighbouring lanes' squares overlap); a candidate that something nearer hides (rgbd_occluded) has no colour either.
+template <bool OCCLUSION>
+__global__ void __launch_bounds__(BLOCK) rgbd_register_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total,
+                                                             const unsigned long long *__restrict__ zbuf, int splat, double margin) {
     const uint32_t g = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
     if (g >= total) return;
     const RgbdRawCamDev &c = cams[camera_of(cams, ncam, 0, g)];
@@ -257,12 +292,26 @@ __global__ void __launch_bounds__(BLOCK) rgbd_register_kernel(const RgbdRawCamDe
     const unsigned d = c.depth[p];
     uint32_t rgb = 0;
     if (d != 0u) {
-        const int v = (int)(p / c.width), u = (int)(p - (uint32_t)v * c.width);
-        const double z = rgbd_z(d, c.t.depth_scale);
-        double xc, yc;
-        rgbd_raw_xy(c.t, c.rays ? c.rays + 2 * (size_t)p : nullptr, u, v, z, xc, yc);
         int at[2];
-        if (rgbd_colour_pixel(c.ct, xc, yc, z, at)) rgb = load_colour(c.raw_colour, (uint32_t)at[1] * (uint32_t)c.ct.width + (uint32_t)at[0], c.raw_bpp);
+        double pz;
+        bool has = colour_of(c, p, d, at, pz);
+        if constexpr (OCCLUSION) {
+            if (has) {
+                int lo[2], hi[2];
+                rgbd_splat_box(c.ct, at, splat, lo, hi);
+                const unsigned long long *__restrict__ plane = zbuf + c.zfirst;
+                unsigned long long key_min = RGBD_KEY_EMPTY;
+                for (int r = lo[1]; r <= hi[1]; r++) {
+                    const unsigned long long *line = plane + (size_t)r * (size_t)c.ct.width;
+                    for (int q = lo[0]; q <= hi[0]; q++) {
+                        const unsigned long long key = line[q];
+                        key_min = key < key_min ? key : key_min;
+                    }
+                }
+                has = !rgbd_occluded(key_min, pz, margin);
+            }
+        }
+        if (has) rgb = load_colour(c.raw_colour, (uint32_t)at[1] * (uint32_t)c.ct.width + (uint32_t)at[0], c.raw_bpp);
         else c.depth_rw[p] = 0;
     }
     uint8_t *out = c.registered + (size_t)p * 3u;
@@ -298,8 +347,19 @@ void rgbd_erode(const RgbdRawCamDev *cams, int ncam, uint32_t total_words, int e
 }
 
 void rgbd_register(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, hipStream_t s) {
-    CW_LAUNCH("rgbd_register", rgbd_register_kernel, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams, ncam,
-              total_pixels);
+    CW_LAUNCH("rgbd_register", rgbd_register_kernel<false>, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams, ncam,
+              total_pixels, (const unsigned long long *)nullptr, 0, 0.0);
+}
+
+void rgbd_zsplat(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, unsigned long long *zbuf, hipStream_t s) {
+    CW_LAUNCH("rgbd_zsplat", rgbd_zsplat_kernel, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams, ncam,
+              total_pixels, zbuf);
+}
+
+void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const unsigned long long *zbuf, int splat, double margin,
+                            hipStream_t s) {
+    CW_LAUNCH("rgbd_register_occluded", rgbd_register_kernel<true>, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams,
+              ncam, total_pixels, zbuf, splat, margin);
 }
 
 }  // namespace k

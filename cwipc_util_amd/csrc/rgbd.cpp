@@ -7,7 +7,8 @@
 // host.  There is NO CPU fallback for the cloud: without a usable GPU the call logs an ERROR and returns NULL.
 //
 // The raw entry (cwipc_hip_rgbd_rig_*, rgbd_lens.hpp) keeps what is constant per camera in a rig: the camera table, the ray tables
-// (computed here at creation) and the frame's device buffers, so that a grab uploads the images and nothing else.
+// (computed here at creation) and the frame's device buffers, so that a grab uploads the images and nothing else.  The occlusion test
+// (cwipc_hip_rgbd_rig_grab_occluded) adds a z-buffer of the colour grids, which the first grab that asks for it allocates.
 #include "internal.hpp"
 
 #include <cmath>
@@ -217,6 +218,8 @@ struct cwipc_hip_rgbd_rig {
     std::vector<k::RgbdRawCamDev> table;         // the host copy of the device table
     uint8_t *dev = nullptr;                      // one pool block: the table | per camera its ray table, depth, colour and registered image | the words
     unsigned long long *words = nullptr;
+    unsigned long long *zbuf = nullptr;          // the occlusion test's z-buffer: a pool block of its own, made by the first occluded grab
+    size_t zwords = 0;                           // one word per colour pixel of every camera
     uint32_t total = 0, total_words = 0;
     uint32_t tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::mutex lock;                             // one grab at a time: the frame's device buffers are the rig's
@@ -326,6 +329,8 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
         const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
         const size_t npix = (size_t)s.width * (size_t)s.height, ncol = (size_t)s.colour_width * (size_t)s.colour_height;
         k::RgbdRawCamDev &t = rig->table[(size_t)k];
+        t.zfirst = rig->zwords;
+        rig->zwords += ncol;
         t.t = sensor_terms(s);
         t.ct = colour_terms(s);
         t.rays = nullptr;
@@ -360,13 +365,17 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
 extern "C" void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig) {
     if (rig == nullptr) return;
     pool_free(rig->dev);
+    pool_free(rig->zbuf);
     delete rig;
 }
 
-extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
-                                                     const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
-                                                     char **errorMessage) {
-    const char *who = "cwipc_hip_rgbd_rig_grab";
+namespace {
+
+// cwipc_hip_rgbd_rig_grab (occlusion == nullptr) and cwipc_hip_rgbd_rig_grab_occluded: one flow, the occlusion test's two steps in
+// place of the plain registration when it is asked for
+cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
+                           const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize,
+                           int attach_flags, char **errorMessage) {
     cwipc_log_set_errorbuf(errorMessage);
     struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
     if (rig == nullptr || frames == nullptr) {
@@ -377,6 +386,14 @@ extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, co
     const int ex = prep ? prep->depth_x_erosion : 0, ey = prep ? prep->depth_y_erosion : 0;
     if (ex < 0 || ex > RGBD_MAX_EROSION || ey < 0 || ey > RGBD_MAX_EROSION) {
         note_error(who, "depth_x_erosion and depth_y_erosion must be between 0 and 32");
+        return nullptr;
+    }
+    if (occlusion && (occlusion->splat < 0 || occlusion->splat > RGBD_MAX_SPLAT)) {
+        note_error(who, "occlusion: splat must be between 0 and 8");
+        return nullptr;
+    }
+    if (occlusion && !(std::isfinite(occlusion->margin) && occlusion->margin >= 0.0)) {
+        note_error(who, "occlusion: margin must be finite and not negative");
         return nullptr;
     }
     const bool attach = (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) != 0;
@@ -415,6 +432,13 @@ extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, co
         note_error(who, "out of memory");
         return nullptr;
     }
+    if (occlusion && !rig->zbuf) {   // (kept from here on: freed with the rig)
+        rig->zbuf = (unsigned long long *)pool_alloc(rig->zwords * sizeof(unsigned long long));
+        if (!rig->zbuf) {
+            note_error(who, "out of memory");
+            return nullptr;
+        }
+    }
     // the attached images come back into memory of their own, which the metadata then own
     std::vector<void *> images;
     struct FreeImages { std::vector<void *> &v; ~FreeImages() { for (void *p : v) ::free(p); } } free_images{images};
@@ -441,10 +465,20 @@ extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, co
     *word = 0ull;
     if (ok) {
         if (ex > 0 || ey > 0) k::rgbd_erode(table, ncam, rig->total_words, ex, ey, rig->words, c.stream);
-        k::rgbd_register(table, ncam, total, c.stream);
+        bool filled = true;
+        if (occlusion) {
+            // all ones is above every key, and a memset needs no launch; under the profiler it shows as a step of its own
+            if (profiling_enabled()) profile_begin("rgbd_zfill", c.stream);
+            filled = hipMemsetAsync(rig->zbuf, 0xff, rig->zwords * sizeof(unsigned long long), c.stream) == hipSuccess;
+            if (profiling_enabled()) profile_end(c.stream);
+            k::rgbd_zsplat(table, ncam, total, rig->zbuf, c.stream);
+            k::rgbd_register_occluded(table, ncam, total, rig->zbuf, occlusion->splat, occlusion->margin, c.stream);
+        } else {
+            k::rgbd_register(table, ncam, total, c.stream);
+        }
         k::rgbd_count(table, ncam, total, f, counts, c.tickets, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
         k::rgbd_scatter(table, ncam, total, f, counts, *dst, c.stream);
-        ok = hipGetLastError() == hipSuccess;
+        ok = hipGetLastError() == hipSuccess && filled;
         for (int k = 0; k < ncam && ok && attach; k++) {
             const k::RgbdRawCamDev &t = rig->table[(size_t)k];
             const size_t npix = (size_t)t.width * (size_t)t.height;
@@ -468,6 +502,20 @@ extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, co
         images.clear();   // (the metadata own them now)
     }
     return rv;
+}
+
+}  // namespace
+
+extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
+                                                     const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
+                                                     char **errorMessage) {
+    return rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, prep, nullptr, filter, timestamp, cellsize, attach_flags, errorMessage);
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_occluded(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
+                                                              const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+                                                              uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
+    return rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
 }
 
 extern "C" const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam) {

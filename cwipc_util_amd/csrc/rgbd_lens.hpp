@@ -33,8 +33,16 @@
 //     Pz <= 0, or Pz not finite: none.  (x', y') = distort(Px / Pz, Py / Pz) with the colour coefficients (always, also all zero)
 //     uc = floor((fxc*x' + cxc) + 0.5);  vc = floor((fyc*y' + cyc) + 0.5)
 //     none unless 0 <= uc < Wc and 0 <= vc < Hc, tested ON THE DOUBLES (a NaN fails); else the pixel (int)uc, (int)vc.
-//   Nearest pixel; occlusion between the two sensors is NOT modelled: a point the colour camera cannot see takes the colour of
-//   whatever is in front of it there.
+//   Nearest pixel; occlusion between the two sensors is NOT modelled unless asked for: without it a point the colour camera cannot
+//   see takes the colour of whatever is in front of it there.
+//   occlusion (splat 0 .. 8 colour pixels, margin >= 0 metres; cwipc_hip_rgbd_rig_grab_occluded), per camera:
+//     candidate: a depth pixel that has depth after erosion and a colour pixel (uc, vc) by the rule above (so a ray, and Pz finite, > 0)
+//     Zmin(a, b) = the minimum of Pz(q) over the candidates q with |uc(q) - a| <= splat and |vc(q) - b| <= splat, (a, b) inside the image
+//     candidate p is occluded iff Zmin(uc(p), vc(p)) < Pz(p) - margin: one subtraction, a strict comparison.  It then is a pixel
+//     without a colour.  A positive finite double's bits order as an unsigned 64-bit integer does (Pz > 0: neither zero occurs), so the
+//     minimum is an unsigned minimum of rgbd_depth_key and does not depend on the order it is taken in; all ones is above every key.
+//     Nor does it depend on whether a candidate's key is written to its whole square and read at one cell, or written to its own
+//     cell and read over the square: the kernels do the latter.
 //   erosion (ex, ey): a pixel keeps its depth iff no pixel (u + du, v + dv), |du| <= ex, |dv| <= ey, INSIDE the image has depth 0.
 #pragma once
 
@@ -129,13 +137,15 @@ CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_ray(const RgbdCamTerms &c, const R
     return false;
 }
 
-// The colour pixel of the point (xc, yc, z) in depth-camera coordinates; false: none.
-CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_colour_pixel(const RgbdColourTerms &c, double xc, double yc, double z, int out[2]) {
+// The colour pixel of the point (xc, yc, z) in depth-camera coordinates and its Pz, the depth along the colour camera's axis; false:
+// none (pz is then whatever the third row gave, a NaN included).
+CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_colour_pixel_depth(const RgbdColourTerms &c, double xc, double yc, double z, int out[2], double &pz) {
     double p[3];
     for (int row = 0; row < 3; row++) {
         const double *m = c.m + 4 * row;
         p[row] = rn_add(rn_add(rn_add(rn_mul(m[0], xc), rn_mul(m[1], yc)), rn_mul(m[2], z)), m[3]);
     }
+    pz = p[2];
     if (!(p[2] > 0.0) || !(p[2] <= 1.7976931348623157e308)) return false;
     double at[2];
     rgbd_distort(c.lens, rn_div(p[0], p[2]), rn_div(p[1], p[2]), at);
@@ -144,6 +154,39 @@ CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_colour_pixel(const RgbdColourTerms
     if (!(uc >= 0.0 && uc < (double)c.width && vc >= 0.0 && vc < (double)c.height)) return false;
     out[0] = (int)uc; out[1] = (int)vc;
     return true;
+}
+
+// The colour pixel of the point (xc, yc, z) in depth-camera coordinates; false: none.
+CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_colour_pixel(const RgbdColourTerms &c, double xc, double yc, double z, int out[2]) {
+    double pz;
+    return rgbd_colour_pixel_depth(c, xc, yc, z, out, pz);
+}
+
+constexpr int RGBD_MAX_SPLAT = 8;
+constexpr unsigned long long RGBD_KEY_EMPTY = ~0ull;   // above the key of every finite Pz
+
+// The z-buffer's word for a candidate's Pz (finite, > 0): its bits, which order as the doubles do.
+CWIPC_HOST_DEVICE CWIPC_FORCEINLINE unsigned long long rgbd_depth_key(double pz) {
+    unsigned long long key;
+    __builtin_memcpy(&key, &pz, sizeof key);
+    return key;
+}
+
+// Is the candidate with depth pz occluded, key_min being the z-buffer's word at its own colour pixel?  (An empty word is a NaN: no.)
+CWIPC_HOST_DEVICE CWIPC_FORCEINLINE bool rgbd_occluded(unsigned long long key_min, double pz, double margin) {
+    double zmin;
+    __builtin_memcpy(&zmin, &key_min, sizeof zmin);
+    return zmin < rn_add(pz, -margin);
+}
+
+// The cells of a candidate's square that lie inside the colour image: columns lo[0] .. hi[0], rows lo[1] .. hi[1] (never empty: the
+// candidate's own pixel is inside).  "q's square reaches p's pixel" and "q's pixel is in p's square" say the same, so Zmin at p's pixel
+// is as well the minimum, over this box round p's pixel, of the per-cell minimum of the candidates that land ON a cell.
+CWIPC_HOST_DEVICE CWIPC_FORCEINLINE void rgbd_splat_box(const RgbdColourTerms &c, const int at[2], int splat, int lo[2], int hi[2]) {
+    lo[0] = at[0] - splat < 0 ? 0 : at[0] - splat;
+    lo[1] = at[1] - splat < 0 ? 0 : at[1] - splat;
+    hi[0] = at[0] + splat > c.width - 1 ? c.width - 1 : at[0] + splat;
+    hi[1] = at[1] + splat > c.height - 1 ? c.height - 1 : at[1] + splat;
 }
 
 // xc, yc of a pixel with camera-axis depth z: from the ray (xn, yn), or rgbd_terms.hpp's for a sensor without depth coefficients

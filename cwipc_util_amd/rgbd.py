@@ -10,7 +10,8 @@ registration tooling asks a grabber for, "map2d3d" and "mapcolordepth", with the
 `RgbdSensor`, `RgbdPrep`, `RgbdRig` and `RgbdRigSource` are the same for RAW sensor pairs (cwipc_hip_rgbd_rig_grab): a depth image that
 is eroded first, a colour image of another size from a second sensor beside the depth sensor, both behind rational-model lenses.  The
 rig holds what is constant per camera; the images it attaches are the depth image the cloud was made from and the colour image
-registered onto the depth grid, so the registration tooling works on them as it does on aligned ones."""
+registered onto the depth grid, so the registration tooling works on them as it does on aligned ones.  `RgbdOcclusion` asks a grab
+to leave out the points the colour sensor cannot see (cwipc_hip_rgbd_rig_grab_occluded) instead of giving them a foreground colour."""
 from __future__ import annotations
 
 import struct
@@ -22,7 +23,7 @@ import numpy
 from . import util
 from .abstract import cwipc_activesource_abstract, cwipc_tileinfo_dict
 
-__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdRig", "RgbdRigSource"]
+__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdOcclusion", "RgbdRig", "RgbdRigSource"]
 
 #: one frame: per camera its (depth uint16[H, W], colour uint8[H, W, bpp]) images, the colour image aligned to the depth image
 Frame = Sequence[Tuple[numpy.ndarray, numpy.ndarray]]
@@ -294,6 +295,20 @@ class RgbdPrep:
         return util.cwipc_hip_rgbd_prep(int(self.depth_x_erosion), int(self.depth_y_erosion))
 
 
+@dataclass
+class RgbdOcclusion:
+    """The occlusion test between a sensor's depth and colour camera.  Every depth sample is drawn into a z-buffer of the colour grid
+    as a square of (2 splat + 1)^2 colour pixels (splat 0 .. 8); a sample is dropped when that buffer holds, at its own colour pixel,
+    something more than `margin` metres nearer.  splat closes the gaps between the samples of a foreground surface where the colour
+    grid is finer than the depth grid: at least ceil(max(colour_fx / fx, colour_fy / fy)) - 1.  margin keeps a slanted surface from
+    hiding itself: the depth it gains over splat colour pixels, plus the depth noise."""
+    splat: int = 1
+    margin: float = 0.02
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_occlusion:
+        return util.cwipc_hip_rgbd_occlusion(int(self.splat), float(self.margin))
+
+
 class RgbdRig:
     """cwipc_hip_rgbd_rig_* on dataclasses and arrays: what is constant per camera, made once.  A context manager; free() gives the
     device memory back."""
@@ -325,8 +340,9 @@ class RgbdRig:
         return self._rig
 
     def grab(self, frame: Frame, filter: Optional[RgbdFilter] = None, prep: Optional[RgbdPrep] = None, timestamp: int = 0, cellsize: float = 0.0,
-             attach_flags: int = 0) -> util.cwipc_pointcloud_wrapper:
-        """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images."""
+             attach_flags: int = 0, occlusion: Optional[RgbdOcclusion] = None) -> util.cwipc_pointcloud_wrapper:
+        """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images.  occlusion: leave out the
+        points the colour sensor cannot see (None: cwipc_hip_rgbd_rig_grab as it is)."""
         if len(frame) != len(self.sensors):
             raise ValueError("RgbdRig: one (depth, colour) pair per sensor")
         structs = []
@@ -336,6 +352,9 @@ class RgbdRig:
             if colour.dtype != numpy.uint8 or colour.shape != (s.colour_height, s.colour_width, s.bpp) or not colour.flags['C_CONTIGUOUS']:
                 raise ValueError("RgbdRig: colour must be a contiguous uint8[colour_height, colour_width, bpp] array")
             structs.append(util.cwipc_hip_rgbd_frame(depth.ctypes.data, colour.ctypes.data))
+        if occlusion is not None:
+            return util.cwipc_hip_rgbd_rig_grab_occluded(self._handle(), structs, prep.as_struct() if prep is not None else None, occlusion.as_struct(),
+                                                         filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
         return util.cwipc_hip_rgbd_rig_grab(self._handle(), structs, prep.as_struct() if prep is not None else None,
                                             filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
 
@@ -359,9 +378,10 @@ class RgbdRigSource(RgbdSource):
     take depth-grid coordinates."""
 
     def __init__(self, sensors: Sequence[RgbdSensor], frames: Union[Iterable[Frame], Callable[[], Optional[Frame]]], filter: Optional[RgbdFilter] = None,
-                 prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0) -> None:
+                 prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0, occlusion: Optional[RgbdOcclusion] = None) -> None:
         super().__init__(sensors, frames, filter, cellsize, first_timestamp)   # type: ignore[arg-type]  # (tile, serial, trafo: all it reads)
         self.prep = prep
+        self.occlusion = occlusion
         self.rig = RgbdRig(sensors)
 
     def free(self) -> None:
@@ -374,7 +394,7 @@ class RgbdRigSource(RgbdSource):
         frame, self._pending = self._pending, None
         flags = (util.CWIPC_HIP_RGBD_ATTACH_RGB if "rgb" in self._requested else 0) | (util.CWIPC_HIP_RGBD_ATTACH_DEPTH if "depth" in self._requested else 0)
         assert frame is not None
-        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags)
+        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags, self.occlusion)
         self._count += 1
         return pc
 

@@ -55,7 +55,7 @@ __all__ = [
     'cwipc_hip_rgbd_camera', 'cwipc_hip_rgbd_filter', 'CWIPC_HIP_RGBD_ATTACH_RGB', 'CWIPC_HIP_RGBD_ATTACH_DEPTH', 'cwipc_hip_from_rgbd',
     'cwipc_hip_rgbd_map2d3d', 'cwipc_hip_rgbd_mapcolordepth',
     'cwipc_hip_rgbd_sensor', 'cwipc_hip_rgbd_frame', 'cwipc_hip_rgbd_prep', 'cwipc_hip_rgbd_rig_create', 'cwipc_hip_rgbd_rig_free',
-    'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
+    'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_occlusion', 'cwipc_hip_rgbd_rig_grab_occluded', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
 ]
 
 # reference util.py:86, 346, 348
@@ -269,6 +269,8 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_rgbd_rig_create': ([_c.c_void_p, _c.c_int, _ERR], _c.c_void_p),
     'cwipc_hip_rgbd_rig_free': ([_c.c_void_p], None),
     'cwipc_hip_rgbd_rig_grab': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR], cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_rig_grab_occluded': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR],
+                                         cwipc_pointcloud_p),
     'cwipc_hip_rgbd_rig_ray_table': ([_c.c_void_p, _c.c_int], _c.POINTER(_c.c_double)),
     'cwipc_hip_rgbd_rig_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_rgbd_rig_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
@@ -1478,6 +1480,31 @@ def cwipc_hip_rgbd_rig_grab(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], pr
     if rv:
         return cwipc_pointcloud_wrapper(rv)
     raise CwipcError("cwipc_hip_rgbd_rig_grab: no pointcloud created, but no specific error returned from C library")
+
+
+class cwipc_hip_rgbd_occlusion(ctypes.Structure):
+    """The occlusion test between a sensor's depth and colour camera: the half width of a depth sample's square in the colour grid's
+    z-buffer (0 .. 8 colour pixels) and the depth margin in metres (finite, >= 0)."""
+    _fields_ = [("splat", ctypes.c_int32), ("margin", ctypes.c_double)]
+
+
+def cwipc_hip_rgbd_rig_grab_occluded(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], prep: Optional[cwipc_hip_rgbd_prep] = None,
+                                     occlusion: Optional[cwipc_hip_rgbd_occlusion] = None, filter: Optional[cwipc_hip_rgbd_filter] = None,
+                                     timestamp: int = 0, cellsize: float = 0.0, attach_flags: int = 0) -> cwipc_pointcloud_wrapper:
+    """cwipc_hip_rgbd_rig_grab with the occlusion between the two sensors modelled: a depth pixel whose point the colour camera cannot
+    see, something nearer lying in front of it there, gives no point instead of taking that thing's colour.  occlusion None: exactly
+    cwipc_hip_rgbd_rig_grab.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_occluded(rig, ctypes.addressof(array) if len(frames) else None,
+                                                                ctypes.addressof(prep) if prep is not None else None,
+                                                                ctypes.addressof(occlusion) if occlusion is not None else None,
+                                                                ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
+                                                                int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError("cwipc_hip_rgbd_rig_grab_occluded: no pointcloud created, but no specific error returned from C library")
 
 
 def cwipc_hip_rgbd_rig_ray_table(rig: int, cam: int, width: int, height: int) -> numpy.ndarray:

@@ -516,7 +516,8 @@ _CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig);
  *  3. Its colour:  P = depth_to_colour . (xc, yc, z), each row ((r0*xc + r1*yc) + r2*z) + r3.  Pz <= 0 or not finite: none.
  *     (x', y') = distort(Px / Pz, Py / Pz) with colour_coeffs;  uc = floor((colour_fx*x' + colour_cx) + 0.5), vc alike; outside
  *     [0, colour_width) x [0, colour_height), tested on the doubles, or NaN: none.  Otherwise the colour of that pixel: the nearest
- *     one.  Occlusion between the two sensors is NOT modelled.  A depth pixel without a ray or without a colour gives no point.
+ *     one.  Occlusion between the two sensors is NOT modelled unless asked for (cwipc_hip_rgbd_rig_grab_occluded below).  A depth
+ *     pixel without a ray or without a colour gives no point.
  *  4. The four filters of cwipc_hip_from_rgbd, unchanged, in their order, on the point and that colour; then stable compaction: the
  *     cameras in argument order, the pixels row-major.
  * attach_flags: "depth.<serial>" is the depth image the cloud was made from -- eroded, and 0 where the pixel has no ray or no colour --
@@ -527,6 +528,30 @@ _CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig);
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
                                                              const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
                                                              char **errorMessage);
+/* The same with the occlusion between the two sensors modelled: a z-buffer of every camera's colour grid, as a camera vendor's
+ * depth-to-colour transformation has one.  Without it the band of background that the depth sensor sees beside a foreground edge and
+ * the colour sensor, a few centimetres to the side, does not, carries the foreground's colour.  This project's own definition, in the
+ * notation of rules 1-4 (csrc/rgbd_lens.hpp; tests/rgbd_occlusion_model.py in numpy); float64, every operation rounded on its own:
+ *  3a. A depth pixel is a CANDIDATE when it has depth after erosion and rule 3 gives it a colour pixel (uc, vc) -- so it has a ray, and
+ *      its Pz is finite and > 0.  Per camera, Zmin(a, b) is the minimum of Pz(q) over the candidates q with |uc(q) - a| <= splat and
+ *      |vc(q) - b| <= splat, for the cells (a, b) inside the colour image.
+ *  3b. Candidate p is OCCLUDED iff Zmin(uc(p), vc(p)) < Pz(p) - margin (one subtraction, a strict comparison; p is in its own square,
+ *      so Zmin <= Pz(p), and equal depths never occlude each other).  An occluded pixel is a pixel without a colour: no point, its depth
+ *      cleared and its registered colour black in the attached images.  Then rule 4.
+ * splat: 0 .. 8 colour pixels; margin: metres, finite, >= 0.  The colour grid is usually finer than the depth grid, so with splat 0 the
+ * foreground's samples leave gaps the background shows through: splat >= ceil(max(colour_fx / fx, colour_fy / fy)) - 1 closes them.  A
+ * slanted surface's own neighbours within the splat are nearer than it, which margin must cover (DESIGN 3.19 has the rule of thumb).
+ * The result does not depend on the order the minimum is taken in.  occlusion == NULL: cwipc_hip_rgbd_rig_grab, byte for byte.  NULL,
+ * and nothing left behind, for a splat outside 0 .. 8, a margin that is negative or not finite, and everything rig_grab refuses.  The
+ * z-buffer (8 bytes per colour pixel) is allocated by a rig's first occluded grab and freed with the rig. */
+typedef struct cwipc_hip_rgbd_occlusion {
+    int32_t splat;
+    double margin;
+} cwipc_hip_rgbd_occlusion;
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_occluded(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames,
+                                                                      const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion,
+                                                                      const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize,
+                                                                      int attach_flags, char **errorMessage);
 /* Camera cam's ray table: 2 * width * height doubles (x then y per pixel, row-major), the rig's own host copy; NULL for a bad argument. */
 _CWIPC_UTIL_EXPORT const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam);
 /* The two mappings for a rig's clouds.  The attached colour image lies on the depth grid, so mapcolordepth is the identity inside the
