@@ -27,6 +27,7 @@
 #include "cwipc_util_amd/hip_ext.h"
 #include "rgbd_terms.hpp"
 #include "rgbd_lens.hpp"
+#include "rgbd_depthfilter.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -513,6 +514,13 @@ void rgbd_register(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, h
 // camera, all ones.  rgbd_zsplat: every candidate's key goes, by atomic minimum, to the cell of its own colour pixel.
 // rgbd_register_occluded: rgbd_register, with Zmin at a candidate's colour pixel taken as the smallest word of its (2 splat + 1)^2
 // square inside the colour image, an occluded candidate being a pixel without a colour.
+// The depth post-processing (rgbd_depthfilter.hpp), in front of the erosion.  rgbd_spatial: `magnitude` iterations of rows forward and
+// backward, then columns forward and backward, in place: two launches per iteration.  rgbd_temporal: the per-pixel update of the
+// depth images and of the rig's state (value, history: one entry per depth pixel of the frame, numbered through as the pixels are).
+void rgbd_spatial(const RgbdRawCamDev *cams, int ncam, uint32_t row_groups, uint32_t col_groups, int magnitude, const RgbdSmoothTerms &t, hipStream_t s);
+uint32_t rgbd_line_groups(uint32_t lines);
+void rgbd_temporal(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdSmoothTerms &t, int persistency, double *value, uint8_t *history,
+                   hipStream_t s);
 void rgbd_zsplat(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, unsigned long long *zbuf, hipStream_t s);
 void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const unsigned long long *zbuf, int splat, double margin,
                             hipStream_t s);

@@ -15,6 +15,9 @@
 // of those the colour camera cannot see: a z-buffer of the colour grid, filled by rgbd_zsplat in front of it).  After it the
 // frame is a depth image with an aligned RGB8 image again; count and scatter are the kernels above instantiated for a camera type
 // that also knows its ray table (Cam = RgbdRawCamDev), the existing instantiation (Cam = RgbdCamDev) computing what it always did.
+// On request (cwipc_hip_rgbd_rig_grab_filtered, rgbd_depthfilter.hpp) the depth post-processing runs in front of the erosion: the
+// spatial filter's line passes, one lane per row or column walking it in LDS, and the temporal filter's per-pixel update of the image
+// and of the state the rig keeps from grab to grab.
 #include "internal.hpp"
 #include "block_scan.hpp"
 
@@ -203,6 +206,142 @@ void scatter_launch(const Cam *cams, int ncam, uint32_t total_pixels, const Rgbd
 
 // ---- the raw entry's own kernels ----
 
+// ---- the depth post-processing (rgbd_depthfilter.hpp), in front of the erosion ----
+//
+// A line of the spatial filter is a chain of dependent float64 steps, so a frame's parallelism is its number of lines.  One workgroup
+// is one wave and owns LINES neighbouring lines of one camera -- rows in the row kernel, columns in the column kernel -- which it holds
+// in LDS as they lie in the image: it loads them coalesced (every lane along a row), lane l < LINES then walks line l forward and
+// backward with the running value in a register (tile_walk: the pixels go through registers eight at a time), and the lines are
+// stored coalesced.  A line of up to LINE_CHUNK pixels is loaded and stored once for its two passes.  A longer one goes through LDS
+// in chunks: forward chunk by chunk with a store each, then backward over the chunks in reverse, the running value carried from chunk
+// to chunk -- the line is NOT cut, the order of its steps is the rule's.  Which lines share a workgroup changes nothing: a lane
+// touches only its own line's pixels between two barriers.  Measured: a launch lasts as long as one line's chain, about
+// 0.1 us per pixel and pass, which is the step's instructions issued by one wave, not memory.
+constexpr int LINES = 32;
+constexpr int LINE_CHUNK = 1020;
+constexpr int ROW_STRIDE = LINE_CHUNK + 2;    // of a row kernel's tile, in pixels: 511 dwords, odd, so the lanes' walks fall on different banks
+
+uint32_t line_groups(uint32_t lines) { return (lines + LINES - 1) / LINES; }
+
+// ROWS: the tile is nlines rows of np pixels from column p0 on, tile[r * ROW_STRIDE + i]; columns: np rows (from row p0 on) of nlines
+// pixels, tile[i * LINES + c].  Either way `line` is the line's number in the tile and i the position along it.
+template <bool ROWS>
+__device__ __forceinline__ uint32_t tile_at(uint32_t line, uint32_t i) {
+    return ROWS ? line * (uint32_t)ROW_STRIDE + i : i * (uint32_t)LINES + line;
+}
+
+// global <-> LDS, coalesced along the image's rows.  line0 + nlines and p0 + np are inside the image (the caller's minima).
+template <bool ROWS, bool STORE>
+__device__ __forceinline__ void tile_copy(uint16_t *__restrict__ image, uint32_t width, uint32_t line0, uint32_t nlines, uint32_t p0, uint32_t np,
+                                          uint16_t *tile) {
+    const uint32_t lane = threadIdx.x;
+    if (ROWS) {
+        for (uint32_t r = 0; r < nlines; r++) {
+            uint16_t *row = image + (size_t)(line0 + r) * width + p0;
+            for (uint32_t i = lane; i < np; i += 64u) {
+                if (STORE) row[i] = tile[tile_at<true>(r, i)];
+                else tile[tile_at<true>(r, i)] = row[i];
+            }
+        }
+    } else {
+        // two rows per step: lanes 0 .. 31 the even one, lanes 32 .. 63 the odd one
+        const uint32_t c = lane & 31u;
+        if (c < nlines)
+            for (uint32_t i = lane >> 5; i < np; i += 2u) {
+                uint16_t *at = image + (size_t)(p0 + i) * width + line0 + c;
+                if (STORE) *at = tile[tile_at<false>(c, i)];
+                else tile[tile_at<false>(c, i)] = *at;
+            }
+    }
+}
+
+// One pass of lane `line` over the np pixels of its line that are in the tile, in pass order.  The chain of steps does not wait for
+// LDS: the pixels go through registers eight at a time, the next eight being read while these are walked.
+template <bool ROWS, bool BACKWARD>
+__device__ __forceinline__ void tile_walk(const RgbdSmoothTerms &t, double &s, uint16_t *tile, uint32_t line, uint32_t np) {
+    constexpr uint32_t B = 8;
+    const auto at = [=](uint32_t i) { return tile_at<ROWS>(line, BACKWARD ? np - 1u - i : i); };   // (i < np)
+    const uint32_t full = np - np % B;
+    uint16_t cur[B], nxt[B];
+    if (full) {
+#pragma unroll
+        for (uint32_t j = 0; j < B; j++) cur[j] = tile[at(j)];
+    }
+    for (uint32_t i0 = 0; i0 < full; i0 += B) {
+        const bool more = i0 + B < full;
+        if (more) {
+#pragma unroll
+            for (uint32_t j = 0; j < B; j++) nxt[j] = tile[at(i0 + B + j)];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < B; j++) rgbd_line_step(t, s, cur[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < B; j++) tile[at(i0 + j)] = cur[j];
+        if (more) {
+#pragma unroll
+            for (uint32_t j = 0; j < B; j++) cur[j] = nxt[j];
+        }
+    }
+    for (uint32_t i = full; i < np; i++) rgbd_line_step(t, s, tile[at(i)]);
+}
+
+template <bool ROWS>
+__global__ void __launch_bounds__(64) rgbd_spatial_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, RgbdSmoothTerms t) {
+    __shared__ uint16_t tile[LINES * ROW_STRIDE];
+    // the camera of this line group and the group's number in it
+    uint32_t group = blockIdx.x;
+    int k = 0;
+    for (; k < ncam; k++) {
+        const uint32_t n = ((ROWS ? cams[k].height : cams[k].width) + (uint32_t)LINES - 1u) / (uint32_t)LINES;
+        if (group < n) break;
+        group -= n;
+    }
+    if (k == ncam) return;   // (the whole workgroup; the host launches exactly the groups there are)
+    const RgbdRawCamDev &c = cams[k];
+    const uint32_t width = c.width, nline_all = ROWS ? c.height : c.width, n = ROWS ? c.width : c.height;
+    const uint32_t line0 = group * (uint32_t)LINES, nlines = nline_all - line0 < (uint32_t)LINES ? nline_all - line0 : (uint32_t)LINES;
+    const uint32_t nchunks = (n + (uint32_t)LINE_CHUNK - 1u) / (uint32_t)LINE_CHUNK;
+    const uint32_t lane = threadIdx.x;
+    double s = 0.0;   // (0 in front of a pass's first pixel: it takes over that pixel's value, rgbd_depthfilter.hpp)
+    for (uint32_t ch = 0; ch < nchunks; ch++) {
+        const uint32_t p0 = ch * (uint32_t)LINE_CHUNK, np = n - p0 < (uint32_t)LINE_CHUNK ? n - p0 : (uint32_t)LINE_CHUNK;
+        tile_copy<ROWS, false>(c.depth_rw, width, line0, nlines, p0, np, tile);
+        __syncthreads();
+        if (lane < nlines) tile_walk<ROWS, false>(t, s, tile, lane, np);
+        __syncthreads();
+        if (nchunks > 1u) {
+            tile_copy<ROWS, true>(c.depth_rw, width, line0, nlines, p0, np, tile);
+            __syncthreads();   // (the next load overwrites the tile, and may read what other lanes stored)
+        }
+    }
+    s = 0.0;
+    for (uint32_t ch = nchunks; ch-- > 0u;) {
+        const uint32_t p0 = ch * (uint32_t)LINE_CHUNK, np = n - p0 < (uint32_t)LINE_CHUNK ? n - p0 : (uint32_t)LINE_CHUNK;
+        if (nchunks > 1u) {
+            tile_copy<ROWS, false>(c.depth_rw, width, line0, nlines, p0, np, tile);
+            __syncthreads();
+        }
+        if (lane < nlines) tile_walk<ROWS, true>(t, s, tile, lane, np);
+        __syncthreads();
+        tile_copy<ROWS, true>(c.depth_rw, width, line0, nlines, p0, np, tile);
+        __syncthreads();
+    }
+}
+
+// The temporal filter: one lane per depth pixel of the frame, whose state entry has the pixel's number.
+__global__ void __launch_bounds__(BLOCK) rgbd_temporal_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total, RgbdSmoothTerms t,
+                                                             int persistency, double *__restrict__ value, uint8_t *__restrict__ history) {
+    const uint32_t g = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
+    if (g >= total) return;
+    const RgbdRawCamDev &c = cams[camera_of(cams, ncam, 0, g)];
+    const uint32_t p = g - c.first;
+    double s = value[g];
+    uint8_t h = history[g];
+    c.depth_rw[p] = rgbd_temporal_step(t, persistency, c.depth_rw[p], s, h);
+    value[g] = s;
+    history[g] = h;
+}
+
 // the camera of validity word g
 __device__ __forceinline__ int camera_of_word(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t g) {
     int k = 0;
@@ -338,6 +477,21 @@ void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, cons
 void rgbd_scatter(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
                   hipStream_t s) {
     scatter_launch(cams, ncam, total_pixels, f, offsets, dst, s);
+}
+
+uint32_t rgbd_line_groups(uint32_t lines) { return line_groups(lines); }
+
+void rgbd_spatial(const RgbdRawCamDev *cams, int ncam, uint32_t row_groups, uint32_t col_groups, int magnitude, const RgbdSmoothTerms &t, hipStream_t s) {
+    for (int it = 0; it < magnitude; it++) {
+        CW_LAUNCH("rgbd_spatial_rows", rgbd_spatial_kernel<true>, dim3(row_groups), dim3(64), 0, s, cams, ncam, t);
+        CW_LAUNCH("rgbd_spatial_cols", rgbd_spatial_kernel<false>, dim3(col_groups), dim3(64), 0, s, cams, ncam, t);
+    }
+}
+
+void rgbd_temporal(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdSmoothTerms &t, int persistency, double *value, uint8_t *history,
+                   hipStream_t s) {
+    CW_LAUNCH("rgbd_temporal", rgbd_temporal_kernel, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams, ncam,
+              total_pixels, t, persistency, value, history);
 }
 
 void rgbd_erode(const RgbdRawCamDev *cams, int ncam, uint32_t total_words, int ex, int ey, unsigned long long *words, hipStream_t s) {

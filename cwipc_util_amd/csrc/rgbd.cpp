@@ -8,7 +8,8 @@
 //
 // The raw entry (cwipc_hip_rgbd_rig_*, rgbd_lens.hpp) keeps what is constant per camera in a rig: the camera table, the ray tables
 // (computed here at creation) and the frame's device buffers, so that a grab uploads the images and nothing else.  The occlusion test
-// (cwipc_hip_rgbd_rig_grab_occluded) adds a z-buffer of the colour grids, which the first grab that asks for it allocates.
+// (cwipc_hip_rgbd_rig_grab_occluded) adds a z-buffer of the colour grids, which the first grab that asks for it allocates.  The depth
+// post-processing (cwipc_hip_rgbd_rig_grab_filtered, rgbd_depthfilter.hpp) adds the temporal filter's per-pixel state in the same way.
 #include "internal.hpp"
 
 #include <cmath>
@@ -220,6 +221,10 @@ struct cwipc_hip_rgbd_rig {
     unsigned long long *words = nullptr;
     unsigned long long *zbuf = nullptr;          // the occlusion test's z-buffer: a pool block of its own, made by the first occluded grab
     size_t zwords = 0;                           // one word per colour pixel of every camera
+    uint8_t *state = nullptr;                    // the temporal filter's state: a pool block of its own, made by the first temporal grab:
+                                                 // total doubles (the running values) | total bytes (the histories), in pixel-number order
+    bool state_empty = true;                     // the state is to be read as all zero: the next temporal grab clears it first
+    uint32_t row_groups = 0, col_groups = 0;     // the spatial filter's workgroups: every camera's rows and columns in groups
     uint32_t total = 0, total_words = 0;
     uint32_t tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::mutex lock;                             // one grab at a time: the frame's device buffers are the rig's
@@ -260,6 +265,13 @@ RgbdColourTerms colour_terms(const cwipc_hip_rgbd_sensor &s) {
     for (int i = 0; i < 12; i++) t.m[i] = s.depth_to_colour[i];
     t.width = s.colour_width; t.height = s.colour_height;
     return t;
+}
+
+// what is wrong with a smoothing stage's numbers, to follow "spatial_" or "temporal_"; nullptr: nothing
+const char *smooth_problem(double alpha, double delta) {
+    if (!(std::isfinite(alpha) && alpha > 0.0 && alpha <= 1.0)) return "alpha must be greater than 0 and at most 1";
+    if (!(std::isfinite(delta) && delta > 0.0)) return "delta must be finite and greater than 0";
+    return nullptr;
 }
 
 bool rig_camera_ok(const cwipc_hip_rgbd_rig *rig, int cam) { return rig != nullptr && cam >= 0 && (size_t)cam < rig->sensors.size(); }
@@ -349,6 +361,8 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
         t.first = first; t.wpr = (uint32_t)(((uint64_t)s.width + 63) / 64); t.wfirst = wfirst;
         first += (uint32_t)npix;
         wfirst += t.height * t.wpr;
+        rig->row_groups += k::rgbd_line_groups(t.height);
+        rig->col_groups += k::rgbd_line_groups(t.width);
     }
     rig->words = (unsigned long long *)at;
     ok = ok && hipMemcpyAsync(rig->dev, rig->table.data(), (size_t)ncam * sizeof(k::RgbdRawCamDev), hipMemcpyHostToDevice, c.stream) == hipSuccess;
@@ -366,16 +380,18 @@ extern "C" void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig) {
     if (rig == nullptr) return;
     pool_free(rig->dev);
     pool_free(rig->zbuf);
+    pool_free(rig->state);
     delete rig;
 }
 
 namespace {
 
 // cwipc_hip_rgbd_rig_grab (occlusion == nullptr) and cwipc_hip_rgbd_rig_grab_occluded: one flow, the occlusion test's two steps in
-// place of the plain registration when it is asked for
-cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
-                           const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize,
-                           int attach_flags, char **errorMessage) {
+// place of the plain registration when it is asked for; and cwipc_hip_rgbd_rig_grab_filtered, which puts the depth post-processing
+// (rgbd_depthfilter.hpp) in front of it all when depthfilter has a stage that is on
+cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_depthfilter *depthfilter,
+                           const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+                           uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
     cwipc_log_set_errorbuf(errorMessage);
     struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
     if (rig == nullptr || frames == nullptr) {
@@ -395,6 +411,28 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
     if (occlusion && !(std::isfinite(occlusion->margin) && occlusion->margin >= 0.0)) {
         note_error(who, "occlusion: margin must be finite and not negative");
         return nullptr;
+    }
+    const int magnitude = depthfilter ? depthfilter->spatial_magnitude : 0;
+    const bool temporal = depthfilter && depthfilter->temporal != 0;
+    if (depthfilter) {
+        if (magnitude < 0 || magnitude > RGBD_MAX_SPATIAL_MAGNITUDE) {
+            note_error(who, "depthfilter: spatial_magnitude must be between 0 and 5");
+            return nullptr;
+        }
+        if (depthfilter->temporal_persistency < 0 || depthfilter->temporal_persistency > RGBD_MAX_PERSISTENCY) {
+            note_error(who, "depthfilter: temporal_persistency must be between 0 and 8");
+            return nullptr;
+        }
+        if (magnitude > 0)
+            if (const char *problem = smooth_problem(depthfilter->spatial_alpha, depthfilter->spatial_delta)) {
+                note_error(who, std::string("depthfilter: spatial_") + problem);
+                return nullptr;
+            }
+        if (temporal)
+            if (const char *problem = smooth_problem(depthfilter->temporal_alpha, depthfilter->temporal_delta)) {
+                note_error(who, std::string("depthfilter: temporal_") + problem);
+                return nullptr;
+            }
     }
     const bool attach = (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) != 0;
     size_t staged_bytes = 0;
@@ -439,6 +477,14 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
             return nullptr;
         }
     }
+    if (temporal && !rig->state) {   // (kept from here on: freed with the rig)
+        rig->state = (uint8_t *)pool_alloc(round256((size_t)total * sizeof(double)) + (size_t)total);
+        if (!rig->state) {
+            note_error(who, "out of memory");
+            return nullptr;
+        }
+        rig->state_empty = true;
+    }
     // the attached images come back into memory of their own, which the metadata then own
     std::vector<void *> images;
     struct FreeImages { std::vector<void *> &v; ~FreeImages() { for (void *p : v) ::free(p); } } free_images{images};
@@ -463,6 +509,21 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
     const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
     volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
     *word = 0ull;
+    bool cleared = true;
+    if (ok && magnitude > 0)
+        k::rgbd_spatial(table, ncam, rig->row_groups, rig->col_groups, magnitude, rgbd_smooth_terms(depthfilter->spatial_alpha, depthfilter->spatial_delta),
+                        c.stream);
+    if (ok && temporal) {
+        double *value = (double *)rig->state;
+        uint8_t *history = rig->state + round256((size_t)total * sizeof(double));
+        if (rig->state_empty) {   // a new state, a reset one, or one a failed grab left behind: s = 0, h = 0 everywhere
+            if (profiling_enabled()) profile_begin("rgbd_history_clear", c.stream);
+            cleared = hipMemsetAsync(rig->state, 0, round256((size_t)total * sizeof(double)) + (size_t)total, c.stream) == hipSuccess;
+            if (profiling_enabled()) profile_end(c.stream);
+        }
+        k::rgbd_temporal(table, ncam, total, rgbd_smooth_terms(depthfilter->temporal_alpha, depthfilter->temporal_delta), depthfilter->temporal_persistency,
+                         value, history, c.stream);
+    }
     if (ok) {
         if (ex > 0 || ey > 0) k::rgbd_erode(table, ncam, rig->total_words, ex, ey, rig->words, c.stream);
         bool filled = true;
@@ -478,7 +539,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         }
         k::rgbd_count(table, ncam, total, f, counts, c.tickets, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
         k::rgbd_scatter(table, ncam, total, f, counts, *dst, c.stream);
-        ok = hipGetLastError() == hipSuccess && filled;
+        ok = hipGetLastError() == hipSuccess && filled && cleared;
         for (int k = 0; k < ncam && ok && attach; k++) {
             const k::RgbdRawCamDev &t = rig->table[(size_t)k];
             const size_t npix = (size_t)t.width * (size_t)t.height;
@@ -488,6 +549,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         }
     }
     ok = c.sync() && ok;   // (also on failure: copies that read the staging buffer and kernels that write the planes may be in flight)
+    if (temporal) rig->state_empty = !ok;   // (a grab that fails on the device leaves the history empty: the next one clears it)
     cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, (size_t)total, dst, rig->tiles, timestamp, cellsize);
     if (!rv) return nullptr;
     if (attach) {
@@ -509,13 +571,45 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
 extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
                                                      const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
                                                      char **errorMessage) {
-    return rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, prep, nullptr, filter, timestamp, cellsize, attach_flags, errorMessage);
+    return rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, nullptr, prep, nullptr, filter, timestamp, cellsize, attach_flags, errorMessage);
 }
 
 extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_occluded(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
                                                               const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
                                                               uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
-    return rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+    return rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, nullptr, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filtered(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames,
+                                                              const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep,
+                                                              const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+                                                              uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
+    return rig_grab("cwipc_hip_rgbd_rig_grab_filtered", rig, frames, depthfilter, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+}
+
+extern "C" void cwipc_hip_rgbd_rig_reset_history(cwipc_hip_rgbd_rig *rig) {
+    if (rig == nullptr) return;
+    std::lock_guard<std::mutex> guard(rig->lock);
+    rig->state_empty = true;   // (no device work here: the next temporal grab clears the state before it reads it)
+}
+
+extern "C" int cwipc_hip_rgbd_rig_history(cwipc_hip_rgbd_rig *rig, int cam, double *value, uint8_t *history) {
+    if (!rig_camera_ok(rig, cam) || value == nullptr || history == nullptr) return -1;
+    const k::RgbdRawCamDev &t = rig->table[(size_t)cam];
+    const size_t npix = (size_t)t.width * (size_t)t.height;
+    std::lock_guard<std::mutex> guard(rig->lock);
+    if (!rig->state || rig->state_empty) {
+        memset(value, 0, npix * sizeof(double));
+        memset(history, 0, npix);
+        return 0;
+    }
+    if (!device_available("cwipc_hip_rgbd_rig_history")) return -1;
+    ThreadCtx &c = tctx();
+    if (!c.ensure() || current_device() != rig->device) return -1;
+    bool ok = hipMemcpyAsync(value, rig->state + (size_t)t.first * sizeof(double), npix * sizeof(double), hipMemcpyDeviceToHost, c.stream) == hipSuccess &&
+              hipMemcpyAsync(history, rig->state + round256((size_t)rig->total * sizeof(double)) + t.first, npix, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    return ok ? 0 : -1;
 }
 
 extern "C" const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam) {

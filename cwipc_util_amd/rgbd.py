@@ -11,7 +11,9 @@ registration tooling asks a grabber for, "map2d3d" and "mapcolordepth", with the
 is eroded first, a colour image of another size from a second sensor beside the depth sensor, both behind rational-model lenses.  The
 rig holds what is constant per camera; the images it attaches are the depth image the cloud was made from and the colour image
 registered onto the depth grid, so the registration tooling works on them as it does on aligned ones.  `RgbdOcclusion` asks a grab
-to leave out the points the colour sensor cannot see (cwipc_hip_rgbd_rig_grab_occluded) instead of giving them a foreground colour."""
+to leave out the points the colour sensor cannot see (cwipc_hip_rgbd_rig_grab_occluded) instead of giving them a foreground colour;
+`RgbdDepthFilter` asks it to smooth the depth images first, along their lines and over time (cwipc_hip_rgbd_rig_grab_filtered), the
+rig keeping the temporal filter's state."""
 from __future__ import annotations
 
 import struct
@@ -23,7 +25,7 @@ import numpy
 from . import util
 from .abstract import cwipc_activesource_abstract, cwipc_tileinfo_dict
 
-__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdOcclusion", "RgbdRig", "RgbdRigSource"]
+__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdOcclusion", "RgbdDepthFilter", "RgbdRig", "RgbdRigSource"]
 
 #: one frame: per camera its (depth uint16[H, W], colour uint8[H, W, bpp]) images, the colour image aligned to the depth image
 Frame = Sequence[Tuple[numpy.ndarray, numpy.ndarray]]
@@ -309,6 +311,26 @@ class RgbdOcclusion:
         return util.cwipc_hip_rgbd_occlusion(int(self.splat), float(self.margin))
 
 
+@dataclass
+class RgbdDepthFilter:
+    """The depth post-processing a depth camera's vendor ships, on the GPU in front of everything else.  Spatial: spatial_magnitude
+    iterations (0 .. 5, 0: off) of an edge-preserving smoother along rows, then columns: a pixel is blended with the running value of
+    its line by spatial_alpha (0 < alpha <= 1; 1: no smoothing) when they differ by less than spatial_delta depth units.  Temporal:
+    the same blend with the pixel's own running value of the earlier grabs, which the rig keeps; a pixel that has lost its depth takes
+    the running value while temporal_persistency (0 .. 8, 0: never, 8: always) says its last eight grabs allow it."""
+    spatial_magnitude: int = 2
+    spatial_alpha: float = 0.5
+    spatial_delta: float = 20.0
+    temporal: bool = True
+    temporal_alpha: float = 0.4
+    temporal_delta: float = 20.0
+    temporal_persistency: int = 3
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_depthfilter:
+        return util.cwipc_hip_rgbd_depthfilter(int(self.spatial_magnitude), float(self.spatial_alpha), float(self.spatial_delta), int(bool(self.temporal)),
+                                               float(self.temporal_alpha), float(self.temporal_delta), int(self.temporal_persistency))
+
+
 class RgbdRig:
     """cwipc_hip_rgbd_rig_* on dataclasses and arrays: what is constant per camera, made once.  A context manager; free() gives the
     device memory back."""
@@ -340,9 +362,10 @@ class RgbdRig:
         return self._rig
 
     def grab(self, frame: Frame, filter: Optional[RgbdFilter] = None, prep: Optional[RgbdPrep] = None, timestamp: int = 0, cellsize: float = 0.0,
-             attach_flags: int = 0, occlusion: Optional[RgbdOcclusion] = None) -> util.cwipc_pointcloud_wrapper:
+             attach_flags: int = 0, occlusion: Optional[RgbdOcclusion] = None, depthfilter: Optional[RgbdDepthFilter] = None) -> util.cwipc_pointcloud_wrapper:
         """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images.  occlusion: leave out the
-        points the colour sensor cannot see (None: cwipc_hip_rgbd_rig_grab as it is)."""
+        points the colour sensor cannot see (None: cwipc_hip_rgbd_rig_grab as it is).  depthfilter: smooth the depth images first
+        (None: the two other entries as they are)."""
         if len(frame) != len(self.sensors):
             raise ValueError("RgbdRig: one (depth, colour) pair per sensor")
         structs = []
@@ -352,11 +375,25 @@ class RgbdRig:
             if colour.dtype != numpy.uint8 or colour.shape != (s.colour_height, s.colour_width, s.bpp) or not colour.flags['C_CONTIGUOUS']:
                 raise ValueError("RgbdRig: colour must be a contiguous uint8[colour_height, colour_width, bpp] array")
             structs.append(util.cwipc_hip_rgbd_frame(depth.ctypes.data, colour.ctypes.data))
+        if depthfilter is not None:
+            return util.cwipc_hip_rgbd_rig_grab_filtered(self._handle(), structs, depthfilter.as_struct(), prep.as_struct() if prep is not None else None,
+                                                         occlusion.as_struct() if occlusion is not None else None,
+                                                         filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
         if occlusion is not None:
             return util.cwipc_hip_rgbd_rig_grab_occluded(self._handle(), structs, prep.as_struct() if prep is not None else None, occlusion.as_struct(),
                                                          filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
         return util.cwipc_hip_rgbd_rig_grab(self._handle(), structs, prep.as_struct() if prep is not None else None,
                                             filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
+
+    def reset_history(self) -> None:
+        """Make the temporal filter's state empty again: the next grab is a new rig's first."""
+        util.cwipc_hip_rgbd_rig_reset_history(self._handle())
+
+    def history(self, i: int) -> Tuple[numpy.ndarray, numpy.ndarray]:
+        """Sensor i's temporal-filter state: (running values float64[height, width], history bytes uint8[height, width])."""
+        if not 0 <= i < len(self.sensors):
+            raise IndexError("RgbdRig: no such sensor")
+        return util.cwipc_hip_rgbd_rig_history(self._handle(), i, self.sensors[i].width, self.sensors[i].height)
 
     def ray_table(self, i: int) -> numpy.ndarray:
         """Sensor i's ray table, float64[height, width, 2]: the undistorted normalised (x, y) of every depth pixel, NaN where the
@@ -378,10 +415,12 @@ class RgbdRigSource(RgbdSource):
     take depth-grid coordinates."""
 
     def __init__(self, sensors: Sequence[RgbdSensor], frames: Union[Iterable[Frame], Callable[[], Optional[Frame]]], filter: Optional[RgbdFilter] = None,
-                 prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0, occlusion: Optional[RgbdOcclusion] = None) -> None:
+                 prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0, occlusion: Optional[RgbdOcclusion] = None,
+                 depthfilter: Optional[RgbdDepthFilter] = None) -> None:
         super().__init__(sensors, frames, filter, cellsize, first_timestamp)   # type: ignore[arg-type]  # (tile, serial, trafo: all it reads)
         self.prep = prep
         self.occlusion = occlusion
+        self.depthfilter = depthfilter
         self.rig = RgbdRig(sensors)
 
     def free(self) -> None:
@@ -394,7 +433,7 @@ class RgbdRigSource(RgbdSource):
         frame, self._pending = self._pending, None
         flags = (util.CWIPC_HIP_RGBD_ATTACH_RGB if "rgb" in self._requested else 0) | (util.CWIPC_HIP_RGBD_ATTACH_DEPTH if "depth" in self._requested else 0)
         assert frame is not None
-        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags, self.occlusion)
+        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags, self.occlusion, self.depthfilter)
         self._count += 1
         return pc
 

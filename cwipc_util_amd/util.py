@@ -55,7 +55,8 @@ __all__ = [
     'cwipc_hip_rgbd_camera', 'cwipc_hip_rgbd_filter', 'CWIPC_HIP_RGBD_ATTACH_RGB', 'CWIPC_HIP_RGBD_ATTACH_DEPTH', 'cwipc_hip_from_rgbd',
     'cwipc_hip_rgbd_map2d3d', 'cwipc_hip_rgbd_mapcolordepth',
     'cwipc_hip_rgbd_sensor', 'cwipc_hip_rgbd_frame', 'cwipc_hip_rgbd_prep', 'cwipc_hip_rgbd_rig_create', 'cwipc_hip_rgbd_rig_free',
-    'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_occlusion', 'cwipc_hip_rgbd_rig_grab_occluded', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
+    'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_occlusion', 'cwipc_hip_rgbd_rig_grab_occluded', 'cwipc_hip_rgbd_depthfilter',
+    'cwipc_hip_rgbd_rig_grab_filtered', 'cwipc_hip_rgbd_rig_reset_history', 'cwipc_hip_rgbd_rig_history', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
 ]
 
 # reference util.py:86, 346, 348
@@ -271,6 +272,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_rgbd_rig_grab': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR], cwipc_pointcloud_p),
     'cwipc_hip_rgbd_rig_grab_occluded': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int, _ERR],
                                          cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_rig_grab_filtered': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int,
+                                          _ERR], cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_rig_reset_history': ([_c.c_void_p], None),
+    'cwipc_hip_rgbd_rig_history': ([_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_rgbd_rig_ray_table': ([_c.c_void_p, _c.c_int], _c.POINTER(_c.c_double)),
     'cwipc_hip_rgbd_rig_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_rgbd_rig_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
@@ -1505,6 +1510,50 @@ def cwipc_hip_rgbd_rig_grab_occluded(rig: int, frames: Sequence[cwipc_hip_rgbd_f
     if rv:
         return cwipc_pointcloud_wrapper(rv)
     raise CwipcError("cwipc_hip_rgbd_rig_grab_occluded: no pointcloud created, but no specific error returned from C library")
+
+
+class cwipc_hip_rgbd_depthfilter(ctypes.Structure):
+    """The depth post-processing of the raw entry: the spatial smoother's iterations (0 .. 5, 0: off), alpha (0 < alpha <= 1) and
+    delta (depth units, > 0), the temporal smoother's switch, alpha, delta and persistency mode (0 .. 8)."""
+    _fields_ = [("spatial_magnitude", ctypes.c_int32), ("spatial_alpha", ctypes.c_double), ("spatial_delta", ctypes.c_double),
+                ("temporal", ctypes.c_int32), ("temporal_alpha", ctypes.c_double), ("temporal_delta", ctypes.c_double),
+                ("temporal_persistency", ctypes.c_int32)]
+
+
+def cwipc_hip_rgbd_rig_grab_filtered(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], depthfilter: Optional[cwipc_hip_rgbd_depthfilter] = None,
+                                     prep: Optional[cwipc_hip_rgbd_prep] = None, occlusion: Optional[cwipc_hip_rgbd_occlusion] = None,
+                                     filter: Optional[cwipc_hip_rgbd_filter] = None, timestamp: int = 0, cellsize: float = 0.0,
+                                     attach_flags: int = 0) -> cwipc_pointcloud_wrapper:
+    """cwipc_hip_rgbd_rig_grab / cwipc_hip_rgbd_rig_grab_occluded with the depth images smoothed on the GPU first: an edge-preserving
+    spatial filter, then a temporal one that keeps its state in the rig from grab to grab.  depthfilter None, or one with both stages
+    off: exactly the other two entries.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
+    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_filtered(rig, ctypes.addressof(array) if len(frames) else None,
+                                                                ctypes.addressof(depthfilter) if depthfilter is not None else None,
+                                                                ctypes.addressof(prep) if prep is not None else None,
+                                                                ctypes.addressof(occlusion) if occlusion is not None else None,
+                                                                ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
+                                                                int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError("cwipc_hip_rgbd_rig_grab_filtered: no pointcloud created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_reset_history(rig: int) -> None:
+    """Make the temporal filter's state of the rig empty again, as a new rig's."""
+    cwipc_util_dll_load().cwipc_hip_rgbd_rig_reset_history(rig)
+
+
+def cwipc_hip_rgbd_rig_history(rig: int, cam: int, width: int, height: int) -> Tuple[numpy.ndarray, numpy.ndarray]:
+    """Camera cam's temporal-filter state, for parity tests: (running values float64[height, width], history bytes uint8[height,
+    width]); zeros for a rig that has none yet (width and height: that camera's depth image)."""
+    value = numpy.zeros((int(height), int(width)), dtype=numpy.float64)
+    history = numpy.zeros((int(height), int(width)), dtype=numpy.uint8)
+    if cwipc_util_dll_load().cwipc_hip_rgbd_rig_history(rig, int(cam), value.ctypes.data, history.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_rgbd_rig_history: no such camera, or the copy failed")
+    return value, history
 
 
 def cwipc_hip_rgbd_rig_ray_table(rig: int, cam: int, width: int, height: int) -> numpy.ndarray:

@@ -508,6 +508,8 @@ typedef struct cwipc_hip_rgbd_rig cwipc_hip_rgbd_rig;
 _CWIPC_UTIL_EXPORT cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage);
 _CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig);
 /* One device-resident cloud from one frame (frames: ncam entries, in the sensors' order).  Per camera:
+ *  0. Only through cwipc_hip_rgbd_rig_grab_filtered (below, where rules 0a and 0b are stated): the depth image is replaced by its
+ *     spatially and temporally filtered version.  Rules 1-4 run on that image.
  *  1. Erosion of the depth image (prep may be NULL: none): a pixel keeps its depth iff no pixel (u + du, v + dv) with |du| <=
  *     depth_x_erosion, |dv| <= depth_y_erosion that lies inside the image has depth 0.  Pixels outside the image do not erode.
  *  2. The point of pixel (u, v), depth d != 0:  z = (double)d * depth_scale;  xc = xn*z;  yc = yn*z, (xn, yn) the ray table's entry;
@@ -552,6 +554,56 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_occluded(cwipc_hip_
                                                                       const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion,
                                                                       const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize,
                                                                       int attach_flags, char **errorMessage);
+/* The same with the depth post-processing every depth-camera vendor ships in front of it: an edge-preserving spatial smoother and a
+ * temporal smoother that also persists depth over dropped samples.  This project's own definition (the camera plug-ins
+ * that hold the vendors' versions are not in the reference tree); csrc/rgbd_depthfilter.hpp is the one statement of the arithmetic,
+ * tests/rgbd_depthfilter_model.py its numpy restatement.  RULE 0, in front of rule 1.  All arithmetic is float64, every operation
+ * rounded on its own; depth values are in depth units, not metres; oma = 1 - alpha is computed once per call;
+ * q(x) = (uint16) floor(x + 0.5).
+ *  0a. The spatial filter, spatial_magnitude iterations (0: off, at most 5).  One iteration is, per camera: (1) every row, forward
+ *      (u rising); (2) every row, backward, on the result of 1; (3) every column, forward (v rising), on the result of 2; (4) every
+ *      column, backward, on the result of 3.  A pass over a line d[0 .. n-1]:
+ *          s = (double) d[first]                                    the running value, 0: none
+ *          for each further i in pass order:   c = (double) d[i]
+ *              if d[i] != 0 and s != 0 and fabs(c - s) < spatial_delta:   s = (spatial_alpha * c) + (oma * s);   d[i] = q(s)
+ *              else:                                                      s = c
+ *      The comparison is strict and s stays unrounded.  A pixel without depth is never filled and resets the running value; the first
+ *      pixel of a pass is never changed by that pass; a line never continues into another row, another column or another camera.  The
+ *      new d[i] is a convex combination of two values in 1 .. 65535 and lies there: no clamp is part of the rule.
+ *  0b. The temporal filter (temporal 0 / 1), after 0a.  Per depth pixel the rig keeps a running value s (float64, 0: none) and a
+ *      history byte h: bit j of h is set iff the pixel had depth -- after 0a, before persistence -- in the j+1-th most recent temporal
+ *      grab.  With c the pixel's value after 0a:
+ *          if c != 0:   if s != 0 and fabs(c - s) < temporal_delta:   s = (temporal_alpha * c) + (oma_t * s);   out = q(s)
+ *                       else:                                         s = c;                                    out = c
+ *          else:        out = (s != 0 and persists(temporal_persistency, h)) ? q(s) : 0                         (s unchanged)
+ *          h = ((h << 1) | (c != 0)) & 0xff
+ *      persists(mode, h), on h as it was before this grab:  0 never;  1 h == 0xff;  2 popcount(h & 0x07) >= 2;
+ *      3 popcount(h & 0x0f) >= 2;  4 popcount(h) >= 2;  5 (h & 0x03) != 0;  6 (h & 0x1f) != 0;  7 h != 0;  8 always.
+ *      out replaces the depth image: erosion, rays and colour (with occlusion when asked for), then the filters, run on it, and the
+ *      attached "depth.<serial>" image is the filtered one, eroded and cleared as before.
+ * The state (9 bytes per depth pixel) is allocated by a rig's first grab with temporal != 0 and freed with the rig.  A new rig starts
+ * empty (s = 0, h = 0 everywhere); cwipc_hip_rgbd_rig_reset_history makes it empty again.  Only a grab with temporal != 0 reads or
+ * writes it; a grab that is refused for its arguments leaves it untouched; a grab that fails on the device leaves it empty.  Grabs
+ * are serialised by the rig's lock, which is what gives "the previous grab" a meaning.
+ * depthfilter == NULL, or one with spatial_magnitude == 0 and temporal == 0: cwipc_hip_rgbd_rig_grab (occlusion == NULL) or
+ * cwipc_hip_rgbd_rig_grab_occluded byte for byte, the history untouched.  NULL, and nothing left behind, for a magnitude outside
+ * 0 .. 5, a persistency outside 0 .. 8, and, for a stage that is on, an alpha outside (0, 1] or not finite or a delta that is not
+ * finite or not > 0 (the parameters of a stage that is off are not judged), and everything the two other entries refuse. */
+typedef struct cwipc_hip_rgbd_depthfilter {
+    int32_t spatial_magnitude;                  /* 0 .. 5 iterations, 0: off */
+    double spatial_alpha, spatial_delta;        /* 0 < alpha <= 1; delta > 0, depth units; both finite */
+    int32_t temporal;                           /* 0 / 1 */
+    double temporal_alpha, temporal_delta;      /* as above */
+    int32_t temporal_persistency;               /* 0 .. 8 */
+} cwipc_hip_rgbd_depthfilter;
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filtered(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames,
+                                                                      const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep,
+                                                                      const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+                                                                      uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage);
+_CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_reset_history(cwipc_hip_rgbd_rig *rig);
+/* For parity tests: camera cam's running values (width * height doubles) and history bytes (width * height) into host memory; 0 ok,
+ * -1 for a bad argument or a failed copy; a rig without state yet reports zeros. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_history(cwipc_hip_rgbd_rig *rig, int cam, double *value, uint8_t *history);
 /* Camera cam's ray table: 2 * width * height doubles (x then y per pixel, row-major), the rig's own host copy; NULL for a bad argument. */
 _CWIPC_UTIL_EXPORT const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam);
 /* The two mappings for a rig's clouds.  The attached colour image lies on the depth grid, so mapcolordepth is the identity inside the
