@@ -31,6 +31,7 @@ SOURCES = [
     "ply.cpp",
     "filters.cpp",
     "rgbd.cpp",
+    "codec.cpp",
     "exchange.cpp",
     "kernels_basic.hip",
     "kernels_voxel.hip",
@@ -44,6 +45,7 @@ SOURCES = [
     "kernels_render.hip",
     "kernels_markers.hip",
     "kernels_rgbd.hip",
+    "kernels_codec.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -1,0 +1,190 @@
+"""An octree codec whose packets are NOT interoperable with cwipc_codec, under the names the reference's callers use (`cwipc.codec`).
+
+The interface is the reference's (`cwipc_new_encoder`, `cwipc_new_encodergroup`, `cwipc_new_decoder`, as
+python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is this library's own (RULE C,
+include/cwipc_util_amd/hip_ext.h) and carries its own magic, the bytes ``cwao``.
+Encoding and decoding run on the GPU; a decoder's clouds are ordinary device-resident clouds.
+
+Out of scope: cwipc_codec's bitstream, entropy coding of the occupancy bytes, transform or JPEG colour coding, inter-frame
+coding, per-leaf point counts in the packet, sockets.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Dict, List, Optional, Union
+
+from . import util
+from .util import CwipcError, cwipc_pointcloud_wrapper
+
+__all__ = [
+    "cwipc_encoder_params", "cwipc_new_encoder_params", "cwipc_new_encoder", "cwipc_new_encodergroup", "cwipc_new_decoder",
+    "cwipc_encoder_wrapper", "cwipc_encodergroup_wrapper", "cwipc_decoder_wrapper", "packet_info",
+]
+
+
+class cwipc_encoder_params(util.cwipc_hip_encoder_params):
+    """do_inter_frame, gop_size, exp_factor, octree_bits, jpeg_quality, macroblock_size, tilenumber, voxelsize: positional in this
+    order, settable by name."""
+
+
+def cwipc_new_encoder_params() -> cwipc_encoder_params:
+    """The defaults of the reference's sink_encoder: 9 octree bits, quality 85, every tile, no downsampling."""
+    return cwipc_encoder_params(False, 1, 1.0, 9, 85, 16, 0, 0)
+
+
+class cwipc_encoder_wrapper:
+    """One encoder: feed(pc), then available(wait) and get_bytes(), first in first out."""
+
+    def __init__(self, handle: int, group: Optional["cwipc_encodergroup_wrapper"] = None):
+        self._enc: Optional[int] = handle
+        self._group = group   # (an encoder of a group is freed with the group)
+
+    def _handle(self) -> int:
+        if not self._enc:
+            raise CwipcError("cwipc_encoder_wrapper: used after free()")
+        return self._enc
+
+    def __del__(self):
+        self.free()
+
+    def free(self) -> None:
+        if self._enc and self._group is None:
+            util.cwipc_hip_encoder_free(self._enc)
+        self._enc = None
+
+    def close(self) -> None:
+        util.cwipc_hip_encoder_close(self._handle())
+
+    def eof(self) -> bool:
+        return util.cwipc_hip_encoder_eof(self._handle())
+
+    def at_gop_boundary(self) -> bool:
+        return util.cwipc_hip_encoder_at_gop_boundary(self._handle())
+
+    def feed(self, pc: cwipc_pointcloud_wrapper) -> None:
+        util.cwipc_hip_encoder_feed(self._handle(), pc)
+
+    def available(self, wait: bool) -> bool:
+        return util.cwipc_hip_encoder_available(self._handle(), wait)
+
+    def get_encoded_size(self) -> int:
+        return util.cwipc_hip_encoder_get_encoded_size(self._handle())
+
+    def get_bytes(self) -> bytearray:
+        """The oldest packet (waits for it when it is still being written)."""
+        size = self.get_encoded_size()
+        if size == 0:
+            raise CwipcError("cwipc_encoder_wrapper.get_bytes: nothing has been fed")
+        rv = bytearray(size)
+        buffer = (ctypes.c_char * size).from_buffer(rv)
+        if not util.cwipc_hip_encoder_copy_data(self._handle(), buffer, size):
+            raise CwipcError("cwipc_encoder_wrapper.get_bytes: the copy failed")
+        del buffer
+        return rv
+
+
+class cwipc_encodergroup_wrapper:
+    """Encoders that are fed together: each delivers byte for byte what it would deliver alone, the filtering and the sort of
+    encoders with equal (tilenumber, voxelsize) being made once."""
+
+    def __init__(self, handle: int):
+        self._group: Optional[int] = handle
+        self._encoders: List[cwipc_encoder_wrapper] = []
+
+    def _handle(self) -> int:
+        if not self._group:
+            raise CwipcError("cwipc_encodergroup_wrapper: used after free()")
+        return self._group
+
+    def __del__(self):
+        self.free()
+
+    def free(self) -> None:
+        if self._group:
+            for enc in self._encoders:
+                enc._enc = None
+            util.cwipc_hip_encodergroup_free(self._group)
+        self._group = None
+        self._encoders = []
+
+    def close(self) -> None:
+        util.cwipc_hip_encodergroup_close(self._handle())
+
+    def addencoder(self, version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
+        enc = cwipc_encoder_wrapper(util.cwipc_hip_encodergroup_addencoder(self._handle(), _params(params, kwargs)), self)
+        self._encoders.append(enc)
+        return enc
+
+    def feed(self, pc: cwipc_pointcloud_wrapper) -> None:
+        util.cwipc_hip_encodergroup_feed(self._handle(), pc)
+
+
+class cwipc_decoder_wrapper:
+    """feed(packet), then available(wait) and get(): a device-resident cloud per packet, first in first out."""
+
+    def __init__(self, handle: int):
+        self._dec: Optional[int] = handle
+
+    def _handle(self) -> int:
+        if not self._dec:
+            raise CwipcError("cwipc_decoder_wrapper: used after free()")
+        return self._dec
+
+    def __del__(self):
+        self.free()
+
+    def free(self) -> None:
+        if self._dec:
+            util.cwipc_hip_decoder_free(self._dec)
+        self._dec = None
+
+    def close(self) -> None:
+        util.cwipc_hip_decoder_close(self._handle())
+
+    def eof(self) -> bool:
+        return util.cwipc_hip_decoder_eof(self._handle())
+
+    def feed(self, buffer: Union[bytes, bytearray, memoryview]) -> None:
+        """CwipcError with the reason for a packet that is not valid; such a packet never reaches the device."""
+        util.cwipc_hip_decoder_feed(self._handle(), buffer)
+
+    def available(self, wait: bool) -> bool:
+        return util.cwipc_hip_decoder_available(self._handle(), wait)
+
+    def get(self) -> Optional[cwipc_pointcloud_wrapper]:
+        return util.cwipc_hip_decoder_get(self._handle())
+
+
+def _params(params: Optional[cwipc_encoder_params], kwargs: Dict[str, Any]) -> cwipc_encoder_params:
+    if params is None:
+        params = cwipc_new_encoder_params()
+    elif kwargs:
+        params = cwipc_encoder_params.from_buffer_copy(params)
+    names = [f[0] for f in cwipc_encoder_params._fields_]
+    for name, value in kwargs.items():
+        if name not in names:
+            raise CwipcError(f"cwipc_new_encoder: unknown parameter {name!r}")
+        setattr(params, name, value)
+    return params
+
+
+def cwipc_new_encoder(version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
+    """An encoder for `params` (default: cwipc_new_encoder_params()), single parameters overridden by keyword."""
+    return cwipc_encoder_wrapper(util.cwipc_hip_new_encoder(_params(params, kwargs)))
+
+
+def cwipc_new_encodergroup() -> cwipc_encodergroup_wrapper:
+    return cwipc_encodergroup_wrapper(util.cwipc_hip_new_encodergroup())
+
+
+def cwipc_new_decoder() -> cwipc_decoder_wrapper:
+    return cwipc_decoder_wrapper(util.cwipc_hip_new_decoder())
+
+
+def packet_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
+    """The header of a valid packet (host code, no GPU); CwipcError with the reason otherwise."""
+    info = util.cwipc_hip_codec_packet_info(packet)
+    return dict(timestamp=info.timestamp, nleaves=info.nleaves, octree_bits=info.octree_bits, colour_bits=info.colour_bits,
+                tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
+                nodes=list(info.nodes)[:info.octree_bits], occupancy_offset=info.occupancy_offset, colour_offset=info.colour_offset,
+                tile_offset=info.tile_offset, total_bytes=info.total_bytes)

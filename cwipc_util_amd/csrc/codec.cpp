@@ -1,0 +1,582 @@
+// codec.cpp -- the octree codec's C boundary and host orchestration: cwipc_hip_new_encoder, cwipc_hip_new_encodergroup,
+// cwipc_hip_new_decoder, cwipc_hip_codec_packet_info.  The interface is the one the reference's callers use
+// (python/cwipc/net/sink_encoder.py, source_decoder.py); the rule (RULE C: hip_ext.h, codec_terms.hpp) and the packets are this
+// library's own and NOT interoperable with cwipc_codec.  The kernels are in kernels_codec.hip.
+//
+// Encode: filter -> cube, keys, sort, per-depth counts and their scan -> ONE wait (nodes[] and the cube size the packet) -> the
+// body's kernels and its copy into page-locked memory, in flight when feed returns.  The header is written by the host; the tile
+// mode, known only when the leaves are, is filled in when the result is taken.
+// Decode: validate on the host (nothing launched or allocated for a packet that is refused) -> upload -> the kernels, in flight
+// when feed returns: the cloud carries a `ready` event.
+#include "internal.hpp"
+#include "codec_terms.hpp"
+
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <exception>
+
+using namespace cwipc_amd;
+
+namespace {
+
+size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+struct ErrorbufScope {
+    explicit ErrorbufScope(char **errorMessage) { cwipc_log_set_errorbuf(errorMessage); }
+    ~ErrorbufScope() { cwipc_log_set_errorbuf(nullptr); }
+};
+
+// One encoded packet, possibly still being written by the device.
+struct EncJob {
+    uint8_t *host = nullptr;
+    bool pinned = false;
+    CodecLayout layout;              // tile_mode 1 until finalize() has looked at the leaves
+    size_t stats_offset = 0;         // where the two tile words land in `host` (0: an empty cloud, nothing in flight)
+    hipEvent_t done = nullptr;
+    std::shared_ptr<DeviceSoA> src;  // the kernels read its planes
+    bool final = false;
+    ~EncJob() {
+        if (done) { (void)hipEventSynchronize(done); event_put(done); }
+        if (host) host_free(host, pinned);
+    }
+    bool ready(bool wait) {
+        if (final || !done) return true;
+        if (wait) return hipEventSynchronize(done) == hipSuccess;
+        const hipError_t e = hipEventQuery(done);
+        if (e != hipSuccess) (void)hipGetLastError();
+        return e == hipSuccess;
+    }
+    void finalize() {
+        if (final) return;
+        if (done) { (void)hipEventSynchronize(done); event_put(done); done = nullptr; }
+        src.reset();
+        if (stats_offset) {
+            uint32_t stats[2];
+            memcpy(stats, host + stats_offset, 8);
+            const bool uniform = (stats[0] & stats[1]) == 0u;
+            layout.tile_mode = uniform ? 0 : 1;
+            layout.tile_value = uniform ? (int)(stats[0] & 255u) : 0;
+        } else {
+            layout.tile_mode = 0;
+            layout.tile_value = 0;
+        }
+        codec_layout_sizes(layout);
+        host[22] = (uint8_t)layout.tile_mode;
+        host[23] = (uint8_t)layout.tile_value;
+        final = true;
+    }
+};
+
+// A cloud sorted for `bits`, with what the one read-back brought.
+struct Sorted {
+    std::shared_ptr<DeviceSoA> src;
+    size_t n = 0;
+    int bits = 0;
+    void *block = nullptr;   // everything below
+    unsigned long long *keys = nullptr;
+    uint32_t *index = nullptr, *counts = nullptr;
+    k::CodecCube *cube_dev = nullptr;
+    k::CodecCube cube{{0, 0, 0}, 0, 1.0};
+    uint32_t nodes[CODEC_MAX_BITS] = {0};
+};
+
+bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits, Sorted &out) {
+    out.src = src;
+    out.n = src->npoints;
+    out.bits = bits;
+    if (out.n == 0) return true;
+    if (out.n > 0xfffffff0ull) { note_error(who, "more than 2^32 points"); return false; }
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    const size_t n = out.n, nb = k::codec_blocks(n);
+    const size_t keys_bytes = round256(2 * n * 8), index_bytes = round256(2 * n * 4), counts_bytes = round256((size_t)bits * (nb + 1) * 4),
+                 bounds_bytes = round256(k::codec_bounds_bytes(n));
+    uint8_t *block = (uint8_t *)pool_alloc(keys_bytes + index_bytes + counts_bytes + bounds_bytes + 256);
+    if (!block) { note_error(who, "out of device memory"); return false; }
+    out.block = block;
+    out.keys = (unsigned long long *)block;
+    out.index = (uint32_t *)(block + keys_bytes);
+    out.counts = (uint32_t *)(block + keys_bytes + index_bytes);
+    void *partial = block + keys_bytes + index_bytes + counts_bytes;
+    out.cube_dev = (k::CodecCube *)(block + keys_bytes + index_bytes + counts_bytes + bounds_bytes);
+    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
+    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    for (int L = 0; L < bits; L++) words[L] = 0ull;
+    k::codec_cube(*src, partial, out.cube_dev, c.stream);
+    bool ok = k::codec_sort(*src, out.cube_dev, bits, out.keys, out.index, c.stream);
+    if (ok) {
+        k::codec_count_scan(out.keys + n, n, out.cube_dev, bits, out.counts, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        ok = hipMemcpyAsync(c.host_words + 32, out.cube_dev, sizeof(k::CodecCube), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipGetLastError() == hipSuccess;
+    }
+    ok = c.sync() && ok;
+    for (int L = 0; ok && L < bits; L++) ok = (uint32_t)(words[L] >> 32) == tag;
+    if (!ok) {
+        hip_failed(hipGetLastError(), "octree encode (sort)", __FILE__, __LINE__);
+        pool_free(block);
+        out.block = nullptr;
+        return false;
+    }
+    memcpy(&out.cube, c.host_words + 32, sizeof(k::CodecCube));
+    for (int L = 0; L < bits; L++) out.nodes[L] = (uint32_t)words[L];
+    return true;
+}
+
+// The packet of (bits <= s.bits, colour shift) from a sorted cloud: queued on the calling thread's stream.
+std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp) {
+    ThreadCtx &c = tctx();
+    std::unique_ptr<EncJob> job(new EncJob());
+    CodecLayout &l = job->layout;
+    l.timestamp = timestamp;
+    l.bits = bits;
+    l.colour_bits = 8 - shift;
+    l.nleaves = s.n && s.cube.nfinite ? s.nodes[bits - 1] : 0u;
+    l.tile_mode = 1;
+    if (l.nleaves) {
+        for (int L = 0; L < bits; L++) l.nodes[L] = s.nodes[L];
+        for (int a = 0; a < 3; a++) l.mn[a] = s.cube.mn[a];
+        l.side = s.cube.side;
+    }
+    codec_layout_sizes(l);
+    const size_t body_bytes = (size_t)(l.tile_offset - l.occupancy_offset) + (size_t)codec_pad4(l.nleaves) + 8;   // ... the tile plane, the two tile words
+    job->host = (uint8_t *)host_alloc((size_t)l.occupancy_offset + body_bytes, &job->pinned);
+    if (!job->host) { note_error(who, "out of host memory"); return nullptr; }
+    codec_write_header(job->host, l);
+    if (!l.nleaves) {
+        job->finalize();
+        return job;
+    }
+    if (!c.ensure()) return nullptr;
+    const size_t sums_offset = (body_bytes + 7) & ~(size_t)7, block_bytes = sums_offset + (size_t)l.nleaves * sizeof(k::CodecLeafSum);
+    uint8_t *block = (uint8_t *)pool_alloc(block_bytes);
+    if (!block) { note_error(who, "out of device memory"); return nullptr; }
+    k::CodecEmit e{};
+    e.bits = bits;
+    e.nleaves = l.nleaves;
+    e.depth_offset[0] = 0;
+    for (int L = 1; L < bits; L++) e.depth_offset[L] = L == 1 ? 1u : e.depth_offset[L - 1] + l.nodes[L - 2];
+    e.occupancy_bytes = l.occupancy_bytes;
+    e.colour_words = codec_pad4(l.colour_bytes) / 4;
+    e.occupancy = (uint32_t *)block;
+    e.colours = (uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
+    e.tiles = block + (l.tile_offset - l.occupancy_offset);
+    e.tile_stats = (uint32_t *)(block + body_bytes - 8);
+    e.sums = (k::CodecLeafSum *)(block + sums_offset);
+    bool ok = hipMemsetAsync(block, 0, block_bytes, c.stream) == hipSuccess;
+    if (ok) {
+        k::codec_emit(s.keys + s.n, s.index + s.n, *s.src, s.cube_dev, s.bits, s.counts, e, shift, c.stream);
+        ok = hipMemcpyAsync(job->host + l.occupancy_offset, block, body_bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipGetLastError() == hipSuccess;
+    }
+    job->done = event_get();
+    ok = ok && job->done && hipEventRecord(job->done, c.stream) == hipSuccess;
+    c.free_later(block);
+    if (!ok) {
+        (void)c.sync();
+        hip_failed(hipGetLastError(), "octree encode", __FILE__, __LINE__);
+        return nullptr;
+    }
+    job->stats_offset = (size_t)l.occupancy_offset + body_bytes - 8;
+    job->src = s.src;
+    return job;
+}
+
+// The cloud an encoder of (tilenumber, voxelsize) works on, on the device.  `made` receives the clouds made on the way.
+std::shared_ptr<DeviceSoA> filtered_input(const char *who, cwipc_pointcloud *pc, int tilenumber, float voxelsize, std::vector<cwipc_pointcloud *> &made,
+                                          std::unique_ptr<cwipc_hip_pointcloud> &keep) {
+    cwipc_pointcloud *cur = pc;
+    if (tilenumber != 0) {
+        cur = cwipc_tilefilter(cur, tilenumber);
+        if (!cur) { note_error(who, "cwipc_tilefilter failed"); return nullptr; }
+        made.push_back(cur);
+    }
+    if (voxelsize > 0) {
+        cur = cwipc_downsample(cur, voxelsize);
+        if (!cur) { note_error(who, "cwipc_downsample failed"); return nullptr; }
+        made.push_back(cur);
+    }
+    cwipc_hip_pointcloud *ours = as_ours(cur);
+    if (!ours) {
+        keep = import_foreign(cur);
+        ours = keep.get();
+    }
+    if (!ours || !ours->has_data()) { note_error(who, "cannot read the point data of the argument"); return nullptr; }
+    if (!device_available(who)) return nullptr;
+    auto dev = ours->device_points();
+    if (!dev) note_error(who, "the cloud cannot be brought to the device");
+    return dev;
+}
+
+// The clouds filtered_input made on the way: they go when the feed that asked for them is over (the planes stay with the packet's job).
+struct MadeClouds {
+    std::vector<cwipc_pointcloud *> list;
+    ~MadeClouds() { for (cwipc_pointcloud *p : list) delete p; }
+};
+
+// No exception crosses the C boundary: what the standard library throws in a call's body (memory) is logged and becomes its error value.
+template <typename T, typename Body>
+T guarded(const char *who, T failed, Body &&body) {
+    try {
+        return body();
+    } catch (const std::exception &e) {
+        note_error(who, e.what());
+    } catch (...) {
+        note_error(who, "unknown exception");
+    }
+    return failed;
+}
+
+const char *params_problem(const cwipc_hip_encoder_params &p) {
+    if (p.do_inter_frame) return "do_inter_frame is not supported (inter-frame coding is out of scope)";
+    if (p.gop_size != 1) return "gop_size must be 1";
+    if (!(p.exp_factor == 1.0f)) return "exp_factor must be 1.0";
+    if (p.octree_bits < 1 || p.octree_bits > CODEC_MAX_BITS) return "octree_bits must be in 1..16";
+    if (p.jpeg_quality < 0 || p.jpeg_quality > 100) return "jpeg_quality must be in 0..100";
+    if (std::isnan(p.voxelsize)) return "voxelsize is not a number";
+    return nullptr;
+}
+
+}  // namespace
+
+struct cwipc_hip_encoder {
+    cwipc_hip_encoder_params params;
+    std::mutex lock;
+    std::deque<std::unique_ptr<EncJob>> queue;
+    bool closed = false;
+    bool in_group = false;
+};
+
+struct cwipc_hip_encodergroup {
+    std::mutex lock;
+    std::vector<cwipc_hip_encoder *> encoders;
+};
+
+struct cwipc_hip_decoder {
+    struct Job {
+        cwipc_pointcloud *cloud = nullptr;
+        std::shared_ptr<DeviceSoA> planes;   // (its `ready` event says when the kernels are done)
+        uint8_t *host = nullptr;             // the packet as the upload reads it
+        bool pinned = false;
+    };
+    std::mutex lock;
+    std::deque<Job> queue;
+    bool closed = false;
+};
+
+namespace {
+
+void release_upload(cwipc_hip_decoder::Job &j) {
+    if (j.host) {
+        if (j.planes) j.planes->wait_host();
+        host_free(j.host, j.pinned);
+        j.host = nullptr;
+    }
+}
+
+int encoder_feed_sorted(const char *who, cwipc_hip_encoder *enc, const Sorted &s, uint64_t timestamp) {
+    auto job = emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp);
+    if (!job) return -1;
+    std::lock_guard<std::mutex> l(enc->lock);
+    enc->queue.push_back(std::move(job));
+    return 0;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// encoder
+// ---------------------------------------------------------------------------
+extern "C" cwipc_hip_encoder *cwipc_hip_new_encoder(const cwipc_hip_encoder_params *params, char **errorMessage) {
+    const char *who = "cwipc_hip_new_encoder";
+    ErrorbufScope scope(errorMessage);
+    if (params == nullptr) { note_error(who, "NULL argument"); return nullptr; }
+    if (const char *problem = params_problem(*params)) { note_error(who, problem); return nullptr; }
+    cwipc_hip_encoder *enc = new (std::nothrow) cwipc_hip_encoder();
+    if (!enc) { note_error(who, "out of memory"); return nullptr; }
+    enc->params = *params;
+    return enc;
+}
+
+extern "C" void cwipc_hip_encoder_free(cwipc_hip_encoder *enc) {
+    if (enc == nullptr || enc->in_group) return;   // (a group's encoders go with the group)
+    delete enc;
+}
+
+extern "C" int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *pc) {
+    const char *who = "cwipc_hip_encoder_feed";
+    return guarded(who, -1, [&]() -> int {
+        if (enc == nullptr || pc == nullptr) { note_error(who, "NULL argument"); return -1; }
+        if (enc->closed) { note_error(who, "the encoder has been closed"); return -1; }
+        MadeClouds made;
+        std::unique_ptr<cwipc_hip_pointcloud> keep;
+        int rv = -1;
+        auto src = filtered_input(who, pc, enc->params.tilenumber, enc->params.voxelsize, made.list, keep);
+        if (src) {
+            Sorted s;
+            if (sort_cloud(who, src, enc->params.octree_bits, s)) {
+                rv = encoder_feed_sorted(who, enc, s, pc->timestamp());
+                tctx().free_later(s.block);
+            }
+        }
+        return rv;
+    });
+}
+
+extern "C" bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait) {
+    if (enc == nullptr) return false;
+    std::lock_guard<std::mutex> l(enc->lock);
+    if (enc->queue.empty()) return false;
+    return enc->queue.front()->ready(wait);
+}
+
+extern "C" size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc) {
+    if (enc == nullptr) return 0;
+    std::lock_guard<std::mutex> l(enc->lock);
+    if (enc->queue.empty()) return 0;
+    enc->queue.front()->finalize();
+    return (size_t)enc->queue.front()->layout.total_bytes;
+}
+
+extern "C" bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size) {
+    if (enc == nullptr || buffer == nullptr) return false;
+    std::lock_guard<std::mutex> l(enc->lock);
+    if (enc->queue.empty()) return false;
+    EncJob &job = *enc->queue.front();
+    job.finalize();
+    if (size < (size_t)job.layout.total_bytes) return false;
+    memcpy(buffer, job.host, (size_t)job.layout.total_bytes);
+    enc->queue.pop_front();
+    return true;
+}
+
+extern "C" bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc) { (void)enc; return true; }
+
+extern "C" bool cwipc_hip_encoder_eof(cwipc_hip_encoder *enc) {
+    if (enc == nullptr) return true;
+    std::lock_guard<std::mutex> l(enc->lock);
+    return enc->closed && enc->queue.empty();
+}
+
+extern "C" void cwipc_hip_encoder_close(cwipc_hip_encoder *enc) {
+    if (enc == nullptr) return;
+    std::lock_guard<std::mutex> l(enc->lock);
+    enc->closed = true;
+}
+
+// ---------------------------------------------------------------------------
+// encoder group
+// ---------------------------------------------------------------------------
+extern "C" cwipc_hip_encodergroup *cwipc_hip_new_encodergroup(char **errorMessage) {
+    ErrorbufScope scope(errorMessage);
+    cwipc_hip_encodergroup *g = new (std::nothrow) cwipc_hip_encodergroup();
+    if (!g) note_error("cwipc_hip_new_encodergroup", "out of memory");
+    return g;
+}
+
+extern "C" cwipc_hip_encoder *cwipc_hip_encodergroup_addencoder(cwipc_hip_encodergroup *group, const cwipc_hip_encoder_params *params, char **errorMessage) {
+    if (group == nullptr) {
+        ErrorbufScope scope(errorMessage);
+        note_error("cwipc_hip_encodergroup_addencoder", "NULL argument");
+        return nullptr;
+    }
+    cwipc_hip_encoder *enc = cwipc_hip_new_encoder(params, errorMessage);
+    if (!enc) return nullptr;
+    enc->in_group = true;
+    std::lock_guard<std::mutex> l(group->lock);
+    try {
+        group->encoders.push_back(enc);
+    } catch (...) {
+        delete enc;
+        ErrorbufScope scope(errorMessage);
+        note_error("cwipc_hip_encodergroup_addencoder", "out of memory");
+        return nullptr;
+    }
+    return enc;
+}
+
+extern "C" int cwipc_hip_encodergroup_feed(cwipc_hip_encodergroup *group, cwipc_pointcloud *pc) {
+    const char *who = "cwipc_hip_encodergroup_feed";
+    return guarded(who, -1, [&]() -> int {
+        if (group == nullptr || pc == nullptr) { note_error(who, "NULL argument"); return -1; }
+        std::lock_guard<std::mutex> l(group->lock);
+        // the encoders that work on the same cloud, in the order of their first member
+        std::vector<std::vector<cwipc_hip_encoder *>> classes;
+        for (cwipc_hip_encoder *enc : group->encoders) {
+            if (enc->closed) continue;
+            bool placed = false;
+            for (auto &cls : classes)
+                if (cls[0]->params.tilenumber == enc->params.tilenumber && cls[0]->params.voxelsize == enc->params.voxelsize) { cls.push_back(enc); placed = true; break; }
+            if (!placed) classes.push_back({enc});
+        }
+        int rv = 0;
+        for (auto &cls : classes) {
+            MadeClouds made;
+            std::unique_ptr<cwipc_hip_pointcloud> keep;
+            int bits = 0;
+            for (cwipc_hip_encoder *enc : cls) bits = enc->params.octree_bits > bits ? enc->params.octree_bits : bits;
+            auto src = filtered_input(who, pc, cls[0]->params.tilenumber, cls[0]->params.voxelsize, made.list, keep);
+            Sorted s;
+            if (src && sort_cloud(who, src, bits, s)) {
+                for (cwipc_hip_encoder *enc : cls)
+                    if (encoder_feed_sorted(who, enc, s, pc->timestamp()) != 0) rv = -1;
+                tctx().free_later(s.block);
+            } else {
+                rv = -1;
+            }
+        }
+        return rv;
+    });
+}
+
+extern "C" void cwipc_hip_encodergroup_close(cwipc_hip_encodergroup *group) {
+    if (group == nullptr) return;
+    std::lock_guard<std::mutex> l(group->lock);
+    for (cwipc_hip_encoder *enc : group->encoders) cwipc_hip_encoder_close(enc);
+}
+
+extern "C" void cwipc_hip_encodergroup_free(cwipc_hip_encodergroup *group) {
+    if (group == nullptr) return;
+    for (cwipc_hip_encoder *enc : group->encoders) delete enc;
+    delete group;
+}
+
+// ---------------------------------------------------------------------------
+// decoder
+// ---------------------------------------------------------------------------
+extern "C" int cwipc_hip_codec_packet_info(const void *bytes, size_t len, cwipc_hip_codec_info *info, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_packet_info";
+    ErrorbufScope scope(errorMessage);
+    CodecLayout l;
+    if (const char *problem = codec_validate((const uint8_t *)bytes, len, l)) { note_error(who, problem); return -1; }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->timestamp = l.timestamp;
+        info->nleaves = l.nleaves;
+        info->octree_bits = l.bits;
+        info->colour_bits = l.colour_bits;
+        info->tile_mode = l.tile_mode;
+        info->tile_value = l.tile_value;
+        for (int a = 0; a < 3; a++) info->min[a] = l.mn[a];
+        info->side = l.side;
+        for (int d = 0; d < l.bits; d++) info->nodes[d] = l.nodes[d];
+        info->occupancy_offset = l.occupancy_offset;
+        info->colour_offset = l.colour_offset;
+        info->tile_offset = l.tile_offset;
+        info->total_bytes = l.total_bytes;
+    }
+    return 0;
+}
+
+extern "C" cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage) {
+    ErrorbufScope scope(errorMessage);
+    cwipc_hip_decoder *d = new (std::nothrow) cwipc_hip_decoder();
+    if (!d) note_error("cwipc_hip_new_decoder", "out of memory");
+    return d;
+}
+
+extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes, size_t len) {
+    const char *who = "cwipc_hip_decoder_feed";
+    return guarded(who, -1, [&]() -> int {
+        if (dec == nullptr) { note_error(who, "NULL argument"); return -1; }
+        if (dec->closed) { note_error(who, "the decoder has been closed"); return -1; }
+        // the validity test: host code, before anything is launched or allocated on the device
+        CodecLayout l;
+        if (const char *problem = codec_validate((const uint8_t *)bytes, len, l)) { note_error(who, problem); return -1; }
+        if (!device_available(who)) return -1;
+        ThreadCtx &c = tctx();
+        if (!c.ensure()) return -1;
+        const double cell = codec_cellsize(l.side, l.bits);
+        cwipc_hip_decoder::Job job;
+        auto dst = soa_alloc(l.nleaves);
+        if (!dst) { note_error(who, "out of device memory"); return -1; }
+        if (l.nleaves) {
+            const size_t body = (size_t)(l.total_bytes - l.occupancy_offset);
+            k::CodecDecode d{};
+            d.bits = l.bits;
+            d.colour_bits = l.colour_bits;
+            d.tile_value = l.tile_value;
+            d.nleaves = l.nleaves;
+            for (int i = 0; i < l.bits; i++) d.nodes[i] = l.nodes[i];
+            for (int a = 0; a < 3; a++) d.mn[a] = l.mn[a];
+            d.cell = cell;
+            d.colour_words = codec_pad4(l.colour_bytes) / 4;
+            const size_t body_bytes = round256(body + 8), ping_bytes = round256((size_t)l.nleaves * 8), scratch_bytes = round256(k::codec_decode_scratch_words(d) * 4);
+            uint8_t *block = (uint8_t *)pool_alloc(body_bytes + 2 * ping_bytes + scratch_bytes);
+            job.host = (uint8_t *)host_alloc(body, &job.pinned);
+            if (!block || !job.host) {
+                pool_free(block);
+                if (job.host) host_free(job.host, job.pinned);
+                note_error(who, "out of memory");
+                return -1;
+            }
+            memcpy(job.host, (const uint8_t *)bytes + l.occupancy_offset, body);
+            d.colours = (const uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
+            d.tiles = l.tile_mode == 1 ? block + (l.tile_offset - l.occupancy_offset) : nullptr;
+            bool ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
+            if (ok) {
+                k::codec_decode(block, d, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
+                                (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
+                ok = hipGetLastError() == hipSuccess;
+            }
+            c.free_later(block);
+            if (!ok) {
+                (void)c.sync();
+                host_free(job.host, job.pinned);
+                hip_failed(hipGetLastError(), "octree decode", __FILE__, __LINE__);
+                return -1;
+            }
+            dst->mark_pending(c.stream);
+        }
+        auto *cloud = new cwipc_hip_pointcloud();
+        cloud->adopt_device(dst, l.timestamp, (float)cell);
+        job.cloud = cloud;
+        job.planes = dst;
+        std::lock_guard<std::mutex> lk(dec->lock);
+        dec->queue.push_back(job);
+        return 0;
+    });
+}
+
+extern "C" bool cwipc_hip_decoder_available(cwipc_hip_decoder *dec, bool wait) {
+    if (dec == nullptr) return false;
+    std::lock_guard<std::mutex> l(dec->lock);
+    if (dec->queue.empty()) return false;
+    const auto &planes = dec->queue.front().planes;
+    if (!planes || !planes->ready) return true;
+    if (wait) { planes->wait_host(); return true; }
+    const hipError_t e = hipEventQuery(planes->ready);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess;
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_decoder_get(cwipc_hip_decoder *dec) {
+    if (dec == nullptr) return nullptr;
+    std::lock_guard<std::mutex> l(dec->lock);
+    if (dec->queue.empty()) return nullptr;
+    cwipc_hip_decoder::Job job = dec->queue.front();
+    dec->queue.pop_front();
+    release_upload(job);
+    return job.cloud;
+}
+
+extern "C" bool cwipc_hip_decoder_eof(cwipc_hip_decoder *dec) {
+    if (dec == nullptr) return true;
+    std::lock_guard<std::mutex> l(dec->lock);
+    return dec->closed && dec->queue.empty();
+}
+
+extern "C" void cwipc_hip_decoder_close(cwipc_hip_decoder *dec) {
+    if (dec == nullptr) return;
+    std::lock_guard<std::mutex> l(dec->lock);
+    dec->closed = true;
+}
+
+extern "C" void cwipc_hip_decoder_free(cwipc_hip_decoder *dec) {
+    if (dec == nullptr) return;
+    for (auto &job : dec->queue) {
+        release_upload(job);
+        delete job.cloud;   // a result nobody took
+    }
+    delete dec;
+}

@@ -7,6 +7,7 @@
 //   synthetic.cpp   cwipc_synthetic source          (reference src/cwipc_synthetic.cpp)
 //   stubs.cpp       out-of-scope constructors that fail loudly
 //   filters.cpp     C entry points of the hot path, host orchestration
+//   codec.cpp       cwipc_hip_new_encoder / _encodergroup / _decoder: the octree codec (packets out, packets in)
 //   rgbd.cpp        cwipc_hip_from_rgbd, cwipc_hip_rgbd_rig_*: the RGB-D source end (images in, device-resident cloud out)
 //   kernels_*.hip   the HIP kernels (gfx950)
 #pragma once
@@ -524,6 +525,55 @@ void rgbd_temporal(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, c
 void rgbd_zsplat(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, unsigned long long *zbuf, hipStream_t s);
 void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const unsigned long long *zbuf, int splat, double margin,
                             hipStream_t s);
+
+// ---- kernels_codec.hip: the octree codec (RULE C: hip_ext.h; the arithmetic: codec_terms.hpp) ----
+// What the bounds leave on the device and the host reads back with nodes[]: the cube and the number of points that take part.
+struct CodecCube {
+    float mn[3];
+    uint32_t nfinite;
+    double side;
+};
+struct CodecLeafSum {
+    unsigned long long r, g, b;
+    uint32_t count, tile;
+};
+// One packet's body on the device, zeroed: occupancy (words; occupancy_bytes of them count), colours (colour_words words), the tile
+// plane (nleaves bytes), tile_stats (2 words); and the leaf sums (nleaves, zeroed).  depth_offset[L]: the first occupancy byte of depth L.
+struct CodecEmit {
+    int bits;
+    uint32_t nleaves;
+    uint64_t depth_offset[16];
+    uint64_t occupancy_bytes, colour_words;
+    uint32_t *occupancy, *colours, *tile_stats;
+    uint8_t *tiles;
+    CodecLeafSum *sums;
+};
+struct CodecDecode {
+    int bits, colour_bits, tile_value;
+    uint32_t nleaves;
+    uint32_t nodes[16];
+    float mn[3];
+    double cell;
+    uint64_t colour_words;
+    const uint32_t *colours;   // device, 4-byte aligned
+    const uint8_t *tiles;      // device, or nullptr: tile_value
+};
+size_t codec_blocks(size_t n);
+size_t codec_bounds_bytes(size_t n);
+// the cube of the points whose coordinates are all finite; partial: codec_bounds_bytes() of device memory
+void codec_cube(const DeviceSoA &src, void *partial, CodecCube *cube, hipStream_t s);
+// keys and index: 2 n entries each; the sorted halves are keys + n and index + n.  A point that is left out sorts behind the cube's nfinite others.
+bool codec_sort(const DeviceSoA &src, const CodecCube *cube, int bits, unsigned long long *keys, uint32_t *index, hipStream_t s);
+// counts: bits rows of codec_blocks(n) + 1 words; row L ends up as the workgroups' offsets at depth L and nodes[L], which also goes to
+// total_host[L] (pinned) below `tag`
+void codec_count_scan(const unsigned long long *sorted_keys, size_t n, const CodecCube *cube, int bits, uint32_t *counts, unsigned long long *total_host,
+                      uint32_t tag, hipStream_t s);
+// the body of a packet of e.bits <= sort_bits from keys sorted at sort_bits and their scanned counts
+void codec_emit(const unsigned long long *sorted_keys, const uint32_t *sorted_index, const DeviceSoA &src, const CodecCube *cube, int sort_bits,
+                const uint32_t *offsets, const CodecEmit &e, int colour_shift, hipStream_t s);
+size_t codec_decode_scratch_words(const CodecDecode &d);
+void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch, const DeviceSoA &dst,
+                  hipStream_t s);
 
 }  // namespace k
 

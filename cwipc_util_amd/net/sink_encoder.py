@@ -1,0 +1,203 @@
+"""A point cloud sink that compresses what it is fed and hands the packets to a raw sink.
+
+The interface of reference python/cwipc/net/sink_encoder.py (`cwipc_sink_encoder(sink, verbose, nodrop)` with `set_encoder_params`,
+`add_stream` through the raw sink, `feed`, `statistics`); written for this library's octree codec (cwipc_util_amd.codec), whose
+packets are NOT interoperable with cwipc_codec.  One encoder per tile x octree_bits x jpeg_quality, all in one encoder group, one
+stream of the raw sink per encoder, in that order.
+
+The raw sink is any object with `feed(packet, stream_index=...)` and, optionally, `add_stream(tile_index, tile_description,
+quality_description)`, `set_fourcc`, `start`, `stop`, `set_producer`, `statistics`; a plain list works too: it is filled with one list of
+packets per stream.
+
+Two ways to run it.  After `start()` a thread takes the clouds from a queue of two, as the reference does (a cloud that finds the
+queue full is dropped unless `nodrop`).  Without `start()`, `feed()` encodes on the calling thread and returns when the packets have
+been handed on: the GPU work needs no thread of its own to overlap with the caller.
+"""
+from __future__ import annotations
+
+import queue
+import threading
+import time
+from typing import Any, Dict, List, Optional, Sequence, Union
+
+from .. import codec
+from ..abstract import cwipc_pointcloud_abstract, cwipc_tileinfo_dict
+
+__all__ = ["cwipc_sink_encoder", "DEFAULT_OCTREE_BITS", "DEFAULT_JPEG_QUALITY"]
+
+DEFAULT_OCTREE_BITS = 9
+DEFAULT_JPEG_QUALITY = 85
+
+
+class _ListSink:
+    """A list as raw sink: entry i becomes the list of stream i's packets."""
+
+    def __init__(self, streams: List[Any]):
+        self.streams = streams
+
+    def add_stream(self, tile_index: int, tile_description: Any, quality_description: Any) -> int:
+        self.streams.append([])
+        return len(self.streams) - 1
+
+    def feed(self, packet: Union[bytes, bytearray], stream_index: int = 0) -> bool:
+        while len(self.streams) <= stream_index:
+            self.streams.append([])
+        self.streams[stream_index].append(bytes(packet))
+        return True
+
+
+def _intlist(value: Union[int, Sequence[int], None], default: List[int]) -> List[int]:
+    if value is None:
+        return default
+    if isinstance(value, int):
+        return [value]
+    return [int(v) for v in value]
+
+
+class _SinkEncoder:
+    FOURCC = "cwao"   # not the reference's "cwi1": the bitstream is another one
+    QUEUE_FULL_TIMEOUT = 0.001
+
+    def __init__(self, sink: Any, verbose: bool = False, nodrop: bool = False):
+        self.sink = _ListSink(sink) if isinstance(sink, list) else sink
+        if hasattr(self.sink, "set_fourcc"):
+            self.sink.set_fourcc(self.FOURCC)
+        self.verbose = verbose
+        self.nodrop = nodrop
+        self.producer: Any = None
+        self.tiledescriptions: List[cwipc_tileinfo_dict] = [{}]
+        self.octree_bits: List[int] = [DEFAULT_OCTREE_BITS]
+        self.jpeg_quality: List[int] = [DEFAULT_JPEG_QUALITY]
+        self.encoder_group: Optional[codec.cwipc_encodergroup_wrapper] = None
+        self.encoders: List[codec.cwipc_encoder_wrapper] = []
+        self.streams: List[int] = []
+        self.times_encode: List[float] = []
+        self.pointcounts: List[int] = []
+        self.packetsizes: List[int] = []
+        self.input_queue: "queue.Queue[Optional[cwipc_pointcloud_abstract]]" = queue.Queue(maxsize=2)
+        self.thread: Optional[threading.Thread] = None
+        self.stopped = False
+
+    def set_encoder_params(self, tiles: Optional[List[cwipc_tileinfo_dict]], octree_bits: Union[int, Sequence[int], None] = None,
+                           jpeg_quality: Union[int, Sequence[int], None] = None) -> None:
+        assert self.encoder_group is None, "set_encoder_params comes before the first cloud"
+        self.tiledescriptions = tiles if tiles else [{}]
+        self.octree_bits = _intlist(octree_bits, self.octree_bits)
+        self.jpeg_quality = _intlist(jpeg_quality, self.jpeg_quality)
+
+    def add_stream(self, tile_index: int, tile_description: Any, quality_description: Dict[str, int]) -> int:
+        """A further stream of the raw sink (the encoders' own streams are added when the encoders are made)."""
+        if hasattr(self.sink, "add_stream"):
+            return self.sink.add_stream(tile_index, tile_description, quality_description)
+        return len(self.streams)
+
+    def set_producer(self, producer: Any) -> None:
+        self.producer = producer
+        if hasattr(self.sink, "set_producer"):
+            self.sink.set_producer(producer)
+
+    def _init_encoders(self) -> None:
+        if self.encoder_group is not None:
+            return
+        self.encoder_group = codec.cwipc_new_encodergroup()
+        for tile_index, tile in enumerate(self.tiledescriptions):
+            mask = int(tile.get("cameraMask", 0))
+            for bits in self.octree_bits:
+                for quality in self.jpeg_quality:
+                    params = codec.cwipc_encoder_params(False, 1, 1.0, bits, quality, 16, mask, 0)
+                    self.encoders.append(self.encoder_group.addencoder(params=params))
+                    self.streams.append(self.add_stream(tile_index, tile, dict(octree_bits=bits, jpeg_quality=quality)))
+                    if self.verbose:
+                        print(f"encoder: stream {self.streams[-1]}: tile={tile_index} mask={mask} octree_bits={bits} jpeg_quality={quality}")
+
+    def _encode(self, pc: cwipc_pointcloud_abstract) -> None:
+        self._init_encoders()
+        assert self.encoder_group is not None
+        self.pointcounts.append(pc.count())
+        t0 = time.time()
+        self.encoder_group.feed(pc)
+        packets = []
+        for enc in self.encoders:
+            if not enc.available(True):
+                raise RuntimeError("encoder: no packet after feed")
+            packets.append(enc.get_bytes())
+        self.times_encode.append(time.time() - t0)
+        self.packetsizes.extend(len(p) for p in packets)
+        if len(packets) == 1:
+            self.sink.feed(packets[0])
+        else:
+            for stream, packet in zip(self.streams, packets):
+                self.sink.feed(packet, stream_index=stream)
+
+    def start(self) -> None:
+        self._init_encoders()
+        self.thread = threading.Thread(target=self._run, name="cwipc_util._Sink_Encoder")
+        self.thread.start()
+        if hasattr(self.sink, "start"):
+            self.sink.start()
+
+    def stop(self) -> None:
+        self.stopped = True
+        if self.thread is not None:
+            try:
+                self.input_queue.put(None, block=self.nodrop)
+            except queue.Full:
+                pass
+            self.thread.join()
+            self.thread = None
+        if hasattr(self.sink, "stop"):
+            self.sink.stop()
+
+    def is_alive(self) -> bool:
+        return not self.stopped
+
+    def _run(self) -> None:
+        while True:
+            try:
+                pc = self.input_queue.get(timeout=0.1)
+            except queue.Empty:
+                if self.stopped:
+                    break
+                continue
+            if pc is None:
+                break
+            self._encode(pc)
+
+    def feed(self, pc: cwipc_pointcloud_abstract) -> None:
+        if self.thread is None:
+            self._encode(pc)
+            return
+        try:
+            if self.nodrop:
+                self.input_queue.put(pc)
+            else:
+                self.input_queue.put(pc, timeout=self.QUEUE_FULL_TIMEOUT)
+        except queue.Full:
+            if self.verbose:
+                print("encoder: queue full, cloud dropped")
+
+    def free(self) -> None:
+        if self.encoder_group is not None:
+            self.encoder_group.free()
+        self.encoder_group = None
+        self.encoders = []
+
+    def statistics(self) -> None:
+        self._print1stat("encode_duration", self.times_encode)
+        self._print1stat("encode_count", self.pointcounts, True)
+        self._print1stat("packetsize", self.packetsizes, True)
+        if hasattr(self.sink, "statistics"):
+            self.sink.statistics()
+
+    @staticmethod
+    def _print1stat(name: str, values: Sequence[Union[int, float]], is_int: bool = False) -> None:
+        if not values:
+            print(f"encoder: {name}: count=0")
+            return
+        lo, hi = (f"{min(values):d}", f"{max(values):d}") if is_int else (f"{min(values):.3f}", f"{max(values):.3f}")
+        print(f"encoder: {name}: count={len(values)}, average={sum(values) / len(values):.3f}, min={lo}, max={hi}")
+
+
+def cwipc_sink_encoder(sink: Any, verbose: bool = False, nodrop: bool = False) -> _SinkEncoder:
+    """A sink that compresses point clouds with this library's octree codec and forwards the packets to the raw sink."""
+    return _SinkEncoder(sink, verbose=verbose, nodrop=nodrop)

@@ -57,6 +57,13 @@ __all__ = [
     'cwipc_hip_rgbd_sensor', 'cwipc_hip_rgbd_frame', 'cwipc_hip_rgbd_prep', 'cwipc_hip_rgbd_rig_create', 'cwipc_hip_rgbd_rig_free',
     'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_occlusion', 'cwipc_hip_rgbd_rig_grab_occluded', 'cwipc_hip_rgbd_depthfilter',
     'cwipc_hip_rgbd_rig_grab_filtered', 'cwipc_hip_rgbd_rig_reset_history', 'cwipc_hip_rgbd_rig_history', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
+    # the octree codec (cwipc_util_amd.codec has the names the reference's callers use)
+    'cwipc_hip_encoder_params', 'cwipc_hip_codec_info', 'cwipc_hip_codec_packet_info',
+    'cwipc_hip_new_encoder', 'cwipc_hip_encoder_free', 'cwipc_hip_encoder_feed', 'cwipc_hip_encoder_available', 'cwipc_hip_encoder_get_encoded_size',
+    'cwipc_hip_encoder_copy_data', 'cwipc_hip_encoder_at_gop_boundary', 'cwipc_hip_encoder_eof', 'cwipc_hip_encoder_close',
+    'cwipc_hip_new_encodergroup', 'cwipc_hip_encodergroup_addencoder', 'cwipc_hip_encodergroup_feed', 'cwipc_hip_encodergroup_close', 'cwipc_hip_encodergroup_free',
+    'cwipc_hip_new_decoder', 'cwipc_hip_decoder_feed', 'cwipc_hip_decoder_available', 'cwipc_hip_decoder_get', 'cwipc_hip_decoder_eof', 'cwipc_hip_decoder_close',
+    'cwipc_hip_decoder_free',
 ]
 
 # reference util.py:86, 346, 348
@@ -279,6 +286,28 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_rgbd_rig_ray_table': ([_c.c_void_p, _c.c_int], _c.POINTER(_c.c_double)),
     'cwipc_hip_rgbd_rig_map2d3d': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_rgbd_rig_mapcolordepth': ([_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int)], _c.c_int),
+    'cwipc_hip_new_encoder': ([_c.c_void_p, _ERR], _c.c_void_p),
+    'cwipc_hip_encoder_free': ([_c.c_void_p], None),
+    'cwipc_hip_encoder_feed': ([_c.c_void_p, cwipc_pointcloud_p], _c.c_int),
+    'cwipc_hip_encoder_available': ([_c.c_void_p, _c.c_bool], _c.c_bool),
+    'cwipc_hip_encoder_get_encoded_size': ([_c.c_void_p], _c.c_size_t),
+    'cwipc_hip_encoder_copy_data': ([_c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_bool),
+    'cwipc_hip_encoder_at_gop_boundary': ([_c.c_void_p], _c.c_bool),
+    'cwipc_hip_encoder_eof': ([_c.c_void_p], _c.c_bool),
+    'cwipc_hip_encoder_close': ([_c.c_void_p], None),
+    'cwipc_hip_new_encodergroup': ([_ERR], _c.c_void_p),
+    'cwipc_hip_encodergroup_addencoder': ([_c.c_void_p, _c.c_void_p, _ERR], _c.c_void_p),
+    'cwipc_hip_encodergroup_feed': ([_c.c_void_p, cwipc_pointcloud_p], _c.c_int),
+    'cwipc_hip_encodergroup_close': ([_c.c_void_p], None),
+    'cwipc_hip_encodergroup_free': ([_c.c_void_p], None),
+    'cwipc_hip_new_decoder': ([_ERR], _c.c_void_p),
+    'cwipc_hip_decoder_feed': ([_c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_decoder_available': ([_c.c_void_p, _c.c_bool], _c.c_bool),
+    'cwipc_hip_decoder_get': ([_c.c_void_p], cwipc_pointcloud_p),
+    'cwipc_hip_decoder_eof': ([_c.c_void_p], _c.c_bool),
+    'cwipc_hip_decoder_close': ([_c.c_void_p], None),
+    'cwipc_hip_decoder_free': ([_c.c_void_p], None),
+    'cwipc_hip_codec_packet_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -1976,6 +2005,148 @@ def cwipc_hip_copy_device_aos(pc: cwipc_pointcloud_wrapper, dev_ptr: int, size: 
     if n < 0:
         raise CwipcError("cwipc_hip_copy_device_aos failed")
     return n
+
+
+# ---------------------------------------------------------------------------
+# the octree codec's C boundary (hip_ext.h: RULE C).  Its packets are NOT interoperable with cwipc_codec; cwipc_util_amd.codec
+# wraps these handles in the classes the reference's callers use.
+# ---------------------------------------------------------------------------
+class cwipc_hip_encoder_params(ctypes.Structure):
+    """The reference's cwipc_encoder_params, fields in the order its callers pass them."""
+    _fields_ = [("do_inter_frame", ctypes.c_bool), ("gop_size", ctypes.c_int), ("exp_factor", ctypes.c_float), ("octree_bits", ctypes.c_int),
+                ("jpeg_quality", ctypes.c_int), ("macroblock_size", ctypes.c_int), ("tilenumber", ctypes.c_int), ("voxelsize", ctypes.c_float)]
+
+
+class cwipc_hip_codec_info(ctypes.Structure):
+    """A valid packet's header and where its parts lie."""
+    _fields_ = [("timestamp", ctypes.c_uint64), ("nleaves", ctypes.c_uint32), ("octree_bits", ctypes.c_int32), ("colour_bits", ctypes.c_int32),
+                ("tile_mode", ctypes.c_int32), ("tile_value", ctypes.c_int32), ("min", ctypes.c_float * 3), ("side", ctypes.c_double),
+                ("nodes", ctypes.c_uint32 * 16), ("occupancy_offset", ctypes.c_uint64), ("colour_offset", ctypes.c_uint64),
+                ("tile_offset", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64)]
+
+
+def _codec_handle(name: str, rv: Any, errorString: ctypes.c_char_p) -> int:
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return rv
+    raise CwipcError(f"{name}: nothing created, but no specific error returned from C library")
+
+
+def _codec_last_error(name: str) -> CwipcError:
+    detail = cwipc_util_dll_load().cwipc_hip_last_error()
+    return CwipcError(f"{name} failed" + (f": {detail.decode('utf8')}" if detail else ""))
+
+
+def cwipc_hip_new_encoder(params: cwipc_hip_encoder_params) -> int:
+    """An encoder handle; CwipcError with the library's message for a parameter set it refuses."""
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_new_encoder(ctypes.addressof(params), ctypes.byref(errorString))
+    return _codec_handle('cwipc_hip_new_encoder', rv, errorString)
+
+
+def cwipc_hip_encoder_free(enc: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_encoder_free(enc)
+
+
+def cwipc_hip_encoder_feed(enc: int, pc: cwipc_pointcloud_wrapper) -> None:
+    if cwipc_util_dll_load().cwipc_hip_encoder_feed(enc, pc.as_cwipc_p()) != 0:
+        raise _codec_last_error('cwipc_hip_encoder_feed')
+
+
+def cwipc_hip_encoder_available(enc: int, wait: bool) -> bool:
+    return bool(cwipc_util_dll_load().cwipc_hip_encoder_available(enc, wait))
+
+
+def cwipc_hip_encoder_get_encoded_size(enc: int) -> int:
+    return cwipc_util_dll_load().cwipc_hip_encoder_get_encoded_size(enc)
+
+
+def cwipc_hip_encoder_copy_data(enc: int, buffer: Any, size: int) -> bool:
+    """The oldest packet into a writable ctypes buffer of at least `size` bytes; it leaves the queue."""
+    return bool(cwipc_util_dll_load().cwipc_hip_encoder_copy_data(enc, ctypes.addressof(buffer), size))
+
+
+def cwipc_hip_encoder_at_gop_boundary(enc: int) -> bool:
+    return bool(cwipc_util_dll_load().cwipc_hip_encoder_at_gop_boundary(enc))
+
+
+def cwipc_hip_encoder_eof(enc: int) -> bool:
+    return bool(cwipc_util_dll_load().cwipc_hip_encoder_eof(enc))
+
+
+def cwipc_hip_encoder_close(enc: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_encoder_close(enc)
+
+
+def cwipc_hip_new_encodergroup() -> int:
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_new_encodergroup(ctypes.byref(errorString))
+    return _codec_handle('cwipc_hip_new_encodergroup', rv, errorString)
+
+
+def cwipc_hip_encodergroup_addencoder(group: int, params: cwipc_hip_encoder_params) -> int:
+    """A new encoder that belongs to the group (and is freed with it)."""
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_encodergroup_addencoder(group, ctypes.addressof(params), ctypes.byref(errorString))
+    return _codec_handle('cwipc_hip_encodergroup_addencoder', rv, errorString)
+
+
+def cwipc_hip_encodergroup_feed(group: int, pc: cwipc_pointcloud_wrapper) -> None:
+    if cwipc_util_dll_load().cwipc_hip_encodergroup_feed(group, pc.as_cwipc_p()) != 0:
+        raise _codec_last_error('cwipc_hip_encodergroup_feed')
+
+
+def cwipc_hip_encodergroup_close(group: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_encodergroup_close(group)
+
+
+def cwipc_hip_encodergroup_free(group: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_encodergroup_free(group)
+
+
+def cwipc_hip_new_decoder() -> int:
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_new_decoder(ctypes.byref(errorString))
+    return _codec_handle('cwipc_hip_new_decoder', rv, errorString)
+
+
+def cwipc_hip_decoder_feed(dec: int, packet: Union[bytes, bytearray, memoryview]) -> None:
+    """CwipcError with the validator's reason for a packet that is not valid: nothing reaches the device then."""
+    data = bytes(packet)
+    if cwipc_util_dll_load().cwipc_hip_decoder_feed(dec, data, len(data)) != 0:
+        raise _codec_last_error('cwipc_hip_decoder_feed')
+
+
+def cwipc_hip_decoder_available(dec: int, wait: bool) -> bool:
+    return bool(cwipc_util_dll_load().cwipc_hip_decoder_available(dec, wait))
+
+
+def cwipc_hip_decoder_get(dec: int) -> Optional[cwipc_pointcloud_wrapper]:
+    rv = cwipc_util_dll_load().cwipc_hip_decoder_get(dec)
+    return cwipc_pointcloud_wrapper(rv) if rv else None
+
+
+def cwipc_hip_decoder_eof(dec: int) -> bool:
+    return bool(cwipc_util_dll_load().cwipc_hip_decoder_eof(dec))
+
+
+def cwipc_hip_decoder_close(dec: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_decoder_close(dec)
+
+
+def cwipc_hip_decoder_free(dec: int) -> None:
+    cwipc_util_dll_load().cwipc_hip_decoder_free(dec)
+
+
+def cwipc_hip_codec_packet_info(packet: Union[bytes, bytearray, memoryview]) -> cwipc_hip_codec_info:
+    """The validity test and the header of a packet, on the host (no GPU needed); CwipcError with the reason for one that is not valid."""
+    data = bytes(packet)
+    info = cwipc_hip_codec_info()
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_codec_packet_info(data, len(data), ctypes.addressof(info), ctypes.byref(errorString))
+    if rv != 0:
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_packet_info: not a valid packet")
+    return info
 
 
 class cwipc_hip_profile:

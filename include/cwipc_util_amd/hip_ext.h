@@ -612,6 +612,95 @@ _CWIPC_UTIL_EXPORT const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rg
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_map2d3d(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int d, float out[3]);
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int out[2]);
 
+/* ---- the octree codec: encoder, encoder group, decoder (csrc/codec.cpp, csrc/kernels_codec.hip) ----
+ * The packets of this codec are NOT interoperable with cwipc_codec: the interface is the reference's (cwipc_new_encoder,
+ * cwipc_new_encodergroup, cwipc_new_decoder as python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is
+ * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, entropy coding of the occupancy bytes,
+ * transform or JPEG colour coding, inter-frame coding, per-leaf point counts in the packet, sockets.
+ *
+ * RULE C.  The arithmetic is csrc/codec_terms.hpp (host and device compile it), tests/codec_model.py its numpy restatement.  All
+ * arithmetic is float64 unless stated otherwise, every operation rounded on its own.
+ *  Input.   tilenumber != 0: the cloud is first filtered exactly as cwipc_tilefilter(pc, tilenumber) does; voxelsize > 0: then
+ *           downsampled exactly as cwipc_downsample(pc, voxelsize) does; then every point with a non-finite coordinate is left out.
+ *           What remains, in input order, is P.  An empty P is legal.
+ *  Cube.    min_a, max_a: the float32 extremes of P per axis (a zero minimum is +0).  side = max_a(fl64(max_a - min_a)); side == 0: side := 1.
+ *  Cell.    For b = octree_bits in 1..16:  u_a = fl64(fl64(p_a - min_a) / side);  q_a = min(2^b - 1, (int) floor(u_a * 2^b)) (the
+ *           product is exact).  Hence q_a(b - 1) == q_a(b) >> 1 for every point, at the clamp too (p <= max gives u <= 1).
+ *  Key.     3b bits, most significant triple first; within a triple x, y, z with x most significant.  Child index = the triple, 0..7.
+ *  Leaves.  The distinct keys in ascending order.  Per leaf over its points: count; per channel m = (sum + count / 2) / count in
+ *           integers; tile = OR of the points' tiles.
+ *  Colour.  jpeg_quality q gives a shift s: q >= 90: 0; 75..89: 1; 50..74: 2; 25..49: 3; below 25: 4.  Stored: m >> s in 8 - s bits.
+ *           Decoded: min(255, (v << s) + ((1 << s) >> 1)).
+ *  Packet, little endian, its total length exact:
+ *      0  u32 magic, the bytes c w a o        4  u32 version = 1            8  u64 timestamp of the cloud fed
+ *     16  u32 nleaves                        20  u8 octree_bits            21  u8 colour bits (8 - s)
+ *     22  u8 tile_mode: 0 = all leaves share tile_value, 1 = tile plane present
+ *     23  u8 tile_value (0 when mode 1 or nleaves == 0)
+ *     24  f32 min_x, min_y, min_z (0 when nleaves == 0)     36  u32 0      40  f64 side (1 when nleaves == 0)
+ *     48  u32 nodes[b]: nodes[L] = number of distinct key prefixes of L + 1 triples; nodes[b - 1] == nleaves; all 0 when nleaves == 0
+ *     then the occupancy bytes, depth 0 (the root, 1 byte) to depth b - 1, the nodes of a depth in ascending prefix order, bit c set
+ *          iff child c exists: 1 + nodes[0] + ... + nodes[b - 2] bytes, absent when nleaves == 0, padded with zeros to a multiple of 4;
+ *     then the colours: per leaf r, g, b of 8 - s bits each, leaf-major, packed LSB first into bytes, padded with zeros to a multiple of 4;
+ *     then the tile plane: nleaves bytes, only when tile_mode == 1.
+ *  Decoding.  One point per leaf in key order: cell = side / 2^b; p_a = (float)(fl64(min_a) + fl64(fl64(q_a + 0.5) * cell)); the colour
+ *           by the colour rule, the tile from the tile byte; the cloud's timestamp is the header's, its cellsize (float) cell.
+ *  Parameters.  macroblock_size is accepted and ignored.  do_inter_frame == true, gop_size != 1, exp_factor != 1.0, octree_bits outside
+ *           1..16 and jpeg_quality outside 0..100 are refused at construction (errorMessage plus NULL).
+ *  Validity.  A packet is valid iff magic, version and ranges are right; nodes[0] <= 8 and nodes[L + 1] <= 8 nodes[L]; no occupancy
+ *           byte is 0; the popcounts of depth L sum to nodes[L] (for the last depth: nleaves); padding is 0; the length is exact.
+ *           Validation is host code, reads the packet once and runs BEFORE anything is launched or allocated on the device.
+ * Results queue first-in first-out per encoder and decoder.  feed returns with the work in flight on the calling thread's stream;
+ * available(false) polls, available(true) waits.  No exception crosses this boundary. */
+typedef struct cwipc_hip_encoder_params {
+    bool do_inter_frame;     /* must be false */
+    int gop_size;            /* must be 1 */
+    float exp_factor;        /* must be 1.0 */
+    int octree_bits;         /* 1..16 */
+    int jpeg_quality;        /* 0..100: the colour shift */
+    int macroblock_size;     /* accepted and ignored */
+    int tilenumber;          /* 0: every point */
+    float voxelsize;         /* > 0: cwipc_downsample first */
+} cwipc_hip_encoder_params;
+typedef struct cwipc_hip_encoder cwipc_hip_encoder;
+typedef struct cwipc_hip_encodergroup cwipc_hip_encodergroup;
+typedef struct cwipc_hip_decoder cwipc_hip_decoder;
+_CWIPC_UTIL_EXPORT cwipc_hip_encoder *cwipc_hip_new_encoder(const cwipc_hip_encoder_params *params, char **errorMessage);
+_CWIPC_UTIL_EXPORT void cwipc_hip_encoder_free(cwipc_hip_encoder *enc);
+_CWIPC_UTIL_EXPORT int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *pc);        /* 0 ok, -1 error (logged) */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait);
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc);               /* of the oldest result; 0: none */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size);   /* takes the oldest result */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc);                   /* always true */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_eof(cwipc_hip_encoder *enc);                               /* closed and nothing queued */
+_CWIPC_UTIL_EXPORT void cwipc_hip_encoder_close(cwipc_hip_encoder *enc);
+_CWIPC_UTIL_EXPORT cwipc_hip_encodergroup *cwipc_hip_new_encodergroup(char **errorMessage);
+/* The new encoder belongs to the group (freed with it).  feed: every encoder of the group receives what it would deliver alone, byte
+ * for byte; encoders with equal (tilenumber, voxelsize) share one filtered cloud and one sort, made at their largest octree_bits. */
+_CWIPC_UTIL_EXPORT cwipc_hip_encoder *cwipc_hip_encodergroup_addencoder(cwipc_hip_encodergroup *group, const cwipc_hip_encoder_params *params,
+                                                                        char **errorMessage);
+_CWIPC_UTIL_EXPORT int cwipc_hip_encodergroup_feed(cwipc_hip_encodergroup *group, cwipc_pointcloud *pc);
+_CWIPC_UTIL_EXPORT void cwipc_hip_encodergroup_close(cwipc_hip_encodergroup *group);
+_CWIPC_UTIL_EXPORT void cwipc_hip_encodergroup_free(cwipc_hip_encodergroup *group);
+_CWIPC_UTIL_EXPORT cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage);
+/* 0 ok; -1 and the reason in cwipc_hip_last_error() for a packet that is not valid (nothing launched, nothing allocated) or a device failure */
+_CWIPC_UTIL_EXPORT int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes, size_t len);
+_CWIPC_UTIL_EXPORT bool cwipc_hip_decoder_available(cwipc_hip_decoder *dec, bool wait);
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_decoder_get(cwipc_hip_decoder *dec);                  /* device-resident; NULL: none */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_decoder_eof(cwipc_hip_decoder *dec);
+_CWIPC_UTIL_EXPORT void cwipc_hip_decoder_close(cwipc_hip_decoder *dec);
+_CWIPC_UTIL_EXPORT void cwipc_hip_decoder_free(cwipc_hip_decoder *dec);
+/* A packet's header after the validity test, without a GPU: 0 and *info filled, or -1 and the reason in *errorMessage. */
+typedef struct cwipc_hip_codec_info {
+    uint64_t timestamp;
+    uint32_t nleaves;
+    int32_t octree_bits, colour_bits, tile_mode, tile_value;
+    float min[3];
+    double side;
+    uint32_t nodes[16];
+    uint64_t occupancy_offset, colour_offset, tile_offset, total_bytes;
+} cwipc_hip_codec_info;
+_CWIPC_UTIL_EXPORT int cwipc_hip_codec_packet_info(const void *bytes, size_t len, cwipc_hip_codec_info *info, char **errorMessage);
+
 /* ---- intermediate results for parity tests ---- */
 /* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
  * pixel; 0 ok, -1 error (the image and parameter checks of cwipc_hip_detect_markers). */
