@@ -95,6 +95,22 @@ def encode(pts, octree_bits, jpeg_quality, timestamp=0):
         stored.append(((total + count // 2) // count) >> s)
     tiles = np.zeros(n, dtype=np.uint8)
     np.bitwise_or.at(tiles, inverse, P['tile'])
+    return build_packet(leaf_keys, np.stack(stored, axis=1), tiles, mn, side, b, 8 - s, timestamp)
+
+
+def build_packet(leaf_keys, stored_colours, tiles, mn, side, bits, colour_bits, timestamp, tile_mode=None):
+    """The packet of a tree given by its leaves: `leaf_keys` ascending and distinct (at least one), `stored_colours` [n, 3] as the
+    packet stores them (below 2^colour_bits), `tiles` [n].  `mn` goes into the header as the float32 bits it has (a -0.0 stays one).
+    tile_mode None: the encoder's choice (0 when every leaf has the same tile); 0: the tiles must be equal; 1: a tile plane, whatever
+    it holds.  Trees that no cloud produces are made this way, for the decoder."""
+    b, cb = int(bits), int(colour_bits)
+    leaf_keys = np.asarray(leaf_keys, dtype=np.uint64).reshape(-1)
+    n = len(leaf_keys)
+    stored = np.asarray(stored_colours, dtype=np.int64).reshape(n, 3)
+    tiles = np.asarray(tiles, dtype=np.uint8).reshape(n)
+    mn = np.asarray(mn, dtype=np.float32).reshape(3)
+    assert 1 <= b <= 16 and 4 <= cb <= 8 and n >= 1 and (n == 1 or (leaf_keys[1:] > leaf_keys[:-1]).all())
+    assert int(leaf_keys[-1]) < (1 << (3 * b)) and stored.min() >= 0 and stored.max() < (1 << cb)
     # nodes[L] and the occupancy bytes, depth by depth
     nodes, occupancy = [], bytearray()
     for depth in range(b):
@@ -106,13 +122,15 @@ def encode(pts, octree_bits, jpeg_quality, timestamp=0):
         occupancy += byte.tobytes()
     assert len(occupancy) == 1 + sum(nodes[:-1]) and nodes[-1] == n
     occupancy += bytes(pad4(len(occupancy)) - len(occupancy))
-    cb = 8 - s
-    colours = pack_bits(np.stack(stored, axis=1).reshape(-1), cb)
+    colours = pack_bits(stored.reshape(-1), cb)
     colours += bytes(pad4(len(colours)) - len(colours))
     uniform = bool((tiles == tiles[0]).all())
-    header = struct.pack("<4sIQIBBBB3fId", MAGIC, 1, timestamp, n, b, cb, 0 if uniform else 1, int(tiles[0]) if uniform else 0,
-                         float(mn[0]), float(mn[1]), float(mn[2]), 0, side)
-    return header + struct.pack("<%dI" % b, *nodes) + bytes(occupancy) + colours + (b"" if uniform else tiles.tobytes())
+    if tile_mode is None:
+        tile_mode = 0 if uniform else 1
+    assert tile_mode == 1 or (tile_mode == 0 and uniform)
+    header = struct.pack("<4sIQIBBBB", MAGIC, 1, timestamp, n, b, cb, tile_mode, 0 if tile_mode else int(tiles[0])) + mn.astype('<f4').tobytes() + \
+        struct.pack("<Id", 0, side)
+    return header + struct.pack("<%dI" % b, *nodes) + bytes(occupancy) + colours + (tiles.tobytes() if tile_mode else b"")
 
 
 def parse(packet):
@@ -197,7 +215,8 @@ def decode(packet):
             for a in range(3):
                 q[:, a] = (q[:, a] << 1) | ((triple >> (2 - a)) & 1)
         mn = info["min"].astype(np.float64)
-        xyz = (mn + (q.astype(np.float64) + 0.5) * cell).astype(np.float32)
+        with np.errstate(over="ignore"):             # a side above float32's range: the rule's (float) gives infinity, and so does this
+            xyz = (mn + (q.astype(np.float64) + 0.5) * cell).astype(np.float32)
         out['x'], out['y'], out['z'] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
         vals = unpack_bits(p[info["colour_offset"]:info["colour_offset"] + info["colour_bytes"]], 3 * n, cb).reshape(n, 3)
         dec = np.minimum(255, (vals << s) + ((1 << s) >> 1)).astype(np.uint8)
@@ -206,7 +225,8 @@ def decode(packet):
             out['tile'] = np.frombuffer(p, dtype=np.uint8, count=n, offset=info["tile_offset"])
         else:
             out['tile'] = info["tile_value"]
-    return out, info["timestamp"], np.float32(cell)
+    with np.errstate(over="ignore", under="ignore"):
+        return out, info["timestamp"], np.float32(cell)
 
 
 def make_cloud(xyz, rgb=None, tile=None):
@@ -225,3 +245,54 @@ def random_cloud(rng, n, scale=1.0, offset=(0.0, 0.0, 0.0), tiles=(1, 2, 4)):
     pts = make_cloud(rng.uniform(-1.0, 1.0, (n, 3)) * scale + np.asarray(offset), rng.integers(0, 256, (n, 3)))
     pts['tile'] = rng.choice(np.asarray(tiles, dtype=np.uint8), n)
     return pts
+
+
+# ---------------------------------------------------------------------------
+# test material: clouds aimed at the cell boundaries, and the near misses of the cell rule they must tell from it
+# ---------------------------------------------------------------------------
+def boundary_cloud(mn, mx, bits, rng):
+    """A cloud whose cube is [mn, mx]^3 (mn < mx, both float32) and whose coordinates lie on the cell boundaries of `bits` bits, as
+    closely as float32 allows: for every boundary k in 0 .. 2^bits (4096 of the inner ones, drawn by rng, plus both ends when there
+    are more than 8192) the float32 nearest to mn + k side / 2^bits, worked out in extended precision, and its two float32
+    neighbours, those inside [mn, mx].  Every axis gets all candidates, each in an order of its own; colours and tiles are random;
+    the last two points are the corners that pin the cube."""
+    mn, mx = np.float32(mn), np.float32(mx)
+    assert mn < mx
+    total = 1 << int(bits)
+    if total > 8192:
+        k = np.concatenate([[0, total], 1 + rng.choice(total - 1, 4096, replace=False)])
+    else:
+        k = np.arange(total + 1)
+    k = np.sort(k).astype(np.longdouble)
+    side = np.longdouble(mx) - np.longdouble(mn)
+    centre = (np.longdouble(mn) + k * side / np.longdouble(total)).astype(np.float32)
+    cand = np.unique(np.concatenate([np.nextafter(centre, np.float32(-np.inf)), centre, np.nextafter(centre, np.float32(np.inf))]))
+    cand = cand[(cand >= mn) & (cand <= mx)]
+    xyz = np.stack([cand[rng.permutation(len(cand))] for _ in range(3)], axis=1)
+    xyz = np.concatenate([xyz, [[mn, mn, mn], [mx, mx, mx]]]).astype(np.float32)
+    pts = make_cloud(xyz, rng.integers(0, 256, (len(xyz), 3)))
+    pts['tile'] = rng.choice(np.array([1, 2, 4], dtype=np.uint8), len(xyz))
+    return pts
+
+
+CELL_VARIANTS = ("recip", "scale", "sub32", "div32")
+
+
+def cells_variant(P, mn, side, bits, name):
+    """cells() as a kernel might compute it by mistake.  recip: (p - min) * (1 / side); scale: (p - min) * (2^b / side), one factor;
+    sub32: the subtraction in float32; div32: the subtraction and the division in float32.  None of them is the rule: the tests'
+    inputs must be able to tell each of them from it."""
+    xyz32 = np.stack([P['x'], P['y'], P['z']], axis=1).astype(np.float32)
+    mn32, side, two_b = np.asarray(mn, dtype=np.float32), np.float64(side), np.float64(1 << bits)
+    d = xyz32.astype(np.float64) - mn32.astype(np.float64)
+    if name == "recip":
+        f = (d * (np.float64(1.0) / side)) * two_b
+    elif name == "scale":
+        f = d * (two_b / side)
+    elif name == "sub32":
+        f = ((xyz32 - mn32).astype(np.float64) / side) * two_b
+    elif name == "div32":
+        f = ((xyz32 - mn32) / np.float32(side)).astype(np.float64) * two_b
+    else:
+        raise ValueError(name)
+    return np.minimum((1 << bits) - 1, np.floor(f).astype(np.int64))

@@ -191,3 +191,105 @@ def test_packet_info_of_the_hand_written_packet(cwipc):
     assert info["min"] == (0.0, 0.0, 0.0)
     with pytest.raises(cwipc.CwipcError, match="magic"):
         codec.packet_info(b"cpcd" + HAND_PACKET[4:])
+
+
+# ---------------------------------------------------------------------------
+# cell boundaries
+# ---------------------------------------------------------------------------
+# The cubes of the boundary clouds (0.1f is the float32 nearest to 0.1).  A near miss of the cell rule differs from it only for a
+# point within an ulp of a cell boundary, and which near miss shows depends on the cube: with min = 0 the subtraction is exact in
+# any precision, so [0, 49] shows only the reciprocal and the folded factor (49 is no power of two), [-1.5, 1.5] the float32
+# subtraction, [0, 0.1f] the float32 division alone, [0.1f, 1] both float32 steps with a minimum that is no short binary fraction.
+BOUNDARY_CUBES = ((0.0, 49.0), (-1.5, 1.5), (0.0, float(np.float32(0.1))), (float(np.float32(0.1)), 1.0))
+_boundary_clouds = {}
+
+
+def boundary_cloud(cube, bits):
+    """cm.boundary_cloud of BOUNDARY_CUBES[cube] at `bits`, made once and shared by the CPU, host-program and GPU tests: read only."""
+    key = (cube, bits)
+    if key not in _boundary_clouds:
+        mn, mx = BOUNDARY_CUBES[cube]
+        pts = cm.boundary_cloud(mn, mx, bits, np.random.default_rng(7000 + 100 * cube + bits))
+        pts.setflags(write=False)
+        _boundary_clouds[key] = pts
+    return _boundary_clouds[key]
+
+
+@pytest.mark.parametrize("bits", [1, 4, 9, 16])
+@pytest.mark.parametrize("cube", range(len(BOUNDARY_CUBES)))
+def test_boundary_clouds_are_what_they_say(cube, bits):
+    """The cube is the one asked for, both end cells are hit on every axis, and every inner boundary has a point on each side of it
+    (4 and 9 bits, where every boundary is taken)."""
+    pts = boundary_cloud(cube, bits)
+    mn, side = cm.cube(pts)
+    lo, hi = np.float32(BOUNDARY_CUBES[cube][0]), np.float32(BOUNDARY_CUBES[cube][1])
+    assert mn.tobytes() == np.array([lo, lo, lo], dtype=np.float32).tobytes() and side == float(np.float64(hi) - np.float64(lo))
+    q = cm.cells(pts, mn, side, bits)
+    assert q.min(axis=0).tolist() == [0, 0, 0] and q.max(axis=0).tolist() == [(1 << bits) - 1] * 3
+    if bits in (4, 9):
+        for a in range(3):
+            assert len(np.unique(q[:, a])) == 1 << bits
+        assert len(pts) == 3 * ((1 << bits) + 1) - 2 + 2      # three per boundary, less the two outside the cube, plus the corners
+
+
+@pytest.mark.parametrize("variant", cm.CELL_VARIANTS)
+@pytest.mark.parametrize("bits", [4, 9, 16])
+def test_boundary_clouds_tell_every_near_miss_from_the_rule(bits, variant):
+    """A condition on the test inputs, not a measurement: for each near miss of the cell rule at least one of the cubes has 5 or more
+    candidate coordinates whose cell it changes (counted on the x axis, which holds every candidate once).  Uniform random points do
+    not deliver this: see test_random_clouds_do_not."""
+    changed = []
+    for cube in range(len(BOUNDARY_CUBES)):
+        pts = boundary_cloud(cube, bits)
+        mn, side = cm.cube(pts)
+        changed.append(int((cm.cells_variant(pts, mn, side, bits, variant)[:, 0] != cm.cells(pts, mn, side, bits)[:, 0]).sum()))
+    print(bits, variant, changed)
+    assert max(changed) >= 5, changed
+    # and each cube earns its place: it is the one, or one of the ones, that shows the variant it was chosen for
+    expected = {"recip": (0,), "scale": (0,), "sub32": (1, 3), "div32": (2, 3)}[variant]
+    assert all(changed[c] >= (5 if bits > 4 else 3) for c in expected), changed
+
+
+def test_random_clouds_do_not():
+    """Why the boundary clouds exist: over 4096 uniform random points the reciprocal and the folded factor change no cell at any depth."""
+    rng = np.random.default_rng(21)
+    pts = cm.random_cloud(rng, 4096, 2.0, (1.0, -0.5, 0.25))
+    mn, side = cm.cube(pts)
+    for bits in (4, 9, 12, 16):
+        q = cm.cells(pts, mn, side, bits)
+        for variant in ("recip", "scale"):
+            assert np.array_equal(cm.cells_variant(pts, mn, side, bits, variant), q), (bits, variant)
+
+
+@pytest.mark.parametrize("cube", range(len(BOUNDARY_CUBES)))
+def test_prefix_property_on_the_boundaries(cube):
+    """q(b - 1) == q(b) >> 1 and key(b - 1) == key(b) >> 3, b in 2..16, on every boundary cloud: what lets the encoder group cut a
+    coarser packet from a finer sort."""
+    for made_for in (1, 4, 9, 16):
+        pts = boundary_cloud(cube, made_for)
+        mn, side = cm.cube(pts)
+        q = {b: cm.cells(pts, mn, side, b) for b in range(1, 17)}
+        k = {b: cm.keys(q[b], b) for b in range(1, 17)}
+        for b in range(2, 17):
+            assert np.array_equal(q[b - 1], q[b] >> 1), (made_for, b)
+            assert np.array_equal(k[b - 1], k[b] >> np.uint64(3)), (made_for, b)
+
+
+# ---------------------------------------------------------------------------
+# build_packet
+# ---------------------------------------------------------------------------
+def test_build_packet_restates_the_hand_written_packet_and_round_trips():
+    assert cm.build_packet([0, 4, 63], [[10, 20, 30], [1, 2, 3], [200, 100, 50]], [1, 1, 1], [0, 0, 0], 1.0, 2, 8, 0x0102) == HAND_PACKET
+    rng = np.random.default_rng(22)
+    for bits, cb, n in ((1, 4, 3), (5, 7, 200), (16, 5, 999)):
+        lk = np.unique(rng.integers(0, 1 << (3 * bits), n, dtype=np.uint64))
+        stored, tiles = rng.integers(0, 1 << cb, (len(lk), 3)), rng.integers(0, 256, len(lk))
+        packet = cm.build_packet(lk, stored, tiles, [-0.0, 1e-42, 3.0], 2.0 ** -60, bits, cb, (1 << 63) + 5)
+        info = cm.parse(packet)
+        assert info["timestamp"] == (1 << 63) + 5 and info["nleaves"] == len(lk) and info["side"] == 2.0 ** -60
+        assert info["min"].tobytes() == np.array([-0.0, 1e-42, 3.0], dtype=np.float32).tobytes()
+        assert np.array_equal(cm.leaf_keys_of(packet, info), lk)
+        dec = cm.decode(packet)[0]
+        s = 8 - cb
+        assert np.array_equal(np.stack([dec['r'], dec['g'], dec['b']], axis=1), np.minimum(255, (stored << s) + ((1 << s) >> 1)))
+        assert np.array_equal(dec['tile'], tiles.astype(np.uint8))

@@ -212,6 +212,9 @@ def test_synthetic_100k(codec, gpu, synth, bits):
     packet = check(codec, gpu, pts, bits, 85)
     info = cm.parse(packet)
     assert 1000 < info["nleaves"] <= 100000
+    # the decoder scans a depth's popcounts per workgroup of 256 nodes: several workgroups at 9 bits, and at 12 more than the 256 that
+    # the scanning workgroup takes in one round (the cloud has 89330 nodes at depth 8 and more below)
+    assert info["nodes"][-1] == info["nleaves"] and max(info["nodes"][:-1]) > (65536 if bits == 12 else 256 * 64), info["nodes"]
 
 
 def test_order_independence_and_repeat(codec, gpu):
