@@ -46,6 +46,7 @@ SOURCES = [
     "kernels_markers.hip",
     "kernels_rgbd.hip",
     "kernels_codec.hip",
+    "kernels_entropy.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -5,8 +5,12 @@ python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream 
 include/cwipc_util_amd/hip_ext.h) and carries its own magic, the bytes ``cwao``.
 Encoding and decoding run on the GPU; a decoder's clouds are ordinary device-resident clouds.
 
-Out of scope: cwipc_codec's bitstream, entropy coding of the occupancy bytes, transform or JPEG colour coding, inter-frame
-coding, per-leaf point counts in the packet, sockets.
+With ``entropy=True`` an encoder delivers the entropy-coded form of the same packets (RULE E, magic ``cwae``: occupancy, colour and
+tile streams through an interleaved rANS coder on the GPU, each stream raw where coding would not shrink it); a decoder takes both
+forms.  `entropy_pack`, `entropy_unpack` and `entropy_info` convert and inspect packets on the host.
+
+Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding, inter-frame coding, per-leaf point counts in the packet,
+sockets.
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ from .util import CwipcError, cwipc_pointcloud_wrapper
 __all__ = [
     "cwipc_encoder_params", "cwipc_new_encoder_params", "cwipc_new_encoder", "cwipc_new_encodergroup", "cwipc_new_decoder",
     "cwipc_encoder_wrapper", "cwipc_encodergroup_wrapper", "cwipc_decoder_wrapper", "packet_info",
+    "entropy_pack", "entropy_unpack", "entropy_info",
 ]
 
 
@@ -54,6 +59,10 @@ class cwipc_encoder_wrapper:
 
     def close(self) -> None:
         util.cwipc_hip_encoder_close(self._handle())
+
+    def set_entropy(self, on: bool = True) -> None:
+        """Deliver the entropy-coded form (RULE E); legal before the first feed, CwipcError afterwards."""
+        util.cwipc_hip_encoder_set_entropy(self._handle(), on)
 
     def eof(self) -> bool:
         return util.cwipc_hip_encoder_eof(self._handle())
@@ -111,8 +120,11 @@ class cwipc_encodergroup_wrapper:
         util.cwipc_hip_encodergroup_close(self._handle())
 
     def addencoder(self, version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
+        entropy = bool(kwargs.pop("entropy", False))
         enc = cwipc_encoder_wrapper(util.cwipc_hip_encodergroup_addencoder(self._handle(), _params(params, kwargs)), self)
         self._encoders.append(enc)
+        if entropy:
+            enc.set_entropy(True)
         return enc
 
     def feed(self, pc: cwipc_pointcloud_wrapper) -> None:
@@ -169,8 +181,13 @@ def _params(params: Optional[cwipc_encoder_params], kwargs: Dict[str, Any]) -> c
 
 
 def cwipc_new_encoder(version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
-    """An encoder for `params` (default: cwipc_new_encoder_params()), single parameters overridden by keyword."""
-    return cwipc_encoder_wrapper(util.cwipc_hip_new_encoder(_params(params, kwargs)))
+    """An encoder for `params` (default: cwipc_new_encoder_params()), single parameters overridden by keyword.  entropy=True: it
+    delivers the entropy-coded form of its packets (RULE E)."""
+    entropy = bool(kwargs.pop("entropy", False))
+    enc = cwipc_encoder_wrapper(util.cwipc_hip_new_encoder(_params(params, kwargs)))
+    if entropy:
+        enc.set_entropy(True)
+    return enc
 
 
 def cwipc_new_encodergroup() -> cwipc_encodergroup_wrapper:
@@ -188,3 +205,26 @@ def packet_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
                 tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
                 nodes=list(info.nodes)[:info.octree_bits], occupancy_offset=info.occupancy_offset, colour_offset=info.colour_offset,
                 tile_offset=info.tile_offset, total_bytes=info.total_bytes)
+
+
+def entropy_pack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The entropy-coded form ("cwae", RULE E) of a valid packet (host code, no GPU); CwipcError with the reason otherwise."""
+    return util.cwipc_hip_codec_entropy_pack(packet)
+
+
+def entropy_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The packet an entropy-coded packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
+    return util.cwipc_hip_codec_entropy_unpack(packet)
+
+
+def entropy_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
+    """The header and the directory of an entropy-coded packet after the container test (host code, no GPU): packet_info()'s keys for
+    the packet it stands for, `streams`: [(mode, payload bytes)], `kinds`: [(kind, which, symbols)] and its own `total_bytes`."""
+    d = util.cwipc_hip_codec_entropy_info(packet)
+    info = d.packet
+    names = ("occupancy", "colour", "tile")
+    return dict(timestamp=info.timestamp, nleaves=info.nleaves, octree_bits=info.octree_bits, colour_bits=info.colour_bits,
+                tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
+                nodes=list(info.nodes)[:info.octree_bits], unpacked_bytes=info.total_bytes,
+                streams=[(d.mode[i], d.payload_bytes[i]) for i in range(d.nstreams)],
+                kinds=[(names[d.kind[i]], d.which[i], d.symbols[i]) for i in range(d.nstreams)], total_bytes=d.total_bytes)

@@ -8,8 +8,15 @@
 // mode, known only when the leaves are, is filled in when the result is taken.
 // Decode: validate on the host (nothing launched or allocated for a packet that is refused) -> upload -> the kernels, in flight
 // when feed returns: the cloud carries a `ready` event.
+//
+// The entropy-coded form (RULE E: hip_ext.h, entropy_terms.hpp; kernels_entropy.hip).  Encode: the entropy stage runs on the body the
+// device holds after codec_leaf; its size is the device's to find, so feed queues the stage and a copy of four report words and
+// returns; whoever polls or takes the result first waits for those words and issues the copy of exactly the packet's bytes (EncJob:
+// stage 0 -> 1), and takes it when that copy is done.  Decode: the container test on the host -> upload -> the streams decoded into
+// the body buffer -> the check -> ONE wait in feed (a packet whose blocks or occupancy bytes fail is refused there) -> the decode above.
 #include "internal.hpp"
 #include "codec_terms.hpp"
+#include "entropy_terms.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -36,19 +43,81 @@ struct EncJob {
     hipEvent_t done = nullptr;
     std::shared_ptr<DeviceSoA> src;  // the kernels read its planes
     bool final = false;
+    // the entropy-coded form: `out` on the device (from the word S on) until its bytes that count have been copied behind the header
+    bool entropy = false, failed = false;
+    void *out_dev = nullptr;
+    size_t out_capacity = 0, out_bytes = 0, report_offset = 0;
+    int stage = 0;                   // 0: the stage's kernels in flight (`done`); 1: the copy in flight (`copied`)
+    hipEvent_t copied = nullptr;
     ~EncJob() {
         if (done) { (void)hipEventSynchronize(done); event_put(done); }
+        if (copied) { (void)hipEventSynchronize(copied); event_put(copied); }
+        if (out_dev) pool_free(out_dev);
         if (host) host_free(host, pinned);
     }
-    bool ready(bool wait) {
-        if (final || !done) return true;
-        if (wait) return hipEventSynchronize(done) == hipSuccess;
-        const hipError_t e = hipEventQuery(done);
+    static bool event_done(hipEvent_t ev, bool wait) {
+        if (wait) return hipEventSynchronize(ev) == hipSuccess;
+        const hipError_t e = hipEventQuery(ev);
         if (e != hipSuccess) (void)hipGetLastError();
         return e == hipSuccess;
     }
+    // `done` has come: the report says how many bytes count; their copy goes out on the calling thread's stream
+    void start_copy() {
+        stage = 1;
+        uint32_t report[4];
+        memcpy(report, host + report_offset, 16);
+        out_bytes = report[0];
+        ThreadCtx &c = tctx();
+        if (out_bytes < 4 || out_bytes > out_capacity || !c.ensure()) { failed = true; return; }
+        const size_t head = CODEC_HEADER_BYTES + 4u * (size_t)layout.bits;
+        copied = event_get();
+        if (!copied || hipMemcpyAsync(host + head, out_dev, out_bytes, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+            hipEventRecord(copied, c.stream) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)c.sync();
+            failed = true;
+        }
+    }
+    bool ready(bool wait) {
+        if (final || !done) return true;
+        if (!entropy) return event_done(done, wait);
+        if (stage == 0) {
+            if (!event_done(done, wait)) return false;
+            start_copy();
+        }
+        if (failed || !copied) return true;
+        return event_done(copied, wait);
+    }
+    void finalize_entropy() {
+        if (done) {
+            if (stage == 0) { (void)hipEventSynchronize(done); start_copy(); }
+            if (copied) { (void)hipEventSynchronize(copied); event_put(copied); copied = nullptr; }
+            event_put(done);
+            done = nullptr;
+        }
+        src.reset();
+        if (out_dev) { pool_free(out_dev); out_dev = nullptr; }
+        const size_t head = CODEC_HEADER_BYTES + 4u * (size_t)layout.bits;
+        layout.tile_mode = 0;
+        layout.tile_value = 0;
+        if (report_offset) {
+            uint32_t report[4];
+            memcpy(report, host + report_offset, 16);
+            const bool uniform = (report[2] & report[3]) == 0u;
+            layout.tile_mode = uniform ? 0 : 1;
+            layout.tile_value = uniform ? (int)(report[2] & 255u) : 0;
+        } else {
+            out_bytes = 4;   // an empty cloud: S = 0, written with the header
+        }
+        host[22] = (uint8_t)layout.tile_mode;
+        host[23] = (uint8_t)layout.tile_value;
+        layout.total_bytes = failed ? 0u : (uint64_t)(head + out_bytes);
+        if (failed) note_error("octree encode", "the entropy stage failed");
+        final = true;
+    }
     void finalize() {
         if (final) return;
+        if (entropy) { finalize_entropy(); return; }
         if (done) { (void)hipEventSynchronize(done); event_put(done); done = nullptr; }
         src.reset();
         if (stats_offset) {
@@ -124,7 +193,7 @@ bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits
 }
 
 // The packet of (bits <= s.bits, colour shift) from a sorted cloud: queued on the calling thread's stream.
-std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp) {
+std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp, bool entropy) {
     ThreadCtx &c = tctx();
     std::unique_ptr<EncJob> job(new EncJob());
     CodecLayout &l = job->layout;
@@ -140,9 +209,38 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     }
     codec_layout_sizes(l);
     const size_t body_bytes = (size_t)(l.tile_offset - l.occupancy_offset) + (size_t)codec_pad4(l.nleaves) + 8;   // ... the tile plane, the two tile words
-    job->host = (uint8_t *)host_alloc((size_t)l.occupancy_offset + body_bytes, &job->pinned);
+    // the entropy-coded form: its streams (with a tile plane, which the plan kernel drops when the tiles turn out uniform) and the
+    // most bytes it can take from the word S on: a stream never takes more than its raw payload
+    k::EntropyStreams st{};
+    size_t out_capacity = 4;
+    if (entropy) {
+        EntropyStream streams[ENTROPY_MAX_STREAMS];
+        st.nstreams = entropy_streams(l, streams);
+        st.colour_bits = l.colour_bits;
+        st.nleaves = l.nleaves;
+        out_capacity += 8u * (size_t)st.nstreams;
+        for (int i = 0; i < st.nstreams; i++) {
+            st.kind[i] = streams[i].kind;
+            st.which[i] = streams[i].which;
+            st.symbols[i] = streams[i].symbols;
+            st.first_block[i] = st.total_blocks;
+            st.total_blocks += streams[i].nblocks;
+            st.plane_offset[i] = streams[i].kind == ENTROPY_OCCUPANCY ? (uint32_t)entropy_depth_offset(l, (int)streams[i].which) : 0u;
+            st.raw_padded[i] = (uint32_t)codec_pad4(streams[i].raw_bytes);
+            out_capacity += st.raw_padded[i];
+        }
+        if (out_capacity > 0x7fffffffull) { note_error(who, "the cloud is too large for the entropy-coded form"); return nullptr; }
+        job->entropy = true;
+        job->out_capacity = out_capacity;
+    }
+    job->host = (uint8_t *)host_alloc(entropy ? (size_t)l.occupancy_offset + out_capacity + 16 : (size_t)l.occupancy_offset + body_bytes, &job->pinned);
     if (!job->host) { note_error(who, "out of host memory"); return nullptr; }
     codec_write_header(job->host, l);
+    if (entropy) {
+        const uint32_t magic = ENTROPY_MAGIC, none = 0;
+        memcpy(job->host, &magic, 4);
+        memcpy(job->host + l.occupancy_offset, &none, 4);
+    }
     if (!l.nleaves) {
         job->finalize();
         return job;
@@ -163,21 +261,62 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     e.tiles = block + (l.tile_offset - l.occupancy_offset);
     e.tile_stats = (uint32_t *)(block + body_bytes - 8);
     e.sums = (k::CodecLeafSum *)(block + sums_offset);
+    uint8_t *work = nullptr;
+    if (entropy) {
+        work = (uint8_t *)pool_alloc(k::entropy_encode_work_bytes(st));
+        job->out_dev = pool_alloc(round256(out_capacity));
+        if (!work || !job->out_dev) {
+            pool_free(work);
+            pool_free(block);
+            note_error(who, "out of device memory");
+            return nullptr;
+        }
+    }
     bool ok = hipMemsetAsync(block, 0, block_bytes, c.stream) == hipSuccess;
     if (ok) {
         k::codec_emit(s.keys + s.n, s.index + s.n, *s.src, s.cube_dev, s.bits, s.counts, e, shift, c.stream);
-        ok = hipMemcpyAsync(job->host + l.occupancy_offset, block, body_bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        if (!entropy) ok = hipMemcpyAsync(job->host + l.occupancy_offset, block, body_bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
         ok = ok && hipGetLastError() == hipSuccess;
+    }
+    if (ok && entropy) {
+        // only the packet's own bytes cross the bus: here the four report words, the rest when the result is polled or taken
+        k::EntropyEncode en{};
+        en.st = st;
+        en.occupancy = (const uint8_t *)e.occupancy;
+        en.tiles = e.tiles;
+        en.colours = e.colours;
+        en.tile_stats = e.tile_stats;
+        en.colour_words = e.colour_words;
+        const size_t S = (size_t)st.nstreams, nb = st.total_blocks;
+        uint8_t *at = work;
+        en.hist = (uint32_t *)at; at += S * 1024;
+        en.block_words = (uint32_t *)at; at += nb * 4;
+        en.block_bytes = (uint32_t *)at; at += nb * 4;
+        en.block_offset = (uint32_t *)at; at += nb * 4;
+        en.plan = (uint32_t *)at; at += S * 12;
+        en.report = (uint32_t *)at; at += 16;
+        en.freq = (uint16_t *)at; at += S * 512;
+        en.slots = work + round256((size_t)(at - work));
+        en.out = (uint8_t *)job->out_dev;
+        en.out_capacity = out_capacity;
+        job->report_offset = (size_t)l.occupancy_offset + (size_t)codec_pad4(out_capacity);
+        ok = hipMemsetAsync(en.hist, 0, S * 1024, c.stream) == hipSuccess && hipMemsetAsync(job->out_dev, 0, out_capacity, c.stream) == hipSuccess;
+        if (ok) {
+            k::entropy_encode(en, c.stream);
+            ok = hipMemcpyAsync(job->host + job->report_offset, en.report, 16, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+            ok = ok && hipGetLastError() == hipSuccess;
+        }
     }
     job->done = event_get();
     ok = ok && job->done && hipEventRecord(job->done, c.stream) == hipSuccess;
     c.free_later(block);
+    c.free_later(work);
     if (!ok) {
         (void)c.sync();
         hip_failed(hipGetLastError(), "octree encode", __FILE__, __LINE__);
         return nullptr;
     }
-    job->stats_offset = (size_t)l.occupancy_offset + body_bytes - 8;
+    if (!entropy) job->stats_offset = (size_t)l.occupancy_offset + body_bytes - 8;
     job->src = s.src;
     return job;
 }
@@ -245,6 +384,8 @@ struct cwipc_hip_encoder {
     std::deque<std::unique_ptr<EncJob>> queue;
     bool closed = false;
     bool in_group = false;
+    bool entropy = false;   // deliver the entropy-coded form (RULE E); chosen before the first feed
+    bool fed = false;
 };
 
 struct cwipc_hip_encodergroup {
@@ -274,8 +415,111 @@ void release_upload(cwipc_hip_decoder::Job &j) {
     }
 }
 
+// The streams of a "cwae" packet that has passed entropy_validate() into `body`, the device copy of the "cwao" body that the octree
+// decoder reads: upload, decode, check, and the one wait for the check's word.  False (logged): a block is not intact or a coded
+// occupancy stream breaks RULE C; the caller launches nothing more for the packet.
+bool entropy_to_body(const char *who, ThreadCtx &c, const uint8_t *bytes, const EntropyLayout &el, uint8_t *body) {
+    const CodecLayout &l = el.cwao;
+    k::EntropyDecode d{};
+    d.st.nstreams = el.nstreams;
+    d.st.colour_bits = l.colour_bits;
+    d.st.nleaves = l.nleaves;
+    for (int i = 0; i < el.nstreams; i++) {
+        const EntropyStream &s = el.stream[i];
+        d.st.kind[i] = s.kind;
+        d.st.which[i] = s.which;
+        d.st.symbols[i] = s.symbols;
+        d.st.first_block[i] = d.st.total_blocks;
+        d.st.total_blocks += s.nblocks;
+        d.st.plane_offset[i] = s.kind == ENTROPY_OCCUPANCY ? (uint32_t)entropy_depth_offset(l, (int)s.which) : 0u;
+        d.st.raw_padded[i] = (uint32_t)codec_pad4(s.raw_bytes);
+        d.mode[i] = s.mode;
+        d.payload_offset[i] = (uint32_t)(s.payload_offset - el.directory_offset);
+        d.payload_bytes[i] = (uint32_t)s.payload_bytes;
+        d.children[i] = s.kind == ENTROPY_OCCUPANCY ? l.nodes[s.which] : 0u;
+    }
+    const size_t in_bytes = (size_t)(el.total_bytes - el.directory_offset), table_offset = (in_bytes + 7) & ~(size_t)7,
+                 table_bytes = 8u * (size_t)d.st.total_blocks, upload_bytes = round256(table_offset + table_bytes),
+                 channel_bytes = round256(3u * (size_t)l.nleaves), flag_bytes = round256(4u * (size_t)(1 + el.nstreams));
+    bool pinned = false;
+    uint8_t *host = (uint8_t *)host_alloc(upload_bytes, &pinned);
+    uint8_t *dev = (uint8_t *)pool_alloc(upload_bytes + channel_bytes + flag_bytes);
+    if (!host || !dev) {
+        if (host) host_free(host, pinned);
+        pool_free(dev);
+        note_error(who, "out of memory");
+        return false;
+    }
+    memcpy(host, bytes + el.directory_offset, in_bytes);
+    uint32_t *table = (uint32_t *)(host + table_offset);
+    memset(table, 0, table_bytes);
+    for (int i = 0; i < el.nstreams; i++) {
+        const EntropyStream &s = el.stream[i];
+        if (s.mode != 1u) continue;
+        uint32_t at = d.payload_offset[i] + ENTROPY_TABLE_BYTES + 4u * s.nblocks;   // (the container test has held the sizes to the payload)
+        for (uint32_t b = 0; b < s.nblocks; b++) {
+            const uint32_t size = codec_read<uint32_t>(bytes + s.payload_offset + ENTROPY_TABLE_BYTES + 4u * (size_t)b);
+            table[2 * (d.st.first_block[i] + b)] = at;
+            table[2 * (d.st.first_block[i] + b) + 1] = size;
+            at += size;
+        }
+    }
+    d.in = dev;
+    d.block_at = (const uint32_t *)(dev + table_offset);
+    d.channels = dev + upload_bytes;
+    d.flags = (uint32_t *)(dev + upload_bytes + channel_bytes);
+    d.occupancy = body;
+    d.colours = (uint32_t *)(body + (l.colour_offset - l.occupancy_offset));
+    d.tiles = body + (l.tile_offset - l.occupancy_offset);
+    d.colour_words = codec_pad4(l.colour_bytes) / 4;
+    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
+    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
+    words[0] = 0ull;
+    bool ok = hipMemcpyAsync(dev, host, table_offset + table_bytes, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+              hipMemsetAsync(d.flags, 0, flag_bytes, c.stream) == hipSuccess;
+    if (ok) {
+        k::entropy_decode(d, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = c.sync() && ok;   // the one wait: the streams are in `body`, the check's word is here
+    host_free(host, pinned);
+    pool_free(dev);
+    if (!ok || (uint32_t)(words[0] >> 32) != tag) {
+        hip_failed(hipGetLastError(), "octree decode (entropy stage)", __FILE__, __LINE__);
+        return false;
+    }
+    const uint32_t status = (uint32_t)words[0];
+    if (status & 1u) { note_error(who, "entropy-coded block is not intact"); return false; }
+    if (status & 2u) { note_error(who, "occupancy byte is 0"); return false; }
+    if (status & 4u) { note_error(who, "occupancy bits differ from the node count"); return false; }
+    return true;
+}
+
+void fill_info(const CodecLayout &l, cwipc_hip_codec_info *info) {
+    memset(info, 0, sizeof(*info));
+    info->timestamp = l.timestamp;
+    info->nleaves = l.nleaves;
+    info->octree_bits = l.bits;
+    info->colour_bits = l.colour_bits;
+    info->tile_mode = l.tile_mode;
+    info->tile_value = l.tile_value;
+    for (int a = 0; a < 3; a++) info->min[a] = l.mn[a];
+    info->side = l.side;
+    for (int d = 0; d < l.bits; d++) info->nodes[d] = l.nodes[d];
+    info->occupancy_offset = l.occupancy_offset;
+    info->colour_offset = l.colour_offset;
+    info->tile_offset = l.tile_offset;
+    info->total_bytes = l.total_bytes;
+}
+
+// the caller-buffer convention of the two host conversions: the size of the result; its bytes are written iff they fit
+size_t hand_out(const std::vector<uint8_t> &made, void *out, size_t capacity) {
+    if (out != nullptr && made.size() <= capacity) memcpy(out, made.data(), made.size());
+    return made.size();
+}
+
 int encoder_feed_sorted(const char *who, cwipc_hip_encoder *enc, const Sorted &s, uint64_t timestamp) {
-    auto job = emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp);
+    auto job = emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp, enc->entropy);
     if (!job) return -1;
     std::lock_guard<std::mutex> l(enc->lock);
     enc->queue.push_back(std::move(job));
@@ -308,6 +552,10 @@ extern "C" int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *
     return guarded(who, -1, [&]() -> int {
         if (enc == nullptr || pc == nullptr) { note_error(who, "NULL argument"); return -1; }
         if (enc->closed) { note_error(who, "the encoder has been closed"); return -1; }
+        {
+            std::lock_guard<std::mutex> l(enc->lock);
+            enc->fed = true;
+        }
         MadeClouds made;
         std::unique_ptr<cwipc_hip_pointcloud> keep;
         int rv = -1;
@@ -321,6 +569,15 @@ extern "C" int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *
         }
         return rv;
     });
+}
+
+extern "C" int cwipc_hip_encoder_set_entropy(cwipc_hip_encoder *enc, int on) {
+    const char *who = "cwipc_hip_encoder_set_entropy";
+    if (enc == nullptr) { note_error(who, "NULL argument"); return -1; }
+    std::lock_guard<std::mutex> l(enc->lock);
+    if (enc->fed) { note_error(who, "the encoder has been fed: the packet form is chosen before the first feed"); return -1; }
+    enc->entropy = on != 0;
+    return 0;
 }
 
 extern "C" bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait) {
@@ -404,6 +661,10 @@ extern "C" int cwipc_hip_encodergroup_feed(cwipc_hip_encodergroup *group, cwipc_
         std::vector<std::vector<cwipc_hip_encoder *>> classes;
         for (cwipc_hip_encoder *enc : group->encoders) {
             if (enc->closed) continue;
+            {
+                std::lock_guard<std::mutex> el(enc->lock);
+                enc->fed = true;
+            }
             bool placed = false;
             for (auto &cls : classes)
                 if (cls[0]->params.tilenumber == enc->params.tilenumber && cls[0]->params.voxelsize == enc->params.voxelsize) { cls.push_back(enc); placed = true; break; }
@@ -449,21 +710,51 @@ extern "C" int cwipc_hip_codec_packet_info(const void *bytes, size_t len, cwipc_
     ErrorbufScope scope(errorMessage);
     CodecLayout l;
     if (const char *problem = codec_validate((const uint8_t *)bytes, len, l)) { note_error(who, problem); return -1; }
+    if (info) fill_info(l, info);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// the entropy-coded form on the host (no GPU)
+// ---------------------------------------------------------------------------
+extern "C" size_t cwipc_hip_codec_entropy_pack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_entropy_pack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = entropy_pack((const uint8_t *)bytes, len, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" size_t cwipc_hip_codec_entropy_unpack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_entropy_unpack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = entropy_unpack((const uint8_t *)bytes, len, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc_hip_codec_entropy_directory *info, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_entropy_info";
+    ErrorbufScope scope(errorMessage);
+    EntropyLayout e;
+    if (const char *problem = entropy_validate((const uint8_t *)bytes, len, e)) { note_error(who, problem); return -1; }
     if (info) {
         memset(info, 0, sizeof(*info));
-        info->timestamp = l.timestamp;
-        info->nleaves = l.nleaves;
-        info->octree_bits = l.bits;
-        info->colour_bits = l.colour_bits;
-        info->tile_mode = l.tile_mode;
-        info->tile_value = l.tile_value;
-        for (int a = 0; a < 3; a++) info->min[a] = l.mn[a];
-        info->side = l.side;
-        for (int d = 0; d < l.bits; d++) info->nodes[d] = l.nodes[d];
-        info->occupancy_offset = l.occupancy_offset;
-        info->colour_offset = l.colour_offset;
-        info->tile_offset = l.tile_offset;
-        info->total_bytes = l.total_bytes;
+        fill_info(e.cwao, &info->packet);
+        info->nstreams = e.nstreams;
+        for (int i = 0; i < e.nstreams; i++) {
+            info->kind[i] = (int32_t)e.stream[i].kind;
+            info->which[i] = (int32_t)e.stream[i].which;
+            info->mode[i] = (int32_t)e.stream[i].mode;
+            info->symbols[i] = e.stream[i].symbols;
+            info->payload_offset[i] = e.stream[i].payload_offset;
+            info->payload_bytes[i] = e.stream[i].payload_bytes;
+        }
+        info->total_bytes = e.total_bytes;
     }
     return 0;
 }
@@ -482,7 +773,16 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
         if (dec->closed) { note_error(who, "the decoder has been closed"); return -1; }
         // the validity test: host code, before anything is launched or allocated on the device
         CodecLayout l;
-        if (const char *problem = codec_validate((const uint8_t *)bytes, len, l)) { note_error(who, problem); return -1; }
+        EntropyLayout el;
+        const bool coded = bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == ENTROPY_MAGIC;
+        if (const char *problem = coded ? entropy_validate((const uint8_t *)bytes, len, el) : codec_validate((const uint8_t *)bytes, len, l)) {
+            note_error(who, problem);
+            return -1;
+        }
+        if (coded) {
+            l = el.cwao;
+            if (el.total_bytes > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
+        }
         if (!device_available(who)) return -1;
         ThreadCtx &c = tctx();
         if (!c.ensure()) return -1;
@@ -503,17 +803,26 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
             d.colour_words = codec_pad4(l.colour_bytes) / 4;
             const size_t body_bytes = round256(body + 8), ping_bytes = round256((size_t)l.nleaves * 8), scratch_bytes = round256(k::codec_decode_scratch_words(d) * 4);
             uint8_t *block = (uint8_t *)pool_alloc(body_bytes + 2 * ping_bytes + scratch_bytes);
-            job.host = (uint8_t *)host_alloc(body, &job.pinned);
-            if (!block || !job.host) {
+            if (!coded) job.host = (uint8_t *)host_alloc(body, &job.pinned);
+            if (!block || (!coded && !job.host)) {
                 pool_free(block);
                 if (job.host) host_free(job.host, job.pinned);
                 note_error(who, "out of memory");
                 return -1;
             }
-            memcpy(job.host, (const uint8_t *)bytes + l.occupancy_offset, body);
             d.colours = (const uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
             d.tiles = l.tile_mode == 1 ? block + (l.tile_offset - l.occupancy_offset) : nullptr;
-            bool ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
+            bool ok = true;
+            if (coded) {
+                // the body comes from the entropy stage; a packet it refuses ends here, before any kernel of the octree decoder
+                if (!entropy_to_body(who, c, (const uint8_t *)bytes, el, block)) {
+                    pool_free(block);
+                    return -1;
+                }
+            } else {
+                memcpy(job.host, (const uint8_t *)bytes + l.occupancy_offset, body);
+                ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
+            }
             if (ok) {
                 k::codec_decode(block, d, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
                                 (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
@@ -522,7 +831,7 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
             c.free_later(block);
             if (!ok) {
                 (void)c.sync();
-                host_free(job.host, job.pinned);
+                if (job.host) host_free(job.host, job.pinned);
                 hip_failed(hipGetLastError(), "octree decode", __FILE__, __LINE__);
                 return -1;
             }

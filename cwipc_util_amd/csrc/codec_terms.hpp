@@ -138,12 +138,12 @@ inline void codec_write_header(uint8_t *p, const CodecLayout &l) {
     memcpy(p + CODEC_HEADER_BYTES, l.nodes, 4u * (size_t)l.bits);
 }
 
-// One pass over the packet.  nullptr: valid, `out` filled; otherwise why not.  Nothing outside [p, p + len) is read.
-inline const char *codec_validate(const uint8_t *p, size_t len, CodecLayout &out) {
-    CodecLayout l;
+// The header and nodes[] of a packet that starts with `magic`: ranges and the tree rule; the offsets and sizes of `l` are those of the
+// "cwao" form.  nullptr: right, `l` filled.  The entropy-coded form (entropy_terms.hpp) carries the same bytes 8 .. 48 + 4 bits.
+inline const char *codec_validate_header(const uint8_t *p, size_t len, uint32_t magic, CodecLayout &l) {
     if (p == nullptr) return "no packet";
     if (len < CODEC_HEADER_BYTES) return "truncated header";
-    if (codec_read<uint32_t>(p) != CODEC_MAGIC) return "wrong magic (not a packet of this library's octree codec)";
+    if (codec_read<uint32_t>(p) != magic) return "wrong magic (not a packet of this library's octree codec)";
     if (codec_read<uint32_t>(p + 4) != CODEC_VERSION) return "unknown version";
     l.timestamp = codec_read<uint64_t>(p + 8);
     l.nleaves = codec_read<uint32_t>(p + 16);
@@ -176,6 +176,13 @@ inline const char *codec_validate(const uint8_t *p, size_t len, CodecLayout &out
             if (l.nodes[d + 1] < l.nodes[d] || (uint64_t)l.nodes[d + 1] > 8u * (uint64_t)l.nodes[d]) return "node counts do not fit a tree";
     }
     codec_layout_sizes(l);
+    return nullptr;
+}
+
+// One pass over the packet.  nullptr: valid, `out` filled; otherwise why not.  Nothing outside [p, p + len) is read.
+inline const char *codec_validate(const uint8_t *p, size_t len, CodecLayout &out) {
+    CodecLayout l;
+    if (const char *problem = codec_validate_header(p, len, CODEC_MAGIC, l)) return problem;
     if ((uint64_t)len < l.total_bytes) return "truncated packet";
     if ((uint64_t)len > l.total_bytes) return "bytes behind the packet";
     // occupancy: depth d has 1, nodes[0], nodes[1] ... bytes, none 0, their bits as many as the next depth's nodes

@@ -575,6 +575,50 @@ size_t codec_decode_scratch_words(const CodecDecode &d);
 void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch, const DeviceSoA &dst,
                   hipStream_t s);
 
+// ---- kernels_entropy.hip: the entropy-coded packet form (RULE E: hip_ext.h; the arithmetic: entropy_terms.hpp) ----
+constexpr int ENTROPY_STREAMS = 20;                      // octree_bits + 3 + 1 at the most
+constexpr size_t ENTROPY_SLOT_BYTES = 256 + 2 * 4096;    // a block's states and the most words it can emit
+// The streams of one packet, in RULE E's order; block b of stream i is the global block first_block[i] + b.
+struct EntropyStreams {
+    int nstreams, colour_bits;
+    uint32_t nleaves, total_blocks;
+    uint32_t kind[ENTROPY_STREAMS], which[ENTROPY_STREAMS], symbols[ENTROPY_STREAMS], first_block[ENTROPY_STREAMS];
+    uint32_t plane_offset[ENTROPY_STREAMS];   // occupancy: where the depth starts in the occupancy plane
+    uint32_t raw_padded[ENTROPY_STREAMS];     // the raw payload with its padding
+};
+// Encode: the body that codec_emit made (the tile stream is listed last and leaves when tile_stats says the tiles are uniform) -> `out`,
+// zeroed by the caller, from the word S on.  report (device, 4 words): the bytes of `out` that count, S, and the two tile words.
+struct EntropyEncode {
+    EntropyStreams st;
+    const uint8_t *occupancy, *tiles;
+    const uint32_t *colours, *tile_stats;
+    uint64_t colour_words;
+    uint32_t *hist;            // nstreams x 256, zeroed by the caller
+    uint16_t *freq;            // nstreams x 256
+    uint32_t *block_words, *block_bytes, *block_offset;   // total_blocks each
+    uint8_t *slots;            // total_blocks x ENTROPY_SLOT_BYTES: states, then the words at the END of the slot in decoder order
+    uint32_t *plan;            // nstreams x (mode, payload offset in `out`, payload bytes)
+    uint32_t *report;
+    uint8_t *out;
+    uint64_t out_capacity;
+};
+size_t entropy_encode_work_bytes(const EntropyStreams &st);
+void entropy_encode(const EntropyEncode &e, hipStream_t s);
+// Decode: `in` is the packet from the word S on; per global block its offset in `in` and its size (coded streams; 0, 0 otherwise).
+// The streams go to the body the octree decoder reads: occupancy bytes, the bit-packed colour plane (through `channels`, 3 x nleaves
+// bytes), the tile plane.  status (pinned): tag << 32 | 1 a block is not intact | 2 an occupancy byte is 0 | 4 occupancy bits differ.
+struct EntropyDecode {
+    EntropyStreams st;
+    uint32_t mode[ENTROPY_STREAMS], payload_offset[ENTROPY_STREAMS], payload_bytes[ENTROPY_STREAMS], children[ENTROPY_STREAMS];
+    const uint8_t *in;
+    const uint32_t *block_at;   // 2 x total_blocks: offset, bytes
+    uint8_t *occupancy, *tiles, *channels;
+    uint32_t *colours;
+    uint64_t colour_words;
+    uint32_t *flags;            // 1 + nstreams words, zeroed by the caller
+};
+void entropy_decode(const EntropyDecode &d, unsigned long long *status_host, uint32_t tag, hipStream_t s);
+
 }  // namespace k
 
 // Voxel-grid downsample (kernels_voxel.hip).  Returns the new cloud's planes or

@@ -68,6 +68,7 @@ class _SinkEncoder:
         self.tiledescriptions: List[cwipc_tileinfo_dict] = [{}]
         self.octree_bits: List[int] = [DEFAULT_OCTREE_BITS]
         self.jpeg_quality: List[int] = [DEFAULT_JPEG_QUALITY]
+        self.entropy = False
         self.encoder_group: Optional[codec.cwipc_encodergroup_wrapper] = None
         self.encoders: List[codec.cwipc_encoder_wrapper] = []
         self.streams: List[int] = []
@@ -79,8 +80,11 @@ class _SinkEncoder:
         self.stopped = False
 
     def set_encoder_params(self, tiles: Optional[List[cwipc_tileinfo_dict]], octree_bits: Union[int, Sequence[int], None] = None,
-                           jpeg_quality: Union[int, Sequence[int], None] = None) -> None:
+                           jpeg_quality: Union[int, Sequence[int], None] = None, entropy: bool = False) -> None:
+        """entropy=True: every encoder delivers the entropy-coded form of its packets (cwipc_util_amd.codec, RULE E); a
+        cwipc_source_decoder takes both forms."""
         assert self.encoder_group is None, "set_encoder_params comes before the first cloud"
+        self.entropy = bool(entropy)
         self.tiledescriptions = tiles if tiles else [{}]
         self.octree_bits = _intlist(octree_bits, self.octree_bits)
         self.jpeg_quality = _intlist(jpeg_quality, self.jpeg_quality)
@@ -105,7 +109,7 @@ class _SinkEncoder:
             for bits in self.octree_bits:
                 for quality in self.jpeg_quality:
                     params = codec.cwipc_encoder_params(False, 1, 1.0, bits, quality, 16, mask, 0)
-                    self.encoders.append(self.encoder_group.addencoder(params=params))
+                    self.encoders.append(self.encoder_group.addencoder(params=params, entropy=self.entropy))
                     self.streams.append(self.add_stream(tile_index, tile, dict(octree_bits=bits, jpeg_quality=quality)))
                     if self.verbose:
                         print(f"encoder: stream {self.streams[-1]}: tile={tile_index} mask={mask} octree_bits={bits} jpeg_quality={quality}")

@@ -64,6 +64,8 @@ __all__ = [
     'cwipc_hip_new_encodergroup', 'cwipc_hip_encodergroup_addencoder', 'cwipc_hip_encodergroup_feed', 'cwipc_hip_encodergroup_close', 'cwipc_hip_encodergroup_free',
     'cwipc_hip_new_decoder', 'cwipc_hip_decoder_feed', 'cwipc_hip_decoder_available', 'cwipc_hip_decoder_get', 'cwipc_hip_decoder_eof', 'cwipc_hip_decoder_close',
     'cwipc_hip_decoder_free',
+    'cwipc_hip_encoder_set_entropy', 'cwipc_hip_codec_entropy_directory', 'cwipc_hip_codec_entropy_pack', 'cwipc_hip_codec_entropy_unpack',
+    'cwipc_hip_codec_entropy_info',
 ]
 
 # reference util.py:86, 346, 348
@@ -308,6 +310,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_decoder_close': ([_c.c_void_p], None),
     'cwipc_hip_decoder_free': ([_c.c_void_p], None),
     'cwipc_hip_codec_packet_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
+    'cwipc_hip_encoder_set_entropy': ([_c.c_void_p, _c.c_int], _c.c_int),
+    'cwipc_hip_codec_entropy_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_entropy_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_entropy_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -2025,6 +2031,14 @@ class cwipc_hip_codec_info(ctypes.Structure):
                 ("tile_offset", ctypes.c_uint64), ("total_bytes", ctypes.c_uint64)]
 
 
+class cwipc_hip_codec_entropy_directory(ctypes.Structure):
+    """The directory of an entropy-coded packet (hip_ext.h: RULE E): the header of the packet it stands for, and per stream its kind
+    (0 occupancy, 1 colour, 2 tile), mode (0 raw, 1 coded), symbol count and payload."""
+    _fields_ = [("packet", cwipc_hip_codec_info), ("nstreams", ctypes.c_int32), ("kind", ctypes.c_int32 * 20), ("which", ctypes.c_int32 * 20),
+                ("mode", ctypes.c_int32 * 20), ("symbols", ctypes.c_uint32 * 20), ("payload_offset", ctypes.c_uint64 * 20),
+                ("payload_bytes", ctypes.c_uint64 * 20), ("total_bytes", ctypes.c_uint64)]
+
+
 def _codec_handle(name: str, rv: Any, errorString: ctypes.c_char_p) -> int:
     _raise_or_warn(errorString, rv)
     if rv:
@@ -2147,6 +2161,46 @@ def cwipc_hip_codec_packet_info(packet: Union[bytes, bytearray, memoryview]) -> 
     if rv != 0:
         raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_packet_info: not a valid packet")
     return info
+
+
+def cwipc_hip_encoder_set_entropy(enc: int, on: bool) -> None:
+    """The encoder delivers the entropy-coded form (hip_ext.h: RULE E) from its first packet on; CwipcError once it has been fed."""
+    if cwipc_util_dll_load().cwipc_hip_encoder_set_entropy(enc, 1 if on else 0) != 0:
+        raise _codec_last_error('cwipc_hip_encoder_set_entropy')
+
+
+def _codec_entropy_convert(name: str, packet: Union[bytes, bytearray, memoryview], capacity: int) -> bytearray:
+    data = bytes(packet)
+    out = bytearray(max(capacity, 1))
+    buffer = (ctypes.c_char * len(out)).from_buffer(out)
+    errorString = ctypes.c_char_p()
+    size = getattr(cwipc_util_dll_load(), name)(data, len(data), ctypes.addressof(buffer), len(out), ctypes.byref(errorString))
+    del buffer
+    if size == 0 or size > len(out):
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else f"{name}: not a valid packet")
+    del out[size:]
+    return out
+
+
+def cwipc_hip_codec_entropy_pack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """A valid "cwao" packet in its entropy-coded form "cwae" (host code, no GPU)."""
+    return _codec_entropy_convert('cwipc_hip_codec_entropy_pack', packet, len(packet) + 4 + 11 * 20)
+
+
+def cwipc_hip_codec_entropy_info(packet: Union[bytes, bytearray, memoryview]) -> cwipc_hip_codec_entropy_directory:
+    """The container test and the directory of a "cwae" packet (host code, no GPU; the coded blocks are not decoded)."""
+    data = bytes(packet)
+    info = cwipc_hip_codec_entropy_directory()
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_codec_entropy_info(data, len(data), ctypes.addressof(info), ctypes.byref(errorString))
+    if rv != 0:
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_entropy_info: not a valid packet")
+    return info
+
+
+def cwipc_hip_codec_entropy_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The "cwao" packet a "cwae" packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
+    return _codec_entropy_convert('cwipc_hip_codec_entropy_unpack', packet, cwipc_hip_codec_entropy_info(packet).packet.total_bytes)
 
 
 class cwipc_hip_profile:

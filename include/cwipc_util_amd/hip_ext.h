@@ -615,8 +615,8 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
 /* ---- the octree codec: encoder, encoder group, decoder (csrc/codec.cpp, csrc/kernels_codec.hip) ----
  * The packets of this codec are NOT interoperable with cwipc_codec: the interface is the reference's (cwipc_new_encoder,
  * cwipc_new_encodergroup, cwipc_new_decoder as python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is
- * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, entropy coding of the occupancy bytes,
- * transform or JPEG colour coding, inter-frame coding, per-leaf point counts in the packet, sockets.
+ * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding,
+ * inter-frame coding, per-leaf point counts in the packet, sockets.  (Entropy coding: RULE E below, off unless asked for.)
  *
  * RULE C.  The arithmetic is csrc/codec_terms.hpp (host and device compile it), tests/codec_model.py its numpy restatement.  All
  * arithmetic is float64 unless stated otherwise, every operation rounded on its own.
@@ -650,7 +650,59 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  *           byte is 0; the popcounts of depth L sum to nodes[L] (for the last depth: nleaves); padding is 0; the length is exact.
  *           Validation is host code, reads the packet once and runs BEFORE anything is launched or allocated on the device.
  * Results queue first-in first-out per encoder and decoder.  feed returns with the work in flight on the calling thread's stream;
- * available(false) polls, available(true) waits.  No exception crosses this boundary. */
+ * available(false) polls, available(true) waits.  No exception crosses this boundary.
+ *
+ * RULE E, the entropy-coded form.  A packet with the magic "cwae" stands for exactly one valid RULE C packet P ("cwao"):
+ * unpack(pack(P)) == P byte for byte, and a decoder fed pack(P) hands out the cloud it hands out for P.  An encoder delivers it only
+ * after cwipc_hip_encoder_set_entropy(enc, 1); a decoder takes both forms.  The arithmetic is csrc/entropy_terms.hpp (host and device
+ * compile it), tests/entropy_model.py its numpy restatement.  All integers little endian.
+ *  Streams.  For nleaves > 0, b = octree_bits, cb = colour bits, in this order: the occupancy bytes of depth 0 .. b - 1 (depth d: 1
+ *           symbol for d == 0, nodes[d - 1] otherwise); the leaves' stored colours, one stream per channel r, g, b, nleaves symbols
+ *           of cb bits each, carried as byte values; the tile plane, nleaves symbols, only when tile_mode == 1.  S = b + 3 + tile_mode
+ *           streams; S = 0 for nleaves == 0.
+ *  Prediction.  Colour streams only: symbol j is (v[j] - v[j - 1]) mod 2^cb, and v[j] itself where j mod 4096 == 0.  The decoder undoes
+ *           it with an inclusive scan mod 2^cb inside each block.  Occupancy and tile symbols are the bytes themselves.
+ *  Blocks.  A stream is cut into blocks of 4096 symbols, the last of m <= 4096.  Symbol j of a block belongs to lane j mod 64 in round
+ *           j div 64.  The coder is rANS: per lane a 32-bit state in [2^16, 2^32), 12-bit frequencies (they sum to M = 4096), 16-bit
+ *           words.  A block is 64 x u32, the states the decoder starts from, then its W u16 word slots, W even: the words and, when
+ *           their number is odd, one padding word 0.  Its size is 256 + 2 W bytes.
+ *  Decoder.  cursor = 0.  For each round r = 0 .., first every lane l with j = 64 r + l < m:  slot = x_l & 4095;  s = the symbol with
+ *           cum[s] <= slot < cum[s] + f[s] (the largest s with cum[s] <= slot);  x_l = f[s] * (x_l >> 12) + slot - cum[s];  out[j] = s.
+ *           Then, in ascending l, every such lane with x_l < 2^16:  x_l = (x_l << 16) | word[cursor++]; a word slot at or past W reads
+ *           as 0.  A block is intact iff every one of its 64 start states is at least 2^16, every one of the 64 states is 2^16 at the
+ *           end (the lanes that never had a symbol included), no read went past W, and the cursor ends at W, or at W - 1 with the last
+ *           slot, the padding word, being 0.
+ *  Encoder.  The exact inverse.  All states start at 2^16; rounds from the last to the first, lanes descending within a round; for
+ *           symbol s:  if x >= f[s] << 20 (64-bit): emit x & 0xffff, x >>= 16;  then x = (x / f[s]) * 4096 + x % f[s] + cum[s] in
+ *           integers.  The block's words are the emitted words in reverse order of emission; at most one per symbol.
+ *  Frequencies.  Per stream, from the 256 counts c of its symbols (u32; 64-bit products), total = their sum:  f[i] = 0 where c[i] == 0,
+ *           else max(1, (c[i] * 4096) / total);  d = 4096 - sum f;  d > 0: d is added to the symbol of the largest c, the lowest symbol on
+ *           ties;  while d < 0: the symbol of the largest f, the lowest on ties, loses 1 (that f is above 1) and d gains 1.  cum is the
+ *           exclusive prefix sum of f.
+ *  Mode.    A stream is coded (mode 1) iff it has at least 4096 symbols AND its coded payload is strictly smaller than its raw one;
+ *           otherwise raw (mode 0).  Raw payload: the occupancy or tile bytes as they are; for a colour channel the plain values (no
+ *           prediction) of cb bits each, packed LSB first; padded with zeros to a multiple of 4.  Coded payload: u16 f[256], then
+ *           u32 block_bytes[nblocks], then the blocks.
+ *  Packet, its total length exact:
+ *      0  u32 magic, the bytes c w a e        4  u32 version = 1
+ *      8  bytes 8 .. 48 + 4 b of P verbatim (timestamp to nodes[b - 1])
+ *     then u32 S, S entries {u32 mode, u32 payload_bytes}, the payloads in stream order.  nleaves == 0: S = 0 and nothing behind it.
+ *     Hence len(pack(P)) <= len(P) + 4 + 11 S.
+ *  Validity, in two steps.  The container, on the host, BEFORE anything is launched or allocated on the device: magic and version; the
+ *           embedded header by RULE C's range and tree rules; S, every mode and every payload size against the counts of the header
+ *           (raw: exactly the padded raw size; coded: at least 4096 symbols, a multiple of 4, room for the table and the states of
+ *           every block, strictly smaller than the raw size); sum f == 4096, f[0] == 0 for an occupancy stream, f[s] == 0 for s >= 2^cb
+ *           for a colour stream; nblocks == ceil(symbols / 4096), every block_bytes a multiple of 4 in [256, 256 + 8192], their sum
+ *           the rest of the payload; padding bytes and bits 0, the length exact; raw occupancy streams by RULE C's rules (no byte 0, the
+ *           bits of depth d as many as nodes[d]).  Then the coded streams, on the device: every block intact, and for a coded
+ *           occupancy stream RULE C's two conditions; the flags reach the host in one wait inside cwipc_hip_decoder_feed, which refuses
+ *           the packet with the reason and launches none of the octree decoder's kernels for it.
+ *  Bounds.  For ANY payload bytes the decoding kernels (and their host twins) read only inside the packet and write only inside the
+ *           header's counts: the slot search stays inside the 256-entry table, a word past the block reads 0 and raises the flag,
+ *           every store is below the stream's symbol count.
+ *  Encoding runs on the device after the leaves are made: histograms, frequencies, one wave per block, a plan (sizes, modes, offsets,
+ *  directory, total) and a gather.  Only then is the size known: feed returns with that work and the copy of four report words in
+ *  flight; whoever polls or takes the result first waits for the report and issues the copy of exactly the packet's bytes. */
 typedef struct cwipc_hip_encoder_params {
     bool do_inter_frame;     /* must be false */
     int gop_size;            /* must be 1 */
@@ -667,6 +719,9 @@ typedef struct cwipc_hip_decoder cwipc_hip_decoder;
 _CWIPC_UTIL_EXPORT cwipc_hip_encoder *cwipc_hip_new_encoder(const cwipc_hip_encoder_params *params, char **errorMessage);
 _CWIPC_UTIL_EXPORT void cwipc_hip_encoder_free(cwipc_hip_encoder *enc);
 _CWIPC_UTIL_EXPORT int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *pc);        /* 0 ok, -1 error (logged) */
+/* on != 0: the encoder delivers RULE E's entropy-coded form ("cwae") of the packets it would deliver otherwise.  Legal before the first
+ * feed, also on an encoder of a group (the group's sort is shared all the same); afterwards -1 and the reason in cwipc_hip_last_error(). */
+_CWIPC_UTIL_EXPORT int cwipc_hip_encoder_set_entropy(cwipc_hip_encoder *enc, int on);
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait);
 _CWIPC_UTIL_EXPORT size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc);               /* of the oldest result; 0: none */
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size);   /* takes the oldest result */
@@ -700,6 +755,24 @@ typedef struct cwipc_hip_codec_info {
     uint64_t occupancy_offset, colour_offset, tile_offset, total_bytes;
 } cwipc_hip_codec_info;
 _CWIPC_UTIL_EXPORT int cwipc_hip_codec_packet_info(const void *bytes, size_t len, cwipc_hip_codec_info *info, char **errorMessage);
+/* RULE E on the host, without a GPU.  pack: a valid "cwao" packet -> its "cwae" form; unpack: a "cwae" packet -> the "cwao" packet it
+ * stands for, after the container test, the blocks' integrity and the occupancy rules.  Both return the size of the result and write it
+ * to out iff out != NULL and it fits capacity (pack never needs more than len + 4 + 11 * 20 bytes; unpack needs
+ * cwipc_hip_codec_entropy_info()'s packet.total_bytes); 0 and the reason in *errorMessage for a packet that is refused. */
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_entropy_pack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage);
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_entropy_unpack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage);
+/* The directory of a "cwae" packet after the container test (the coded blocks are not decoded): 0 and *info filled, or -1 and the reason. */
+typedef struct cwipc_hip_codec_entropy_directory {
+    cwipc_hip_codec_info packet;      /* the header; offsets and total_bytes are those of the "cwao" packet it stands for */
+    int32_t nstreams;                 /* S */
+    int32_t kind[20];                 /* 0 occupancy, 1 colour, 2 tile */
+    int32_t which[20];                /* occupancy: the depth; colour: the channel */
+    int32_t mode[20];                 /* 0 raw, 1 coded */
+    uint32_t symbols[20];
+    uint64_t payload_offset[20], payload_bytes[20];
+    uint64_t total_bytes;             /* of the "cwae" packet */
+} cwipc_hip_codec_entropy_directory;
+_CWIPC_UTIL_EXPORT int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc_hip_codec_entropy_directory *info, char **errorMessage);
 
 /* ---- intermediate results for parity tests ---- */
 /* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
