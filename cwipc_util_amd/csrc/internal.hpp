@@ -29,6 +29,7 @@
 #include "rgbd_terms.hpp"
 #include "rgbd_lens.hpp"
 #include "rgbd_depthfilter.hpp"
+#include "rgbd_decimate.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -493,7 +494,9 @@ void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const
 // to write through.  rays: the ray table (2 doubles per depth pixel), nullptr for a sensor without depth lens coefficients.
 // raw_colour: the colour image as the camera sent it (raw_bpp bytes per pixel, ct.width x ct.height, 4-byte aligned, 8 readable
 // bytes behind it).  The validity words of the erosion: wpr words per row, this camera's first is number wfirst.  The occlusion
-// test's z-buffer: one word per colour pixel, row-major, this camera's first is number zfirst.
+// test's z-buffer: one word per colour pixel, row-major, this camera's first is number zfirst.  A decimated rig (rgbd_decimate.hpp): all
+// of the above is on the decimated grid; full_depth is the depth image as the sensor delivers it, full_width pixels wide, 16-byte
+// aligned with readable bytes up to the next 16-byte boundary behind it; nullptr without decimation.
 struct RgbdRawCamDev : RgbdCamDev {
     uint16_t *depth_rw;
     uint8_t *registered;
@@ -502,6 +505,8 @@ struct RgbdRawCamDev : RgbdCamDev {
     RgbdColourTerms ct;
     uint32_t raw_bpp, height, wpr, wfirst;
     size_t zfirst;
+    const uint16_t *full_depth;
+    uint32_t full_width;
 };
 void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
                 unsigned long long *total_host, uint32_t tag, hipStream_t s);
@@ -523,6 +528,13 @@ uint32_t rgbd_line_groups(uint32_t lines);
 void rgbd_temporal(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdSmoothTerms &t, int persistency, double *value, uint8_t *history,
                    hipStream_t s);
 void rgbd_zsplat(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, unsigned long long *zbuf, hipStream_t s);
+// Decimation and hole filling (rgbd_decimate.hpp).  rgbd_decimate: every camera's full_depth, k = 2 .. 8, into its depth_rw, in front
+// of everything else; tiles: the sum of rgbd_decimate_tiles(width, height) over the cameras (the decimated sizes).
+// rgbd_holefill: rule 0c, mode 1 .. 3, in place as far as the caller sees; rows: the sum of the cameras' heights; scratch: total_pixels
+// depth values (modes 2 and 3 only: they write it from the images and then copy it back, two launches).
+uint32_t rgbd_decimate_tiles(uint32_t width, uint32_t height);
+void rgbd_decimate(const RgbdRawCamDev *cams, int ncam, int k, uint32_t tiles, hipStream_t s);
+void rgbd_holefill(const RgbdRawCamDev *cams, int ncam, int mode, uint32_t rows, uint32_t total_pixels, uint16_t *scratch, hipStream_t s);
 void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const unsigned long long *zbuf, int splat, double margin,
                             hipStream_t s);
 

@@ -17,7 +17,9 @@
 // that also knows its ray table (Cam = RgbdRawCamDev), the existing instantiation (Cam = RgbdCamDev) computing what it always did.
 // On request (cwipc_hip_rgbd_rig_grab_filtered, rgbd_depthfilter.hpp) the depth post-processing runs in front of the erosion: the
 // spatial filter's line passes, one lane per row or column walking it in LDS, and the temporal filter's per-pixel update of the image
-// and of the state the rig keeps from grab to grab.
+// and of the state the rig keeps from grab to grab.  A decimated rig (cwipc_hip_rgbd_rig_create_decimated, rgbd_decimate.hpp) runs
+// rgbd_decimate in front of all of it, full-size depth images in, the rig's grid out; cwipc_hip_rgbd_rig_grab_filled fills holes
+// between the temporal filter and the erosion, along rows as a wave scan or from a pixel's eight neighbours.
 #include "internal.hpp"
 #include "block_scan.hpp"
 
@@ -457,6 +459,172 @@ __global__ void __launch_bounds__(BLOCK) rgbd_register_kernel(const RgbdRawCamDe
     out[0] = (uint8_t)rgb; out[1] = (uint8_t)(rgb >> 8); out[2] = (uint8_t)(rgb >> 16);
 }
 
+// ---- decimation and hole filling (rgbd_decimate.hpp), DESIGN 3.23 ----
+//
+// Decimation by K.  A workgroup owns a tile of DEC_W x DEC_H pixels of one camera's decimated image, one per lane, and so K * DEC_H
+// source rows of K * DEC_W pixels.  A lane does NOT fetch its K * K source pixels itself (K * K two-byte loads, K * 2 bytes apart from
+// its neighbour's): the workgroup brings every source row in with 16-byte loads, 1 KB contiguous per wave, and shares them through LDS.
+// A source row starts wherever its image's width puts it, so a row's loads start at the 16-byte boundary at or below its first
+// pixel and the row keeps that offset (0 .. 7 pixels) in LDS; the vectors are whole in global memory because the host leaves the
+// image 16-byte aligned with readable bytes up to the next boundary behind it.  Rows from K * H' and columns from K * W' on belong to
+// no block: such rows are not loaded, such columns only as the rest of a vector that nobody reads.
+constexpr int DEC_W = 128;
+constexpr int DEC_H = BLOCK / DEC_W;
+
+__host__ __device__ __forceinline__ uint32_t decimate_tiles(uint32_t width, uint32_t height) {
+    return ((width + (uint32_t)DEC_W - 1u) / (uint32_t)DEC_W) * ((height + (uint32_t)DEC_H - 1u) / (uint32_t)DEC_H);
+}
+
+template <int K>
+__global__ void __launch_bounds__(BLOCK) rgbd_decimate_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam) {
+    constexpr uint32_t SPAN = K * DEC_W;          // source pixels of a full tile's row
+    constexpr uint32_t STRIDE = SPAN + 8;         // of a row in LDS, in pixels: the up to 7 pixels in front of the span come with its first vector
+    __shared__ uint4 tile4[K * DEC_H * STRIDE / 8];
+    const uint16_t *tile = reinterpret_cast<const uint16_t *>(tile4);
+    // the camera of this tile and the tile's number in it
+    uint32_t t = blockIdx.x;
+    int k = 0;
+    for (; k < ncam; k++) {
+        const uint32_t n = decimate_tiles(cams[k].width, cams[k].height);
+        if (t < n) break;
+        t -= n;
+    }
+    if (k == ncam) return;   // (the whole workgroup; the host launches exactly the tiles there are)
+    const RgbdRawCamDev &c = cams[k];
+    const uint32_t tiles_x = (c.width + (uint32_t)DEC_W - 1u) / (uint32_t)DEC_W;
+    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
+    const uint32_t u0 = tx * (uint32_t)DEC_W, v0 = ty * (uint32_t)DEC_H;
+    const uint32_t nu = c.width - u0 < (uint32_t)DEC_W ? c.width - u0 : (uint32_t)DEC_W, nv = c.height - v0 < (uint32_t)DEC_H ? c.height - v0 : (uint32_t)DEC_H;
+    const uint32_t span = nu * (uint32_t)K, nrows = nv * (uint32_t)K;
+    // source row r of the tile: pixels first(r) .. first(r) + span - 1 of the full image, all inside it: (K v0 + r) < K H' <= H and
+    // K u0 + span <= K W' <= W
+    const auto first = [&](uint32_t r) { return (size_t)((uint32_t)K * v0 + r) * (size_t)c.full_width + (size_t)((uint32_t)K * u0); };
+    const uint32_t nvec = (span + 14u) / 8u;      // at most: 7 pixels in front, span, up to the next boundary; <= STRIDE / 8
+    const uint4 *__restrict__ full4 = reinterpret_cast<const uint4 *>(c.full_depth);
+    for (uint32_t idx = threadIdx.x; idx < nrows * nvec; idx += (uint32_t)BLOCK) {
+        const uint32_t r = idx / nvec, i = idx - r * nvec;
+        const size_t e0 = first(r), a0 = e0 & ~(size_t)7;
+        if (i * 8u < (uint32_t)(e0 - a0) + span) tile4[r * (STRIDE / 8u) + i] = full4[a0 / 8u + i];
+    }
+    __syncthreads();
+    const uint32_t u = threadIdx.x % (uint32_t)DEC_W, v = threadIdx.x / (uint32_t)DEC_W;
+    if (u >= nu || v >= nv) return;
+    uint16_t block[K * K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const uint32_t r = v * (uint32_t)K + (uint32_t)j;
+        const uint16_t *row = tile + r * STRIDE + (uint32_t)(first(r) & (size_t)7) + u * (uint32_t)K;
+#pragma unroll
+        for (int i = 0; i < K; i++) block[j * K + i] = row[i];
+    }
+    c.depth_rw[(size_t)(v0 + v) * c.width + u0 + u] = rgbd_block_value<K>(block);
+}
+
+// Hole filling from the left (rule 0c, mode 1): out[i] = op(out[i - 1], d[i]) is a scan with an associative operator, so a row is NOT
+// walked as the spatial filter's lines are.  One wave per row.  A lane owns 8 neighbouring pixels -- one 16-byte vector, taken at the
+// 16-byte boundaries of the image, so the first and the last vector of a row may hold pixels of the rows beside it: those are read as
+// 0, the operator's identity, and never written (such a vector is stored pixel by pixel) -- folds them, the wave scans the 64 folds
+// with shuffles (6 steps), and every lane runs over its pixels again from what is left of it.  A row longer than 512 pixels takes
+// more than one such chunk: `carry`, the last value with depth of the chunks before, goes in front of the next one's scan.
+constexpr int FILL_PPL = 8;
+constexpr int FILL_CHUNK = 64 * FILL_PPL;
+
+__global__ void __launch_bounds__(BLOCK) rgbd_holefill_left_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t rows) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t row = blockIdx.x * (uint32_t)WAVES + (threadIdx.x >> 6);
+    if (row >= rows) return;   // (the whole wave)
+    int k = 0;
+    while (k + 1 < ncam && row >= cams[k].height) {
+        row -= cams[k].height;
+        k++;
+    }
+    const RgbdRawCamDev &c = cams[k];
+    const size_t e0 = (size_t)row * c.width, e1 = e0 + c.width;   // the row's pixels in its image
+    uint16_t carry = 0;
+    for (size_t base = e0 & ~(size_t)7; base < e1; base += (size_t)FILL_CHUNK) {   // (the same trip count in every lane)
+        const size_t at = base + (size_t)lane * (size_t)FILL_PPL;   // at + 8 > e0 always
+        const bool any = at < e1, whole = at >= e0 && at + (size_t)FILL_PPL <= e1;
+        uint16_t v[FILL_PPL];
+#pragma unroll
+        for (int j = 0; j < FILL_PPL; j++) v[j] = 0;
+        if (any) {   // at < e1 <= the image's pixels: the vector ends at or before the 16-byte boundary behind the image
+            const uint4 w = *reinterpret_cast<const uint4 *>(c.depth_rw + at);
+            const uint32_t words[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int j = 0; j < FILL_PPL; j++) {
+                const bool mine = at + (size_t)j >= e0 && at + (size_t)j < e1;
+                v[j] = mine ? (uint16_t)(words[j >> 1] >> (16 * (j & 1))) : (uint16_t)0;
+            }
+        }
+        uint16_t fold = 0;
+#pragma unroll
+        for (int j = 0; j < FILL_PPL; j++) fold = rgbd_fill_op(fold, v[j]);
+        uint32_t x = fold;   // the inclusive scan of the folds, lane 0 first
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t left = (uint32_t)__shfl_up((int)x, d);
+            if (lane >= d) x = rgbd_fill_op((uint16_t)left, (uint16_t)x);
+        }
+        const uint32_t before = (uint32_t)__shfl_up((int)x, 1u);
+        uint16_t run = rgbd_fill_op(carry, lane == 0u ? (uint16_t)0 : (uint16_t)before);
+        carry = rgbd_fill_op(carry, (uint16_t)__shfl((int)x, 63));
+#pragma unroll
+        for (int j = 0; j < FILL_PPL; j++) {
+            run = rgbd_fill_op(run, v[j]);
+            v[j] = run;
+        }
+        if (whole) {
+            uint4 w;
+            w.x = (uint32_t)v[0] | ((uint32_t)v[1] << 16); w.y = (uint32_t)v[2] | ((uint32_t)v[3] << 16);
+            w.z = (uint32_t)v[4] | ((uint32_t)v[5] << 16); w.w = (uint32_t)v[6] | ((uint32_t)v[7] << 16);
+            *reinterpret_cast<uint4 *>(c.depth_rw + at) = w;
+        } else if (any) {
+#pragma unroll
+            for (int j = 0; j < FILL_PPL; j++)
+                if (at + (size_t)j >= e0 && at + (size_t)j < e1) c.depth_rw[at + (size_t)j] = v[j];
+        }
+    }
+}
+
+// Hole filling from around (rule 0c, modes 2 and 3): one lane per depth pixel of the frame.  The rule reads the stage's input, so
+// the first launch writes every pixel's new value to a plane of its own (scratch, in pixel-number order) and the second copies the
+// plane over the images.  Only a pixel without depth looks at its neighbours, each inside the image before an index is formed.
+template <bool BACK>
+__global__ void __launch_bounds__(BLOCK) rgbd_holefill_around_kernel(const RgbdRawCamDev *__restrict__ cams, int ncam, uint32_t total, int mode,
+                                                                    uint16_t *__restrict__ scratch) {
+    const uint32_t g = blockIdx.x * (uint32_t)BLOCK + threadIdx.x;
+    if (g >= total) return;
+    const RgbdRawCamDev &c = cams[camera_of(cams, ncam, 0, g)];
+    const uint32_t p = g - c.first;
+    if constexpr (BACK) {
+        c.depth_rw[p] = scratch[g];
+    } else {
+        const uint16_t d = c.depth[p];
+        if (d != 0) {
+            scratch[g] = d;
+            return;
+        }
+        const int width = (int)c.width, height = (int)c.height;
+        const int v = (int)(p / c.width), u = (int)(p - (uint32_t)v * c.width);
+        uint16_t n[9];
+#pragma unroll
+        for (int dv = -1; dv <= 1; dv++) {
+#pragma unroll
+            for (int du = -1; du <= 1; du++) {
+                const int y = v + dv, x = u + du;
+                const bool inside = y >= 0 && y < height && x >= 0 && x < width;
+                n[(dv + 1) * 3 + du + 1] = inside ? c.depth[(size_t)y * c.width + (size_t)x] : (uint16_t)0;
+            }
+        }
+        scratch[g] = rgbd_fill_pick(mode, n);
+    }
+}
+
+template <int K>
+void decimate_launch(const RgbdRawCamDev *cams, int ncam, uint32_t tiles, hipStream_t s) {
+    CW_LAUNCH("rgbd_decimate", rgbd_decimate_kernel<K>, dim3(tiles), dim3(BLOCK), 0, s, cams, ncam);
+}
+
 }  // namespace
 
 void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
@@ -514,6 +682,31 @@ void rgbd_register_occluded(const RgbdRawCamDev *cams, int ncam, uint32_t total_
                             hipStream_t s) {
     CW_LAUNCH("rgbd_register_occluded", rgbd_register_kernel<true>, dim3((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, cams,
               ncam, total_pixels, zbuf, splat, margin);
+}
+
+uint32_t rgbd_decimate_tiles(uint32_t width, uint32_t height) { return decimate_tiles(width, height); }
+
+void rgbd_decimate(const RgbdRawCamDev *cams, int ncam, int k, uint32_t tiles, hipStream_t s) {
+    switch (k) {
+        case 2: decimate_launch<2>(cams, ncam, tiles, s); break;
+        case 3: decimate_launch<3>(cams, ncam, tiles, s); break;
+        case 4: decimate_launch<4>(cams, ncam, tiles, s); break;
+        case 5: decimate_launch<5>(cams, ncam, tiles, s); break;
+        case 6: decimate_launch<6>(cams, ncam, tiles, s); break;
+        case 7: decimate_launch<7>(cams, ncam, tiles, s); break;
+        case 8: decimate_launch<8>(cams, ncam, tiles, s); break;
+        default: break;   // (1: nothing to do; the host has refused everything else)
+    }
+}
+
+void rgbd_holefill(const RgbdRawCamDev *cams, int ncam, int mode, uint32_t rows, uint32_t total_pixels, uint16_t *scratch, hipStream_t s) {
+    if (mode == 1) {
+        CW_LAUNCH("rgbd_holefill_left", rgbd_holefill_left_kernel, dim3((unsigned)(((size_t)rows + WAVES - 1) / WAVES)), dim3(BLOCK), 0, s, cams, ncam, rows);
+    } else if (mode == 2 || mode == 3) {
+        const dim3 grid((unsigned)(((size_t)total_pixels + BLOCK - 1) / BLOCK));
+        CW_LAUNCH("rgbd_holefill_around", rgbd_holefill_around_kernel<false>, grid, dim3(BLOCK), 0, s, cams, ncam, total_pixels, mode, scratch);
+        CW_LAUNCH("rgbd_holefill_around", rgbd_holefill_around_kernel<true>, grid, dim3(BLOCK), 0, s, cams, ncam, total_pixels, mode, scratch);
+    }
 }
 
 }  // namespace k

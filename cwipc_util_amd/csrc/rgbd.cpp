@@ -10,6 +10,8 @@
 // (computed here at creation) and the frame's device buffers, so that a grab uploads the images and nothing else.  The occlusion test
 // (cwipc_hip_rgbd_rig_grab_occluded) adds a z-buffer of the colour grids, which the first grab that asks for it allocates.  The depth
 // post-processing (cwipc_hip_rgbd_rig_grab_filtered, rgbd_depthfilter.hpp) adds the temporal filter's per-pixel state in the same way.
+// A decimated rig (cwipc_hip_rgbd_rig_create_decimated, rgbd_decimate.hpp) keeps the caller's sensors for the size of the uploads and
+// derived ones for everything else; hole filling (cwipc_hip_rgbd_rig_grab_filled) adds a scratch depth plane as the z-buffer is added.
 #include "internal.hpp"
 
 #include <cmath>
@@ -212,7 +214,9 @@ extern "C" int cwipc_hip_rgbd_mapcolordepth(const cwipc_hip_rgbd_camera *cam, in
 
 struct cwipc_hip_rgbd_rig {
     int device = -1;
-    std::vector<cwipc_hip_rgbd_sensor> sensors;
+    std::vector<cwipc_hip_rgbd_sensor> sensors;  // on the rig's grid: the caller's when decimation == 1, else derived from them (RULE D)
+    std::vector<cwipc_hip_rgbd_sensor> full;     // the caller's: the size of the depth images a grab is handed
+    int decimation = 1;
     std::vector<std::string> serials;            // copies; has_serial says which sensors had one
     std::vector<bool> has_serial;
     std::vector<std::vector<double>> rays;       // per camera 2 * W * H doubles
@@ -224,6 +228,9 @@ struct cwipc_hip_rgbd_rig {
     uint8_t *state = nullptr;                    // the temporal filter's state: a pool block of its own, made by the first temporal grab:
                                                  // total doubles (the running values) | total bytes (the histories), in pixel-number order
     bool state_empty = true;                     // the state is to be read as all zero: the next temporal grab clears it first
+    uint16_t *fill = nullptr;                    // hole filling from around: a depth plane of `total` pixels, a pool block of its own, made by the
+                                                 // first grab that needs it
+    uint32_t rows = 0, decimate_tiles = 0;       // every camera's rows; the decimation kernel's workgroups
     uint32_t row_groups = 0, col_groups = 0;     // the spatial filter's workgroups: every camera's rows and columns in groups
     uint32_t total = 0, total_words = 0;
     uint32_t tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -276,25 +283,33 @@ const char *smooth_problem(double alpha, double delta) {
 
 bool rig_camera_ok(const cwipc_hip_rgbd_rig *rig, int cam) { return rig != nullptr && cam >= 0 && (size_t)cam < rig->sensors.size(); }
 
-}  // namespace
-
-extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage) {
-    const char *who = "cwipc_hip_rgbd_rig_create";
+// cwipc_hip_rgbd_rig_create (decimation 1) and cwipc_hip_rgbd_rig_create_decimated
+cwipc_hip_rgbd_rig *rig_create(const char *who, const cwipc_hip_rgbd_sensor *sensors, int ncam, int decimation, char **errorMessage) {
     cwipc_log_set_errorbuf(errorMessage);
     struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
     if (sensors == nullptr || ncam <= 0) {
         note_error(who, sensors == nullptr ? "NULL argument" : "ncam must be at least 1");
         return nullptr;
     }
-    uint64_t total = 0, total_words = 0;
+    if (decimation < 1 || decimation > RGBD_MAX_DECIMATION) {
+        note_error(who, "decimation must be between 1 and 8");
+        return nullptr;
+    }
+    uint64_t total = 0, total_words = 0, full_total = 0;
     for (int k = 0; k < ncam; k++) {
         if (const char *problem = sensor_problem(sensors[k])) {
             note_error(who, "camera " + std::to_string(k) + ": " + problem);
             return nullptr;
         }
-        total += (uint64_t)sensors[k].width * (uint64_t)sensors[k].height;
-        total_words += (uint64_t)sensors[k].height * (((uint64_t)sensors[k].width + 63) / 64);
-        if (total > 0x7fffffffull) {
+        if (sensors[k].width < decimation || sensors[k].height < decimation) {
+            note_error(who, "camera " + std::to_string(k) + ": width and height must be at least the decimation");
+            return nullptr;
+        }
+        const uint64_t width = (uint64_t)(sensors[k].width / decimation), height = (uint64_t)(sensors[k].height / decimation);
+        total += width * height;
+        total_words += height * ((width + 63) / 64);
+        full_total += (uint64_t)sensors[k].width * (uint64_t)sensors[k].height;
+        if (full_total > 0x7fffffffull) {
             note_error(who, "more than 2^31 - 1 pixels");
             return nullptr;
         }
@@ -306,6 +321,8 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
     std::unique_ptr<cwipc_hip_rgbd_rig> rig(new cwipc_hip_rgbd_rig());
     rig->device = current_device();
     rig->sensors.assign(sensors, sensors + ncam);
+    rig->full.assign(sensors, sensors + ncam);
+    rig->decimation = decimation;
     rig->total = (uint32_t)total;
     rig->total_words = (uint32_t)total_words;
     rig->table.resize((size_t)ncam);
@@ -317,6 +334,11 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
         rig->has_serial.push_back(s.serial != nullptr);
         rig->serials.push_back(s.serial ? s.serial : "");
         s.serial = nullptr;   // (the caller's string is not kept)
+        rig->full[(size_t)k].serial = nullptr;
+        if (decimation > 1) {   // (1 would give the same bits: a subtraction of 0, divisions by 1)
+            const RgbdGrid g = rgbd_derived_grid(s.width, s.height, s.fx, s.fy, s.cx, s.cy, decimation);
+            s.width = g.width; s.height = g.height; s.fx = g.fx; s.fy = g.fy; s.cx = g.cx; s.cy = g.cy;
+        }
         const size_t npix = (size_t)s.width * (size_t)s.height, ncol = (size_t)s.colour_width * (size_t)s.colour_height;
         const RgbdCamTerms t = sensor_terms(s);
         const RgbdLens lens = lens_of(s.coeffs);
@@ -326,6 +348,7 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
             for (int u = 0; u < s.width; u++) rgbd_ray(t, lens, u, v, &rays[2 * ((size_t)v * (size_t)s.width + (size_t)u)]);
         if (!rgbd_lens_is_pinhole(lens)) bytes += round256(npix * 16);
         bytes += round256(npix * 2) + round256(ncol * (size_t)s.colour_bpp + 8) + round256(npix * 3 + 8);
+        if (decimation > 1) bytes += round256((size_t)rig->full[(size_t)k].width * (size_t)rig->full[(size_t)k].height * 2);
         rig->tiles[s.tile >> 5] |= 1u << (s.tile & 31u);
     }
     bytes += round256((size_t)total_words * 8);
@@ -357,12 +380,20 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
         at += round256(ncol * (size_t)s.colour_bpp + 8);
         t.registered = at; t.colour = t.registered;
         at += round256(npix * 3 + 8);
+        t.full_depth = nullptr; t.full_width = 0;
+        if (decimation > 1) {   // (256-byte aligned and rounded: the decimation kernel's 16-byte loads stay inside it)
+            const cwipc_hip_rgbd_sensor &whole = rig->full[(size_t)k];
+            t.full_depth = (const uint16_t *)at; t.full_width = (uint32_t)whole.width;
+            at += round256((size_t)whole.width * (size_t)whole.height * 2);
+        }
         t.width = (uint32_t)s.width; t.height = (uint32_t)s.height; t.bpp = 3u; t.raw_bpp = (uint32_t)s.colour_bpp; t.tile = s.tile;
         t.first = first; t.wpr = (uint32_t)(((uint64_t)s.width + 63) / 64); t.wfirst = wfirst;
         first += (uint32_t)npix;
         wfirst += t.height * t.wpr;
         rig->row_groups += k::rgbd_line_groups(t.height);
         rig->col_groups += k::rgbd_line_groups(t.width);
+        rig->rows += t.height;
+        rig->decimate_tiles += k::rgbd_decimate_tiles(t.width, t.height);
     }
     rig->words = (unsigned long long *)at;
     ok = ok && hipMemcpyAsync(rig->dev, rig->table.data(), (size_t)ncam * sizeof(k::RgbdRawCamDev), hipMemcpyHostToDevice, c.stream) == hipSuccess;
@@ -376,11 +407,24 @@ extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_se
     return rig.release();
 }
 
+}  // namespace
+
+extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage) {
+    return rig_create("cwipc_hip_rgbd_rig_create", sensors, ncam, 1, errorMessage);
+}
+
+extern "C" cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create_decimated(const cwipc_hip_rgbd_sensor *sensors, int ncam, int decimation, char **errorMessage) {
+    return rig_create("cwipc_hip_rgbd_rig_create_decimated", sensors, ncam, decimation, errorMessage);
+}
+
+extern "C" int cwipc_hip_rgbd_rig_decimation(const cwipc_hip_rgbd_rig *rig) { return rig ? rig->decimation : 0; }
+
 extern "C" void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig) {
     if (rig == nullptr) return;
     pool_free(rig->dev);
     pool_free(rig->zbuf);
     pool_free(rig->state);
+    pool_free(rig->fill);
     delete rig;
 }
 
@@ -388,9 +432,11 @@ namespace {
 
 // cwipc_hip_rgbd_rig_grab (occlusion == nullptr) and cwipc_hip_rgbd_rig_grab_occluded: one flow, the occlusion test's two steps in
 // place of the plain registration when it is asked for; and cwipc_hip_rgbd_rig_grab_filtered, which puts the depth post-processing
-// (rgbd_depthfilter.hpp) in front of it all when depthfilter has a stage that is on
-cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_depthfilter *depthfilter,
-                           const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+// (rgbd_depthfilter.hpp) in front of it all when depthfilter has a stage that is on; and cwipc_hip_rgbd_rig_grab_filled, which fills
+// holes (rgbd_decimate.hpp) between that and the erosion.  A decimated rig decimates the depth images before any of it.
+cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_holefill *holefill,
+                           const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion,
+                           const cwipc_hip_rgbd_filter *filter,
                            uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
     cwipc_log_set_errorbuf(errorMessage);
     struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
@@ -434,10 +480,15 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
                 return nullptr;
             }
     }
+    const int fill_mode = holefill ? holefill->mode : 0;
+    if (fill_mode < 0 || fill_mode > RGBD_MAX_HOLEFILL) {
+        note_error(who, "holefill: mode must be between 0 and 3");
+        return nullptr;
+    }
     const bool attach = (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) != 0;
     size_t staged_bytes = 0;
     for (int k = 0; k < ncam; k++) {
-        const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        const cwipc_hip_rgbd_sensor &s = rig->full[(size_t)k];
         if (frames[k].depth == nullptr || frames[k].colour == nullptr || (attach_flags != 0 && !rig->has_serial[(size_t)k])) {
             note_error(who, "camera " + std::to_string(k) + ": NULL argument");
             return nullptr;
@@ -485,6 +536,13 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         }
         rig->state_empty = true;
     }
+    if (fill_mode >= 2 && !rig->fill) {   // (kept from here on: freed with the rig)
+        rig->fill = (uint16_t *)pool_alloc((size_t)total * sizeof(uint16_t));
+        if (!rig->fill) {
+            note_error(who, "out of memory");
+            return nullptr;
+        }
+    }
     // the attached images come back into memory of their own, which the metadata then own
     std::vector<void *> images;
     struct FreeImages { std::vector<void *> &v; ~FreeImages() { for (void *p : v) ::free(p); } } free_images{images};
@@ -501,15 +559,16 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
     const k::RgbdRawCamDev *table = (const k::RgbdRawCamDev *)rig->dev;
     bool ok = true;
     for (int k = 0; k < ncam && ok; k++) {
-        const cwipc_hip_rgbd_sensor &s = rig->sensors[(size_t)k];
+        const cwipc_hip_rgbd_sensor &s = rig->full[(size_t)k];
         const k::RgbdRawCamDev &t = rig->table[(size_t)k];
-        ok = upload(frames[k].depth, (size_t)s.width * (size_t)s.height * 2, (uint8_t *)t.depth_rw, &stage, c.stream) &&
+        ok = upload(frames[k].depth, (size_t)s.width * (size_t)s.height * 2, t.full_depth ? (uint8_t *)t.full_depth : (uint8_t *)t.depth_rw, &stage, c.stream) &&
              upload(frames[k].colour, (size_t)s.colour_width * (size_t)s.colour_height * (size_t)s.colour_bpp, (uint8_t *)t.raw_colour, &stage, c.stream);
     }
     const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
     volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
     *word = 0ull;
     bool cleared = true;
+    if (ok && rig->decimation > 1) k::rgbd_decimate(table, ncam, rig->decimation, rig->decimate_tiles, c.stream);
     if (ok && magnitude > 0)
         k::rgbd_spatial(table, ncam, rig->row_groups, rig->col_groups, magnitude, rgbd_smooth_terms(depthfilter->spatial_alpha, depthfilter->spatial_delta),
                         c.stream);
@@ -524,6 +583,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         k::rgbd_temporal(table, ncam, total, rgbd_smooth_terms(depthfilter->temporal_alpha, depthfilter->temporal_delta), depthfilter->temporal_persistency,
                          value, history, c.stream);
     }
+    if (ok && fill_mode > 0) k::rgbd_holefill(table, ncam, fill_mode, rig->rows, total, rig->fill, c.stream);
     if (ok) {
         if (ex > 0 || ey > 0) k::rgbd_erode(table, ncam, rig->total_words, ex, ey, rig->words, c.stream);
         bool filled = true;
@@ -571,20 +631,28 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
 extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
                                                      const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize, int attach_flags,
                                                      char **errorMessage) {
-    return rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, nullptr, prep, nullptr, filter, timestamp, cellsize, attach_flags, errorMessage);
+    return rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, nullptr, nullptr, prep, nullptr, filter, timestamp, cellsize, attach_flags, errorMessage);
 }
 
 extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_occluded(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_prep *prep,
                                                               const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
                                                               uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
-    return rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, nullptr, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+    return rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, nullptr, nullptr, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
 }
 
 extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filtered(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames,
                                                               const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep,
                                                               const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
                                                               uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
-    return rig_grab("cwipc_hip_rgbd_rig_grab_filtered", rig, frames, depthfilter, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+    return rig_grab("cwipc_hip_rgbd_rig_grab_filtered", rig, frames, nullptr, depthfilter, prep, occlusion, filter, timestamp, cellsize, attach_flags, errorMessage);
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filled(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames, const cwipc_hip_rgbd_holefill *holefill,
+                                                            const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep,
+                                                            const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
+                                                            uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
+    return rig_grab("cwipc_hip_rgbd_rig_grab_filled", rig, frames, holefill, depthfilter, prep, occlusion, filter, timestamp, cellsize, attach_flags,
+                    errorMessage);
 }
 
 extern "C" void cwipc_hip_rgbd_rig_reset_history(cwipc_hip_rgbd_rig *rig) {
@@ -614,6 +682,12 @@ extern "C" int cwipc_hip_rgbd_rig_history(cwipc_hip_rgbd_rig *rig, int cam, doub
 
 extern "C" const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rgbd_rig *rig, int cam) {
     return rig_camera_ok(rig, cam) ? rig->rays[(size_t)cam].data() : nullptr;
+}
+
+extern "C" int cwipc_hip_rgbd_rig_grid_sensor(const cwipc_hip_rgbd_rig *rig, int cam, cwipc_hip_rgbd_sensor *out) {
+    if (!rig_camera_ok(rig, cam) || out == nullptr) return -1;
+    *out = rig->sensors[(size_t)cam];   // (serial is NULL in it: the caller's string was not kept)
+    return 0;
 }
 
 extern "C" int cwipc_hip_rgbd_rig_map2d3d(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int d, float out[3]) {

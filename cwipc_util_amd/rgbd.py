@@ -13,11 +13,13 @@ rig holds what is constant per camera; the images it attaches are the depth imag
 registered onto the depth grid, so the registration tooling works on them as it does on aligned ones.  `RgbdOcclusion` asks a grab
 to leave out the points the colour sensor cannot see (cwipc_hip_rgbd_rig_grab_occluded) instead of giving them a foreground colour;
 `RgbdDepthFilter` asks it to smooth the depth images first, along their lines and over time (cwipc_hip_rgbd_rig_grab_filtered), the
-rig keeping the temporal filter's state."""
+rig keeping the temporal filter's state.  `RgbdRig(sensors, decimation=k)` decimates the depth images on the GPU before any of that:
+the rig takes full-size frames and works on the grid of its `grid_sensors` from there on; `RgbdHoleFill` asks a grab to fill the
+holes of the depth images in front of the erosion (cwipc_hip_rgbd_rig_grab_filled)."""
 from __future__ import annotations
 
 import struct
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy
@@ -25,7 +27,8 @@ import numpy
 from . import util
 from .abstract import cwipc_activesource_abstract, cwipc_tileinfo_dict
 
-__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdOcclusion", "RgbdDepthFilter", "RgbdRig", "RgbdRigSource"]
+__all__ = ["RgbdCamera", "RgbdFilter", "RgbdSource", "Frame", "from_rgbd", "RgbdSensor", "RgbdPrep", "RgbdOcclusion", "RgbdDepthFilter", "RgbdHoleFill", "RgbdRig",
+           "RgbdRigSource"]
 
 #: one frame: per camera its (depth uint16[H, W], colour uint8[H, W, bpp]) images, the colour image aligned to the depth image
 Frame = Sequence[Tuple[numpy.ndarray, numpy.ndarray]]
@@ -331,13 +334,33 @@ class RgbdDepthFilter:
                                                float(self.temporal_alpha), float(self.temporal_delta), int(self.temporal_persistency))
 
 
+@dataclass
+class RgbdHoleFill:
+    """Hole filling of the depth images, after the depth filters and in front of the erosion.  mode 1: a pixel without depth takes the
+    nearest depth to its left in its row; 2: the farthest, 3: the nearest depth among its up to eight neighbours, as they were before
+    the stage (nothing propagates); 0: off.  A pixel that has depth is never changed."""
+    mode: int = 1
+
+    def as_struct(self) -> util.cwipc_hip_rgbd_holefill:
+        return util.cwipc_hip_rgbd_holefill(int(self.mode))
+
+
 class RgbdRig:
     """cwipc_hip_rgbd_rig_* on dataclasses and arrays: what is constant per camera, made once.  A context manager; free() gives the
-    device memory back."""
+    device memory back.  decimation k (1 .. 8): the rig is handed full-size frames -- depth images of the size its `sensors` say --
+    and decimates them by k on the GPU first; everything else (the attached images, history, ray_table, map2d3d, mapcolordepth)
+    is on the decimated grid, whose sensors `grid_sensors` holds."""
 
-    def __init__(self, sensors: Sequence[RgbdSensor]) -> None:
+    def __init__(self, sensors: Sequence[RgbdSensor], decimation: int = 1) -> None:
         self.sensors: List[RgbdSensor] = list(sensors)
-        self._rig: Optional[int] = util.cwipc_hip_rgbd_rig_create([s.as_struct() for s in self.sensors])
+        self.decimation = int(decimation)
+        structs = [s.as_struct() for s in self.sensors]
+        self._rig: Optional[int] = (util.cwipc_hip_rgbd_rig_create(structs) if self.decimation == 1
+                                    else util.cwipc_hip_rgbd_rig_create_decimated(structs, self.decimation))
+        self.grid_sensors: List[RgbdSensor] = []
+        for i, s in enumerate(self.sensors):
+            g = util.cwipc_hip_rgbd_rig_grid_sensor(self._rig, i)
+            self.grid_sensors.append(replace(s, width=g.width, height=g.height, fx=g.fx, fy=g.fy, cx=g.cx, cy=g.cy))
 
     def __enter__(self) -> "RgbdRig":
         return self
@@ -362,10 +385,12 @@ class RgbdRig:
         return self._rig
 
     def grab(self, frame: Frame, filter: Optional[RgbdFilter] = None, prep: Optional[RgbdPrep] = None, timestamp: int = 0, cellsize: float = 0.0,
-             attach_flags: int = 0, occlusion: Optional[RgbdOcclusion] = None, depthfilter: Optional[RgbdDepthFilter] = None) -> util.cwipc_pointcloud_wrapper:
-        """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images.  occlusion: leave out the
-        points the colour sensor cannot see (None: cwipc_hip_rgbd_rig_grab as it is).  depthfilter: smooth the depth images first
-        (None: the two other entries as they are)."""
+             attach_flags: int = 0, occlusion: Optional[RgbdOcclusion] = None, depthfilter: Optional[RgbdDepthFilter] = None,
+             holefill: Optional[RgbdHoleFill] = None) -> util.cwipc_pointcloud_wrapper:
+        """One cloud from one frame: per sensor its (depth uint16[H, W], colour uint8[Hc, Wc, bpp]) images, the depth image FULL-SIZE
+        also on a decimated rig.  occlusion: leave out the points the colour sensor cannot see (None: cwipc_hip_rgbd_rig_grab as it
+        is).  depthfilter: smooth the depth images first (None: the two other entries as they are).  holefill: fill the depth
+        images' holes after that (None: the three other entries as they are)."""
         if len(frame) != len(self.sensors):
             raise ValueError("RgbdRig: one (depth, colour) pair per sensor")
         structs = []
@@ -375,6 +400,10 @@ class RgbdRig:
             if colour.dtype != numpy.uint8 or colour.shape != (s.colour_height, s.colour_width, s.bpp) or not colour.flags['C_CONTIGUOUS']:
                 raise ValueError("RgbdRig: colour must be a contiguous uint8[colour_height, colour_width, bpp] array")
             structs.append(util.cwipc_hip_rgbd_frame(depth.ctypes.data, colour.ctypes.data))
+        if holefill is not None:
+            return util.cwipc_hip_rgbd_rig_grab_filled(self._handle(), structs, holefill.as_struct(), depthfilter.as_struct() if depthfilter is not None else None,
+                                                       prep.as_struct() if prep is not None else None, occlusion.as_struct() if occlusion is not None else None,
+                                                       filter.as_struct() if filter is not None else None, timestamp, cellsize, attach_flags)
         if depthfilter is not None:
             return util.cwipc_hip_rgbd_rig_grab_filtered(self._handle(), structs, depthfilter.as_struct(), prep.as_struct() if prep is not None else None,
                                                          occlusion.as_struct() if occlusion is not None else None,
@@ -390,17 +419,18 @@ class RgbdRig:
         util.cwipc_hip_rgbd_rig_reset_history(self._handle())
 
     def history(self, i: int) -> Tuple[numpy.ndarray, numpy.ndarray]:
-        """Sensor i's temporal-filter state: (running values float64[height, width], history bytes uint8[height, width])."""
+        """Sensor i's temporal-filter state: (running values float64[height, width], history bytes uint8[height, width]), on the
+        rig's grid."""
         if not 0 <= i < len(self.sensors):
             raise IndexError("RgbdRig: no such sensor")
-        return util.cwipc_hip_rgbd_rig_history(self._handle(), i, self.sensors[i].width, self.sensors[i].height)
+        return util.cwipc_hip_rgbd_rig_history(self._handle(), i, self.grid_sensors[i].width, self.grid_sensors[i].height)
 
     def ray_table(self, i: int) -> numpy.ndarray:
-        """Sensor i's ray table, float64[height, width, 2]: the undistorted normalised (x, y) of every depth pixel, NaN where the
-        lens model has none."""
+        """Sensor i's ray table, float64[height, width, 2]: the undistorted normalised (x, y) of every depth pixel of the rig's grid,
+        NaN where the lens model has none."""
         if not 0 <= i < len(self.sensors):
             raise IndexError("RgbdRig: no such sensor")
-        return util.cwipc_hip_rgbd_rig_ray_table(self._handle(), i, self.sensors[i].width, self.sensors[i].height)
+        return util.cwipc_hip_rgbd_rig_ray_table(self._handle(), i, self.grid_sensors[i].width, self.grid_sensors[i].height)
 
     def map2d3d(self, i: int, u: int, v: int, d: int) -> Optional[Tuple[float, float, float]]:
         return util.cwipc_hip_rgbd_rig_map2d3d(self._handle(), i, u, v, d)
@@ -412,16 +442,17 @@ class RgbdRig:
 class RgbdRigSource(RgbdSource):
     """RgbdSource for raw sensor pairs: the same surface -- get, request_metadata, auxiliary_operation("map2d3d" / "mapcolordepth"),
     serial_dict -- over an RgbdRig, which it makes and frees.  The attached "rgb." image lies on the depth grid, so both mappings
-    take depth-grid coordinates."""
+    take depth-grid coordinates: those of the decimated grid when decimation > 1, which is also the size of the attached images."""
 
     def __init__(self, sensors: Sequence[RgbdSensor], frames: Union[Iterable[Frame], Callable[[], Optional[Frame]]], filter: Optional[RgbdFilter] = None,
                  prep: Optional[RgbdPrep] = None, cellsize: float = 0.0, first_timestamp: int = 0, occlusion: Optional[RgbdOcclusion] = None,
-                 depthfilter: Optional[RgbdDepthFilter] = None) -> None:
+                 depthfilter: Optional[RgbdDepthFilter] = None, decimation: int = 1, holefill: Optional[RgbdHoleFill] = None) -> None:
         super().__init__(sensors, frames, filter, cellsize, first_timestamp)   # type: ignore[arg-type]  # (tile, serial, trafo: all it reads)
         self.prep = prep
         self.occlusion = occlusion
         self.depthfilter = depthfilter
-        self.rig = RgbdRig(sensors)
+        self.holefill = holefill
+        self.rig = RgbdRig(sensors, decimation)
 
     def free(self) -> None:
         super().free()
@@ -433,7 +464,8 @@ class RgbdRigSource(RgbdSource):
         frame, self._pending = self._pending, None
         flags = (util.CWIPC_HIP_RGBD_ATTACH_RGB if "rgb" in self._requested else 0) | (util.CWIPC_HIP_RGBD_ATTACH_DEPTH if "depth" in self._requested else 0)
         assert frame is not None
-        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags, self.occlusion, self.depthfilter)
+        pc = self.rig.grab(frame, self.filter, self.prep, self._first_timestamp + self._count, self.cellsize, flags, self.occlusion, self.depthfilter,
+                           self.holefill)
         self._count += 1
         return pc
 

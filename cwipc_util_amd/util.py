@@ -56,7 +56,8 @@ __all__ = [
     'cwipc_hip_rgbd_map2d3d', 'cwipc_hip_rgbd_mapcolordepth',
     'cwipc_hip_rgbd_sensor', 'cwipc_hip_rgbd_frame', 'cwipc_hip_rgbd_prep', 'cwipc_hip_rgbd_rig_create', 'cwipc_hip_rgbd_rig_free',
     'cwipc_hip_rgbd_rig_grab', 'cwipc_hip_rgbd_occlusion', 'cwipc_hip_rgbd_rig_grab_occluded', 'cwipc_hip_rgbd_depthfilter',
-    'cwipc_hip_rgbd_rig_grab_filtered', 'cwipc_hip_rgbd_rig_reset_history', 'cwipc_hip_rgbd_rig_history', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
+    'cwipc_hip_rgbd_rig_grab_filtered', 'cwipc_hip_rgbd_rig_create_decimated', 'cwipc_hip_rgbd_rig_decimation', 'cwipc_hip_rgbd_rig_grid_sensor',
+    'cwipc_hip_rgbd_holefill', 'cwipc_hip_rgbd_rig_grab_filled', 'cwipc_hip_rgbd_rig_reset_history', 'cwipc_hip_rgbd_rig_history', 'cwipc_hip_rgbd_rig_ray_table', 'cwipc_hip_rgbd_rig_map2d3d', 'cwipc_hip_rgbd_rig_mapcolordepth',
     # the octree codec (cwipc_util_amd.codec has the names the reference's callers use)
     'cwipc_hip_encoder_params', 'cwipc_hip_codec_info', 'cwipc_hip_codec_packet_info',
     'cwipc_hip_new_encoder', 'cwipc_hip_encoder_free', 'cwipc_hip_encoder_feed', 'cwipc_hip_encoder_available', 'cwipc_hip_encoder_get_encoded_size',
@@ -283,6 +284,11 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
                                          cwipc_pointcloud_p),
     'cwipc_hip_rgbd_rig_grab_filtered': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float, _c.c_int,
                                           _ERR], cwipc_pointcloud_p),
+    'cwipc_hip_rgbd_rig_create_decimated': ([_c.c_void_p, _c.c_int, _c.c_int, _ERR], _c.c_void_p),
+    'cwipc_hip_rgbd_rig_decimation': ([_c.c_void_p], _c.c_int),
+    'cwipc_hip_rgbd_rig_grid_sensor': ([_c.c_void_p, _c.c_int, _c.c_void_p], _c.c_int),
+    'cwipc_hip_rgbd_rig_grab_filled': ([_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_float,
+                                        _c.c_int, _ERR], cwipc_pointcloud_p),
     'cwipc_hip_rgbd_rig_reset_history': ([_c.c_void_p], None),
     'cwipc_hip_rgbd_rig_history': ([_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_rgbd_rig_ray_table': ([_c.c_void_p, _c.c_int], _c.POINTER(_c.c_double)),
@@ -1574,6 +1580,60 @@ def cwipc_hip_rgbd_rig_grab_filtered(rig: int, frames: Sequence[cwipc_hip_rgbd_f
     if rv:
         return cwipc_pointcloud_wrapper(rv)
     raise CwipcError("cwipc_hip_rgbd_rig_grab_filtered: no pointcloud created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_create_decimated(sensors: Sequence[cwipc_hip_rgbd_sensor], decimation: int) -> int:
+    """cwipc_hip_rgbd_rig_create for a rig that decimates its depth images by `decimation` (1 .. 8) on the device before anything
+    else: it is handed full-size frames and works on the decimated grid with derived sensors from there on.  decimation 1: exactly
+    cwipc_hip_rgbd_rig_create.  The exact contract (RULE D) is in include/cwipc_util_amd/hip_ext.h."""
+    n = len(sensors)
+    array = (cwipc_hip_rgbd_sensor * max(n, 1))(*sensors)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_create_decimated(ctypes.addressof(array), n, int(decimation), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return rv
+    raise CwipcError("cwipc_hip_rgbd_rig_create_decimated: no rig created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_decimation(rig: int) -> int:
+    """The rig's decimation, 1 .. 8."""
+    return cwipc_util_dll_load().cwipc_hip_rgbd_rig_decimation(rig)
+
+
+def cwipc_hip_rgbd_rig_grid_sensor(rig: int, cam: int) -> cwipc_hip_rgbd_sensor:
+    """Camera cam's sensor on the rig's grid: the derived one of a decimated rig, the caller's own otherwise; serial is None in it."""
+    out = cwipc_hip_rgbd_sensor()
+    if cwipc_util_dll_load().cwipc_hip_rgbd_rig_grid_sensor(rig, int(cam), ctypes.addressof(out)) != 0:
+        raise CwipcError("cwipc_hip_rgbd_rig_grid_sensor: no such camera")
+    return out
+
+
+class cwipc_hip_rgbd_holefill(ctypes.Structure):
+    """Hole filling of the raw entry's depth images: 0 off, 1 from the left, 2 the farthest around, 3 the nearest around."""
+    _fields_ = [("mode", ctypes.c_int32)]
+
+
+def cwipc_hip_rgbd_rig_grab_filled(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], holefill: Optional[cwipc_hip_rgbd_holefill] = None,
+                                   depthfilter: Optional[cwipc_hip_rgbd_depthfilter] = None, prep: Optional[cwipc_hip_rgbd_prep] = None,
+                                   occlusion: Optional[cwipc_hip_rgbd_occlusion] = None, filter: Optional[cwipc_hip_rgbd_filter] = None,
+                                   timestamp: int = 0, cellsize: float = 0.0, attach_flags: int = 0) -> cwipc_pointcloud_wrapper:
+    """cwipc_hip_rgbd_rig_grab_filtered with the holes of the depth images filled on the GPU between the temporal filter and the
+    erosion.  holefill None, or mode 0: exactly cwipc_hip_rgbd_rig_grab_filtered.  The exact contract (rule 0c) is in
+    include/cwipc_util_amd/hip_ext.h."""
+    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_filled(rig, ctypes.addressof(array) if len(frames) else None,
+                                                              ctypes.addressof(holefill) if holefill is not None else None,
+                                                              ctypes.addressof(depthfilter) if depthfilter is not None else None,
+                                                              ctypes.addressof(prep) if prep is not None else None,
+                                                              ctypes.addressof(occlusion) if occlusion is not None else None,
+                                                              ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
+                                                              int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError("cwipc_hip_rgbd_rig_grab_filled: no pointcloud created, but no specific error returned from C library")
 
 
 def cwipc_hip_rgbd_rig_reset_history(rig: int) -> None:

@@ -507,9 +507,38 @@ typedef struct cwipc_hip_rgbd_rig cwipc_hip_rgbd_rig;
  * depth_scale or matrix entry that is not finite, a focal length that is zero.  One grab at a time per rig (calls are serialised). */
 _CWIPC_UTIL_EXPORT cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create(const cwipc_hip_rgbd_sensor *sensors, int ncam, char **errorMessage);
 _CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_free(cwipc_hip_rgbd_rig *rig);
+/* A rig that DECIMATES its depth images by `decimation` = k (1 .. 8) on the device, as the first step of every grab entry.
+ * Such a rig is handed FULL-SIZE frames, width x height depth pixels as the sensor delivers them; everything after the decimation
+ * lives on the decimated grid with DERIVED sensors: rules 0a - 0c and their per-pixel state, erosion, ray table, registration,
+ * occlusion, compaction, the attached "depth.<serial>" / "rgb.<serial>" images and their "width=..,height=.." strings, rig_history,
+ * rig_ray_table, rig_map2d3d and rig_mapcolordepth.  This project's own definition (the camera plug-ins that hold the vendors'
+ * versions are not in the reference tree); csrc/rgbd_decimate.hpp is the one statement of it, tests/rgbd_decimate_model.py its numpy
+ * restatement.
+ * RULE D.  Arithmetic is float64, every operation rounded on its own;  q(x) = (uint16) floor(x + 0.5)  as in rule 0.
+ *   The derived sensor:  W' = W div k;  H' = H div k.  Source columns from k*W' and rows from k*H' onward are never read.
+ *     fx' = fx / k;  fy' = fy / k;  cx' = (cx - (k - 1) * 0.5) / k;  cy' alike: decimated pixel U sits at the centre of source pixels
+ *     kU .. kU + k - 1.  The lens coefficients, depth_scale, every colour-side field, both matrices and the tile are unchanged.  The ray
+ *     table is the rule above on the derived sensor, and the pinhole exception of rule 2 uses fx' and cx'.
+ *   The value of decimated pixel (U, V), n the number of NON-ZERO values among the k * k source pixels (kU + i, kV + j), 0 <= i, j < k:
+ *     n == 0:       0
+ *     k = 2 or 3:   the LOWER MEDIAN: with the non-zero values sorted ascending, a[(n - 1) div 2]
+ *     k = 4 .. 8:   q((double) sum / (double) n), sum the exact integer sum of the non-zero values
+ *   The result lies in 1 .. 65535 whenever n > 0: no clamp is part of the rule.
+ * decimation == 1 is cwipc_hip_rgbd_rig_create itself, byte for byte in everything observable.  NULL (the text in errorMessage and
+ * cwipc_hip_last_error(), nothing allocated) for a decimation outside 1 .. 8, a sensor with width < k or height < k, and everything
+ * cwipc_hip_rgbd_rig_create refuses (its limit of 2^31 - 1 depth pixels counts the full-size images). */
+_CWIPC_UTIL_EXPORT cwipc_hip_rgbd_rig *cwipc_hip_rgbd_rig_create_decimated(const cwipc_hip_rgbd_sensor *sensors, int ncam, int decimation,
+                                                                           char **errorMessage);
+/* 1 .. 8; 0 for NULL */
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_decimation(const cwipc_hip_rgbd_rig *rig);
+/* Camera cam's sensor on the rig's grid -- the derived one of RULE D, the caller's own when decimation == 1 -- with serial = NULL in the
+ * copy; 0 ok, -1 for a bad argument. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_grid_sensor(const cwipc_hip_rgbd_rig *rig, int cam, cwipc_hip_rgbd_sensor *out);
 /* One device-resident cloud from one frame (frames: ncam entries, in the sensors' order).  Per camera:
- *  0. Only through cwipc_hip_rgbd_rig_grab_filtered (below, where rules 0a and 0b are stated): the depth image is replaced by its
- *     spatially and temporally filtered version.  Rules 1-4 run on that image.
+ *  D. Only on a rig made by cwipc_hip_rgbd_rig_create_decimated with decimation > 1 (above, RULE D): the full-size depth image is
+ *     replaced by its decimated version, and "the sensor" below is the derived one.
+ *  0. Only through cwipc_hip_rgbd_rig_grab_filtered (below, where rules 0a and 0b are stated) and cwipc_hip_rgbd_rig_grab_filled (rule
+ *     0c): the depth image is replaced by its spatially and temporally filtered, then hole-filled version.  Rules 1-4 run on that image.
  *  1. Erosion of the depth image (prep may be NULL: none): a pixel keeps its depth iff no pixel (u + du, v + dv) with |du| <=
  *     depth_x_erosion, |dv| <= depth_y_erosion that lies inside the image has depth 0.  Pixels outside the image do not erode.
  *  2. The point of pixel (u, v), depth d != 0:  z = (double)d * depth_scale;  xc = xn*z;  yc = yn*z, (xn, yn) the ray table's entry;
@@ -600,6 +629,27 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filtered(cwipc_hip_
                                                                       const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep,
                                                                       const cwipc_hip_rgbd_occlusion *occlusion, const cwipc_hip_rgbd_filter *filter,
                                                                       uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage);
+/* The same with HOLE FILLING between rule 0b and rule 1; this project's own definition, stated in csrc/rgbd_decimate.hpp
+ * and restated in tests/rgbd_decimate_model.py.  RULE 0c, per camera, on the rig's grid, on the image rules 0a and 0b leave:
+ *   mode 1 (from the left):      a pixel without depth takes the value of the nearest pixel WITH depth to its left in the same row; if
+ *                                there is none it stays 0.
+ *   mode 2 (farthest around):    a pixel without depth takes the largest non-zero value among its up to eight neighbours inside the
+ *                                image, read from the stage's INPUT: the fill is not in place, nothing propagates, the result does not
+ *                                depend on an order.  If no neighbour has depth it stays 0.
+ *   mode 3 (nearest around):     the same with the smallest non-zero value.
+ * A pixel that has depth is never changed.  The temporal state (s, h) is what it would be without this stage: rule 0b has run before it
+ * and sees the holes.  Modes 2 and 3 use a scratch depth plane (2 bytes per depth pixel), allocated by a rig's first grab that needs
+ * it and freed with the rig.  holefill == NULL or mode == 0: cwipc_hip_rgbd_rig_grab_filtered byte for byte, in launches as well.
+ * NULL, and nothing left behind (the history untouched), for a mode outside 0 .. 3 and everything cwipc_hip_rgbd_rig_grab_filtered
+ * refuses. */
+typedef struct cwipc_hip_rgbd_holefill {
+    int32_t mode;                               /* 0 off, 1 from the left, 2 farthest around, 3 nearest around */
+} cwipc_hip_rgbd_holefill;
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_rgbd_rig_grab_filled(cwipc_hip_rgbd_rig *rig, const cwipc_hip_rgbd_frame *frames,
+                                                                    const cwipc_hip_rgbd_holefill *holefill, const cwipc_hip_rgbd_depthfilter *depthfilter,
+                                                                    const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion,
+                                                                    const cwipc_hip_rgbd_filter *filter, uint64_t timestamp, float cellsize,
+                                                                    int attach_flags, char **errorMessage);
 _CWIPC_UTIL_EXPORT void cwipc_hip_rgbd_rig_reset_history(cwipc_hip_rgbd_rig *rig);
 /* For parity tests: camera cam's running values (width * height doubles) and history bytes (width * height) into host memory; 0 ok,
  * -1 for a bad argument or a failed copy; a rig without state yet reports zeros. */
