@@ -25,6 +25,11 @@ def word_of_bits(bits):
     return word
 
 
+def bits_of_word(word):
+    """word_of_bits' inverse: the 5 x 5 of 0/1 of a payload word (bits 25-31 are not looked at)."""
+    return [[(int(word) >> (24 - (5 * r + c))) & 1 for c in range(5)] for r in range(5)]
+
+
 def fixture_bits():
     with open(FIXTURE) as f:
         return json.load(f)
@@ -88,8 +93,13 @@ def _arg_extreme(value, index):
     return int(index[value == best].min())
 
 
-def quad_of_component(index, W):
-    """index: the component's linear indices (any order).  Q0..Q3 as (x, y) tuples, or None."""
+ONE_SIDED = "no pixel on one side of AC"
+NOT_CONVEX = "A, B, C, D is not strictly convex"
+
+
+def quad_verdict(index, W):
+    """index: the component's linear indices (any order).  (Q0..Q3 as (x, y) tuples, None), or (None, the reason step 5 rejects the
+    component for: ONE_SIDED when k(B) > 0 > k(D) fails, NOT_CONVEX)."""
     index = np.asarray(index, dtype=np.int64)
     x, y = index % W, index // W
     p0 = int(index.min())
@@ -100,7 +110,7 @@ def quad_of_component(index, W):
     k = (x - ax) * (cy - ay) - (y - ay) * (cx - ax)
     b, d = _arg_extreme(k, index), _arg_extreme(-k, index)
     if not (k.max() > 0 > k.min()):
-        return None
+        return None, ONE_SIDED
     P = [(int(i % W), int(i // W)) for i in (a, b, c, d)]
     cross = []
     shoelace = 0
@@ -109,8 +119,13 @@ def quad_of_component(index, W):
         cross.append((x1 - x0) * (y2 - y1) - (y1 - y0) * (x2 - x1))
         shoelace += x0 * y1 - x1 * y0
     if not (all(v > 0 for v in cross) or all(v < 0 for v in cross)):
-        return None
-    return P if shoelace > 0 else [P[0], P[3], P[2], P[1]]
+        return None, NOT_CONVEX
+    return (P if shoelace > 0 else [P[0], P[3], P[2], P[1]]), None
+
+
+def quad_of_component(index, W):
+    """Q0..Q3 as (x, y) tuples, or None."""
+    return quad_verdict(index, W)[0]
 
 
 def map_coefficients(Q):
@@ -152,12 +167,15 @@ def read_cells(dark, Q):
     return black
 
 
-def decode_cells(black, words, max_border_errors=2, max_bit_errors=0):
-    """(id, k) or None."""
+def code_of_cells(black):
+    """(the number of white border cells, the 25 inner cells as a code, white = 1)."""
     border_white = sum(1 for i in range(7) for j in range(7) if (i in (0, 6) or j in (0, 6)) and not black[i][j])
-    if border_white > max_border_errors:
-        return None
-    code = word_of_bits([[0 if black[i + 1][j + 1] else 1 for j in range(5)] for i in range(5)])
+    return border_white, word_of_bits([[0 if black[i + 1][j + 1] else 1 for j in range(5)] for i in range(5)])
+
+
+def search_words_loop(code, words, max_bit_errors=0):
+    """(id, k) of the smallest Hamming distance between the code's four rotations and the words, ties to the smallest id, then the
+    smallest k, or None when that distance is above max_bit_errors: one comparison after the other."""
     rot = [rotate_code(code, k) for k in range(4)]
     best = None
     for id, word in enumerate(words):
@@ -170,36 +188,90 @@ def decode_cells(black, words, max_border_errors=2, max_bit_errors=0):
     return best[1], best[2]
 
 
+_POPCOUNT8 = np.array([bin(v).count("1") for v in range(256)], dtype=np.int64)
+
+
+def masked_words(words):
+    """The dictionary as search_words reads it: uint32[n], bits 25-31 cleared."""
+    return (np.asarray([int(w) for w in words], dtype=np.uint64) & 0x1FFFFFF).astype(np.uint32)
+
+
+def search_words(code, words, max_bit_errors=0):
+    """search_words_loop in numpy: xor of every word with the four rotations, a popcount per byte, and the lexicographic minimum
+    over (distance, id, k).  words: a sequence of ints, or what masked_words() made of one."""
+    if not (isinstance(words, np.ndarray) and words.dtype == np.uint32):
+        words = masked_words(words)
+    if len(words) == 0:
+        return None
+    rot = np.array([rotate_code(code, k) for k in range(4)], dtype=np.uint32)
+    x = np.ascontiguousarray(words[:, None] ^ rot[None, :])           # [id, k]
+    dist = _POPCOUNT8[x.view(np.uint8)].reshape(len(words), 4, 4).sum(axis=2)
+    id, k = np.nonzero(dist == dist.min())                            # row-major: ascending id, then ascending k
+    if dist[id[0], k[0]] > max_bit_errors:
+        return None
+    return int(id[0]), int(k[0])
+
+
+def decode_cells_loop(black, words, max_border_errors=2, max_bit_errors=0):
+    """(id, k) or None, the dictionary searched by search_words_loop."""
+    border_white, code = code_of_cells(black)
+    if border_white > max_border_errors:
+        return None
+    return search_words_loop(code, words, max_bit_errors)
+
+
+def decode_cells(black, words, max_border_errors=2, max_bit_errors=0):
+    """(id, k) or None."""
+    border_white, code = code_of_cells(black)
+    if border_white > max_border_errors:
+        return None
+    return search_words(code, words, max_bit_errors)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the whole detector
 # ---------------------------------------------------------------------------------------------------------------------------------
-def detect(rgb, words, **params):
-    """(ids: list of int, corners: int64[n, 4, 2] as (u, v)), sorted by id."""
+def candidates(rgb, words, **params):
+    """Steps 1 to 7: per component that passes step 4, in the order of the labels, the tuple (label, area, Q, hit): Q = the
+    quadrilateral Q0..Q3 of step 5 as (x, y) tuples, or None when step 5 rejects the component; hit = (id, k) of step 7, or None when
+    there is no quadrilateral or step 7 rejects it."""
     p = dict(DEFAULTS)
     p.update(params)
     H, W = rgb.shape[:2]
+    words = masked_words(words)
     dark = dark_mask(rgb, p['window_half'], p['threshold_offset'])
     lab = label_image(dark).reshape(-1)
     where = np.nonzero(lab >= 0)[0]
     order = np.argsort(lab[where], kind='stable')
     where = where[order]
-    bounds = np.nonzero(np.diff(lab[where], prepend=-1))[0].tolist() + [len(where)]
-    found = {}
-    for s, e in zip(bounds[:-1], bounds[1:]):
+    starts = np.nonzero(np.diff(lab[where], prepend=-1))[0]
+    out = []
+    if len(starts) == 0:
+        return out
+    # step 4 for all components at once (an image of noise has a hundred thousand): the bounding boxes of the runs of equal labels
+    xs, ys = where % W, where // W
+    x0, x1 = np.minimum.reduceat(xs, starts), np.maximum.reduceat(xs, starts)
+    y0, y1 = np.minimum.reduceat(ys, starts), np.maximum.reduceat(ys, starts)
+    passes = (x0 > 0) & (y0 > 0) & (x1 < W - 1) & (y1 < H - 1) & (x1 - x0 + 1 >= p['min_side']) & (y1 - y0 + 1 >= p['min_side'])
+    ends = np.append(starts[1:], len(where))
+    for s, e in zip(starts[passes].tolist(), ends[passes].tolist()):
         index = where[s:e]
-        x, y = index % W, index // W
-        if x.min() == 0 or y.min() == 0 or x.max() == W - 1 or y.max() == H - 1:
-            continue
-        if x.max() - x.min() + 1 < p['min_side'] or y.max() - y.min() + 1 < p['min_side']:
-            continue
         Q = quad_of_component(index, W)
-        if Q is None:
-            continue
-        hit = decode_cells(read_cells(dark, Q), words, p['max_border_errors'], p['max_bit_errors'])
+        hit = None
+        if Q is not None:
+            hit = decode_cells(read_cells(dark, Q), words, p['max_border_errors'], p['max_bit_errors'])
+        out.append((int(lab[index[0]]), len(index), Q, hit))
+    return out
+
+
+def detect(rgb, words, **params):
+    """(ids: list of int, corners: int64[n, 4, 2] as (u, v)), sorted by id: step 8 on candidates()."""
+    found = {}
+    for label, area, Q, hit in candidates(rgb, words, **params):
         if hit is None:
             continue
         id, k = hit
-        rank = (-len(index), int(lab[index[0]]))   # largest area, then smallest label
+        rank = (-area, label)   # largest area, then smallest label
         if id not in found or rank < found[id][0]:
             found[id] = (rank, [Q[(q + k) % 4] for q in range(4)])
     ids = sorted(found)
