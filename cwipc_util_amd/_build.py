@@ -30,6 +30,8 @@ SOURCES = [
     "stubs.cpp",
     "ply.cpp",
     "filters.cpp",
+    "registration.cpp",
+    "render.cpp",
     "rgbd.cpp",
     "codec.cpp",
     "exchange.cpp",

@@ -169,18 +169,17 @@ bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits
     out.counts = (uint32_t *)(block + keys_bytes + index_bytes);
     void *partial = block + keys_bytes + index_bytes + counts_bytes;
     out.cube_dev = (k::CodecCube *)(block + keys_bytes + index_bytes + counts_bytes + bounds_bytes);
-    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
-    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    for (int L = 0; L < bits; L++) words[L] = 0ull;
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, bits);
     k::codec_cube(*src, partial, out.cube_dev, c.stream);
     bool ok = k::codec_sort(*src, out.cube_dev, bits, out.keys, out.index, c.stream);
     if (ok) {
-        k::codec_count_scan(out.keys + n, n, out.cube_dev, bits, out.counts, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        k::codec_count_scan(out.keys + n, n, out.cube_dev, bits, out.counts, report.device(), tag, c.stream);
         ok = hipMemcpyAsync(c.host_words + 32, out.cube_dev, sizeof(k::CodecCube), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
         ok = ok && hipGetLastError() == hipSuccess;
     }
     ok = c.sync() && ok;
-    for (int L = 0; ok && L < bits; L++) ok = (uint32_t)(words[L] >> 32) == tag;
+    ok = ok && report.landed(tag, 0, bits);
     if (!ok) {
         hip_failed(hipGetLastError(), "octree encode (sort)", __FILE__, __LINE__);
         pool_free(block);
@@ -188,7 +187,7 @@ bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits
         return false;
     }
     memcpy(&out.cube, c.host_words + 32, sizeof(k::CodecCube));
-    for (int L = 0; L < bits; L++) out.nodes[L] = (uint32_t)words[L];
+    for (int L = 0; L < bits; L++) out.nodes[L] = report.value(L);
     return true;
 }
 
@@ -472,23 +471,22 @@ bool entropy_to_body(const char *who, ThreadCtx &c, const uint8_t *bytes, const 
     d.colours = (uint32_t *)(body + (l.colour_offset - l.occupancy_offset));
     d.tiles = body + (l.tile_offset - l.occupancy_offset);
     d.colour_words = codec_pad4(l.colour_bytes) / 4;
-    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
-    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    words[0] = 0ull;
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 1);
     bool ok = hipMemcpyAsync(dev, host, table_offset + table_bytes, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
               hipMemsetAsync(d.flags, 0, flag_bytes, c.stream) == hipSuccess;
     if (ok) {
-        k::entropy_decode(d, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        k::entropy_decode(d, report.device(), tag, c.stream);
         ok = hipGetLastError() == hipSuccess;
     }
     ok = c.sync() && ok;   // the one wait: the streams are in `body`, the check's word is here
     host_free(host, pinned);
     pool_free(dev);
-    if (!ok || (uint32_t)(words[0] >> 32) != tag) {
+    if (!ok || !report.landed(tag, 0)) {
         hip_failed(hipGetLastError(), "octree decode (entropy stage)", __FILE__, __LINE__);
         return false;
     }
-    const uint32_t status = (uint32_t)words[0];
+    const uint32_t status = report.value(0);
     if (status & 1u) { note_error(who, "entropy-coded block is not intact"); return false; }
     if (status & 2u) { note_error(who, "occupancy byte is 0"); return false; }
     if (status & 4u) { note_error(who, "occupancy bits differ from the node count"); return false; }

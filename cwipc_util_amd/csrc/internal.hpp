@@ -6,7 +6,10 @@
 //   pointcloud.cpp  cwipc_hip_pointcloud container, C accessors, packet / dump I/O
 //   synthetic.cpp   cwipc_synthetic source          (reference src/cwipc_synthetic.cpp)
 //   stubs.cpp       out-of-scope constructors that fail loudly
-//   filters.cpp     C entry points of the hot path, host orchestration
+//   filters.cpp     C entry points of the hot path (compaction, exact filters, join, downsample, SOR, direction), host orchestration
+//   registration.cpp  C entry points of the registration tooling: distances, KDE, ICP, the floor and tile helpers, bounds
+//   render.cpp      C entry points of the renderer and the marker detector
+//   entry.hpp       how those three resolve and wrap their clouds
 //   codec.cpp       cwipc_hip_new_encoder / _encodergroup / _decoder: the octree codec (packets out, packets in)
 //   rgbd.cpp        cwipc_hip_from_rgbd, cwipc_hip_rgbd_rig_*: the RGB-D source end (images in, device-resident cloud out)
 //   kernels_*.hip   the HIP kernels (gfx950)
@@ -30,6 +33,7 @@
 #include "rgbd_lens.hpp"
 #include "rgbd_depthfilter.hpp"
 #include "rgbd_decimate.hpp"
+#include "pinned_report.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -101,6 +105,8 @@ struct ThreadCtx {
     void *scratch = nullptr;          // device scratch of this thread's calls (block counts of a compaction): work on one
     size_t scratch_bytes = 0;         //   stream is ordered, so the next call may overwrite it while nobody else can
     uint32_t tag = 0;                 // sequence number of the last value a kernel published into host_words
+    // host_words as 64-bit report words under `tag` (pinned_report.hpp)
+    PinnedReport report() { return PinnedReport(reinterpret_cast<volatile unsigned long long *>(host_words), tag); }
     void *device_scratch(size_t bytes);
     std::vector<void *> deferred;     // pool blocks whose last kernel may still run: given back at the next sync()
     void free_later(void *pool_block) { if (pool_block) deferred.push_back(pool_block); }
@@ -220,6 +226,14 @@ std::shared_ptr<DeviceSoA> soa_alloc(size_t npoints);
 std::shared_ptr<DeviceSoA> soa_with_new_rgbt(const std::shared_ptr<DeviceSoA> &src);
 // ... and the other way round: `src`'s colour / tile words, coordinate planes of its own.
 std::shared_ptr<DeviceSoA> soa_with_new_xyz(const std::shared_ptr<DeviceSoA> &src);
+// A cloud that holds `src`'s planes, all four (clouds are immutable): its blocks, count, stride and device, nothing else of it.
+std::shared_ptr<DeviceSoA> share_planes(const DeviceSoA &src);
+// A result of `kept` points at the front of planes with room for `room` stays in them when it uses a sixteenth of the room or more.
+inline bool soa_keeps_planes(size_t kept, size_t room) { return kept * 16 >= room; }
+// The result that is the first `kept` points of `dst` (room: dst->npoints): dst itself with its count shrunk -- the planes keep their
+// spacing (stride) -- or, when few survive, planes of their own size, copied on the calling thread's stream and waited for.  What
+// writes `dst` must be complete before the copy: the caller has waited.  nullptr: out of memory, or the copy failed (logged as `what`).
+std::shared_ptr<DeviceSoA> soa_keep(const std::shared_ptr<DeviceSoA> &dst, size_t kept, const char *what);
 
 // A filter result that is still being computed when the call returns: its planes exist, its point count does not yet.
 // cwipc_downsample (octree path) hands these out in a stream of frames, so that the host does not stand between one
@@ -679,7 +693,7 @@ bool nn_distance2_jobs(const DeviceSoA &source, const DeviceSoA &reference, cons
 bool gaussian_kde(const double *dev_samples, size_t n, double h, const double *dev_at, size_t m, double *dev_density);
 
 // ICP fine alignment (kernels_icp.hip; the contracts are at the top of that file).  T, init: 16 f64, row-major 4x4.  All of them wait
-// for their results.  False on failure (logged).  THE CALLER HAS CHECKED the scalar arguments (filters.cpp, once for both layers):
+// for their results.  False on failure (logged).  THE CALLER HAS CHECKED the scalar arguments (registration.cpp, once for both layers):
 // max_distance > 0 (not NaN), a finite matrix, the criteria, radius and max_nn where normals are estimated, epsilon; what depends
 // on a cloud's size is checked here: false also for a caller's normal that is not finite.
 struct IcpCriteria { double relative_fitness, relative_rmse; int max_iteration; };   // open3d's ICPConvergenceCriteria

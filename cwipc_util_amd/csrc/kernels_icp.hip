@@ -52,7 +52,7 @@
 // iteration (open3d moves an f64 copy step by step).  The updates: rigid_fit.hpp (umeyama without scaling, with the pivot
 // cp = T cp0 that follows the cloud) for point-to-point; plane_fit.hpp (A x = -b with A the 21 sums, b the 6) for the other two.
 //
-// The entry points at the bottom take arguments that their caller has checked (filters.cpp: the C entry points check every scalar
+// The entry points at the bottom take arguments that their caller has checked (registration.cpp: the C entry points check every scalar
 // argument, once); what depends on a cloud's size is checked here (the caller's normals), and so are the pivots of icp_sums.
 #include "point_grid.hpp"
 #include "rigid_fit.hpp"
@@ -341,7 +341,7 @@ void launch_sums(typename Pair::Args S, const DeviceSoA &source, const DeviceSoA
     S.chunk = w.chunk;
     CW_LAUNCH(Pair::PARTIAL, (icp_sums_partial_kernel<Pair>), dim3((unsigned)w.nchunks), dim3(GRID_BLK), 0, s, S, w.partial);
     CW_LAUNCH(Pair::FINAL, (icp_sums_final_kernel<Pair::NSUM>), dim3(1), dim3(ICP_FINAL_THREADS), 0, s, w.partial, w.nchunks,
-              reinterpret_cast<unsigned long long *>(c.host_words), (unsigned long long)tag);
+              c.report().device(), (unsigned long long)tag);
 }
 
 PointPair::Args point_args(const double cp[3], const double cq[3]) {
@@ -358,23 +358,21 @@ PlanePair::Args plane_args(const float *normals, size_t nr) {
 
 // after a wait on the stream: the pinned words into n and the nsum - 1 sums
 bool read_sums(ThreadCtx &c, uint32_t tag, int nsum, uint64_t *n, double *sums) {
-    const volatile unsigned long long *words = reinterpret_cast<const volatile unsigned long long *>(c.host_words);
-    if (words[nsum] != (unsigned long long)tag) {
+    const PinnedReport report = c.report();
+    if (!report.landed_plain(tag, nsum)) {
         cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip_icp", nsum == PointPair::NSUM ? "the sums kernel did not report" : "the plane sums kernel did not report");
         return false;
     }
-    *n = words[0];
+    *n = report.raw(0);
     for (int v = 0; v < nsum - 1; v++) {
-        const unsigned long long bits = words[1 + v];
+        const unsigned long long bits = report.raw(1 + v);
         memcpy(&sums[v], &bits, sizeof(double));
     }
     return true;
 }
 
 uint32_t next_tag(ThreadCtx &c, int nsum) {
-    volatile unsigned long long *words = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    words[nsum] = 0ull;
-    return ++c.tag ? c.tag : ++c.tag;
+    return c.report().arm(nsum, 1);   // (the word behind the nsum values is the tag's)
 }
 
 // The reference cloud's normals as three planes of count(reference) floats in one pool block (and, behind them, the three doubles

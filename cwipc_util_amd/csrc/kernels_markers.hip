@@ -22,7 +22,7 @@
 //                  compared in the four rotations with dictionary[id] & 0x1FFFFFF (bit 24 - (5*row + col)); rotation k: the
 //                  marker's top-left corner is Q_k; smallest Hamming distance, ties to the smallest id, then the smallest k;
 //                  accepted iff the distance is <= max_bit_errors; corners out: Q_k, Q_(k+1), Q_(k+2), Q_(k+3).
-//   8. output      per id the candidate of largest area (ties: smallest label), sorted by id (host side, filters.cpp).
+//   8. output      per id the candidate of largest area (ties: smallest label), sorted by id (host side, render.cpp).
 //
 // Magnitudes, L = the larger image side.  Coordinates are < L, so squared distances and |k| are < 2 L^2 and are packed into 32 bits
 // (k with a bias of 2^31): L <= 2^14 keeps them below 2^29.  In the map, |Dn| < 2 L^2, |G|, |H| < 4 L^2, the numerator

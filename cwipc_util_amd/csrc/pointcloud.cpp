@@ -98,6 +98,35 @@ std::shared_ptr<DeviceSoA> soa_with_new_rgbt(const std::shared_ptr<DeviceSoA> &s
     return soa;
 }
 
+std::shared_ptr<DeviceSoA> share_planes(const DeviceSoA &src) {
+    auto same = std::make_shared<DeviceSoA>();
+    same->xyz_block = src.xyz_block;
+    same->rgbt_block = src.rgbt_block;
+    same->npoints = src.npoints;
+    same->stride = src.stride;
+    same->device = src.device;
+    return same;
+}
+
+std::shared_ptr<DeviceSoA> soa_keep(const std::shared_ptr<DeviceSoA> &dst, size_t kept, const char *what) {
+    if (soa_keeps_planes(kept, dst->npoints)) {
+        dst->npoints = kept;
+        return dst;
+    }
+    ThreadCtx &c = tctx();
+    auto small = soa_alloc(kept);
+    if (!small) return nullptr;
+    if (kept) {
+        bool copied = hipMemcpyAsync(small->x(), dst->x(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                      hipMemcpyAsync(small->y(), dst->y(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                      hipMemcpyAsync(small->z(), dst->z(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
+                      hipMemcpyAsync(small->rgbt(), dst->rgbt(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess;
+        copied = c.sync() && copied;
+        if (!copied) { hip_failed(hipGetLastError(), what, __FILE__, __LINE__); return nullptr; }
+    }
+    return small;
+}
+
 // ---------------------------------------------------------------------------
 // cwipc_hip_pointcloud
 // ---------------------------------------------------------------------------

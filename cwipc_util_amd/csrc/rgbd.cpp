@@ -64,33 +64,36 @@ void attach_image(cwipc_metadata *meta, const std::string &name, const cwipc_hip
     meta->_add(name, "width=" + std::to_string(cam.width) + ",height=" + std::to_string(cam.height) + ",bpp=" + std::to_string(bpp), copy, bytes, ::free);
 }
 
+// The caller's errorMessage is where the log's errors go for as long as an entry point runs.
+struct ErrorbufScope {
+    explicit ErrorbufScope(char **errorMessage) { cwipc_log_set_errorbuf(errorMessage); }
+    ~ErrorbufScope() { cwipc_log_set_errorbuf(nullptr); }
+};
+
+RgbdFilterTerms filter_terms(const cwipc_hip_rgbd_filter *filter) {
+    RgbdFilterTerms f{};
+    if (filter) {
+        f.near_z = filter->threshold_near; f.far_z = filter->threshold_far;
+        f.height_min = filter->height_min; f.height_max = filter->height_max;
+        f.radius = filter->radius; f.green = filter->greenscreen;
+    }
+    return f;
+}
+
 // After the stream has been waited for (ok: everything until then went well): the cloud of the `kept` points the scan published under
 // `tag`, in dst's planes (room for total points) or, when few survive, in planes of their own.  nullptr: the error has been noted.
-cwipc_hip_pointcloud *finish_cloud(const char *who, ThreadCtx &c, bool ok, uint32_t tag, size_t total, std::shared_ptr<DeviceSoA> dst, const uint32_t tiles[8],
+cwipc_hip_pointcloud *finish_cloud(const char *who, ThreadCtx &c, bool ok, uint32_t tag, std::shared_ptr<DeviceSoA> dst, const uint32_t tiles[8],
                                    uint64_t timestamp, float cellsize) {
-    volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    const size_t kept = (uint32_t)*word;
-    if (!ok || (uint32_t)(*word >> 32) != tag || kept > total) {
+    const PinnedReport report = c.report();
+    const size_t kept = report.value(0);
+    if (!ok || !report.landed(tag, 0) || kept > dst->npoints) {
         if (ok) note_error(who, "inconsistent point count");
         else if (!*cwipc_hip_last_error()) note_error(who, "a kernel or a copy failed");
         else cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, cwipc_hip_last_error());
         return nullptr;
     }
-    if (kept * 16 >= total) {
-        dst->npoints = kept;   // the planes keep their spacing, only the count shrinks (as a compaction's result)
-    } else {
-        auto small = soa_alloc(kept);
-        if (!small) return nullptr;
-        if (kept) {
-            bool copied = hipMemcpyAsync(small->x(), dst->x(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->y(), dst->y(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->z(), dst->z(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess &&
-                          hipMemcpyAsync(small->rgbt(), dst->rgbt(), kept * 4, hipMemcpyDeviceToDevice, c.stream) == hipSuccess;
-            copied = c.sync() && copied;
-            if (!copied) { hip_failed(hipGetLastError(), who, __FILE__, __LINE__); return nullptr; }
-        }
-        dst = small;
-    }
+    dst = soa_keep(dst, kept, who);   // (as a compaction's result)
+    if (!dst) return nullptr;
     dst->set_tiles(tiles);
     auto *rv = new cwipc_hip_pointcloud();
     rv->adopt_device(dst, timestamp, cellsize);
@@ -102,8 +105,7 @@ cwipc_hip_pointcloud *finish_cloud(const char *who, ThreadCtx &c, bool ok, uint3
 extern "C" cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_camera *cams, int ncam, const cwipc_hip_rgbd_filter *filter, uint64_t timestamp,
                                                  float cellsize, int attach_flags, char **errorMessage) {
     const char *who = "cwipc_hip_from_rgbd";
-    cwipc_log_set_errorbuf(errorMessage);
-    struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
+    ErrorbufScope errors(errorMessage);
     if (cams == nullptr || ncam <= 0) {
         note_error(who, cams == nullptr ? "NULL argument" : "ncam must be at least 1");
         return nullptr;
@@ -134,12 +136,7 @@ extern "C" cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_camera *ca
     ThreadCtx &c = tctx();
     if (!c.ensure()) return nullptr;
 
-    RgbdFilterTerms f{};
-    if (filter) {
-        f.near_z = filter->threshold_near; f.far_z = filter->threshold_far;
-        f.height_min = filter->height_min; f.height_max = filter->height_max;
-        f.radius = filter->radius; f.green = filter->greenscreen;
-    }
+    const RgbdFilterTerms f = filter_terms(filter);
     // one device block: the table of cameras | every camera's depth image | its colour image, each part on a 256-byte boundary
     const size_t table_bytes = round256((size_t)ncam * sizeof(k::RgbdCamDev));
     const size_t nb = k::rgbd_blocks((uint32_t)total);
@@ -173,17 +170,16 @@ extern "C" cwipc_pointcloud *cwipc_hip_from_rgbd(const cwipc_hip_rgbd_camera *ca
     }
     ok = ok && hipMemcpyAsync(dev, table, (size_t)ncam * sizeof(k::RgbdCamDev), hipMemcpyHostToDevice, c.stream) == hipSuccess;
     // the scan publishes the point count with this tag in the upper half of the first 64-bit pinned word (as the compaction driver's)
-    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
-    volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    *word = 0ull;
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 1);
     if (ok) {
-        k::rgbd_count((const k::RgbdCamDev *)dev, ncam, (uint32_t)total, f, counts, c.tickets, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        k::rgbd_count((const k::RgbdCamDev *)dev, ncam, (uint32_t)total, f, counts, c.tickets, report.device(), tag, c.stream);
         k::rgbd_scatter((const k::RgbdCamDev *)dev, ncam, (uint32_t)total, f, counts, *dst, c.stream);
         ok = hipGetLastError() == hipSuccess;
     }
     ok = c.sync() && ok;   // (also on failure: copies that read the staging buffer and kernels that write the planes may be in flight)
     pool_free(dev);
-    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, (size_t)total, dst, tiles, timestamp, cellsize);
+    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, dst, tiles, timestamp, cellsize);
     if (!rv) return nullptr;
     if (attach_flags & (CWIPC_HIP_RGBD_ATTACH_RGB | CWIPC_HIP_RGBD_ATTACH_DEPTH)) {
         cwipc_metadata *meta = rv->access_metadata();
@@ -285,8 +281,7 @@ bool rig_camera_ok(const cwipc_hip_rgbd_rig *rig, int cam) { return rig != nullp
 
 // cwipc_hip_rgbd_rig_create (decimation 1) and cwipc_hip_rgbd_rig_create_decimated
 cwipc_hip_rgbd_rig *rig_create(const char *who, const cwipc_hip_rgbd_sensor *sensors, int ncam, int decimation, char **errorMessage) {
-    cwipc_log_set_errorbuf(errorMessage);
-    struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
+    ErrorbufScope errors(errorMessage);
     if (sensors == nullptr || ncam <= 0) {
         note_error(who, sensors == nullptr ? "NULL argument" : "ncam must be at least 1");
         return nullptr;
@@ -438,8 +433,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
                            const cwipc_hip_rgbd_depthfilter *depthfilter, const cwipc_hip_rgbd_prep *prep, const cwipc_hip_rgbd_occlusion *occlusion,
                            const cwipc_hip_rgbd_filter *filter,
                            uint64_t timestamp, float cellsize, int attach_flags, char **errorMessage) {
-    cwipc_log_set_errorbuf(errorMessage);
-    struct ErrorbufReset { ~ErrorbufReset() { cwipc_log_set_errorbuf(nullptr); } } reset;
+    ErrorbufScope errors(errorMessage);
     if (rig == nullptr || frames == nullptr) {
         note_error(who, "NULL argument");
         return nullptr;
@@ -506,12 +500,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
     }
     std::lock_guard<std::mutex> guard(rig->lock);
 
-    RgbdFilterTerms f{};
-    if (filter) {
-        f.near_z = filter->threshold_near; f.far_z = filter->threshold_far;
-        f.height_min = filter->height_min; f.height_max = filter->height_max;
-        f.radius = filter->radius; f.green = filter->greenscreen;
-    }
+    const RgbdFilterTerms f = filter_terms(filter);
     const uint32_t total = rig->total;
     const size_t nb = k::rgbd_blocks(total);
     uint8_t *stage = (uint8_t *)c.staging(staged_bytes ? staged_bytes : 256);
@@ -564,9 +553,8 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         ok = upload(frames[k].depth, (size_t)s.width * (size_t)s.height * 2, t.full_depth ? (uint8_t *)t.full_depth : (uint8_t *)t.depth_rw, &stage, c.stream) &&
              upload(frames[k].colour, (size_t)s.colour_width * (size_t)s.colour_height * (size_t)s.colour_bpp, (uint8_t *)t.raw_colour, &stage, c.stream);
     }
-    const uint32_t tag = ++c.tag ? c.tag : ++c.tag;
-    volatile unsigned long long *word = reinterpret_cast<volatile unsigned long long *>(c.host_words);
-    *word = 0ull;
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 1);
     bool cleared = true;
     if (ok && rig->decimation > 1) k::rgbd_decimate(table, ncam, rig->decimation, rig->decimate_tiles, c.stream);
     if (ok && magnitude > 0)
@@ -597,7 +585,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
         } else {
             k::rgbd_register(table, ncam, total, c.stream);
         }
-        k::rgbd_count(table, ncam, total, f, counts, c.tickets, reinterpret_cast<unsigned long long *>(c.host_words), tag, c.stream);
+        k::rgbd_count(table, ncam, total, f, counts, c.tickets, report.device(), tag, c.stream);
         k::rgbd_scatter(table, ncam, total, f, counts, *dst, c.stream);
         ok = hipGetLastError() == hipSuccess && filled && cleared;
         for (int k = 0; k < ncam && ok && attach; k++) {
@@ -610,7 +598,7 @@ cwipc_pointcloud *rig_grab(const char *who, cwipc_hip_rgbd_rig *rig, const cwipc
     }
     ok = c.sync() && ok;   // (also on failure: copies that read the staging buffer and kernels that write the planes may be in flight)
     if (temporal) rig->state_empty = !ok;   // (a grab that fails on the device leaves the history empty: the next one clears it)
-    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, (size_t)total, dst, rig->tiles, timestamp, cellsize);
+    cwipc_hip_pointcloud *rv = finish_cloud(who, c, ok, tag, dst, rig->tiles, timestamp, cellsize);
     if (!rv) return nullptr;
     if (attach) {
         cwipc_metadata *meta = rv->access_metadata();

@@ -1494,21 +1494,41 @@ class cwipc_hip_rgbd_prep(ctypes.Structure):
     _fields_ = [("depth_x_erosion", ctypes.c_int32), ("depth_y_erosion", ctypes.c_int32)]
 
 
-def cwipc_hip_rgbd_rig_create(sensors: Sequence[cwipc_hip_rgbd_sensor]) -> int:
-    """The rig of these sensors (an opaque handle for the calls below; cwipc_hip_rgbd_rig_free gives it back): the sensor table and the
-    depth cameras' ray tables, computed and uploaded once."""
+def _rgbd_rig_create(symbol: str, sensors: Sequence[cwipc_hip_rgbd_sensor], *more: int) -> int:
+    """The body of the rig constructors: the C entry point `symbol` with the sensor array, what it takes behind it, the error string."""
     n = len(sensors)
     array = (cwipc_hip_rgbd_sensor * max(n, 1))(*sensors)
     errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_create(ctypes.addressof(array), n, ctypes.byref(errorString))
+    rv = getattr(cwipc_util_dll_load(), symbol)(ctypes.addressof(array), n, *more, ctypes.byref(errorString))
     _raise_or_warn(errorString, rv)
     if rv:
         return rv
-    raise CwipcError("cwipc_hip_rgbd_rig_create: no rig created, but no specific error returned from C library")
+    raise CwipcError(symbol + ": no rig created, but no specific error returned from C library")
+
+
+def cwipc_hip_rgbd_rig_create(sensors: Sequence[cwipc_hip_rgbd_sensor]) -> int:
+    """The rig of these sensors (an opaque handle for the calls below; cwipc_hip_rgbd_rig_free gives it back): the sensor table and the
+    depth cameras' ray tables, computed and uploaded once."""
+    return _rgbd_rig_create("cwipc_hip_rgbd_rig_create", sensors)
 
 
 def cwipc_hip_rgbd_rig_free(rig: int) -> None:
     cwipc_util_dll_load().cwipc_hip_rgbd_rig_free(rig)
+
+
+def _rgbd_rig_grab(symbol: str, rig: int, frames: Sequence[cwipc_hip_rgbd_frame], structs: Sequence[Optional[ctypes.Structure]], timestamp: int,
+                   cellsize: float, attach_flags: int) -> cwipc_pointcloud_wrapper:
+    """The body of the grab entries: the C entry point `symbol` with the frame array, its optional structures in C order (None: a
+    NULL pointer), the scalars and the error string."""
+    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
+    errorString = ctypes.c_char_p()
+    rv = getattr(cwipc_util_dll_load(), symbol)(rig, ctypes.addressof(array) if len(frames) else None,
+                                                *[ctypes.addressof(s) if s is not None else None for s in structs], int(timestamp), float(cellsize),
+                                                int(attach_flags), ctypes.byref(errorString))
+    _raise_or_warn(errorString, rv)
+    if rv:
+        return cwipc_pointcloud_wrapper(rv)
+    raise CwipcError(symbol + ": no pointcloud created, but no specific error returned from C library")
 
 
 def cwipc_hip_rgbd_rig_grab(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], prep: Optional[cwipc_hip_rgbd_prep] = None,
@@ -1517,15 +1537,7 @@ def cwipc_hip_rgbd_rig_grab(rig: int, frames: Sequence[cwipc_hip_rgbd_frame], pr
     """One device-resident cloud from one frame of raw sensor images, built on the GPU: depth erosion, the ray tables, registration of
     the colour image onto the depth grid, then cwipc_hip_from_rgbd's filters and order.  frames: one entry per sensor of the rig, in
     their order; the images must stay alive during the call.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
-    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
-    errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab(rig, ctypes.addressof(array) if len(frames) else None, ctypes.addressof(prep) if prep is not None else None,
-                                                       ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
-                                                       int(attach_flags), ctypes.byref(errorString))
-    _raise_or_warn(errorString, rv)
-    if rv:
-        return cwipc_pointcloud_wrapper(rv)
-    raise CwipcError("cwipc_hip_rgbd_rig_grab: no pointcloud created, but no specific error returned from C library")
+    return _rgbd_rig_grab("cwipc_hip_rgbd_rig_grab", rig, frames, (prep, filter), timestamp, cellsize, attach_flags)
 
 
 class cwipc_hip_rgbd_occlusion(ctypes.Structure):
@@ -1540,17 +1552,7 @@ def cwipc_hip_rgbd_rig_grab_occluded(rig: int, frames: Sequence[cwipc_hip_rgbd_f
     """cwipc_hip_rgbd_rig_grab with the occlusion between the two sensors modelled: a depth pixel whose point the colour camera cannot
     see, something nearer lying in front of it there, gives no point instead of taking that thing's colour.  occlusion None: exactly
     cwipc_hip_rgbd_rig_grab.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
-    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
-    errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_occluded(rig, ctypes.addressof(array) if len(frames) else None,
-                                                                ctypes.addressof(prep) if prep is not None else None,
-                                                                ctypes.addressof(occlusion) if occlusion is not None else None,
-                                                                ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
-                                                                int(attach_flags), ctypes.byref(errorString))
-    _raise_or_warn(errorString, rv)
-    if rv:
-        return cwipc_pointcloud_wrapper(rv)
-    raise CwipcError("cwipc_hip_rgbd_rig_grab_occluded: no pointcloud created, but no specific error returned from C library")
+    return _rgbd_rig_grab("cwipc_hip_rgbd_rig_grab_occluded", rig, frames, (prep, occlusion, filter), timestamp, cellsize, attach_flags)
 
 
 class cwipc_hip_rgbd_depthfilter(ctypes.Structure):
@@ -1568,32 +1570,14 @@ def cwipc_hip_rgbd_rig_grab_filtered(rig: int, frames: Sequence[cwipc_hip_rgbd_f
     """cwipc_hip_rgbd_rig_grab / cwipc_hip_rgbd_rig_grab_occluded with the depth images smoothed on the GPU first: an edge-preserving
     spatial filter, then a temporal one that keeps its state in the rig from grab to grab.  depthfilter None, or one with both stages
     off: exactly the other two entries.  The exact contract is in include/cwipc_util_amd/hip_ext.h."""
-    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
-    errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_filtered(rig, ctypes.addressof(array) if len(frames) else None,
-                                                                ctypes.addressof(depthfilter) if depthfilter is not None else None,
-                                                                ctypes.addressof(prep) if prep is not None else None,
-                                                                ctypes.addressof(occlusion) if occlusion is not None else None,
-                                                                ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
-                                                                int(attach_flags), ctypes.byref(errorString))
-    _raise_or_warn(errorString, rv)
-    if rv:
-        return cwipc_pointcloud_wrapper(rv)
-    raise CwipcError("cwipc_hip_rgbd_rig_grab_filtered: no pointcloud created, but no specific error returned from C library")
+    return _rgbd_rig_grab("cwipc_hip_rgbd_rig_grab_filtered", rig, frames, (depthfilter, prep, occlusion, filter), timestamp, cellsize, attach_flags)
 
 
 def cwipc_hip_rgbd_rig_create_decimated(sensors: Sequence[cwipc_hip_rgbd_sensor], decimation: int) -> int:
     """cwipc_hip_rgbd_rig_create for a rig that decimates its depth images by `decimation` (1 .. 8) on the device before anything
     else: it is handed full-size frames and works on the decimated grid with derived sensors from there on.  decimation 1: exactly
     cwipc_hip_rgbd_rig_create.  The exact contract (RULE D) is in include/cwipc_util_amd/hip_ext.h."""
-    n = len(sensors)
-    array = (cwipc_hip_rgbd_sensor * max(n, 1))(*sensors)
-    errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_create_decimated(ctypes.addressof(array), n, int(decimation), ctypes.byref(errorString))
-    _raise_or_warn(errorString, rv)
-    if rv:
-        return rv
-    raise CwipcError("cwipc_hip_rgbd_rig_create_decimated: no rig created, but no specific error returned from C library")
+    return _rgbd_rig_create("cwipc_hip_rgbd_rig_create_decimated", sensors, int(decimation))
 
 
 def cwipc_hip_rgbd_rig_decimation(rig: int) -> int:
@@ -1621,19 +1605,7 @@ def cwipc_hip_rgbd_rig_grab_filled(rig: int, frames: Sequence[cwipc_hip_rgbd_fra
     """cwipc_hip_rgbd_rig_grab_filtered with the holes of the depth images filled on the GPU between the temporal filter and the
     erosion.  holefill None, or mode 0: exactly cwipc_hip_rgbd_rig_grab_filtered.  The exact contract (rule 0c) is in
     include/cwipc_util_amd/hip_ext.h."""
-    array = (cwipc_hip_rgbd_frame * max(len(frames), 1))(*frames)
-    errorString = ctypes.c_char_p()
-    rv = cwipc_util_dll_load().cwipc_hip_rgbd_rig_grab_filled(rig, ctypes.addressof(array) if len(frames) else None,
-                                                              ctypes.addressof(holefill) if holefill is not None else None,
-                                                              ctypes.addressof(depthfilter) if depthfilter is not None else None,
-                                                              ctypes.addressof(prep) if prep is not None else None,
-                                                              ctypes.addressof(occlusion) if occlusion is not None else None,
-                                                              ctypes.addressof(filter) if filter is not None else None, int(timestamp), float(cellsize),
-                                                              int(attach_flags), ctypes.byref(errorString))
-    _raise_or_warn(errorString, rv)
-    if rv:
-        return cwipc_pointcloud_wrapper(rv)
-    raise CwipcError("cwipc_hip_rgbd_rig_grab_filled: no pointcloud created, but no specific error returned from C library")
+    return _rgbd_rig_grab("cwipc_hip_rgbd_rig_grab_filled", rig, frames, (holefill, depthfilter, prep, occlusion, filter), timestamp, cellsize, attach_flags)
 
 
 def cwipc_hip_rgbd_rig_reset_history(rig: int) -> None:

@@ -1,4 +1,4 @@
-"""The floor and tile helpers of the registration pipeline on the GPU (csrc/kernels_floor.hip, the entry points in csrc/filters.cpp,
+"""The floor and tile helpers of the registration pipeline on the GPU (csrc/kernels_floor.hip, the entry points in csrc/registration.cpp,
 the wrappers in util.py) against the numpy model of tests/floor_model.py, which tests/test_floor_model.py pins on the CPU.
 
 Every cloud the library returns is compared with the model's as bytes -- count, order and all four planes -- and its timestamp and
@@ -157,6 +157,33 @@ def test_partition_of_a_filter_result_and_shared_planes(gpu):
     assert gpu.cwipc_hip_device_planes(out)[:4] == gpu.cwipc_hip_device_planes(hpc)[:4]
     check(gpu.cwipc_floor_filter(hpc, 0.1, True), high[:0], "no point kept")
     assert hpc.cellsize() == CS and hpc.get_numpy_array().tobytes() == high.tobytes()      # the input is untouched
+
+
+@pytest.mark.parametrize("y,name", [(-1.0, "all floor"), (1.0, "no floor")])
+def test_same_planes_exit_and_its_result_as_an_input(gpu, y, name):
+    """One class holds every one of 4096 points: the partition's result holds the input's planes, with the input's tile set.  It is
+    the input point for point, and a cloud like any other: into a join with itself, a tile filter, a second partition that splits it."""
+    n = 4096
+    pts = random_points(n).copy()
+    pts['y'] = y
+    pc = make_cloud(gpu, pts, CS, TS)
+    assert gpu.get_tiles_used(pc) == [1, 2, 3, 4, 8]        # (a census: the cloud knows its tiles from here on)
+    out, n_first = gpu.cwipc_hip_floor_partition(pc, 0.1, KEEP_FLOOR | KEEP_REST, 0.0)
+    assert n_first == (n if y < 0 else 0)
+    check(out, pts, name)
+    assert gpu.cwipc_hip_device_planes(out) == gpu.cwipc_hip_device_planes(pc)
+    assert gpu.cwipc_tilefilter(out, 16).count() == 0      # (not a point looked at: the tile set came along)
+    joined = gpu.cwipc_join(out, out)
+    assert joined.count() == 2 * n and joined.get_numpy_array().tobytes() == np.concatenate((pts, pts)).tobytes()
+    assert gpu.cwipc_tilefilter(out, 2).get_numpy_array().tobytes() == pts[pts['tile'] == 2].tobytes()
+    # a second partition, at a level in x's terms: turn the cloud so that x becomes y
+    turn = np.array([[0, 1, 0, 0], [1, 0, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
+    turned = pts.copy()
+    turned['x'], turned['y'] = pts['y'], pts['x']
+    again, first = gpu.cwipc_hip_floor_partition(gpu.cwipc_transform(out, turn), 0.0, KEEP_FLOOR | KEEP_REST, 0.0)
+    exp, exp_first = partition_model(turned, 0.0, KEEP_FLOOR | KEEP_REST, 0.0)
+    assert 0 < first == exp_first < n and again.get_numpy_array().tobytes() == exp.tobytes()
+    assert pc.get_numpy_array().tobytes() == pts.tobytes()                                  # the input is untouched
 
 
 # ---------------------------------------------------------------------------

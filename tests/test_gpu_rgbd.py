@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 
 import rgbd_model as rm
-from cwipc_util_amd.rgbd import RgbdCamera, RgbdFilter, RgbdSource, from_rgbd
+from test_gpu_exact_filters import round_up, spacing
+from cwipc_util_amd.rgbd import RgbdCamera, RgbdFilter, RgbdRig, RgbdSensor, RgbdSource, from_rgbd
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +98,45 @@ def test_nothing_survives(gpu, three):
     assert gpu.get_tiles_used(pc) == [] and gpu.cwipc_tilefilter(pc, 2).count() == 0
     other = from_rgbd(cams, frame)
     assert gpu.cwipc_join(pc, other).count() == other.count()
+
+
+@pytest.fixture(scope="module")
+def square(gpu):
+    """One 64 x 64 camera (4096 pixels) for the library and the model; the one-sensor pinhole rig that it is (depth and colour both
+    64 x 64, identity depth_to_colour); a colour image; the points of a second cloud for a join."""
+    rng = np.random.default_rng(202)
+    cam, model_cam = camera_pair(64, 64, 2, "sq", 3, rng)
+    sensor = RgbdSensor(64, 64, cam.fx, cam.fy, cam.cx, cam.cy, 64, 64, cam.fx, cam.fy, cam.cx, cam.cy, depth_scale=cam.depth_scale, trafo=cam.trafo,
+                        tile=cam.tile, serial=cam.serial, bpp=cam.bpp)
+    colour = images(64, 64, 3, rng)[1]
+    second = rm.cloud([model_cam], [images(64, 64, 3, rng, zeros=0.9)])
+    assert 100 < len(second) < 4096
+    with RgbdRig([sensor]) as rig:
+        yield cam, model_cam, rig, colour, second
+
+
+@pytest.mark.parametrize("entry", ["from_rgbd", "rig_grab"])
+@pytest.mark.parametrize("kept", [0, 1, 255, 256, 257, 4095, 4096])
+def test_result_size_exits(gpu, square, kept, entry):
+    """Exactly `kept` of the 4096 pixels have depth, no filter.  kept * 16 >= 4096 (256 and up): the result stays in the planes that
+    had room for every pixel, with their spacing, and only the count shrinks; below that (0, 1, 255) it is copied to planes of its
+    own size.  Either way the cloud is the model's, and so is its join with a second cloud, in both orders: a shrunk cloud is a
+    cloud.  Through cwipc_hip_from_rgbd and through cwipc_hip_rgbd_rig_grab."""
+    cam, model_cam, rig, colour, second = square
+    rng = np.random.default_rng(300 + kept)
+    depth = np.zeros(4096, dtype=np.uint16)
+    depth[rng.permutation(4096)[:kept]] = rng.integers(300, 4000, kept)
+    frame = [(depth.reshape(64, 64), colour)]
+    want = rm.cloud([model_cam], frame)
+    assert len(want) == kept
+    pc = from_rgbd([cam], frame, None, 31, 0.5) if entry == "from_rgbd" else rig.grab(frame, None, None, 31, 0.5)
+    assert_cloud(pc, want, 31, 0.5)
+    assert spacing(gpu, pc) == (round_up(4096) if kept * 16 >= 4096 else round_up(kept)), (kept, spacing(gpu, pc))
+    other = gpu.cwipc_from_numpy_array(second, 30)
+    other._set_cellsize(0.25)
+    assert_cloud(gpu.cwipc_join(pc, other), np.concatenate([want, second]), 30, 0.25)
+    assert_cloud(gpu.cwipc_join(other, pc), np.concatenate([second, want]), 30, 0.25)
+    assert_cloud(pc, want, 31, 0.5)   # (and the cloud is as it was)
 
 
 @pytest.mark.parametrize("pinned", [False, True])
