@@ -730,6 +730,12 @@ bool icp_gicp_sums(const DeviceSoA &source, const DeviceSoA &reference, const do
 // open3d's registration_generalized_icp: the same loop with these sums and the point-to-plane update.
 bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const float *source_normals,
                      const float *reference_normals, float radius, int max_nn, double epsilon, const IcpCriteria &k, IcpResult &res);
+// RULE Q (hip_ext.h; the terms are quality_terms.hpp): the distortion sums of `degraded` against `original`, out[0] forward (source
+// the original), out[1] backward.  host_normals: the ORIGINAL's, as for point-to-plane; plane false: no normals are made or read.
+// Two passes of grid, search and sums, one wait each.  The caller has also checked that host_normals are finite (before either cloud
+// is brought to the device: a refused call launches and allocates nothing).
+bool icp_distortion(const DeviceSoA &original, const DeviceSoA &degraded, double max_distance, const float *host_normals, float radius, int max_nn,
+                    bool plane, cwipc_hip_distortion_sums out[2]);
 // the mean of a cloud's points (the direction filter's centroid kernels) on the host; non-finite where a coordinate is
 bool icp_centroid(const DeviceSoA &cloud, double cen[3]);
 

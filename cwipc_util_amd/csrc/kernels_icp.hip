@@ -44,6 +44,16 @@
 //     in include/cwipc_util_amd/hip_ext.h), in PlanePair's layout: n | sum (A^T N A)_ij (21) | sum (A^T g)_i (6) | sum e^T g |
 //     sum d2.  Both clouds have covariances, made once per run from their normals (gicp_covariance_kernel): six planes for the
 //     source, loaded once per four points, and records of six doubles for the reference, gathered by idx.
+//   DistortionPair (10): no aligner, a measure (cwipc_hip_distortion, RULE Q of hip_ext.h): the 10 terms of quality_terms.hpp
+//       n | n_plane | sum d2 | sum r^2 | sum dR^2, dG^2, dB^2 | sum dY^2, dU^2, dV^2
+//     T is the identity.  The source's four colour words are one 16-byte load per step, the reference's word and the normal are
+//     gathered by index.  The normals are those of the ORIGINAL cloud, whichever side it is on: the normal's index is idx itself
+//     (the original is the reference) or normal_of[idx] (the original is the source: normal_of is the other pass's idx array), and
+//     it is checked against the original's count before it is an address; a pair whose index fails the test has no normal.
+//     This Pair also has a MAXIMUM (HAS_MAX): the largest d2 over the matched pairs.  d2 >= 0, so its bit pattern orders as an
+//     unsigned 64-bit integer; a lane keeps the largest pattern of its points, shuffles close the wave, lane 0 of the workgroup takes
+//     the largest of the four waves into one more slot of the chunk's row, and the final kernel reduces that slot by maximum into
+//     the word behind the sums (0 without a pair).  A maximum is order-free: no atomics here either.
 //
 // 3. THE LOOP (icp_loop) is open3d's registration_icp: evaluate (search, sums, wait, read), then up to max_iteration times: the
 // update U from the sums, T = U T, evaluate; fitness = n / count(source) and inlier_rmse = sqrt(sum d2 / n) (the point distances,
@@ -58,6 +68,7 @@
 #include "rigid_fit.hpp"
 #include "plane_fit.hpp"
 #include "gicp_terms.hpp"
+#include "quality_terms.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -161,9 +172,10 @@ struct IcpSumBase {
 
 // A Pair: NSUM (the count and its sums); the launches' names; Args; Step, what step() loads once per four points of a lane
 // (point u of the four is the one terms() is asked about); terms(), which writes t[1 .. NSUM - 1] for the source point moved to p
-// and matched with reference point i at squared distance d2.
+// and matched with reference point i at squared distance d2; HAS_MAX, whether the largest d2 is kept next to the sums.
 struct PointPair {
     static constexpr int NSUM = 17;           // n, sum a, sum b, sum a b^T, sum d2
+    static constexpr bool HAS_MAX = false;
     static constexpr const char *PARTIAL = "icp_sums_partial", *FINAL = "icp_sums_final";
     struct Args : IcpSumBase { double cp[3], cq[3]; };
     struct Step {};
@@ -184,6 +196,7 @@ struct PointPair {
 
 struct PlanePair {
     static constexpr int NSUM = 30;           // n, sum J J^T (21), sum J r (6), sum r^2, sum d2
+    static constexpr bool HAS_MAX = false;
     static constexpr const char *PARTIAL = "icp_plane_sums_partial", *FINAL = "icp_plane_sums_final";
     struct Args : IcpSumBase { const float *mx, *my, *mz; };   // the reference's normals' planes, in the order of its points
     struct Step {};
@@ -207,6 +220,7 @@ struct PlanePair {
 
 struct GicpPair {
     static constexpr int NSUM = GICP_NTERM;
+    static constexpr bool HAS_MAX = false;
     static constexpr const char *PARTIAL = "icp_gicp_sums_partial", *FINAL = "icp_plane_sums_final";
     struct Args : IcpSumBase {
         const double *cs;        // the source's covariances: six planes of cs_stride doubles (cs_stride a multiple of 256)
@@ -233,12 +247,49 @@ struct GicpPair {
 };
 static_assert(GicpPair::NSUM == PlanePair::NSUM, "the generalized sums have the plane sums' layout: one update, one set of pinned words");
 
+struct DistortionPair {
+    static constexpr int NSUM = QUALITY_NTERM;   // n, n_plane, sum d2, sum r^2, sum dRGB^2 (3), sum dYUV^2 (3)
+    static constexpr bool HAS_MAX = true;        // ... and max d2
+    static constexpr const char *PARTIAL = "distortion_sums_partial", *FINAL = "distortion_sums_final";
+    struct Args : IcpSumBase {
+        const uint32_t *srgbt, *rrgbt;   // the colour words of the source (padded like its planes) and of the reference
+        const float *mx, *my, *mz;       // the ORIGINAL cloud's normals' planes, in the order of its points; nullptr: no pair has a normal
+        size_t na;                       // the original's count: what a normal's index is checked against
+        const uint32_t *normal_of;       // nullptr: the normal's index is idx; else normal_of[idx] (nr entries: the other pass's idx)
+    };
+    struct Step { uint32_t c[4]; };      // the four source points' colour words
+    static __device__ __forceinline__ void step(const Args &A, size_t base, Step &S) {
+        const uint4 c4 = *reinterpret_cast<const uint4 *>(A.srgbt + base);
+        S.c[0] = c4.x; S.c[1] = c4.y; S.c[2] = c4.z; S.c[3] = c4.w;
+    }
+    static __device__ __forceinline__ void terms(const Args &A, const Step &S, int u, const double (&p)[3], uint32_t i, double d2, double (&t)[NSUM]) {
+        const double q[3] = {(double)A.rx[i], (double)A.ry[i], (double)A.rz[i]};
+        double m[3] = {0.0, 0.0, 0.0};
+        bool has_normal = false;
+        if (A.mx != nullptr) {
+            // (i is below nr: the skeleton has checked it; the normal's index is checked against the original's count here)
+            const size_t j = A.normal_of ? (size_t)A.normal_of[i] : (size_t)i;
+            if (j < A.na) {
+                m[0] = (double)A.mx[j]; m[1] = (double)A.my[j]; m[2] = (double)A.mz[j];
+                has_normal = true;
+            }
+        }
+        quality_pair_terms(p, q, m, has_normal, S.c[u], A.rrgbt[i], d2, t);   // (t[0] is 1: the skeleton counts)
+    }
+};
+static_assert(DistortionPair::NSUM + 2 <= 32, "the 10 sums, the maximum and the tag fit the 32 pinned words of a thread");
+
+// a chunk's row in `partial`: the NSUM sums and, for a Pair with a maximum, its bit pattern behind them
 template <class Pair>
-__global__ void __launch_bounds__(GRID_BLK) icp_sums_partial_kernel(typename Pair::Args A, double *__restrict__ partial /* [chunks][NSUM] */) {
-    constexpr int NSUM = Pair::NSUM;
+constexpr int icp_row() { return Pair::NSUM + (Pair::HAS_MAX ? 1 : 0); }
+
+template <class Pair>
+__global__ void __launch_bounds__(GRID_BLK) icp_sums_partial_kernel(typename Pair::Args A, double *__restrict__ partial /* [chunks][icp_row<Pair>()] */) {
+    constexpr int NSUM = Pair::NSUM, ROW = icp_row<Pair>();
     __shared__ double red[GRID_BLK / 64][NSUM];
     const size_t lo = (size_t)blockIdx.x * A.chunk, hi = lo + A.chunk < A.ns ? lo + A.chunk : A.ns;
     double s[NSUM];
+    unsigned long long largest = 0ull;   // HAS_MAX: the bit pattern of the largest d2 of this lane's matched pairs (+0.0: none)
 #pragma unroll
     for (int v = 0; v < NSUM; v++) s[v] = 0.0;
     // (chunk is a multiple of 4 * GRID_BLK: a lane's points are the same whatever the launch looks like)
@@ -262,6 +313,10 @@ __global__ void __launch_bounds__(GRID_BLK) icp_sums_partial_kernel(typename Pai
             s[0] += 1.0;   // (a count below 2^53 is exact in f64)
 #pragma unroll
             for (int v = 1; v < NSUM; v++) s[v] += t[v];
+            if constexpr (Pair::HAS_MAX) {
+                const unsigned long long bits = (unsigned long long)__double_as_longlong(ds[u]);   // (d2 >= 0: the pattern orders as the value)
+                largest = bits > largest ? bits : largest;
+            }
         }
     }
 #pragma unroll
@@ -269,25 +324,52 @@ __global__ void __launch_bounds__(GRID_BLK) icp_sums_partial_kernel(typename Pai
         for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][v] = s[v];
     }
-    __syncthreads();
+    if constexpr (Pair::HAS_MAX) {
+        __shared__ unsigned long long red_largest[GRID_BLK / 64];
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long other = __shfl_down(largest, off, 64);
+            largest = other > largest ? other : largest;
+        }
+        if ((threadIdx.x & 63) == 0) red_largest[threadIdx.x >> 6] = largest;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long t = 0ull;
+            for (int w = 0; w < GRID_BLK / 64; w++) t = red_largest[w] > t ? red_largest[w] : t;
+            partial[(size_t)blockIdx.x * ROW + NSUM] = __longlong_as_double((long long)t);   // (stored, never computed with)
+        }
+    } else {
+        __syncthreads();
+    }
     if (threadIdx.x < NSUM) {
         double t = 0.0;
         for (int w = 0; w < GRID_BLK / 64; w++) t += red[w][threadIdx.x];
-        partial[(size_t)blockIdx.x * NSUM + threadIdx.x] = t;
+        partial[(size_t)blockIdx.x * ROW + threadIdx.x] = t;
     }
 }
 
-// out: NSUM + 1 pinned 64-bit words -- n as an integer, the NSUM - 1 sums, the tag
-template <int NSUM>
+// out: NSUM + 1 pinned 64-bit words -- n as an integer, the NSUM - 1 sums, the tag; with a maximum NSUM + 2 -- its bit pattern goes
+// between the sums and the tag.  `partial` has rows of NSUM + (HAS_MAX ? 1 : 0) values.
+template <int NSUM, bool HAS_MAX>
 __global__ void __launch_bounds__(ICP_FINAL_THREADS) icp_sums_final_kernel(const double *__restrict__ partial, size_t nchunks, unsigned long long *__restrict__ out,
                                                                           unsigned long long tag) {
+    constexpr int ROW = NSUM + (HAS_MAX ? 1 : 0);
+    static_assert(ROW <= ICP_FINAL_THREADS, "one lane per value");
     const int v = threadIdx.x;
-    if (v >= NSUM) return;
+    if (v >= ROW) return;
+    if (HAS_MAX && v == NSUM) {
+        unsigned long long largest = 0ull;
+        for (size_t c = 0; c < nchunks; c++) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(partial[c * ROW + v]);
+            largest = bits > largest ? bits : largest;
+        }
+        out[v] = largest;
+        return;
+    }
     double acc = 0.0;
-    for (size_t c = 0; c < nchunks; c++) acc += partial[c * NSUM + v];
+    for (size_t c = 0; c < nchunks; c++) acc += partial[c * ROW + v];
     if (v == 0) {
         out[0] = (unsigned long long)acc;
-        out[NSUM] = tag;
+        out[ROW] = tag;
     } else {
         out[v] = (unsigned long long)__double_as_longlong(acc);
     }
@@ -340,7 +422,7 @@ void launch_sums(typename Pair::Args S, const DeviceSoA &source, const DeviceSoA
     for (int i = 0; i < 12; i++) S.T[i] = T[i];
     S.chunk = w.chunk;
     CW_LAUNCH(Pair::PARTIAL, (icp_sums_partial_kernel<Pair>), dim3((unsigned)w.nchunks), dim3(GRID_BLK), 0, s, S, w.partial);
-    CW_LAUNCH(Pair::FINAL, (icp_sums_final_kernel<Pair::NSUM>), dim3(1), dim3(ICP_FINAL_THREADS), 0, s, w.partial, w.nchunks,
+    CW_LAUNCH(Pair::FINAL, (icp_sums_final_kernel<Pair::NSUM, Pair::HAS_MAX>), dim3(1), dim3(ICP_FINAL_THREADS), 0, s, w.partial, w.nchunks,
               c.report().device(), (unsigned long long)tag);
 }
 
@@ -379,13 +461,14 @@ uint32_t next_tag(ThreadCtx &c, int nsum) {
 // direction_normals wants for its centroid): the caller's, copied, or estimated there.  On the calling thread's stream, no wait.
 struct IcpNormals {
     float *planes = nullptr;
-    bool make(const char *who, const DeviceSoA &reference, const float *host_normals, float radius, int max_nn, ThreadCtx &c) {
+    // (checked: the caller has looked at host_normals already)
+    bool make(const char *who, const DeviceSoA &reference, const float *host_normals, float radius, int max_nn, ThreadCtx &c, bool checked = false) {
         const size_t nr = reference.npoints;
         const size_t cen_at = (3 * nr * sizeof(float) + 127) & ~(size_t)127;
         planes = (float *)pool_alloc(cen_at + 3 * sizeof(double));
         if (!planes) return false;
         if (host_normals) {
-            for (size_t i = 0; i < 3 * nr; i++)
+            for (size_t i = 0; !checked && i < 3 * nr; i++)
                 if (!std::isfinite(host_normals[i])) {
                     cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the normals must be finite");
                     return false;
@@ -723,6 +806,81 @@ bool icp_generalized(const DeviceSoA &source, const DeviceSoA &reference, double
         launch_sums<GicpPair>(gicp_args(clouds), source, reference, T, w, c, tag, s);
     };
     return icp_loop(who, source, reference, max_distance, k, w, c, GicpPair::NSUM, launch, plane_update, res);
+}
+
+namespace {
+
+// One pass of cwipc_hip_distortion in a grid hook of its own: the grid over the pass's reference, the search (T the identity), the
+// two sums kernels; waits, and reads the 10 sums and the maximum from the pinned words.  normal_planes: the original's (nullptr: no
+// normals), na its count, normal_of: see DistortionPair.
+bool distortion_pass(const DeviceSoA &source, const DeviceSoA &reference, double max_distance, const float *normal_planes, size_t na,
+                     const uint32_t *normal_of, const IcpWork &w, ThreadCtx &c, cwipc_hip_distortion_sums &out) {
+    constexpr int NV = icp_row<DistortionPair>();   // the values in front of the tag
+    static const double identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    DistortionPair::Args S{};
+    S.srgbt = source.rgbt();
+    S.rrgbt = reference.rgbt();
+    S.mx = normal_planes;
+    S.my = normal_planes ? normal_planes + na : nullptr;
+    S.mz = normal_planes ? normal_planes + 2 * na : nullptr;
+    S.na = na;
+    S.normal_of = normal_of;
+    const IcpArgs A = correspond_args(source, identity, max_distance, w);
+    const uint32_t tag = next_tag(c, NV);
+    const GridSearch search = [&](const GridView &v, hipStream_t s) {
+        launch_correspond(v, A, s);
+        launch_sums<DistortionPair>(S, source, reference, identity, w, c, tag, s);
+        return hipGetLastError() == hipSuccess;
+    };
+    bool ok = grid_and_search(reference, ICP_GRID_WIDTH, true, search);
+    ok = c.sync() && ok;   // (also on failure: kernels that write the block may still be in flight)
+    if (!ok) return false;
+    const PinnedReport report = c.report();
+    if (!report.landed_plain(tag, NV)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, "cwipc_hip_distortion", "the sums kernel did not report");
+        return false;
+    }
+    auto as_double = [&](int i) {
+        const unsigned long long bits = report.raw(i);
+        double v;
+        memcpy(&v, &bits, sizeof(v));
+        return v;
+    };
+    out.n = report.raw(0);
+    // (the counts and the three RGB sums are sums of integers below 2^53: exact in f64 in any order)
+    out.n_plane = (uint64_t)as_double(1);
+    out.sum_d2 = as_double(2);
+    out.sum_r2 = as_double(3);
+    for (int k = 0; k < 3; k++) {
+        out.sum_rgb2[k] = (uint64_t)as_double(4 + k);
+        out.sum_yuv2[k] = as_double(7 + k);
+    }
+    out.max_d2 = as_double(DistortionPair::NSUM);
+    return true;
+}
+
+}  // namespace
+
+bool icp_distortion(const DeviceSoA &original, const DeviceSoA &degraded, double max_distance, const float *host_normals, float radius, int max_nn,
+                    bool plane, cwipc_hip_distortion_sums out[2]) {
+    const char *who = "cwipc_hip_distortion";
+    const size_t na = original.npoints, nb = degraded.npoints;
+    memset(out, 0, 2 * sizeof(out[0]));
+    out[0].n_source = na;
+    out[1].n_source = nb;
+    if (na == 0 || nb == 0) return true;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    IcpNormals normals;
+    IcpWork backward, forward;
+    // the original's normals, once per call and before the grid hooks: direction_normals builds a grid of its own width
+    bool ok = !plane || normals.make(who, original, host_normals, radius, max_nn, c, true);
+    ok = ok && backward.alloc(nb, icp_row<DistortionPair>()) && forward.alloc(na, icp_row<DistortionPair>());
+    if (!ok) return c.sync() && ok;   // (a wait also on failure: kernels that write the blocks may still be in flight)
+    // backward: source the degraded cloud, reference the original; its idx array stays on the device and hands the forward pass,
+    // whose reference is the degraded cloud, the original's normals
+    return distortion_pass(degraded, original, max_distance, normals.planes, na, nullptr, backward, c, out[1]) &&
+           distortion_pass(original, degraded, max_distance, normals.planes, na, backward.idx, forward, c, out[0]);
 }
 
 // the mean of the cloud's points (the direction filter's centroid kernels), on the host; non-finite where a point is

@@ -1,5 +1,5 @@
 // registration.cpp -- C entry points of the registration tooling and their host orchestration: nearest-neighbour distances and
-// their jobs, the kernel density estimate, every ICP and GICP entry, the floor and tile helpers, bounds.  The per-point work is in
+// their jobs, the kernel density estimate, every ICP and GICP entry, the distortion measure, the floor and tile helpers, bounds.  The per-point work is in
 // kernels_nn.hip, kernels_kde.hip, kernels_icp.hip and kernels_floor.hip.  There is NO CPU fallback.
 #include "entry.hpp"
 
@@ -337,6 +337,48 @@ extern "C" int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc_pointcl
         if (!gicp_epsilon_ok(who, epsilon) || !icp_criteria_ok(who, k)) return false;
         if (!icp_generalized(*in.src, *in.ref, max_distance, source_normals, reference_normals, radius, max_nn, epsilon, k, res)) return false;
         icp_result_out(res, T_out, fitness, inlier_rmse, iterations);
+        return true;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// no reference counterpart: the distortion of a degraded cloud against its original (RULE Q of hip_ext.h; DistortionPair of
+// kernels_icp.hip, quality_terms.hpp)
+// ---------------------------------------------------------------------------
+extern "C" int cwipc_hip_distortion(cwipc_pointcloud *original, cwipc_pointcloud *degraded, double max_distance, const float *normals, float radius,
+                                    int max_nn, int flags, cwipc_hip_distortion_sums out[2]) {
+    const char *who = "cwipc_hip_distortion";
+    if (out) memset(out, 0, 2 * sizeof(out[0]));
+    return icp_entry(who, [&] {
+        if (out == nullptr) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL result");
+            return false;
+        }
+        if ((flags & ~CWIPC_HIP_DISTORTION_NO_PLANE) != 0) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "unknown flag");
+            return false;
+        }
+        const bool plane = (flags & CWIPC_HIP_DISTORTION_NO_PLANE) == 0;
+        if (original == nullptr || degraded == nullptr) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+            return false;
+        }
+        if (!(max_distance > 0.0)) {
+            cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "max_distance must be positive (inf: no bound)");
+            return false;
+        }
+        if (plane && !normals && !direction_args_ok(who, radius, max_nn)) return false;
+        // (before either cloud is brought to the device: a refused call launches and allocates nothing)
+        for (size_t i = 0, n3 = 3 * (size_t)original->count(); plane && normals && i < n3; i++)
+            if (!std::isfinite(normals[i])) {
+                cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the normals must be finite");
+                return false;
+            }
+        IcpClouds in;
+        if (!icp_inputs(who, original, degraded, nullptr, max_distance, in)) return false;
+        cwipc_hip_distortion_sums sums[2];
+        if (!icp_distortion(*in.src, *in.ref, max_distance, normals, radius, max_nn, plane, sums)) return false;
+        memcpy(out, sums, sizeof(sums));
         return true;
     });
 }

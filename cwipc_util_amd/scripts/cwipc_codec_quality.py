@@ -1,0 +1,79 @@
+"""
+Print the rate-distortion table of the octree codec on one point cloud.
+
+The cloud is encoded and decoded at every combination of the given octree depths and colour qualities, and each decoded cloud is
+compared with the original on the GPU: the packet's size, the bits it spends per input point, and the symmetric PSNRs of the
+point-to-point error (D1), the point-to-plane error (D2) and the colour error in BT.709 YUV -- the measures of MPEG's pc_error,
+by this library's RULE Q (include/cwipc_util_amd/hip_ext.h).  No decoded cloud leaves the device.  No reference counterpart.
+"""
+import argparse
+from typing import Any, Dict, List, Optional, Sequence
+
+from .. import util as cwipc
+from .. import quality
+
+__all__ = ["CodecQualityTable", "build_parser", "main"]
+
+COLUMNS = ("octree_bits", "jpeg_quality", "entropy", "bytes", "bits_per_input_point", "psnr_d1", "psnr_d2", "psnr_y", "psnr_u", "psnr_v")
+
+
+class CodecQualityTable:
+    """args: the namespace of build_parser(); input_pc: the cloud to measure on (or load_input() later)."""
+
+    def __init__(self, args: argparse.Namespace, input_pc: Optional[cwipc.cwipc_pointcloud_wrapper] = None):
+        self.args = args
+        self.octree_bits: Sequence[int] = args.octree_bits or [9]
+        self.jpeg_quality: Sequence[int] = args.jpeg_quality or [85]
+        self.entropy = bool(args.entropy)
+        self.input_pc = input_pc
+        self.rows: List[Dict[str, Any]] = []
+
+    def load_input(self, source: Optional[str], synthetic: int = 0) -> None:
+        if synthetic:
+            src = cwipc.cwipc_synthetic(0, synthetic)
+            src.start()
+            self.input_pc = src.get()
+            src.stop()
+        else:
+            assert source
+            self.input_pc = cwipc.cwipc_read(source, 0)
+
+    def settings(self) -> List[Dict[str, Any]]:
+        return [dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy) for b in self.octree_bits for q in self.jpeg_quality]
+
+    def run(self) -> None:
+        assert self.input_pc
+        self.rows = quality.rate_distortion(self.input_pc, self.settings())
+
+    def table(self) -> str:
+        lines = ["%11s %12s %7s %10s %20s %8s %8s %8s %8s %8s" % COLUMNS]
+        for row in self.rows:
+            flat = dict(row["settings"], **{k: v for k, v in row.items() if k != "settings"})
+            lines.append("%11d %12d %7s %10d %20.4f %8.2f %8.2f %8.2f %8.2f %8.2f" % tuple(flat[c] for c in COLUMNS))
+        return "\n".join(lines)
+
+
+def build_parser() -> argparse.ArgumentParser:
+    assert __doc__ is not None
+    parser = argparse.ArgumentParser(description=__doc__.strip(), formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument("input", nargs="?", help="Input point cloud .ply file")
+    parser.add_argument("--synthetic", type=int, metavar="NPOINTS", default=0, help="Measure on the synthetic cloud of about this many points instead of a file")
+    parser.add_argument("--octree_bits", type=int, action="append", metavar="BITS", help="Octree depth to encode at. Repeat for each depth (default: 9)")
+    parser.add_argument("--jpeg_quality", type=int, action="append", metavar="Q", help="Colour quality to encode at. Repeat for each quality (default: 85)")
+    parser.add_argument("--entropy", action="store_true", help="Measure the entropy-coded packets (same distortion, fewer bytes)")
+    return parser
+
+
+def main() -> None:
+    parser = build_parser()
+    args = parser.parse_args()
+    if bool(args.input) == bool(args.synthetic):
+        parser.error("give either an input file or --synthetic NPOINTS")
+    creator = CodecQualityTable(args)
+    creator.load_input(args.input, args.synthetic)
+    creator.run()
+    print(creator.table())
+
+
+if __name__ == '__main__':
+    main()

@@ -46,6 +46,7 @@ __all__ = [
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde', 'NNJob', 'cwipc_hip_nn_distance_jobs', 'compact_job_rows',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
+    'cwipc_hip_distortion_sums', 'CWIPC_HIP_DISTORTION_NO_PLANE', 'cwipc_hip_distortion',
     'cwipc_floor_filter', 'cwipc_randomize_floor', 'cwipc_compute_tile_occupancy', 'cwipc_compute_radius', 'cwipc_limit_floor_to_radius',
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
@@ -262,6 +263,7 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
                                  _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_icp_generalized': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_int, _c.c_double,
                                    _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_distortion': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_double, _c.c_void_p, _c.c_float, _c.c_int, _c.c_int, _c.c_void_p], _c.c_int),
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
@@ -1987,6 +1989,36 @@ def cwipc_hip_icp_generalized(source: cwipc_pointcloud_wrapper, reference: cwipc
     if rc != 0:
         raise CwipcError("cwipc_hip_icp_generalized failed")
     return T, float(fitness.value), float(rmse.value), int(iterations.value)
+
+
+CWIPC_HIP_DISTORTION_NO_PLANE = 1
+
+
+class cwipc_hip_distortion_sums(ctypes.Structure):
+    """One direction of cwipc_hip_distortion (include/cwipc_util_amd/hip_ext.h, RULE Q): the pass's source points, the matched pairs,
+    those with a normal; over the matched pairs the sum and the maximum of d2, the sum of the squared point-to-plane residuals, of
+    the squared colour differences in RGB (integers) and in BT.709 YUV."""
+    _fields_ = [("n_source", ctypes.c_uint64), ("n", ctypes.c_uint64), ("n_plane", ctypes.c_uint64),
+                ("sum_d2", ctypes.c_double), ("max_d2", ctypes.c_double), ("sum_r2", ctypes.c_double),
+                ("sum_rgb2", ctypes.c_uint64 * 3), ("sum_yuv2", ctypes.c_double * 3)]
+
+
+def cwipc_hip_distortion(original: cwipc_pointcloud_wrapper, degraded: cwipc_pointcloud_wrapper, max_distance: float = float('inf'), normals: Any = None,
+                         radius: float = 0.02, max_nn: int = 30, plane: bool = True) -> Tuple[cwipc_hip_distortion_sums, cwipc_hip_distortion_sums]:
+    """What `degraded` lost against `original`, nothing per point leaves the device: (forward, backward) sums of RULE Q -- forward
+    matches every point of the original to its nearest point of the degraded cloud, backward the other way round, among the points
+    strictly closer than max_distance.  normals: the ORIGINAL's, float32 (count(original), 3) as cwipc_hip_estimate_normals returns
+    them, or None: estimated on the device with (radius, max_nn); a degraded point inherits the normal of its nearest original point.
+    plane=False: no normals are made or read (n_plane and sum_r2 are 0).  cwipc_util_amd.quality turns the sums into mse and PSNR."""
+    if original is None or degraded is None:
+        raise CwipcError("cwipc_hip_distortion: NULL pointcloud")
+    planes = _normal_planes('cwipc_hip_distortion', normals, original) if plane else None
+    out = (cwipc_hip_distortion_sums * 2)()
+    rc = cwipc_util_dll_load().cwipc_hip_distortion(original.as_cwipc_p(), degraded.as_cwipc_p(), float(max_distance), _p(planes), float(radius), int(max_nn),
+                                                    0 if plane else CWIPC_HIP_DISTORTION_NO_PLANE, ctypes.addressof(out))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_distortion failed")
+    return cwipc_hip_distortion_sums.from_buffer_copy(out[0]), cwipc_hip_distortion_sums.from_buffer_copy(out[1])
 
 
 def cwipc_hip_gaussian_kde(samples: Any, at: Any, bw_method: Union[None, str, float] = None) -> numpy.ndarray:

@@ -331,6 +331,56 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_icp_generalized(cwipc_pointcloud *source, cwipc
                                                  double relative_fitness, double relative_rmse, int max_iteration, double *T_out, double *fitness,
                                                  double *inlier_rmse, int *iterations);
 
+/* ---- cloud distortion: what a degraded cloud (a decoded packet, a downsampled or filtered cloud) lost against its original ----
+ * No reference counterpart.  The measures are those of MPEG's pc_error -- point-to-point error (D1), point-to-plane error (D2),
+ * colour error in BT.709 YUV, each in both directions -- the rule is this library's own, stated here once and pinned by a numpy
+ * model (tests/quality_model.py); the arithmetic is csrc/quality_terms.hpp (host and device compile it).
+ *
+ * RULE Q.  Two clouds: `original`, called A, and `degraded`, called B.  Two passes; each is "every source point is matched to its
+ * nearest reference point", with exactly the correspondences cwipc_hip_correspondences gives for T the identity:
+ *   d2 = (dx*dx + dy*dy) + dz*dz in f64 from the float32 coordinates; only d2 < max_distance^2 (strictly; INFINITY: no bound); among
+ *   equal d2 the smallest original index wins; a source point with a non-finite coordinate has no match; a non-finite reference
+ *   point is never a match.
+ *   BACKWARD (out[1]): source B, reference A.  The normal of a matched pair is A's normal at the matched index.  This pass runs
+ *     first; its index array idxBA stays on the device.
+ *   FORWARD (out[0]): source A, reference B.  Reference point j of B inherits the normal nA[idxBA[j]]; it has none when idxBA[j] is
+ *     none.  The degraded cloud's own normals are never estimated: a decoded cloud is a lattice of cell centres, its normals mean
+ *     nothing.
+ * PER MATCHED PAIR, every operation rounded on its own in f64: p the source point, q the reference point, m the normal when there
+ * is one, all (double) of float32:
+ *     e = p - q,  r = (e0*m0 + e1*m1) + e2*m2
+ *     dR, dG, dB = the source's colour byte minus the reference's, as doubles (integers in -255 .. 255)
+ *     dY = (0.2126*dR + 0.7152*dG) + 0.0722*dB
+ *     dU = (-0.1146*dR - 0.3854*dG) + 0.5*dB
+ *     dV = (0.5*dR - 0.4542*dG) - 0.0458*dB                         (BT.709, as in pc_error; the offsets of 128 cancel)
+ * and the pair's terms are  1 | 1.0 with a normal, 0.0 without | d2 | r*r (0.0 without a normal) | dR*dR, dG*dG, dB*dB | dY*dY,
+ * dU*dU, dV*dV.  Negating a normal leaves every term's bits as they are.  Per pass the terms are summed over the matched pairs in
+ * f64, in the order of the ICP sums (fixed by the source's count: the same clouds give the same bytes); the counts and the three RGB
+ * sums are sums of integers below 2^53, exact in any order, and are handed out as integers.  Besides the sums: max_d2, the largest
+ * d2 over the matched pairs, 0 when there are none.
+ * From the sums (cwipc_util_amd.quality does this): mse_d1 = sum_d2 / n, mse_d2 = sum_r2 / n_plane, hausdorff = sqrt(max_d2),
+ * mse of a colour channel = its sum / n; symmetric = the larger of the two directions; psnr = 10 log10(3 peak^2 / mse) for the
+ * geometry and 10 log10(255^2 / mse) for a colour channel.
+ * NOT pc_error's: a pair's normal is inherited through the nearest index (pc_error averages the normals of equally near points);
+ * peak is the caller's (the Python layer takes the largest extent of the original's bounding box); there is no reflectance.
+ *
+ * normals: the ORIGINAL's, three planes of count(original) floats, x then y then z, in host memory; NULL: estimated on the device
+ * as cwipc_hip_estimate_normals(radius, max_nn) does, once per call.  flags: CWIPC_HIP_DISTORTION_NO_PLANE or 0.  The clouds may be
+ * the same one; they are neither consumed nor changed.  An empty cloud on either side gives n = 0 in both directions and returns 0
+ * (n_source is the count of each pass's source all the same).  Nothing per point leaves the device.  0, or -1 (logged, nothing is
+ * launched, out is zeroed) for a NULL cloud, max_distance NaN or <= 0, unknown flag bits, a NULL out and, without NO_PLANE, a normal
+ * that is not finite or, with normals NULL, radius <= 0 or not finite, max_nn < 1 or > 128. */
+#define CWIPC_HIP_DISTORTION_NO_PLANE 1   /* no normals are made or read: n_plane = 0, sum_r2 = 0 in both passes */
+typedef struct cwipc_hip_distortion_sums {
+    uint64_t n_source, n, n_plane;   /* the pass's source points; the matched pairs; those with a normal */
+    double   sum_d2, max_d2, sum_r2;
+    uint64_t sum_rgb2[3];
+    double   sum_yuv2[3];
+} cwipc_hip_distortion_sums;
+_CWIPC_UTIL_EXPORT int cwipc_hip_distortion(cwipc_pointcloud *original, cwipc_pointcloud *degraded, double max_distance,
+                                            const float *normals, float radius, int max_nn, int flags,
+                                            cwipc_hip_distortion_sums out[2]);
+
 /* ---- a cloud seen through a pinhole camera (reference python/cwipc/registration/multicoarse.py:333-360: MultiCameraCoarseAruco looks at
  * a camera's tile from the origin in an open3d window and grabs the window's colour and depth buffers) ----
  * Camera space looks along +z, image x runs right and image y down: the conventions of the reference's _deproject
