@@ -217,13 +217,7 @@ __device__ __forceinline__ uint32_t count_tile(const PredArgs &p, const float *_
                                    : lane_mask<false, true>(p, x, y, z, rgbt, base, n, vx, vy, vz, vw);
         cnt += __popc(m);
     }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    uint32_t t = 0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < WAVES; w++) t += wave_sum[w];
-    return t;   // (thread 0's value is the tile's count)
+    return block_sum<BLOCK>(cnt, wave_sum);   // (thread 0's value is the tile's count)
 }
 
 // The outlier filter's threshold from its 1024 pairs of partial sums (kernels_sor.hip, stats_partial_kernel): the pairwise tree and the f64
@@ -273,33 +267,21 @@ __global__ void __launch_bounds__(BLOCK) compact_count_kernel(PredArgs p, const 
     if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
 }
 
-// Count and scan in one launch: every workgroup leaves its count and takes a ticket; the one that takes the last ticket has
-// every count in front of it (release / acquire at device scope around the ticket) and scans them.  For small clouds, whose
-// kernels cost the device less than their launches cost the host (a camera tile through the outlier filter: sixteen launches).
+// Count and scan in one launch (last_block_scans, block_scan.hpp).  For small clouds, whose kernels cost the device less than their
+// launches cost the host (a camera tile through the outlier filter: sixteen launches).
 template <int S>
 __global__ void __launch_bounds__(BLOCK) compact_count_scan_kernel(PredArgs p, const float *__restrict__ x, const float *__restrict__ y,
                                                                   const float *__restrict__ z, const uint32_t *__restrict__ rgbt, size_t n,
                                                                   uint32_t *__restrict__ block_counts, uint32_t *__restrict__ ticket,
                                                                   unsigned long long *__restrict__ total, uint32_t tag) {
     __shared__ uint32_t wave_sum[WAVES];
-    __shared__ uint32_t is_last;
     if (p.mode == 3 && p.stat_partial) {
         const double thr = threshold_from_partials(p.stat_partial, p.stat_n, p.stat_mul);
         if (blockIdx.x == 0 && threadIdx.x == 0) *p.thr_out = thr;   // (the scatter kernel reads it there)
         p.thr = thr;
         p.thr_dev = nullptr;
     }
-    const uint32_t t = count_tile<S>(p, x, y, z, rgbt, n, wave_sum);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&block_counts[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t before = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = before == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next kernel that uses it
-    scan_block_counts<BLOCK>(block_counts, gridDim.x, total, tag);
+    last_block_scans<BLOCK>(count_tile<S>(p, x, y, z, rgbt, n, wave_sum), block_counts, ticket, total, tag);
 }
 
 // Exclusive scan of up to millions of block counts by ONE workgroup of 1024 lanes
@@ -332,7 +314,7 @@ __global__ void __launch_bounds__(BLOCK) compact_scatter_kernel(PredArgs p, cons
             all += v;
             if (i < blockIdx.x) lo += v;
         }
-        for (int off = 32; off > 0; off >>= 1) { lo += __shfl_down(lo, off, 64); all += __shfl_down(all, off, 64); }
+        for (int off = 32; off > 0; off >>= 1) { lo += __shfl_down(lo, off, 64); all += __shfl_down(all, off, 64); }   // (two sums a step)
         if ((threadIdx.x & 63) == 0) { prefix_sum[0][threadIdx.x >> 6] = lo; prefix_sum[1][threadIdx.x >> 6] = all; }
         __syncthreads();
         for (int w = 0; w < WAVES; w++) { before_me += prefix_sum[0][w]; everything += prefix_sum[1][w]; }
@@ -366,10 +348,7 @@ __global__ void __launch_bounds__(BLOCK) compact_scatter_kernel(PredArgs p, cons
 #pragma unroll
     for (int s = 0; s < S; s++) {
         const uint32_t c = inc[s];
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(inc[s], off, 64);
-            if (lane >= off) inc[s] += t;
-        }
+        inc[s] = wave_inclusive_scan(c);
         if (lane == 63) wave_sum[s][wave] = inc[s];
         inc[s] -= c;   // exclusive inside the wave
     }
@@ -459,9 +438,7 @@ void compact_count(const DeviceSoA &src, const Predicate &p, uint32_t *block_cou
 bool compact_count_scan(const DeviceSoA &src, const Predicate &p, uint32_t *block_counts, uint32_t *ticket, unsigned long long *total_host, uint32_t tag,
                         hipStream_t s) {
     size_t nb = compact_blocks(src.npoints);
-    // Small clouds only.  (r4: tried at every size -- 2441 workgroups for 10 M points, each with its release / acquire around the one
-    // ticket word: tilefilter 81 -> 129 us, crop 70 -> 147.  An agent-scope release writes the XCD's L2 back, and all tickets
-    // are one address at the memory side.)
+    // Small clouds only: last_block_scans (block_scan.hpp) has the measurement.
     if (!nb || src.npoints > SMALL_CLOUD || !ticket) return false;
     CW_LAUNCH("compact_count", compact_count_scan_kernel<SMALL_STEPS>, dim3((unsigned)nb), dim3(BLOCK), 0, s, to_args(p), src.x(), src.y(), src.z(), src.rgbt(),
               src.npoints, block_counts, ticket, total_host, tag);

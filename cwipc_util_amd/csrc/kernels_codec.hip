@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(CB) codec_bounds_kernel(const float *__restric
             lo[a] = fminf(lo[a], __shfl_down(lo[a], off, 64));
             hi[a] = fmaxf(hi[a], __shfl_down(hi[a], off, 64));
         }
-        count += __shfl_down(count, off, 64);
+        count += __shfl_down(count, off, 64);   // (a step folds the box and the count)
     }
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(64) codec_cube_kernel(const BoundsPartial *__r
             lo[a] = fminf(lo[a], __shfl_down(lo[a], off, 64));
             hi[a] = fmaxf(hi[a], __shfl_down(hi[a], off, 64));
         }
-        count += __shfl_down(count, off, 64);
+        count += __shfl_down(count, off, 64);   // (a step folds the box and the count)
     }
     if (threadIdx.x == 0) {
         CodecCube c;
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(CB) codec_emit_kernel(const unsigned long long
     const uint32_t w = valid ? rgbt[index[i]] : 0u;
     uint32_t rg = (w & 0xffu) | ((w & 0xff00u) << 8), bc = ((w >> 16) & 0xffu) | (1u << 16), tl = w >> 24;   // r | g << 16,  b | count << 16
     if (!valid) { rg = 0; bc = 0; tl = 0; }
-    for (int off = 1; off < 64; off <<= 1) {
+    for (int off = 1; off < 64; off <<= 1) {   // (a segmented scan: four values a step, added only within a leaf)
         const uint32_t o_leaf = __shfl_up(leaf, off, 64), o_rg = __shfl_up(rg, off, 64), o_bc = __shfl_up(bc, off, 64), o_tl = __shfl_up(tl, off, 64);
         if (lane >= off && o_leaf == leaf) { rg += o_rg; bc += o_bc; tl |= o_tl; }
     }
@@ -308,15 +308,8 @@ void codec_emit(const unsigned long long *sorted_keys, const uint32_t *sorted_in
 __global__ void __launch_bounds__(CB) codec_popcount_kernel(const uint8_t *__restrict__ occupancy, size_t n, uint32_t *__restrict__ counts) {
     __shared__ uint32_t wave_tot[CWAVES];
     const size_t i = (size_t)blockIdx.x * CB + threadIdx.x;
-    uint32_t c = i < n ? (uint32_t)__popc((unsigned)occupancy[i]) : 0u;
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t v = 0;
-        for (int w = 0; w < CWAVES; w++) v += wave_tot[w];
-        counts[blockIdx.x] = v;
-    }
+    const uint32_t v = block_sum<CB>(i < n ? (uint32_t)__popc((unsigned)occupancy[i]) : 0u, wave_tot);
+    if (threadIdx.x == 0) counts[blockIdx.x] = v;
 }
 
 __global__ void __launch_bounds__(CB) codec_decode_scan_kernel(uint32_t *__restrict__ counts, size_t nblocks, unsigned long long *__restrict__ sink) {
@@ -333,7 +326,7 @@ __global__ void __launch_bounds__(CB) codec_expand_kernel(const uint8_t *__restr
     const uint32_t c = (uint32_t)__popc(byte);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t inc = c;
-    for (int off = 1; off < 64; off <<= 1) {
+    for (int off = 1; off < 64; off <<= 1) {   // (kept: wave_inclusive_scan changed this kernel, and its times left the parent's spread)
         const uint32_t t = __shfl_up(inc, off, 64);
         if (lane >= off) inc += t;
     }

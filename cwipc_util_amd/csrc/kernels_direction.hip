@@ -14,6 +14,7 @@
 // result does not depend on the order of the points in a cell), count, sum(q - p) and sum((q - p)(q - p)^T) in int64 fixed point
 // (2^-20 of the cutoff distance), which no order of the candidates changes: the normals are the same bits run after run.
 #include "point_grid.hpp"
+#include "block_scan.hpp"
 #include "smallest_eigvec.hpp"
 
 #include <algorithm>
@@ -34,7 +35,7 @@ __global__ void __launch_bounds__(GRID_BLK) centroid_partial_kernel(const float 
     const size_t lo = (size_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
     for (size_t i = lo + threadIdx.x; i < hi; i += GRID_BLK) { s[0] += (double)x[i]; s[1] += (double)y[i]; s[2] += (double)z[i]; }
     for (int a = 0; a < 3; a++) {
-        for (int off = 32; off > 0; off >>= 1) s[a] += __shfl_down(s[a], off, 64);
+        k::wave_reduce_sum(s[a]);
         if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = s[a];
     }
     __syncthreads();

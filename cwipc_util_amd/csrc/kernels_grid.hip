@@ -6,6 +6,7 @@
 // 16 cells along x that exist only where points are, see SEG).  Three flows build them (grid_and_search, at the end); each ends
 // by calling the search it was given, on its stream, and gives the grid's arrays back to the pool behind it.
 #include "point_grid.hpp"
+#include "block_scan.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -147,7 +148,7 @@ __global__ void __launch_bounds__(GRID_BLK) cell_count_kernel(const GridMeta *__
     }
     if (!census) return;
     __shared__ uint32_t wsum[GRID_BLK / 64];
-    for (int off = 32; off > 0; off >>= 1) fresh += __shfl_down(fresh, off, 64);
+    k::wave_reduce_sum(fresh);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = fresh;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -329,7 +330,7 @@ __global__ void __launch_bounds__(GRID_BLK) small_count_kernel(const float *__re
         }
     }
     if (PHASE != 0) return;
-    for (int off = 32; off > 0; off >>= 1) fresh += __shfl_down(fresh, off, 64);
+    k::wave_reduce_sum(fresh);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = fresh;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -390,7 +391,7 @@ __global__ void __launch_bounds__(GRID_BLK) seg_census_kernel(const uint32_t *__
         cells += (uint32_t)__popc(m);
         segs += m != 0u;
     }
-    for (int off = 32; off > 0; off >>= 1) { cells += __shfl_down(cells, off, 64); segs += __shfl_down(segs, off, 64); }
+    for (int off = 32; off > 0; off >>= 1) { cells += __shfl_down(cells, off, 64); segs += __shfl_down(segs, off, 64); }   // (two sums a step)
     if ((threadIdx.x & 63) == 0) { wsum[0][threadIdx.x >> 6] = cells; wsum[1][threadIdx.x >> 6] = segs; }
     __syncthreads();
     if (threadIdx.x == 0) {

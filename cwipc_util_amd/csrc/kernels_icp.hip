@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(GRID_BLK) icp_sums_partial_kernel(typename Pai
     }
 #pragma unroll
     for (int v = 0; v < NSUM; v++) {
-        for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);
+        for (int off = 32; off > 0; off >>= 1) s[v] += __shfl_down(s[v], off, 64);   // (kept: a call changed this kernel)
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][v] = s[v];
     }
     if constexpr (Pair::HAS_MAX) {

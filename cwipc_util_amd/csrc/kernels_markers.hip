@@ -35,6 +35,7 @@
 // kernel's stores are visible to the next; inside the merge kernel, the only one in which workgroups read what others write, every
 // access to the parent array is an agent-scope atomic.
 #include "internal.hpp"
+#include "block_scan.hpp"
 
 namespace cwipc_amd {
 namespace k {
@@ -55,7 +56,6 @@ static inline unsigned marker_grid(size_t items) {
 __global__ void __launch_bounds__(MBLOCK) marker_grey_rows_kernel(const uint8_t *__restrict__ rgb, int width, int height, uint8_t *__restrict__ grey,
                                                                  uint32_t *__restrict__ sat) {
     __shared__ uint32_t wave_sum[MBLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int r = blockIdx.x; r < height; r += gridDim.x) {
         uint32_t carry = 0;
         for (int base = 0; base < width; base += MBLOCK) {
@@ -66,19 +66,9 @@ __global__ void __launch_bounds__(MBLOCK) marker_grey_rows_kernel(const uint8_t 
                 y = (77u * p[0] + 150u * p[1] + 29u * p[2] + 128u) >> 8;
                 grey[(size_t)r * width + c] = (uint8_t)y;
             }
-            uint32_t v = y;
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t o = __shfl_up(v, off, 64);
-                if (lane >= off) v += o;
-            }
-            if (lane == 63) wave_sum[wave] = v;
-            __syncthreads();
-            uint32_t before = 0, total = 0;
-            for (int i = 0; i < MBLOCK / 64; i++) {
-                if (i < wave) before += wave_sum[i];
-                total += wave_sum[i];
-            }
-            if (c < width) sat[(size_t)r * width + c] = carry + before + v;
+            uint32_t total;
+            const uint32_t before = block_exclusive_scan<MBLOCK>(y, wave_sum, &total);
+            if (c < width) sat[(size_t)r * width + c] = carry + before + y;
             carry += total;
             __syncthreads();   // wave_sum is written again in the next step
         }

@@ -17,6 +17,7 @@
 // four pixels unpacking the winners.  The minimum of a set does not depend on the order its members arrive in: the same input
 // gives the same bytes.
 #include "internal.hpp"
+#include "block_scan.hpp"
 
 #include <cmath>
 
@@ -131,7 +132,7 @@ __global__ void __launch_bounds__(RBLOCK) render_resolve_kernel(const unsigned l
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+    wave_reduce_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(covered, mine);
 }
 

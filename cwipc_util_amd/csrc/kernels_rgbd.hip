@@ -112,24 +112,13 @@ __global__ void __launch_bounds__(BLOCK) rgbd_count_kernel(const Cam *__restrict
     if (threadIdx.x == 0) counts[blockIdx.x] = t;
 }
 
-// count and scan in one launch: compact_count_scan_kernel's ticket (kernels_basic.hip)
+// count and scan in one launch (last_block_scans, block_scan.hpp)
 template <class Cam>
 __global__ void __launch_bounds__(BLOCK) rgbd_count_scan_kernel(const Cam *__restrict__ cams, int ncam, uint32_t total, RgbdFilterTerms f,
                                                                unsigned active, uint32_t *__restrict__ counts, uint32_t *__restrict__ ticket,
                                                                unsigned long long *__restrict__ total_host, uint32_t tag) {
     __shared__ uint32_t wave_sum[WAVES];
-    __shared__ uint32_t is_last;
-    const uint32_t t = count_tile(cams, ncam, total, f, active, wave_sum);
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(&counts[blockIdx.x], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t before = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = before == gridDim.x - 1 ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next kernel that uses it
-    scan_block_counts<BLOCK>(counts, gridDim.x, total_host, tag);
+    last_block_scans<BLOCK>(count_tile(cams, ncam, total, f, active, wave_sum), counts, ticket, total_host, tag);
 }
 
 // offsets: the scanned counts.  A kept pixel's rank inside the tile: the kept pixels of the steps before its own, of the waves before

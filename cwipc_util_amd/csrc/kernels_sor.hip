@@ -357,7 +357,7 @@ __global__ void __launch_bounds__(GRID_BLK) stats_partial_kernel(const float *__
         s += (double)v;
         q += (double)__fmul_rn(v, v);   // "distance * distance" is an fp32 product upstream
     }
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {   // (two sums a step)
         s += __shfl_down(s, off, 64);
         q += __shfl_down(q, off, 64);
     }

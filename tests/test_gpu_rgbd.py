@@ -77,6 +77,36 @@ def test_vga_camera_crosses_the_flow_boundary(gpu, name):
     assert_cloud(from_rgbd([cam], frame, to_filter(FILTERS[name]), 5, 0.0), want, 5, 0.0)
 
 
+def test_megapixel_camera_fills_one_scan_round(gpu):
+    """1024 x 1024 pixels are 1024 workgroups of 1024 pixels: exactly one round of the 1024-lane scan of their counts."""
+    rng = np.random.default_rng(11)
+    cam, model_cam = camera_pair(1024, 1024, 3, "mp", 3, rng)
+    frame = [images(1024, 1024, 3, rng, zeros=0.01)]
+    want = rm.cloud([model_cam], frame)
+    assert len(want) > 1000000
+    assert_cloud(from_rgbd([cam], frame, to_filter(FILTERS["off"]), 6, 0.0), want, 6, 0.0)
+
+
+@pytest.mark.parametrize("depth", ["random", "sparse"])
+def test_one_workgroup_past_a_scan_round(gpu, depth):
+    """1025 x 1024 pixels are 1025 workgroups: the scan's second round holds a single count, and what the first round carries over is
+    its offset.  sparse: depth only in workgroups 0, 1023 and 1024 (a hundred pixels each) and at the last pixel, so a wrong carry
+    shows as points at wrong places, not only as a wrong total."""
+    rng = np.random.default_rng(12)
+    width, height = 1025, 1024
+    cam, model_cam = camera_pair(width, height, 5, "mp1", 3, rng)
+    frame = [images(width, height, 3, rng, zeros=0.01)]
+    if depth == "sparse":
+        flat = np.zeros(width * height, dtype=np.uint16)
+        for group in (0, 1023, 1024):
+            flat[group * 1024 + rng.choice(1024, 100, replace=False)] = rng.integers(300, 4000, 100)
+        flat[-1] = 1234
+        frame = [(flat.reshape(height, width), frame[0][1])]
+    want = rm.cloud([model_cam], frame)
+    assert 300 <= len(want) <= 301 if depth == "sparse" else len(want) > 1000000
+    assert_cloud(from_rgbd([cam], frame, to_filter(FILTERS["off"]), 7, 0.0), want, 7, 0.0)
+
+
 def test_middle_camera_without_depth(gpu, three):
     cams, model_cams, frame = three
     rng = np.random.default_rng(3)
