@@ -49,6 +49,7 @@ SOURCES = [
     "kernels_rgbd.hip",
     "kernels_codec.hip",
     "kernels_entropy.hip",
+    "kernels_inter.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -9,8 +9,13 @@ With ``entropy=True`` an encoder delivers the entropy-coded form of the same pac
 tile streams through an interleaved rANS coder on the GPU, each stream raw where coding would not shrink it); a decoder takes both
 forms.  `entropy_pack`, `entropy_unpack` and `entropy_info` convert and inspect packets on the host.
 
-Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding, inter-frame coding, per-leaf point counts in the packet,
-sockets.
+With ``do_inter_frame=True, gop_size=n, exp_factor=f`` an encoder codes a stream of frames (RULE P, magic ``cwap``): a key packet
+every `gop_size` frames (and whenever a frame leaves the GOP's cube, which is the key frame's cube grown by `exp_factor`), delta
+packets against the frame before in between.  A decoder fed the packets in order hands out the clouds it would hand out for the
+frames coded one by one.  `inter_pack`, `inter_unpack` and `inter_info` do the same on the host.
+
+Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding, motion compensation, inter-frame coding inside an encoder
+group, per-leaf point counts in the packet, sockets.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ from .util import CwipcError, cwipc_pointcloud_wrapper
 __all__ = [
     "cwipc_encoder_params", "cwipc_new_encoder_params", "cwipc_new_encoder", "cwipc_new_encodergroup", "cwipc_new_decoder",
     "cwipc_encoder_wrapper", "cwipc_encodergroup_wrapper", "cwipc_decoder_wrapper", "packet_info",
-    "entropy_pack", "entropy_unpack", "entropy_info",
+    "entropy_pack", "entropy_unpack", "entropy_info", "inter_pack", "inter_unpack", "inter_info",
 ]
 
 
@@ -228,3 +233,43 @@ def entropy_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
                 nodes=list(info.nodes)[:info.octree_bits], unpacked_bytes=info.total_bytes,
                 streams=[(d.mode[i], d.payload_bytes[i]) for i in range(d.nstreams)],
                 kinds=[(names[d.kind[i]], d.which[i], d.symbols[i]) for i in range(d.nstreams)], total_bytes=d.total_bytes)
+
+
+def inter_pack(reference: Union[bytes, bytearray, memoryview], packet: Union[bytes, bytearray, memoryview], gop_index: int = 1) -> bytearray:
+    """The delta packet ("cwap", RULE P) of the plain packet `packet` against the plain packet `reference`, both with leaves and in
+    one cube (host code, no GPU); CwipcError with the reason otherwise."""
+    return util.cwipc_hip_codec_inter_pack(reference, packet, gop_index)
+
+
+def inter_unpack(reference: Optional[Union[bytes, bytearray, memoryview]], packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The plain packet an inter-frame packet stands for after `reference` (host code, no GPU); a key packet gives its embedded packet
+    verbatim and needs no reference; CwipcError with the reason for a packet that is refused."""
+    return util.cwipc_hip_codec_inter_unpack(reference, packet)
+
+
+def inter_info_kind(packet: Union[bytes, bytearray, memoryview]) -> Optional[str]:
+    """"key" or "delta" by the prefix of an inter-frame packet alone, None for anything else (no validity test)."""
+    p = bytes(packet[:12])
+    if len(p) < 12 or p[:4] != b"cwap":
+        return None
+    return {0: "key", 1: "delta"}.get(int.from_bytes(p[8:12], "little"))
+
+
+def inter_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
+    """An inter-frame packet after the container test (host code, no GPU): `kind` ("key" or "delta"), `gop_index`, `ref_timestamp`,
+    `ref_nleaves`, the header fields of the packet it stands for, and for a delta `nadded`, `nodes_added`, `streams`: [(mode, payload
+    bytes)] and `kinds`: [(name, which, symbols)]."""
+    d = util.cwipc_hip_codec_inter_info(packet)
+    info = d.packet
+    names = {0: "occupancy", 3: "bytes", 4: "colour"}
+    kinds = []
+    for i in range(d.nstreams):
+        name = names[d.kind_of[i]]
+        if name == "bytes":
+            name = "tile" if d.which[i] else "keep"
+        kinds.append((name, d.which[i], d.symbols[i]))
+    return dict(kind="delta" if d.kind else "key", gop_index=d.gop_index, ref_timestamp=d.ref_timestamp, ref_nleaves=d.ref_nleaves,
+                entropy=bool(d.embedded_entropy), timestamp=info.timestamp, nleaves=info.nleaves, octree_bits=info.octree_bits,
+                colour_bits=info.colour_bits, tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
+                nadded=d.nadded, nodes_added=list(d.nodes_added)[:info.octree_bits],
+                streams=[(d.mode[i], d.payload_bytes[i]) for i in range(d.nstreams)], kinds=kinds, total_bytes=d.total_bytes)

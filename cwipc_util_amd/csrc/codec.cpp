@@ -14,9 +14,18 @@
 // returns; whoever polls or takes the result first waits for those words and issues the copy of exactly the packet's bytes (EncJob:
 // stage 0 -> 1), and takes it when that copy is done.  Decode: the container test on the host -> upload -> the streams decoded into
 // the body buffer -> the check -> ONE wait in feed (a packet whose blocks or occupancy bytes fail is refused there) -> the decode above.
+//
+// Inter-frame coding (RULE P: hip_ext.h, inter_terms.hpp; kernels_inter.hip).  Encode: one wave behind the cube kernel decides between
+// key and delta and leaves the cube to quantise in; the choice rides to the host with the cube in the sort's one wait.  A key frame
+// is the packet above behind a prefix; its leaves are taken out of the body as the next reference.  A delta frame matches the
+// frame's leaves against the reference on the device and WAITS A SECOND TIME for the number of added leaves and their node counts,
+// which size the entropy stage's streams; from there on it is the entropy-coded form's path (report, then the copy of exactly the
+// packet's bytes).  Decode: the container test on the host -> upload -> the streams decoded, the added keys expanded, the checks ->
+// ONE wait -> merge, rebuild, points.  Both keep the frame's leaves on the device with the event of the work that made them.
 #include "internal.hpp"
 #include "codec_terms.hpp"
 #include "entropy_terms.hpp"
+#include "inter_terms.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -49,11 +58,16 @@ struct EncJob {
     size_t out_capacity = 0, out_bytes = 0, report_offset = 0;
     int stage = 0;                   // 0: the stage's kernels in flight (`done`); 1: the copy in flight (`copied`)
     hipEvent_t copied = nullptr;
+    // inter-frame packets: a key packet's prefix lies in front of `host` (the packet starts at host - prefix); a delta packet has
+    // the word S at `head` and the header's tile bytes at `tile_at`
+    size_t prefix = 0, head = 0, tile_at = 22;
+    size_t head_bytes() const { return head ? head : CODEC_HEADER_BYTES + 4u * (size_t)layout.bits; }
+    size_t packet_bytes() const { return layout.total_bytes ? prefix + (size_t)layout.total_bytes : 0; }
     ~EncJob() {
         if (done) { (void)hipEventSynchronize(done); event_put(done); }
         if (copied) { (void)hipEventSynchronize(copied); event_put(copied); }
         if (out_dev) pool_free(out_dev);
-        if (host) host_free(host, pinned);
+        if (host) host_free(host - prefix, pinned);
     }
     static bool event_done(hipEvent_t ev, bool wait) {
         if (wait) return hipEventSynchronize(ev) == hipSuccess;
@@ -69,7 +83,7 @@ struct EncJob {
         out_bytes = report[0];
         ThreadCtx &c = tctx();
         if (out_bytes < 4 || out_bytes > out_capacity || !c.ensure()) { failed = true; return; }
-        const size_t head = CODEC_HEADER_BYTES + 4u * (size_t)layout.bits;
+        const size_t head = head_bytes();
         copied = event_get();
         if (!copied || hipMemcpyAsync(host + head, out_dev, out_bytes, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
             hipEventRecord(copied, c.stream) != hipSuccess) {
@@ -97,7 +111,7 @@ struct EncJob {
         }
         src.reset();
         if (out_dev) { pool_free(out_dev); out_dev = nullptr; }
-        const size_t head = CODEC_HEADER_BYTES + 4u * (size_t)layout.bits;
+        const size_t head = head_bytes();
         layout.tile_mode = 0;
         layout.tile_value = 0;
         if (report_offset) {
@@ -109,8 +123,8 @@ struct EncJob {
         } else {
             out_bytes = 4;   // an empty cloud: S = 0, written with the header
         }
-        host[22] = (uint8_t)layout.tile_mode;
-        host[23] = (uint8_t)layout.tile_value;
+        host[tile_at] = (uint8_t)layout.tile_mode;
+        host[tile_at + 1] = (uint8_t)layout.tile_value;
         layout.total_bytes = failed ? 0u : (uint64_t)(head + out_bytes);
         if (failed) note_error("octree encode", "the entropy stage failed");
         final = true;
@@ -150,7 +164,64 @@ struct Sorted {
     uint32_t nodes[CODEC_MAX_BITS] = {0};
 };
 
-bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits, Sorted &out) {
+// A frame's leaves on the device as a decoder has them (RULE P's reference), what a delta packet names of it, and the event of the
+// work that made it: a feed from another thread's stream waits for that event first.
+struct InterRefDev {
+    void *block = nullptr;
+    k::InterLeavesDev leaves{nullptr, nullptr, nullptr, 0};
+    InterReference meta;
+    hipEvent_t ready = nullptr;
+    ~InterRefDev() {
+        if (ready) { (void)hipEventSynchronize(ready); event_put(ready); }
+        if (block) pool_free(block);
+    }
+    static std::unique_ptr<InterRefDev> make(const CodecLayout &l) {
+        std::unique_ptr<InterRefDev> r(new InterRefDev());
+        const size_t n = l.nleaves, keys_bytes = round256(8 * n);
+        uint8_t *block = (uint8_t *)pool_alloc(keys_bytes + 4 * n);
+        if (!block) return nullptr;
+        r->block = block;
+        r->leaves = k::InterLeavesDev{(unsigned long long *)block, block + keys_bytes, block + keys_bytes + 3 * n, l.nleaves};
+        r->meta.timestamp = l.timestamp;
+        r->meta.nleaves = l.nleaves;
+        r->meta.bits = l.bits;
+        r->meta.colour_bits = l.colour_bits;
+        memcpy(r->meta.mn, l.mn, 12);
+        r->meta.side = l.side;
+        return r;
+    }
+    // the work that filled the leaves has been queued on the stream
+    bool published(hipStream_t stream) {
+        ready = event_get();
+        return ready && hipEventRecord(ready, stream) == hipSuccess;
+    }
+    void wait_on(hipStream_t consumer) const {
+        if (ready && hipStreamWaitEvent(consumer, ready, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipEventSynchronize(ready);
+        }
+    }
+};
+
+// `held` gives way to `next` (may be null); kernels queued on the calling thread's stream may still read the old leaves
+void replace_reference(std::unique_ptr<InterRefDev> &held, std::unique_ptr<InterRefDev> next) {
+    if (held) {
+        tctx().free_later(held->block);
+        held->block = nullptr;
+    }
+    held = std::move(next);
+}
+
+// What an inter-mode encoder asks of the sort: the choice between key and delta, made on the device behind the cube kernel.
+struct InterAsk {
+    bool allow_delta = false;
+    float gop_mn[3] = {0, 0, 0};
+    double gop_side = 1.0;
+    float exp_factor = 1.0f;
+    bool delta = false;   // the answer
+};
+
+bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits, Sorted &out, InterAsk *ask = nullptr) {
     out.src = src;
     out.n = src->npoints;
     out.bits = bits;
@@ -172,10 +243,12 @@ bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits
     PinnedReport report = c.report();
     const uint32_t tag = report.arm(0, bits);
     k::codec_cube(*src, partial, out.cube_dev, c.stream);
+    k::InterCubeReport *inter_report = (k::InterCubeReport *)out.cube_dev;
+    if (ask) k::inter_cube(partial, n, inter_report, ask->allow_delta, ask->gop_mn, ask->gop_side, ask->exp_factor, c.stream);
     bool ok = k::codec_sort(*src, out.cube_dev, bits, out.keys, out.index, c.stream);
     if (ok) {
         k::codec_count_scan(out.keys + n, n, out.cube_dev, bits, out.counts, report.device(), tag, c.stream);
-        ok = hipMemcpyAsync(c.host_words + 32, out.cube_dev, sizeof(k::CodecCube), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = hipMemcpyAsync(c.host_words + 32, out.cube_dev, ask ? sizeof(k::InterCubeReport) : sizeof(k::CodecCube), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
         ok = ok && hipGetLastError() == hipSuccess;
     }
     ok = c.sync() && ok;
@@ -187,15 +260,37 @@ bool sort_cloud(const char *who, const std::shared_ptr<DeviceSoA> &src, int bits
         return false;
     }
     memcpy(&out.cube, c.host_words + 32, sizeof(k::CodecCube));
+    if (ask) {
+        k::InterCubeReport got;
+        memcpy(&got, c.host_words + 32, sizeof(got));
+        ask->delta = got.delta != 0u;
+    }
     for (int L = 0; L < bits; L++) out.nodes[L] = report.value(L);
     return true;
 }
 
-// The packet of (bits <= s.bits, colour shift) from a sorted cloud: queued on the calling thread's stream.
-std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp, bool entropy) {
-    ThreadCtx &c = tctx();
-    std::unique_ptr<EncJob> job(new EncJob());
-    CodecLayout &l = job->layout;
+// the bytes of a packet's body on the device: occupancy, colours, the tile plane, the two tile words
+size_t emit_body_bytes(const CodecLayout &l) { return (size_t)(l.tile_offset - l.occupancy_offset) + (size_t)codec_pad4(l.nleaves) + 8; }
+
+// where codec_emit writes in `block` (zeroed): the body, then the leaf sums at sums_offset
+k::CodecEmit emit_planes(const CodecLayout &l, uint8_t *block, size_t body_bytes, size_t sums_offset) {
+    k::CodecEmit e{};
+    e.bits = l.bits;
+    e.nleaves = l.nleaves;
+    e.depth_offset[0] = 0;
+    for (int L = 1; L < l.bits; L++) e.depth_offset[L] = L == 1 ? 1u : e.depth_offset[L - 1] + l.nodes[L - 2];
+    e.occupancy_bytes = l.occupancy_bytes;
+    e.colour_words = codec_pad4(l.colour_bytes) / 4;
+    e.occupancy = (uint32_t *)block;
+    e.colours = (uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
+    e.tiles = block + (l.tile_offset - l.occupancy_offset);
+    e.tile_stats = (uint32_t *)(block + body_bytes - 8);
+    e.sums = (k::CodecLeafSum *)(block + sums_offset);
+    return e;
+}
+
+// the header fields of the packet of (bits, colour shift) from a sorted cloud; tile_mode 1 until the leaves are known
+void emit_layout(const Sorted &s, int bits, int shift, uint64_t timestamp, CodecLayout &l) {
     l.timestamp = timestamp;
     l.bits = bits;
     l.colour_bits = 8 - shift;
@@ -207,7 +302,18 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
         l.side = s.cube.side;
     }
     codec_layout_sizes(l);
-    const size_t body_bytes = (size_t)(l.tile_offset - l.occupancy_offset) + (size_t)codec_pad4(l.nleaves) + 8;   // ... the tile plane, the two tile words
+}
+
+// The packet of (bits <= s.bits, colour shift) from a sorted cloud: queued on the calling thread's stream.
+// key_leaves (inter mode): the packet is a key packet, `prefix` bytes are kept free in front of it, and the frame's leaves are taken
+// out of the body into *key_leaves (sized for the packet's leaf count; unused for an empty cloud).
+std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp, bool entropy, size_t prefix = 0,
+                                    const k::InterLeavesDev *key_leaves = nullptr) {
+    ThreadCtx &c = tctx();
+    std::unique_ptr<EncJob> job(new EncJob());
+    CodecLayout &l = job->layout;
+    emit_layout(s, bits, shift, timestamp, l);
+    const size_t body_bytes = emit_body_bytes(l);
     // the entropy-coded form: its streams (with a tile plane, which the plan kernel drops when the tiles turn out uniform) and the
     // most bytes it can take from the word S on: a stream never takes more than its raw payload
     k::EntropyStreams st{};
@@ -232,8 +338,10 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
         job->entropy = true;
         job->out_capacity = out_capacity;
     }
-    job->host = (uint8_t *)host_alloc(entropy ? (size_t)l.occupancy_offset + out_capacity + 16 : (size_t)l.occupancy_offset + body_bytes, &job->pinned);
+    job->host = (uint8_t *)host_alloc(prefix + (entropy ? (size_t)l.occupancy_offset + out_capacity + 16 : (size_t)l.occupancy_offset + body_bytes), &job->pinned);
     if (!job->host) { note_error(who, "out of host memory"); return nullptr; }
+    job->host += prefix;
+    job->prefix = prefix;
     codec_write_header(job->host, l);
     if (entropy) {
         const uint32_t magic = ENTROPY_MAGIC, none = 0;
@@ -248,18 +356,7 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     const size_t sums_offset = (body_bytes + 7) & ~(size_t)7, block_bytes = sums_offset + (size_t)l.nleaves * sizeof(k::CodecLeafSum);
     uint8_t *block = (uint8_t *)pool_alloc(block_bytes);
     if (!block) { note_error(who, "out of device memory"); return nullptr; }
-    k::CodecEmit e{};
-    e.bits = bits;
-    e.nleaves = l.nleaves;
-    e.depth_offset[0] = 0;
-    for (int L = 1; L < bits; L++) e.depth_offset[L] = L == 1 ? 1u : e.depth_offset[L - 1] + l.nodes[L - 2];
-    e.occupancy_bytes = l.occupancy_bytes;
-    e.colour_words = codec_pad4(l.colour_bytes) / 4;
-    e.occupancy = (uint32_t *)block;
-    e.colours = (uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
-    e.tiles = block + (l.tile_offset - l.occupancy_offset);
-    e.tile_stats = (uint32_t *)(block + body_bytes - 8);
-    e.sums = (k::CodecLeafSum *)(block + sums_offset);
+    const k::CodecEmit e = emit_planes(l, block, body_bytes, sums_offset);
     uint8_t *work = nullptr;
     if (entropy) {
         work = (uint8_t *)pool_alloc(k::entropy_encode_work_bytes(st));
@@ -274,6 +371,7 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     bool ok = hipMemsetAsync(block, 0, block_bytes, c.stream) == hipSuccess;
     if (ok) {
         k::codec_emit(s.keys + s.n, s.index + s.n, *s.src, s.cube_dev, s.bits, s.counts, e, shift, c.stream);
+        if (key_leaves) k::inter_leaves_of_body(s.keys + s.n, s.n, s.cube_dev, s.counts, e, l.colour_bits, *key_leaves, c.stream);
         if (!entropy) ok = hipMemcpyAsync(job->host + l.occupancy_offset, block, body_bytes, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
         ok = ok && hipGetLastError() == hipSuccess;
     }
@@ -316,6 +414,148 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
         return nullptr;
     }
     if (!entropy) job->stats_offset = (size_t)l.occupancy_offset + body_bytes - 8;
+    job->src = s.src;
+    return job;
+}
+
+// The delta packet (RULE P) of the sorted cloud's frame against the reference R, queued on the calling thread's stream after a wait
+// of its own for the number of added leaves and their node counts.  The frame's leaves go to P (sized for its leaf count, above 0).
+std::unique_ptr<EncJob> emit_delta(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp, uint32_t gop_index, const InterRefDev &R,
+                                   const k::InterLeavesDev &P) {
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    std::unique_ptr<EncJob> job(new EncJob());
+    CodecLayout &l = job->layout;
+    emit_layout(s, bits, shift, timestamp, l);
+    const size_t n = l.nleaves, nr = R.leaves.n, nb = k::codec_blocks(n);
+    const size_t body_bytes = emit_body_bytes(l), sums_offset = (body_bytes + 7) & ~(size_t)7, body_block_bytes = sums_offset + n * sizeof(k::CodecLeafSum);
+    // the planes the entropy stage reads: keep, then the four residual planes; behind them what the match and the count of A need
+    const size_t keep_bytes = (nr + 7) / 8, res_offset = round256(keep_bytes), added_offset = res_offset + round256(4 * n),
+                 counts_offset = added_offset + round256(9 * n), counts_added_offset = counts_offset + round256((nb + 1) * 4),
+                 cube_offset = counts_added_offset + round256((size_t)bits * (nb + 1) * 4), match_bytes = cube_offset + 256;
+    if (match_bytes > 0x7fffffffull) { note_error(who, "the cloud is too large for a delta packet"); return nullptr; }
+    // (given back by hand: a block handed to free_later would return to the pool in the wait below)
+    struct Blocks {
+        uint8_t *body = nullptr, *match = nullptr, *occupancy = nullptr, *work = nullptr;
+        bool queued = false;   // kernels that read them are in flight on the calling thread's stream
+        ~Blocks() {
+            for (uint8_t *p : {body, match, occupancy, work})
+                if (queued) tctx().free_later(p); else pool_free(p);
+        }
+    } blocks;
+    blocks.body = (uint8_t *)pool_alloc(body_block_bytes);
+    blocks.match = (uint8_t *)pool_alloc(match_bytes);
+    if (!blocks.body || !blocks.match) { note_error(who, "out of device memory"); return nullptr; }
+    uint8_t *match = blocks.match;
+    const k::CodecEmit e = emit_planes(l, blocks.body, body_bytes, sums_offset);
+    unsigned long long *added = (unsigned long long *)(match + added_offset);
+    uint32_t *counts_added = (uint32_t *)(match + counts_added_offset);
+    k::CodecCube *cube_added = (k::CodecCube *)(match + cube_offset);
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 17);   // words 0 .. bits - 1: nodesA[]; word 16: nadded
+    bool ok = hipMemsetAsync(blocks.body, 0, body_block_bytes, c.stream) == hipSuccess;
+    if (ok) {
+        k::codec_emit(s.keys + s.n, s.index + s.n, *s.src, s.cube_dev, s.bits, s.counts, e, shift, c.stream);
+        k::inter_leaves_of_body(s.keys + s.n, s.n, s.cube_dev, s.counts, e, l.colour_bits, P, c.stream);
+        k::inter_match(R.leaves, P, l.colour_bits, match, match + res_offset, added, (uint32_t *)(match + counts_offset), cube_added, report.device() + 16, tag,
+                       c.stream);
+        k::codec_count_scan(added, n, cube_added, bits, counts_added, report.device(), tag, c.stream);
+        ok = hipMemcpyAsync(c.host_words + 40, e.tile_stats, 8, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipGetLastError() == hipSuccess;
+    }
+    ok = c.sync() && ok;   // the second wait of a delta frame
+    ok = ok && report.landed(tag, 0, bits) && report.landed(tag, 16);
+    if (!ok) {
+        hip_failed(hipGetLastError(), "octree encode (match)", __FILE__, __LINE__);
+        return nullptr;
+    }
+    const uint32_t nadded = report.value(16);
+    uint32_t nodes_added[CODEC_MAX_BITS] = {0};
+    for (int L = 0; L < bits; L++) nodes_added[L] = report.value(L);
+    uint32_t stats[2];
+    memcpy(stats, c.host_words + 40, 8);
+    const bool uniform = (stats[0] & stats[1]) == 0u;
+    l.tile_mode = uniform ? 0 : 1;
+    l.tile_value = uniform ? (int)(stats[0] & 255u) : 0;
+    if (nadded > n || (nadded ? nodes_added[bits - 1] != nadded : nodes_added[bits - 1] != 0u)) { note_error(who, "the match lost count of the added leaves"); return nullptr; }
+    // the streams, now that every count is known, and the most bytes the packet can take from the word S on
+    EntropyStream streams[INTER_MAX_STREAMS];
+    k::EntropyStreams st{};
+    st.nstreams = inter_streams((uint32_t)nr, l.nleaves, bits, l.colour_bits, l.tile_mode, nadded, nodes_added, streams);
+    st.colour_bits = l.colour_bits;
+    st.nleaves = l.nleaves;
+    size_t out_capacity = 4 + 8u * (size_t)st.nstreams;
+    for (int i = 0; i < st.nstreams; i++) {
+        const EntropyStream &es = streams[i];
+        st.kind[i] = es.kind;
+        st.which[i] = es.which;
+        st.symbols[i] = es.symbols;
+        st.first_block[i] = st.total_blocks;
+        st.total_blocks += es.nblocks;
+        st.plane_offset[i] = es.kind == ENTROPY_OCCUPANCY ? (uint32_t)inter_depth_offset(nodes_added, (int)es.which)
+                             : es.kind == ENTROPY_BITS    ? (uint32_t)(res_offset + (size_t)es.which * n)
+                             : es.which == 1u             ? (uint32_t)(res_offset + 3 * n)
+                                                          : 0u;
+        st.raw_padded[i] = (uint32_t)codec_pad4(es.raw_bytes);
+        out_capacity += st.raw_padded[i];
+    }
+    if (out_capacity > 0x7fffffffull) { note_error(who, "the cloud is too large for a delta packet"); return nullptr; }
+    const size_t head = INTER_PREFIX_BYTES + INTER_HEADER_BYTES + 4u + 4u * (size_t)bits;
+    job->entropy = true;
+    job->out_capacity = out_capacity;
+    job->head = head;
+    job->tile_at = INTER_PREFIX_BYTES + 22 - 8;
+    job->report_offset = head + (size_t)codec_pad4(out_capacity);
+    job->host = (uint8_t *)host_alloc(job->report_offset + 16, &job->pinned);
+    if (!job->host) { note_error(who, "out of host memory"); return nullptr; }
+    uint8_t header[CODEC_HEADER_BYTES + 4 * CODEC_MAX_BITS];
+    codec_write_header(header, l);
+    inter_write_prefix(job->host, INTER_DELTA, gop_index, R.meta.timestamp, R.meta.nleaves);
+    memcpy(job->host + INTER_PREFIX_BYTES, header + 8, INTER_HEADER_BYTES);
+    memcpy(job->host + INTER_PREFIX_BYTES + INTER_HEADER_BYTES, &nadded, 4);
+    memcpy(job->host + INTER_PREFIX_BYTES + INTER_HEADER_BYTES + 4, nodes_added, 4u * (size_t)bits);
+    // the occupancy bytes of the added leaves
+    uint64_t depth_offset[CODEC_MAX_BITS] = {0};
+    for (int L = 0; L < bits; L++) depth_offset[L] = inter_depth_offset(nodes_added, L);
+    const uint64_t occupancy_bytes = nadded ? depth_offset[bits - 1] + (bits > 1 ? nodes_added[bits - 2] : 1u) : 0u;
+    const size_t occupancy_block = round256((size_t)codec_pad4(occupancy_bytes) + 4);
+    blocks.occupancy = (uint8_t *)pool_alloc(occupancy_block);
+    blocks.work = (uint8_t *)pool_alloc(k::entropy_encode_work_bytes(st));
+    job->out_dev = pool_alloc(round256(out_capacity));
+    if (!blocks.occupancy || !blocks.work || !job->out_dev) { note_error(who, "out of device memory"); return nullptr; }
+    k::EntropyEncode en{};
+    en.st = st;
+    en.planes = match;
+    en.occupancy = blocks.occupancy;
+    en.tile_stats = e.tile_stats;
+    const size_t S = (size_t)st.nstreams, nblocks = st.total_blocks;
+    uint8_t *at = blocks.work;
+    en.hist = (uint32_t *)at; at += S * 1024;
+    en.block_words = (uint32_t *)at; at += nblocks * 4;
+    en.block_bytes = (uint32_t *)at; at += nblocks * 4;
+    en.block_offset = (uint32_t *)at; at += nblocks * 4;
+    en.plan = (uint32_t *)at; at += S * 12;
+    en.report = (uint32_t *)at; at += 16;
+    en.freq = (uint16_t *)at; at += S * 512;
+    en.slots = blocks.work + round256((size_t)(at - blocks.work));
+    en.out = (uint8_t *)job->out_dev;
+    en.out_capacity = out_capacity;
+    blocks.queued = true;
+    ok = hipMemsetAsync(blocks.occupancy, 0, occupancy_block, c.stream) == hipSuccess && hipMemsetAsync(en.hist, 0, S * 1024, c.stream) == hipSuccess &&
+         hipMemsetAsync(job->out_dev, 0, out_capacity, c.stream) == hipSuccess;
+    if (ok) {
+        k::inter_occupancy(added, nadded, n, bits, counts_added, depth_offset, occupancy_bytes, (uint32_t *)blocks.occupancy, c.stream);
+        k::entropy_encode(en, c.stream);
+        ok = hipMemcpyAsync(job->host + job->report_offset, en.report, 16, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipGetLastError() == hipSuccess;
+    }
+    job->done = event_get();
+    ok = ok && job->done && hipEventRecord(job->done, c.stream) == hipSuccess;
+    if (!ok) {
+        (void)c.sync();
+        hip_failed(hipGetLastError(), "octree encode (delta)", __FILE__, __LINE__);
+        return nullptr;
+    }
     job->src = s.src;
     return job;
 }
@@ -366,9 +606,11 @@ T guarded(const char *who, T failed, Body &&body) {
 }
 
 const char *params_problem(const cwipc_hip_encoder_params &p) {
-    if (p.do_inter_frame) return "do_inter_frame is not supported (inter-frame coding is out of scope)";
-    if (p.gop_size != 1) return "gop_size must be 1";
-    if (!(p.exp_factor == 1.0f)) return "exp_factor must be 1.0";
+    if (!inter_params_on(p.do_inter_frame, p.gop_size, p.exp_factor)) {
+        if (p.do_inter_frame) return "do_inter_frame needs gop_size in 2..65535 and exp_factor in 1..16 with it (RULE P)";
+        if (p.gop_size != 1) return "gop_size must be 1 (inter mode: do_inter_frame with gop_size in 2..65535 and exp_factor in 1..16)";
+        if (!(p.exp_factor == 1.0f)) return "exp_factor must be 1.0 (inter mode: do_inter_frame with gop_size in 2..65535 and exp_factor in 1..16)";
+    }
     if (p.octree_bits < 1 || p.octree_bits > CODEC_MAX_BITS) return "octree_bits must be in 1..16";
     if (p.jpeg_quality < 0 || p.jpeg_quality > 100) return "jpeg_quality must be in 0..100";
     if (std::isnan(p.voxelsize)) return "voxelsize is not a number";
@@ -385,6 +627,13 @@ struct cwipc_hip_encoder {
     bool in_group = false;
     bool entropy = false;   // deliver the entropy-coded form (RULE E); chosen before the first feed
     bool fed = false;
+    // inter mode (RULE P): the sequence, the GOP's cube and the reference, under a lock of their own that a feed holds throughout
+    bool inter = false;
+    std::mutex inter_lock;
+    InterSequence sequence;
+    float gop_mn[3] = {0, 0, 0};
+    double gop_side = 1.0;
+    std::unique_ptr<InterRefDev> reference;
 };
 
 struct cwipc_hip_encodergroup {
@@ -402,6 +651,9 @@ struct cwipc_hip_decoder {
     std::mutex lock;
     std::deque<Job> queue;
     bool closed = false;
+    // the frame of the last "cwap" packet (RULE P), under a lock of its own that a feed of such a packet holds throughout
+    std::mutex inter_lock;
+    std::unique_ptr<InterRefDev> reference;
 };
 
 namespace {
@@ -516,6 +768,61 @@ size_t hand_out(const std::vector<uint8_t> &made, void *out, size_t capacity) {
     return made.size();
 }
 
+// A frame of an inter-mode encoder: key or delta as the sequence rules and the device's answer say; the frame's leaves become the reference.
+int encoder_feed_inter(const char *who, cwipc_hip_encoder *enc, const std::shared_ptr<DeviceSoA> &src, uint64_t timestamp) {
+    std::lock_guard<std::mutex> guard(enc->inter_lock);
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const int bits = enc->params.octree_bits, shift = codec_colour_shift(enc->params.jpeg_quality);
+    if (enc->reference) enc->reference->wait_on(c.stream);
+    InterAsk ask;
+    ask.allow_delta = !enc->sequence.at_gop_boundary();
+    for (int a = 0; a < 3; a++) ask.gop_mn[a] = enc->gop_mn[a];
+    ask.gop_side = enc->gop_side;
+    ask.exp_factor = enc->params.exp_factor;
+    Sorted s;
+    std::unique_ptr<EncJob> job;
+    std::unique_ptr<InterRefDev> next;
+    if (sort_cloud(who, src, bits, s, &ask)) {
+        CodecLayout l;
+        emit_layout(s, bits, shift, timestamp, l);
+        uint32_t gop_index = 0;
+        const uint32_t kind = enc->sequence.next(l.nleaves == 0u, ask.delta, gop_index);
+        bool ok = true;
+        if (l.nleaves) {
+            next = InterRefDev::make(l);
+            if (!next) { note_error(who, "out of device memory"); ok = false; }
+        }
+        if (ok && kind == INTER_KEY) {
+            job = emit_packet(who, s, bits, shift, timestamp, enc->entropy, INTER_PREFIX_BYTES, next ? &next->leaves : nullptr);
+            if (job) {
+                inter_write_prefix(job->host - INTER_PREFIX_BYTES, INTER_KEY, 0, 0, 0);
+                if (l.nleaves) {
+                    for (int a = 0; a < 3; a++) enc->gop_mn[a] = l.mn[a];
+                    enc->gop_side = l.side;
+                }
+            }
+        } else if (ok) {
+            job = emit_delta(who, s, bits, shift, timestamp, gop_index, *enc->reference, next->leaves);
+        }
+        if (job && next && !next->published(c.stream)) {
+            (void)c.sync();
+            job.reset();
+        }
+        c.free_later(s.block);
+    }
+    if (!job) {   // the sequence starts anew with a key frame
+        next.reset();
+        enc->sequence = InterSequence();
+        enc->sequence.gop_size = enc->params.gop_size;
+    }
+    replace_reference(enc->reference, std::move(next));
+    if (!job) return -1;
+    std::lock_guard<std::mutex> l(enc->lock);
+    enc->queue.push_back(std::move(job));
+    return 0;
+}
+
 int encoder_feed_sorted(const char *who, cwipc_hip_encoder *enc, const Sorted &s, uint64_t timestamp) {
     auto job = emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp, enc->entropy);
     if (!job) return -1;
@@ -537,6 +844,8 @@ extern "C" cwipc_hip_encoder *cwipc_hip_new_encoder(const cwipc_hip_encoder_para
     cwipc_hip_encoder *enc = new (std::nothrow) cwipc_hip_encoder();
     if (!enc) { note_error(who, "out of memory"); return nullptr; }
     enc->params = *params;
+    enc->inter = inter_params_on(params->do_inter_frame, params->gop_size, params->exp_factor);
+    enc->sequence.gop_size = enc->inter ? params->gop_size : 1;
     return enc;
 }
 
@@ -558,7 +867,9 @@ extern "C" int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_pointcloud *
         std::unique_ptr<cwipc_hip_pointcloud> keep;
         int rv = -1;
         auto src = filtered_input(who, pc, enc->params.tilenumber, enc->params.voxelsize, made.list, keep);
-        if (src) {
+        if (src && enc->inter) {
+            rv = encoder_feed_inter(who, enc, src, pc->timestamp());
+        } else if (src) {
             Sorted s;
             if (sort_cloud(who, src, enc->params.octree_bits, s)) {
                 rv = encoder_feed_sorted(who, enc, s, pc->timestamp());
@@ -590,7 +901,7 @@ extern "C" size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc) {
     std::lock_guard<std::mutex> l(enc->lock);
     if (enc->queue.empty()) return 0;
     enc->queue.front()->finalize();
-    return (size_t)enc->queue.front()->layout.total_bytes;
+    return enc->queue.front()->packet_bytes();
 }
 
 extern "C" bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size) {
@@ -599,13 +910,17 @@ extern "C" bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer
     if (enc->queue.empty()) return false;
     EncJob &job = *enc->queue.front();
     job.finalize();
-    if (size < (size_t)job.layout.total_bytes) return false;
-    memcpy(buffer, job.host, (size_t)job.layout.total_bytes);
+    if (size < job.packet_bytes()) return false;
+    memcpy(buffer, job.host - job.prefix, job.packet_bytes());
     enc->queue.pop_front();
     return true;
 }
 
-extern "C" bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc) { (void)enc; return true; }
+extern "C" bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc) {
+    if (enc == nullptr || !enc->inter) return true;
+    std::lock_guard<std::mutex> guard(enc->inter_lock);
+    return enc->sequence.at_gop_boundary();
+}
 
 extern "C" bool cwipc_hip_encoder_eof(cwipc_hip_encoder *enc) {
     if (enc == nullptr) return true;
@@ -633,6 +948,11 @@ extern "C" cwipc_hip_encoder *cwipc_hip_encodergroup_addencoder(cwipc_hip_encode
     if (group == nullptr) {
         ErrorbufScope scope(errorMessage);
         note_error("cwipc_hip_encodergroup_addencoder", "NULL argument");
+        return nullptr;
+    }
+    if (params != nullptr && inter_params_on(params->do_inter_frame, params->gop_size, params->exp_factor)) {
+        ErrorbufScope scope(errorMessage);
+        note_error("cwipc_hip_encodergroup_addencoder", "do_inter_frame: inter-frame coding is not available inside an encoder group (out of scope)");
         return nullptr;
     }
     cwipc_hip_encoder *enc = cwipc_hip_new_encoder(params, errorMessage);
@@ -757,6 +1077,59 @@ extern "C" int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// inter-frame packets on the host (no GPU)
+// ---------------------------------------------------------------------------
+extern "C" size_t cwipc_hip_codec_inter_pack(const void *r, size_t rlen, const void *p, size_t plen, uint32_t gop_index, void *out, size_t capacity,
+                                             char **errorMessage) {
+    const char *who = "cwipc_hip_codec_inter_pack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = inter_pack((const uint8_t *)r, rlen, (const uint8_t *)p, plen, gop_index, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" size_t cwipc_hip_codec_inter_unpack(const void *r, size_t rlen, const void *d, size_t dlen, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_inter_unpack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = inter_unpack((const uint8_t *)r, rlen, (const uint8_t *)d, dlen, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" int cwipc_hip_codec_inter_info(const void *bytes, size_t len, cwipc_hip_codec_inter_directory *info, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_inter_info";
+    ErrorbufScope scope(errorMessage);
+    InterLayout e;
+    if (const char *problem = inter_validate((const uint8_t *)bytes, len, nullptr, e)) { note_error(who, problem); return -1; }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->kind = e.kind;
+        info->gop_index = e.gop_index;
+        info->ref_timestamp = e.ref_timestamp;
+        info->ref_nleaves = e.ref_nleaves;
+        info->embedded_entropy = e.embedded_entropy ? 1 : 0;
+        fill_info(e.cwao, &info->packet);
+        info->nadded = e.nadded;
+        for (int d = 0; d < e.cwao.bits; d++) info->nodes_added[d] = e.nodes_added[d];
+        info->nstreams = e.nstreams;
+        for (int i = 0; i < e.nstreams; i++) {
+            info->kind_of[i] = (int32_t)e.stream[i].kind;
+            info->which[i] = (int32_t)e.stream[i].which;
+            info->mode[i] = (int32_t)e.stream[i].mode;
+            info->symbols[i] = e.stream[i].symbols;
+            info->payload_offset[i] = e.stream[i].payload_offset;
+            info->payload_bytes[i] = e.stream[i].payload_bytes;
+        }
+        info->total_bytes = e.total_bytes;
+    }
+    return 0;
+}
+
 extern "C" cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage) {
     ErrorbufScope scope(errorMessage);
     cwipc_hip_decoder *d = new (std::nothrow) cwipc_hip_decoder();
@@ -764,84 +1137,260 @@ extern "C" cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage) {
     return d;
 }
 
+namespace {
+
+// A "cwao" or "cwae" packet into a cloud on the decoder's queue.  keep_reference (the packet is a key packet's, RULE P; the caller
+// holds the decoder's inter_lock): the frame's leaves become the decoder's reference, none for an empty cloud.
+int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *bytes, size_t len, bool keep_reference) {
+    // the validity test: host code, before anything is launched or allocated on the device
+    CodecLayout l;
+    EntropyLayout el;
+    const bool coded = bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == ENTROPY_MAGIC;
+    if (const char *problem = coded ? entropy_validate((const uint8_t *)bytes, len, el) : codec_validate((const uint8_t *)bytes, len, l)) {
+        note_error(who, problem);
+        return -1;
+    }
+    if (coded) {
+        l = el.cwao;
+        if (el.total_bytes > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
+    }
+    if (!device_available(who)) return -1;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const double cell = codec_cellsize(l.side, l.bits);
+    cwipc_hip_decoder::Job job;
+    auto dst = soa_alloc(l.nleaves);
+    if (!dst) { note_error(who, "out of device memory"); return -1; }
+    if (l.nleaves) {
+        const size_t body = (size_t)(l.total_bytes - l.occupancy_offset);
+        k::CodecDecode d{};
+        d.bits = l.bits;
+        d.colour_bits = l.colour_bits;
+        d.tile_value = l.tile_value;
+        d.nleaves = l.nleaves;
+        for (int i = 0; i < l.bits; i++) d.nodes[i] = l.nodes[i];
+        for (int a = 0; a < 3; a++) d.mn[a] = l.mn[a];
+        d.cell = cell;
+        d.colour_words = codec_pad4(l.colour_bytes) / 4;
+        const size_t body_bytes = round256(body + 8), ping_bytes = round256((size_t)l.nleaves * 8), scratch_bytes = round256(k::codec_decode_scratch_words(d) * 4);
+        uint8_t *block = (uint8_t *)pool_alloc(body_bytes + 2 * ping_bytes + scratch_bytes);
+        if (!coded) job.host = (uint8_t *)host_alloc(body, &job.pinned);
+        if (!block || (!coded && !job.host)) {
+            pool_free(block);
+            if (job.host) host_free(job.host, job.pinned);
+            note_error(who, "out of memory");
+            return -1;
+        }
+        d.colours = (const uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
+        d.tiles = l.tile_mode == 1 ? block + (l.tile_offset - l.occupancy_offset) : nullptr;
+        bool ok = true;
+        if (coded) {
+            // the body comes from the entropy stage; a packet it refuses ends here, before any kernel of the octree decoder
+            if (!entropy_to_body(who, c, (const uint8_t *)bytes, el, block)) {
+                pool_free(block);
+                return -1;
+            }
+        } else {
+            memcpy(job.host, (const uint8_t *)bytes + l.occupancy_offset, body);
+            ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
+        }
+        if (ok) {
+            k::codec_decode(block, d, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
+                            (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        c.free_later(block);
+        if (!ok) {
+            (void)c.sync();
+            if (job.host) host_free(job.host, job.pinned);
+            hip_failed(hipGetLastError(), "octree decode", __FILE__, __LINE__);
+            return -1;
+        }
+        if (keep_reference) {
+            // the leaves as the kernels above left them: the keys where the last depth's expansion wrote them
+            std::unique_ptr<InterRefDev> next = InterRefDev::make(l);
+            const uint8_t *leaf_keys = block + body_bytes + (l.bits % 2 ? ping_bytes : 0);
+            if (!next || hipMemcpyAsync(next->leaves.keys, leaf_keys, 8u * (size_t)l.nleaves, hipMemcpyDeviceToDevice, c.stream) != hipSuccess) {
+                (void)c.sync();
+                if (job.host) host_free(job.host, job.pinned);
+                note_error(who, "the reference could not be kept");
+                return -1;
+            }
+            k::inter_leaves_of_planes(d.colours, d.colour_words, d.tiles, d.tile_value, l.colour_bits, next->leaves, c.stream);
+            if (!next->published(c.stream)) (void)c.sync();
+            replace_reference(dec->reference, std::move(next));
+        }
+        dst->mark_pending(c.stream);
+    } else if (keep_reference) {
+        replace_reference(dec->reference, nullptr);
+    }
+    auto *cloud = new cwipc_hip_pointcloud();
+    cloud->adopt_device(dst, l.timestamp, (float)cell);
+    job.cloud = cloud;
+    job.planes = dst;
+    std::lock_guard<std::mutex> lk(dec->lock);
+    dec->queue.push_back(job);
+    return 0;
+}
+
+// A delta packet (RULE P) that has passed inter_validate() against the reference held (the caller holds the decoder's inter_lock):
+// upload, the streams decoded into byte planes, the added keys expanded, the checks, ONE wait; a delta that fails a check ends there,
+// with the reference as it was.  Then the merge, the colours and tiles, the points; the frame becomes the reference.
+int decoder_feed_delta(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, const InterLayout &il) {
+    if (!device_available(who)) return -1;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const CodecLayout &l = il.cwao;
+    const InterRefDev &R = *dec->reference;
+    const size_t n = l.nleaves, nr = R.leaves.n, nadded = il.nadded;
+    const size_t keep_bytes = (nr + 7) / 8, res_offset = round256(keep_bytes), planes_bytes = res_offset + round256(4 * n);
+    k::EntropyDecode d{};
+    d.st.nstreams = il.nstreams;
+    d.st.colour_bits = l.colour_bits;
+    d.st.nleaves = l.nleaves;
+    for (int i = 0; i < il.nstreams; i++) {
+        const EntropyStream &es = il.stream[i];
+        d.st.kind[i] = es.kind;
+        d.st.which[i] = es.which;
+        d.st.symbols[i] = es.symbols;
+        d.st.first_block[i] = d.st.total_blocks;
+        d.st.total_blocks += es.nblocks;
+        d.st.plane_offset[i] = es.kind == ENTROPY_OCCUPANCY ? (uint32_t)inter_depth_offset(il.nodes_added, (int)es.which)
+                               : es.kind == ENTROPY_BITS    ? (uint32_t)(res_offset + (size_t)es.which * n)
+                               : es.which == 1u             ? (uint32_t)(res_offset + 3 * n)
+                                                            : 0u;
+        d.st.raw_padded[i] = (uint32_t)codec_pad4(es.raw_bytes);
+        d.mode[i] = es.mode;
+        d.payload_offset[i] = (uint32_t)(es.payload_offset - il.directory_offset);
+        d.payload_bytes[i] = (uint32_t)es.payload_bytes;
+        d.children[i] = es.children;
+    }
+    k::CodecDecode added_tree{};   // the tree of the added leaves, for codec_expand
+    added_tree.bits = l.bits;
+    added_tree.nleaves = il.nadded;
+    for (int i = 0; i < l.bits; i++) added_tree.nodes[i] = il.nodes_added[i];
+    const uint64_t occupancy_bytes = nadded ? inter_depth_offset(il.nodes_added, l.bits - 1) + (l.bits > 1 ? il.nodes_added[l.bits - 2] : 1u) : 0u;
+    const size_t in_bytes = (size_t)(il.total_bytes - il.directory_offset), table_offset = (in_bytes + 7) & ~(size_t)7,
+                 table_bytes = 8u * (size_t)d.st.total_blocks, upload_bytes = round256(table_offset + table_bytes),
+                 occupancy_block = round256((size_t)occupancy_bytes + 8), ping_bytes = round256(8 * nadded + 8),
+                 scratch_bytes = round256(k::codec_decode_scratch_words(added_tree) * 4), nrb = k::codec_blocks(nr),
+                 rank_bytes = round256((nr + 1) * 4), counts_bytes = round256((nrb + 1) * 4), flag_bytes = 256;
+    const size_t planes_at = upload_bytes, occupancy_at = planes_at + planes_bytes, ping_at = occupancy_at + occupancy_block, scratch_at = ping_at + 2 * ping_bytes,
+                 rank_at = scratch_at + scratch_bytes, counts_at = rank_at + rank_bytes, flags_at = counts_at + counts_bytes;
+    bool pinned = false;
+    uint8_t *host = (uint8_t *)host_alloc(upload_bytes, &pinned);
+    uint8_t *dev = (uint8_t *)pool_alloc(flags_at + flag_bytes);
+    if (!host || !dev) {
+        if (host) host_free(host, pinned);
+        pool_free(dev);
+        note_error(who, "out of memory");
+        return -1;
+    }
+    memcpy(host, bytes + il.directory_offset, in_bytes);
+    uint32_t *table = (uint32_t *)(host + table_offset);
+    memset(table, 0, table_bytes);
+    for (int i = 0; i < il.nstreams; i++) {
+        const EntropyStream &es = il.stream[i];
+        if (es.mode != 1u) continue;
+        uint32_t at = d.payload_offset[i] + ENTROPY_TABLE_BYTES + 4u * es.nblocks;   // (the container test has held the sizes to the payload)
+        for (uint32_t b = 0; b < es.nblocks; b++) {
+            const uint32_t size = codec_read<uint32_t>(bytes + es.payload_offset + ENTROPY_TABLE_BYTES + 4u * (size_t)b);
+            table[2 * (d.st.first_block[i] + b)] = at;
+            table[2 * (d.st.first_block[i] + b) + 1] = size;
+            at += size;
+        }
+    }
+    d.in = dev;
+    d.block_at = (const uint32_t *)(dev + table_offset);
+    d.planes = dev + planes_at;
+    d.occupancy = dev + occupancy_at;
+    d.flags = (uint32_t *)(dev + flags_at);   // words 0 .. S: the entropy stage's; word 32: the checks'
+    const uint8_t *keep = d.planes, *res = d.planes + res_offset;
+    unsigned long long *ping = (unsigned long long *)(dev + ping_at), *pong = (unsigned long long *)(dev + ping_at + ping_bytes);
+    uint32_t *rank = (uint32_t *)(dev + rank_at);
+    R.wait_on(c.stream);
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 3);   // word 0: the entropy stage's status; word 1: the checks'; word 2: the kept leaves
+    bool ok = hipMemcpyAsync(dev, host, table_offset + table_bytes, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+              hipMemsetAsync(d.flags, 0, flag_bytes, c.stream) == hipSuccess;
+    const unsigned long long *added = ping;
+    if (ok) {
+        k::entropy_decode(d, report.device(), tag, c.stream);
+        if (nadded) added = k::codec_expand(d.occupancy, added_tree, ping, pong, (uint32_t *)(dev + scratch_at), c.stream);
+        k::inter_check(R.leaves, keep, added, il.nadded, l.nleaves, rank, (uint32_t *)(dev + counts_at), d.flags + 32, report.device() + 1, tag, c.stream);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = c.sync() && ok;   // the one wait: the streams are in their planes, the two status words are here
+    host_free(host, pinned);
+    if (!ok || !report.landed(tag, 0) || !report.landed(tag, 1)) {
+        pool_free(dev);
+        hip_failed(hipGetLastError(), "octree decode (delta)", __FILE__, __LINE__);
+        return -1;
+    }
+    const uint32_t status = report.value(0) | report.value(1);
+    const char *problem = status & 1u    ? "entropy-coded block is not intact"
+                          : status & 2u  ? "occupancy byte is 0"
+                          : status & 4u  ? "occupancy bits differ from the node count"
+                          : status & 16u ? "padding bits of the kept leaves are not 0"
+                          : status & 32u ? "kept and added leaves differ from the leaf count"
+                          : status & 8u  ? "an added leaf is a leaf of the reference"
+                                         : nullptr;
+    if (problem) {
+        pool_free(dev);
+        note_error(who, problem);
+        return -1;
+    }
+    const double cell = codec_cellsize(l.side, l.bits);
+    auto dst = soa_alloc(l.nleaves);
+    std::unique_ptr<InterRefDev> next = InterRefDev::make(l);
+    if (!dst || !next) {
+        pool_free(dev);
+        note_error(who, "out of device memory");
+        return -1;
+    }
+    k::CodecDecode points{};
+    points.bits = l.bits;
+    points.colour_bits = l.colour_bits;
+    points.tile_value = l.tile_value;
+    points.nleaves = l.nleaves;
+    for (int a = 0; a < 3; a++) points.mn[a] = l.mn[a];
+    points.cell = cell;
+    k::inter_apply(R.leaves, keep, rank, added, il.nadded, res, points, l.tile_mode, next->leaves, *dst, c.stream);
+    ok = hipGetLastError() == hipSuccess && next->published(c.stream);
+    c.free_later(dev);
+    if (!ok) {
+        (void)c.sync();
+        hip_failed(hipGetLastError(), "octree decode (delta)", __FILE__, __LINE__);
+        return -1;
+    }
+    dst->mark_pending(c.stream);
+    replace_reference(dec->reference, std::move(next));
+    cwipc_hip_decoder::Job job;
+    auto *cloud = new cwipc_hip_pointcloud();
+    cloud->adopt_device(dst, l.timestamp, (float)cell);
+    job.cloud = cloud;
+    job.planes = dst;
+    std::lock_guard<std::mutex> lk(dec->lock);
+    dec->queue.push_back(job);
+    return 0;
+}
+}  // namespace
+
 extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes, size_t len) {
     const char *who = "cwipc_hip_decoder_feed";
     return guarded(who, -1, [&]() -> int {
         if (dec == nullptr) { note_error(who, "NULL argument"); return -1; }
         if (dec->closed) { note_error(who, "the decoder has been closed"); return -1; }
-        // the validity test: host code, before anything is launched or allocated on the device
-        CodecLayout l;
-        EntropyLayout el;
-        const bool coded = bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == ENTROPY_MAGIC;
-        if (const char *problem = coded ? entropy_validate((const uint8_t *)bytes, len, el) : codec_validate((const uint8_t *)bytes, len, l)) {
-            note_error(who, problem);
-            return -1;
-        }
-        if (coded) {
-            l = el.cwao;
-            if (el.total_bytes > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
-        }
-        if (!device_available(who)) return -1;
-        ThreadCtx &c = tctx();
-        if (!c.ensure()) return -1;
-        const double cell = codec_cellsize(l.side, l.bits);
-        cwipc_hip_decoder::Job job;
-        auto dst = soa_alloc(l.nleaves);
-        if (!dst) { note_error(who, "out of device memory"); return -1; }
-        if (l.nleaves) {
-            const size_t body = (size_t)(l.total_bytes - l.occupancy_offset);
-            k::CodecDecode d{};
-            d.bits = l.bits;
-            d.colour_bits = l.colour_bits;
-            d.tile_value = l.tile_value;
-            d.nleaves = l.nleaves;
-            for (int i = 0; i < l.bits; i++) d.nodes[i] = l.nodes[i];
-            for (int a = 0; a < 3; a++) d.mn[a] = l.mn[a];
-            d.cell = cell;
-            d.colour_words = codec_pad4(l.colour_bytes) / 4;
-            const size_t body_bytes = round256(body + 8), ping_bytes = round256((size_t)l.nleaves * 8), scratch_bytes = round256(k::codec_decode_scratch_words(d) * 4);
-            uint8_t *block = (uint8_t *)pool_alloc(body_bytes + 2 * ping_bytes + scratch_bytes);
-            if (!coded) job.host = (uint8_t *)host_alloc(body, &job.pinned);
-            if (!block || (!coded && !job.host)) {
-                pool_free(block);
-                if (job.host) host_free(job.host, job.pinned);
-                note_error(who, "out of memory");
-                return -1;
-            }
-            d.colours = (const uint32_t *)(block + (l.colour_offset - l.occupancy_offset));
-            d.tiles = l.tile_mode == 1 ? block + (l.tile_offset - l.occupancy_offset) : nullptr;
-            bool ok = true;
-            if (coded) {
-                // the body comes from the entropy stage; a packet it refuses ends here, before any kernel of the octree decoder
-                if (!entropy_to_body(who, c, (const uint8_t *)bytes, el, block)) {
-                    pool_free(block);
-                    return -1;
-                }
-            } else {
-                memcpy(job.host, (const uint8_t *)bytes + l.occupancy_offset, body);
-                ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
-            }
-            if (ok) {
-                k::codec_decode(block, d, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
-                                (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
-                ok = hipGetLastError() == hipSuccess;
-            }
-            c.free_later(block);
-            if (!ok) {
-                (void)c.sync();
-                if (job.host) host_free(job.host, job.pinned);
-                hip_failed(hipGetLastError(), "octree decode", __FILE__, __LINE__);
-                return -1;
-            }
-            dst->mark_pending(c.stream);
-        }
-        auto *cloud = new cwipc_hip_pointcloud();
-        cloud->adopt_device(dst, l.timestamp, (float)cell);
-        job.cloud = cloud;
-        job.planes = dst;
-        std::lock_guard<std::mutex> lk(dec->lock);
-        dec->queue.push_back(job);
-        return 0;
+        if (bytes == nullptr || len < 4 || codec_read<uint32_t>((const uint8_t *)bytes) != INTER_MAGIC) return decoder_feed_plain(who, dec, bytes, len, false);
+        // an inter-frame packet: the container test, with the reference held, before anything is launched or allocated
+        std::lock_guard<std::mutex> guard(dec->inter_lock);
+        InterReference held;
+        if (dec->reference) held = dec->reference->meta;
+        InterLayout il;
+        if (const char *problem = inter_validate((const uint8_t *)bytes, len, &held, il)) { note_error(who, problem); return -1; }
+        if (il.total_bytes > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
+        if (il.kind == INTER_KEY) return decoder_feed_plain(who, dec, (const uint8_t *)bytes + INTER_PREFIX_BYTES, len - INTER_PREFIX_BYTES, true);
+        return decoder_feed_delta(who, dec, (const uint8_t *)bytes, il);
     });
 }
 

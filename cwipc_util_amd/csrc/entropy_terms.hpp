@@ -23,7 +23,10 @@ constexpr uint32_t ENTROPY_STATES_BYTES = 4u * ENTROPY_LANES;
 constexpr uint32_t ENTROPY_TABLE_BYTES = 512u;    // u16 f[256]
 constexpr int ENTROPY_MAX_STREAMS = CODEC_MAX_BITS + 4;
 
-enum EntropyKind : uint32_t { ENTROPY_OCCUPANCY = 0, ENTROPY_COLOUR = 1, ENTROPY_TILE = 2 };
+// The first three are RULE E's streams, read from a packet's body.  The last two are plain byte planes, one byte per symbol, coded
+// without prediction (RULE P's streams, inter_terms.hpp): BYTES is raw as it is, BITS is raw packed at colour-bits per symbol.
+enum EntropyKind : uint32_t { ENTROPY_OCCUPANCY = 0, ENTROPY_COLOUR = 1, ENTROPY_TILE = 2, ENTROPY_BYTES = 3, ENTROPY_BITS = 4 };
+CW_CODEC_HD inline bool entropy_kind_packed(uint32_t kind) { return kind == ENTROPY_COLOUR || kind == ENTROPY_BITS; }
 
 // ---------------------------------------------------------------------------
 // the arithmetic (host and device)
@@ -114,6 +117,7 @@ CW_CODEC_HD inline uint32_t entropy_block_bytes(uint32_t words) { return ENTROPY
 struct EntropyStream {
     uint32_t kind = 0, which = 0;      // occupancy: the depth; colour: the channel
     uint32_t symbols = 0, nblocks = 0;
+    uint32_t children = 0;             // occupancy: the bits its bytes must hold (the node count of its depth)
     uint64_t raw_bytes = 0;            // the raw payload without its padding
     uint32_t mode = 0;
     uint64_t payload_offset = 0, payload_bytes = 0;
@@ -136,6 +140,7 @@ inline int entropy_streams(const CodecLayout &l, EntropyStream s[ENTROPY_MAX_STR
         e.kind = ENTROPY_OCCUPANCY;
         e.which = (uint32_t)d;
         e.symbols = d == 0 ? 1u : l.nodes[d - 1];
+        e.children = l.nodes[d];
         e.raw_bytes = e.symbols;
         s[n++] = e;
     }
@@ -178,22 +183,19 @@ inline void entropy_bits_put(uint8_t *plane, uint64_t bit, int width, uint32_t v
     if (((bit & 7u) + (uint64_t)width) > 8u) plane[(bit >> 3) + 1] |= (uint8_t)(v >> 8);
 }
 
-// The container test: host code, one pass over the directory, the tables and the raw streams; the coded blocks are not decoded here.
-// nullptr: the container is right and `out` filled; otherwise why not.  Nothing outside [p, p + len) is read.
-inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout &out) {
-    EntropyLayout e;
-    CodecLayout &l = e.cwao;
-    if (const char *problem = codec_validate_header(p, len, ENTROPY_MAGIC, l)) return problem;
-    e.directory_offset = CODEC_HEADER_BYTES + 4u * (uint64_t)l.bits;
-    if ((uint64_t)len < e.directory_offset + 4u) return "truncated stream count";
-    e.nstreams = entropy_streams(l, e.stream);
-    if (codec_read<uint32_t>(p + e.directory_offset) != (uint32_t)e.nstreams) return "stream count differs from the header's";
-    uint64_t at = e.directory_offset + 4u + 8u * (uint64_t)e.nstreams;
+// The directory at `directory_offset` (the u32 S, the S entries) and the payloads behind it, held to the counts of `stream[]` (kind,
+// symbols, nblocks, raw_bytes, children filled): mode, payload_offset and payload_bytes are filled in, `total_bytes` is where the
+// last payload ends, which must be `len`.  The coded blocks are not decoded here.  Nothing outside [p, p + len) is read.
+inline const char *entropy_validate_streams(const uint8_t *p, size_t len, uint64_t directory_offset, int nstreams, EntropyStream *stream, int colour_bits,
+                                            uint64_t &total_bytes) {
+    if ((uint64_t)len < directory_offset + 4u) return "truncated stream count";
+    if (codec_read<uint32_t>(p + directory_offset) != (uint32_t)nstreams) return "stream count differs from the header's";
+    uint64_t at = directory_offset + 4u + 8u * (uint64_t)nstreams;
     if ((uint64_t)len < at) return "truncated directory";
-    for (int i = 0; i < e.nstreams; i++) {
-        EntropyStream &s = e.stream[i];
-        s.mode = codec_read<uint32_t>(p + e.directory_offset + 4u + 8u * (uint64_t)i);
-        s.payload_bytes = codec_read<uint32_t>(p + e.directory_offset + 8u + 8u * (uint64_t)i);
+    for (int i = 0; i < nstreams; i++) {
+        EntropyStream &s = stream[i];
+        s.mode = codec_read<uint32_t>(p + directory_offset + 4u + 8u * (uint64_t)i);
+        s.payload_bytes = codec_read<uint32_t>(p + directory_offset + 8u + 8u * (uint64_t)i);
         if (s.mode > 1u) return "unknown stream mode";
         if (s.mode == 0u) {
             if (s.payload_bytes != codec_pad4(s.raw_bytes)) return "raw payload size differs from the header's counts";
@@ -206,11 +208,11 @@ inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout 
         s.payload_offset = at;
         at += s.payload_bytes;
     }
-    e.total_bytes = at;
-    if ((uint64_t)len < e.total_bytes) return "truncated packet";
-    if ((uint64_t)len > e.total_bytes) return "bytes behind the packet";
-    for (int i = 0; i < e.nstreams; i++) {
-        const EntropyStream &s = e.stream[i];
+    total_bytes = at;
+    if ((uint64_t)len < total_bytes) return "truncated packet";
+    if ((uint64_t)len > total_bytes) return "bytes behind the packet";
+    for (int i = 0; i < nstreams; i++) {
+        const EntropyStream &s = stream[i];
         const uint8_t *q = p + s.payload_offset;
         if (s.mode == 0u) {
             if (s.kind == ENTROPY_OCCUPANCY) {
@@ -219,9 +221,9 @@ inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout 
                     if (q[k] == 0) return "occupancy byte is 0";
                     children += (uint64_t)__builtin_popcount(q[k]);
                 }
-                if (children != l.nodes[s.which]) return "occupancy bits differ from the node count";
-            } else if (s.kind == ENTROPY_COLOUR) {
-                const uint64_t bit_count = (uint64_t)s.symbols * (uint64_t)l.colour_bits;
+                if (children != s.children) return "occupancy bits differ from the node count";
+            } else if (entropy_kind_packed(s.kind)) {
+                const uint64_t bit_count = (uint64_t)s.symbols * (uint64_t)colour_bits;
                 if ((bit_count & 7u) && (q[s.raw_bytes - 1] >> (bit_count & 7u))) return "padding is not 0";
             }
             for (uint64_t k = s.raw_bytes; k < s.payload_bytes; k++)
@@ -232,8 +234,8 @@ inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout 
         for (int k = 0; k < 256; k++) sum += codec_read<uint16_t>(q + 2 * k);
         if (sum != ENTROPY_M) return "frequencies do not sum to 4096";
         if (s.kind == ENTROPY_OCCUPANCY && codec_read<uint16_t>(q) != 0) return "occupancy byte 0 has a frequency";
-        if (s.kind == ENTROPY_COLOUR)
-            for (int k = 1 << l.colour_bits; k < 256; k++)
+        if (entropy_kind_packed(s.kind))
+            for (int k = 1 << colour_bits; k < 256; k++)
                 if (codec_read<uint16_t>(q + 2 * k) != 0) return "a colour value above its bits has a frequency";
         uint64_t blocks = 0;
         for (uint32_t k = 0; k < s.nblocks; k++) {
@@ -245,6 +247,18 @@ inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout 
         }
         if (blocks != s.payload_bytes - ENTROPY_TABLE_BYTES - 4u * (uint64_t)s.nblocks) return "block sizes differ from the payload size";
     }
+    return nullptr;
+}
+
+// The container test: host code, one pass over the directory, the tables and the raw streams; the coded blocks are not decoded here.
+// nullptr: the container is right and `out` filled; otherwise why not.  Nothing outside [p, p + len) is read.
+inline const char *entropy_validate(const uint8_t *p, size_t len, EntropyLayout &out) {
+    EntropyLayout e;
+    CodecLayout &l = e.cwao;
+    if (const char *problem = codec_validate_header(p, len, ENTROPY_MAGIC, l)) return problem;
+    e.directory_offset = CODEC_HEADER_BYTES + 4u * (uint64_t)l.bits;
+    e.nstreams = entropy_streams(l, e.stream);
+    if (const char *problem = entropy_validate_streams(p, len, e.directory_offset, e.nstreams, e.stream, l.colour_bits, e.total_bytes)) return problem;
     out = e;
     return nullptr;
 }
@@ -307,6 +321,86 @@ inline void entropy_stream_values(const uint8_t *p, const CodecLayout &l, const 
     }
 }
 
+// The payload of stream s from its plain values v (one a byte) and its mode, by RULE E: raw (a packed kind at cb bits a value), or
+// coded where the stream has at least 4096 symbols and comes out strictly smaller.  Only ENTROPY_COLOUR is predicted.
+inline void entropy_make_payload(EntropyStream &s, const std::vector<uint8_t> &v, int cb, std::vector<uint8_t> &payload) {
+    std::vector<uint8_t> raw((size_t)codec_pad4(s.raw_bytes), 0);
+    if (entropy_kind_packed(s.kind)) {
+        for (uint64_t j = 0; j < s.symbols; j++) entropy_bits_put(raw.data(), j * (uint64_t)cb, cb, v[j]);
+    } else {
+        memcpy(raw.data(), v.data(), s.symbols);
+    }
+    s.mode = 0;
+    if (s.symbols >= ENTROPY_BLOCK) {
+        std::vector<uint8_t> sym = v;
+        if (s.kind == ENTROPY_COLOUR) {
+            const uint32_t mask = (1u << cb) - 1u;
+            for (uint64_t j = 0; j < s.symbols; j++)
+                if (j % ENTROPY_BLOCK) sym[j] = (uint8_t)(((uint32_t)v[j] - (uint32_t)v[j - 1]) & mask);
+        }
+        uint32_t counts[256] = {0};
+        for (uint8_t b : sym) counts[b]++;
+        uint16_t f[256], cum[256];
+        entropy_normalise(counts, f);
+        entropy_cumulate(f, cum);
+        std::vector<uint8_t> coded(ENTROPY_TABLE_BYTES + 4u * (size_t)s.nblocks, 0);
+        memcpy(coded.data(), f, ENTROPY_TABLE_BYTES);
+        std::vector<uint16_t> words;
+        for (uint32_t k = 0; k < s.nblocks; k++) {
+            uint32_t states[ENTROPY_LANES];
+            entropy_block_encode(sym.data() + (size_t)k * ENTROPY_BLOCK, entropy_block_symbols(s.symbols, k), f, cum, states, words);
+            const uint32_t bytes = entropy_block_bytes((uint32_t)words.size());
+            memcpy(coded.data() + ENTROPY_TABLE_BYTES + 4u * (size_t)k, &bytes, 4);
+            const size_t at = coded.size();
+            coded.resize(at + bytes, 0);
+            memcpy(coded.data() + at, states, ENTROPY_STATES_BYTES);
+            if (!words.empty()) memcpy(coded.data() + at + ENTROPY_STATES_BYTES, words.data(), 2u * words.size());
+        }
+        if (coded.size() < raw.size()) {
+            s.mode = 1;
+            raw.swap(coded);
+        }
+    }
+    payload.swap(raw);
+}
+
+// The plain values of stream s (mode and sizes as entropy_validate_streams() left them) from its payload q: nullptr and v filled, or
+// why the stream is refused: a block that is not intact, or, for occupancy, RULE C's two conditions.
+inline const char *entropy_read_payload(const uint8_t *q, const EntropyStream &s, int cb, std::vector<uint8_t> &v) {
+    v.assign(s.symbols, 0);
+    if (s.mode == 0u) {
+        if (entropy_kind_packed(s.kind)) {
+            for (uint64_t j = 0; j < s.symbols; j++) v[j] = (uint8_t)entropy_bits_at(q, s.raw_bytes, j * (uint64_t)cb, cb);
+        } else {
+            memcpy(v.data(), q, s.symbols);
+        }
+        return nullptr;
+    }
+    uint16_t f[256], cum[256];
+    memcpy(f, q, ENTROPY_TABLE_BYTES);
+    entropy_cumulate(f, cum);
+    const uint8_t *block = q + ENTROPY_TABLE_BYTES + 4u * (size_t)s.nblocks;
+    for (uint32_t k = 0; k < s.nblocks; k++) {
+        const uint32_t bytes = codec_read<uint32_t>(q + ENTROPY_TABLE_BYTES + 4u * (size_t)k);
+        if (!entropy_block_decode(block, bytes, entropy_block_symbols(s.symbols, k), f, cum, v.data() + (size_t)k * ENTROPY_BLOCK))
+            return "entropy-coded block is not intact";
+        block += bytes;
+    }
+    if (s.kind == ENTROPY_COLOUR) {
+        const uint32_t mask = (1u << cb) - 1u;
+        for (uint64_t j = 0; j < s.symbols; j++)
+            if (j % ENTROPY_BLOCK) v[j] = (uint8_t)(((uint32_t)v[j] + (uint32_t)v[j - 1]) & mask);
+    } else if (s.kind == ENTROPY_OCCUPANCY) {
+        uint64_t children = 0;
+        for (uint8_t b : v) {
+            if (b == 0) return "occupancy byte is 0";
+            children += (uint64_t)__builtin_popcount(b);
+        }
+        if (children != s.children) return "occupancy bits differ from the node count";
+    }
+    return nullptr;
+}
+
 // "cwao" -> "cwae".  nullptr and `out` filled, or why the input is not a valid packet.
 inline const char *entropy_pack(const uint8_t *p, size_t len, std::vector<uint8_t> &out) {
     CodecLayout l;
@@ -314,48 +408,10 @@ inline const char *entropy_pack(const uint8_t *p, size_t len, std::vector<uint8_
     EntropyStream streams[ENTROPY_MAX_STREAMS];
     const int S = entropy_streams(l, streams);
     std::vector<std::vector<uint8_t>> payload((size_t)S);
-    std::vector<uint8_t> v, sym;
+    std::vector<uint8_t> v;
     for (int i = 0; i < S; i++) {
-        EntropyStream &s = streams[i];
-        entropy_stream_values(p, l, s, v);
-        std::vector<uint8_t> raw((size_t)codec_pad4(s.raw_bytes), 0);
-        if (s.kind == ENTROPY_COLOUR) {
-            for (uint64_t j = 0; j < s.symbols; j++) entropy_bits_put(raw.data(), j * (uint64_t)l.colour_bits, l.colour_bits, v[j]);
-        } else {
-            memcpy(raw.data(), v.data(), s.symbols);
-        }
-        s.mode = 0;
-        if (s.symbols >= ENTROPY_BLOCK) {
-            sym = v;
-            if (s.kind == ENTROPY_COLOUR) {
-                const uint32_t mask = (1u << l.colour_bits) - 1u;
-                for (uint64_t j = 0; j < s.symbols; j++)
-                    if (j % ENTROPY_BLOCK) sym[j] = (uint8_t)(((uint32_t)v[j] - (uint32_t)v[j - 1]) & mask);
-            }
-            uint32_t counts[256] = {0};
-            for (uint8_t b : sym) counts[b]++;
-            uint16_t f[256], cum[256];
-            entropy_normalise(counts, f);
-            entropy_cumulate(f, cum);
-            std::vector<uint8_t> coded(ENTROPY_TABLE_BYTES + 4u * (size_t)s.nblocks, 0);
-            memcpy(coded.data(), f, ENTROPY_TABLE_BYTES);
-            std::vector<uint16_t> words;
-            for (uint32_t k = 0; k < s.nblocks; k++) {
-                uint32_t states[ENTROPY_LANES];
-                entropy_block_encode(sym.data() + (size_t)k * ENTROPY_BLOCK, entropy_block_symbols(s.symbols, k), f, cum, states, words);
-                const uint32_t bytes = entropy_block_bytes((uint32_t)words.size());
-                memcpy(coded.data() + ENTROPY_TABLE_BYTES + 4u * (size_t)k, &bytes, 4);
-                const size_t at = coded.size();
-                coded.resize(at + bytes, 0);
-                memcpy(coded.data() + at, states, ENTROPY_STATES_BYTES);
-                if (!words.empty()) memcpy(coded.data() + at + ENTROPY_STATES_BYTES, words.data(), 2u * words.size());
-            }
-            if (coded.size() < raw.size()) {
-                s.mode = 1;
-                raw.swap(coded);
-            }
-        }
-        payload[(size_t)i].swap(raw);
+        entropy_stream_values(p, l, streams[i], v);
+        entropy_make_payload(streams[i], v, l.colour_bits, payload[(size_t)i]);
     }
     const size_t head = CODEC_HEADER_BYTES + 4u * (size_t)l.bits;
     out.assign(p, p + head);
@@ -388,38 +444,7 @@ inline const char *entropy_unpack(const uint8_t *p, size_t len, std::vector<uint
     const int cb = l.colour_bits;
     for (int i = 0; i < e.nstreams; i++) {
         const EntropyStream &s = e.stream[i];
-        const uint8_t *q = p + s.payload_offset;
-        v.assign(s.symbols, 0);
-        if (s.mode == 0u) {
-            if (s.kind == ENTROPY_COLOUR) {
-                for (uint64_t j = 0; j < s.symbols; j++) v[j] = (uint8_t)entropy_bits_at(q, s.raw_bytes, j * (uint64_t)cb, cb);
-            } else {
-                memcpy(v.data(), q, s.symbols);
-            }
-        } else {
-            uint16_t f[256], cum[256];
-            memcpy(f, q, ENTROPY_TABLE_BYTES);
-            entropy_cumulate(f, cum);
-            const uint8_t *block = q + ENTROPY_TABLE_BYTES + 4u * (size_t)s.nblocks;
-            for (uint32_t k = 0; k < s.nblocks; k++) {
-                const uint32_t bytes = codec_read<uint32_t>(q + ENTROPY_TABLE_BYTES + 4u * (size_t)k);
-                if (!entropy_block_decode(block, bytes, entropy_block_symbols(s.symbols, k), f, cum, v.data() + (size_t)k * ENTROPY_BLOCK))
-                    return "entropy-coded block is not intact";
-                block += bytes;
-            }
-            if (s.kind == ENTROPY_COLOUR) {
-                const uint32_t mask = (1u << cb) - 1u;
-                for (uint64_t j = 0; j < s.symbols; j++)
-                    if (j % ENTROPY_BLOCK) v[j] = (uint8_t)(((uint32_t)v[j] + (uint32_t)v[j - 1]) & mask);
-            } else if (s.kind == ENTROPY_OCCUPANCY) {
-                uint64_t children = 0;
-                for (uint8_t b : v) {
-                    if (b == 0) return "occupancy byte is 0";
-                    children += (uint64_t)__builtin_popcount(b);
-                }
-                if (children != l.nodes[s.which]) return "occupancy bits differ from the node count";
-            }
-        }
+        if (const char *problem = entropy_read_payload(p + s.payload_offset, s, cb, v)) return problem;
         if (s.kind == ENTROPY_OCCUPANCY) {
             memcpy(out.data() + l.occupancy_offset + entropy_depth_offset(l, (int)s.which), v.data(), s.symbols);
         } else if (s.kind == ENTROPY_TILE) {

@@ -559,6 +559,11 @@ struct CodecCube {
     uint32_t nfinite;
     double side;
 };
+// what a workgroup of the bounds kernel leaves of its points: the box of the finite ones and their number
+struct CodecBounds {
+    float lo[3], hi[3];
+    uint32_t count, pad;
+};
 struct CodecLeafSum {
     unsigned long long r, g, b;
     uint32_t count, tile;
@@ -598,24 +603,28 @@ void codec_count_scan(const unsigned long long *sorted_keys, size_t n, const Cod
 void codec_emit(const unsigned long long *sorted_keys, const uint32_t *sorted_index, const DeviceSoA &src, const CodecCube *cube, int sort_bits,
                 const uint32_t *offsets, const CodecEmit &e, int colour_shift, hipStream_t s);
 size_t codec_decode_scratch_words(const CodecDecode &d);
+// the leaves' keys from the occupancy bytes, depth by depth: returns ping or pong, whichever holds them (d.nleaves > 0)
+unsigned long long *codec_expand(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch,
+                                 hipStream_t s);
 void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch, const DeviceSoA &dst,
                   hipStream_t s);
 
 // ---- kernels_entropy.hip: the entropy-coded packet form (RULE E: hip_ext.h; the arithmetic: entropy_terms.hpp) ----
-constexpr int ENTROPY_STREAMS = 20;                      // octree_bits + 3 + 1 at the most
+constexpr int ENTROPY_STREAMS = 21;                      // RULE E: octree_bits + 3 + 1 at the most; RULE P: one more (keep)
 constexpr size_t ENTROPY_SLOT_BYTES = 256 + 2 * 4096;    // a block's states and the most words it can emit
 // The streams of one packet, in RULE E's order; block b of stream i is the global block first_block[i] + b.
 struct EntropyStreams {
     int nstreams, colour_bits;
     uint32_t nleaves, total_blocks;
     uint32_t kind[ENTROPY_STREAMS], which[ENTROPY_STREAMS], symbols[ENTROPY_STREAMS], first_block[ENTROPY_STREAMS];
-    uint32_t plane_offset[ENTROPY_STREAMS];   // occupancy: where the depth starts in the occupancy plane
+    uint32_t plane_offset[ENTROPY_STREAMS];   // occupancy: where the depth starts in the occupancy plane; ENTROPY_BYTES / _BITS: in `planes`
     uint32_t raw_padded[ENTROPY_STREAMS];     // the raw payload with its padding
 };
 // Encode: the body that codec_emit made (the tile stream is listed last and leaves when tile_stats says the tiles are uniform) -> `out`,
 // zeroed by the caller, from the word S on.  report (device, 4 words): the bytes of `out` that count, S, and the two tile words.
 struct EntropyEncode {
     EntropyStreams st;
+    const uint8_t *planes;     // the byte planes of ENTROPY_BYTES / ENTROPY_BITS streams (RULE P), or nullptr
     const uint8_t *occupancy, *tiles;
     const uint32_t *colours, *tile_stats;
     uint64_t colour_words;
@@ -638,12 +647,52 @@ struct EntropyDecode {
     uint32_t mode[ENTROPY_STREAMS], payload_offset[ENTROPY_STREAMS], payload_bytes[ENTROPY_STREAMS], children[ENTROPY_STREAMS];
     const uint8_t *in;
     const uint32_t *block_at;   // 2 x total_blocks: offset, bytes
+    uint8_t *planes;            // where ENTROPY_BYTES / ENTROPY_BITS streams go (RULE P), or nullptr
     uint8_t *occupancy, *tiles, *channels;
-    uint32_t *colours;
+    uint32_t *colours;          // nullptr: no colour plane is packed (RULE P's streams)
     uint64_t colour_words;
     uint32_t *flags;            // 1 + nstreams words, zeroed by the caller
 };
 void entropy_decode(const EntropyDecode &d, unsigned long long *status_host, uint32_t tag, hipStream_t s);
+
+// ---- kernels_inter.hip: inter-frame coding (RULE P: hip_ext.h; the arithmetic: inter_terms.hpp) ----
+// A frame's leaves as a decoder has them: keys ascending, the stored colours as three byte planes of n, the tiles.
+struct InterLeavesDev {
+    unsigned long long *keys;
+    uint8_t *colour, *tiles;   // colour + ch * n
+    uint32_t n;
+};
+// What the cube kernel leaves behind the cube for the one read-back.
+struct InterCubeReport {
+    CodecCube cube;
+    uint32_t delta, pad;       // 1: the frame is contained in the GOP's cube, which is now `cube`
+};
+// After codec_cube: the frame's cube becomes the GOP's cube where `allow_delta` and the frame is contained in it (delta), else the
+// frame's own cube grown by exp_factor (key).  One wave.
+void inter_cube(const void *partial, size_t npoints, InterCubeReport *report, bool allow_delta, const float gop_mn[3], double gop_side, float exp_factor,
+                hipStream_t s);
+// The leaves of the packet body that codec_emit made from keys sorted at e.bits: keys compacted, colours unpacked, tiles copied.
+void inter_leaves_of_body(const unsigned long long *sorted_keys, size_t npoints, const CodecCube *cube, const uint32_t *offsets, const CodecEmit &e,
+                          int colour_bits, const InterLeavesDev &out, hipStream_t s);
+// The same from a decoder's body: the keys are there already (out.keys), tiles == nullptr: tile_value throughout.
+void inter_leaves_of_planes(const uint32_t *colours, uint64_t colour_words, const uint8_t *tiles, int tile_value, int colour_bits, const InterLeavesDev &out,
+                            hipStream_t s);
+// Encoder.  keep (ceil(R.n / 8) bytes), the residual planes res (4 x P.n: r, g, b, tile), the added keys compacted into `added`
+// (P.n words) and their number into total_host (pinned, under tag) and cube_added->nfinite.  counts: codec_blocks(P.n) + 1 words.
+void inter_match(const InterLeavesDev &R, const InterLeavesDev &P, int colour_bits, uint8_t *keep, uint8_t *res, unsigned long long *added, uint32_t *counts,
+                 CodecCube *cube_added, unsigned long long *total_host, uint32_t tag, hipStream_t s);
+// the occupancy bytes (zeroed words) of the tree of `n` ascending keys, from codec_count_scan's offsets over a grid for `grid_n` keys
+void inter_occupancy(const unsigned long long *keys, uint32_t n, size_t grid_n, int bits, const uint32_t *offsets, const uint64_t depth_offset[16],
+                     uint64_t occupancy_bytes, uint32_t *occupancy, hipStream_t s);
+// Decoder.  The checks RULE P leaves to the device, after the streams are decoded and A's keys expanded: status (pinned, under tag) =
+// 8 an added leaf is a leaf of R | 16 keep's padding bits | 32 kept + added != nleaves.  rank: R.n + 1 words, the kept leaves in
+// front of each leaf of R; counts: codec_blocks(R.n) + 1 words; flags: a zeroed word.
+void inter_check(const InterLeavesDev &R, const uint8_t *keep, const unsigned long long *added, uint32_t nadded, uint32_t nleaves, uint32_t *rank,
+                 uint32_t *counts, uint32_t *flags, unsigned long long *status_host, uint32_t tag, hipStream_t s);
+// The frame a checked delta stands for: the merge of the kept and the added keys into P.keys, then per leaf the colours and the tile
+// (res: the decoded residual planes, 4 x P.n, the tile plane only with tile_mode 1) into P's planes and the point into dst.
+void inter_apply(const InterLeavesDev &R, const uint8_t *keep, const uint32_t *rank, const unsigned long long *added, uint32_t nadded, const uint8_t *res,
+                 const CodecDecode &d, int tile_mode, const InterLeavesDev &P, const DeviceSoA &dst, hipStream_t s);
 
 }  // namespace k
 

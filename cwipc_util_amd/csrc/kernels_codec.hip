@@ -32,10 +32,7 @@ __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v
 // ---------------------------------------------------------------------------
 // encode: cube
 // ---------------------------------------------------------------------------
-struct BoundsPartial {
-    float lo[3], hi[3];
-    uint32_t count, pad;
-};
+using BoundsPartial = CodecBounds;
 
 __global__ void __launch_bounds__(CB) codec_bounds_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z, size_t n,
                                                          BoundsPartial *__restrict__ partial) {
@@ -372,9 +369,8 @@ size_t codec_decode_scratch_words(const CodecDecode &d) {
 }
 
 // occupancy: the device copy of the occupancy bytes; ping, pong: nleaves 64-bit words each; scratch: codec_decode_scratch_words()
-void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch, const DeviceSoA &dst,
-                  hipStream_t s) {
-    if (!d.nleaves) return;
+unsigned long long *codec_expand(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch,
+                                 hipStream_t s) {
     (void)hipMemsetAsync(ping, 0, sizeof(unsigned long long), s);   // the root: the empty prefix
     size_t at = 0;
     for (int depth = 0; depth < d.bits; depth++) {
@@ -390,6 +386,13 @@ void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long 
         at += n;
         unsigned long long *t = ping; ping = pong; pong = t;
     }
+    return ping;
+}
+
+void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long long *ping, unsigned long long *pong, uint32_t *scratch, const DeviceSoA &dst,
+                  hipStream_t s) {
+    if (!d.nleaves) return;
+    ping = codec_expand(occupancy, d, ping, pong, scratch, s);
     CW_LAUNCH("codec_points", codec_points_kernel, dim3((unsigned)codec_blocks(d.nleaves)), dim3(CB), 0, s, ping, d, dst.x(), dst.y(), dst.z(), dst.rgbt());
 }
 

@@ -63,6 +63,7 @@ __device__ __forceinline__ uint32_t stream_value(const EntropyEncode &e, int s, 
     const uint32_t kind = e.st.kind[s];
     if (kind == ENTROPY_OCCUPANCY) return e.occupancy[(size_t)e.st.plane_offset[s] + j];
     if (kind == ENTROPY_TILE) return e.tiles[j];
+    if (kind == ENTROPY_BYTES || kind == ENTROPY_BITS) return e.planes[(size_t)e.st.plane_offset[s] + j];
     return colour_value(e.colours, e.colour_words, e.st.colour_bits, j, e.st.which[s]);
 }
 
@@ -250,7 +251,7 @@ __global__ void __launch_bounds__(EB) entropy_gather_kernel(EntropyEncode e) {
         return;
     }
     const uint32_t first = local * ENTROPY_BLOCK;
-    if (e.st.kind[s] != ENTROPY_COLOUR) {
+    if (!entropy_kind_packed(e.st.kind[s])) {
         for (uint32_t i = threadIdx.x; i < ENTROPY_BLOCK; i += EB) {
             const uint32_t j = first + i;
             if (j < symbols && j < bytes) dst[j] = (uint8_t)stream_value(e, s, j);
@@ -303,12 +304,15 @@ __global__ void __launch_bounds__(64) entropy_block_decode_kernel(EntropyDecode 
     const uint32_t first = local * ENTROPY_BLOCK, m = entropy_block_symbols(symbols, local);
     const uint32_t cb = (uint32_t)d.st.colour_bits, mask = (1u << cb) - 1u;
     const uint8_t *payload = d.in + d.payload_offset[s];
-    uint8_t *plain = kind == ENTROPY_OCCUPANCY ? d.occupancy + d.st.plane_offset[s] : kind == ENTROPY_TILE ? d.tiles : d.channels + (size_t)d.st.which[s] * d.st.nleaves;
+    uint8_t *plain = kind == ENTROPY_OCCUPANCY ? d.occupancy + d.st.plane_offset[s]
+                     : kind == ENTROPY_TILE    ? d.tiles
+                     : kind == ENTROPY_COLOUR  ? d.channels + (size_t)d.st.which[s] * d.st.nleaves
+                                               : d.planes + d.st.plane_offset[s];
     if (d.mode[s] == 0u) {
         // raw: the bytes as they are (the host has tested a raw occupancy stream), a colour's cb-bit values unpacked
         for (uint32_t i = lane; i < m; i += 64u) {
             const uint32_t j = first + i;
-            plain[j] = kind == ENTROPY_COLOUR ? (uint8_t)entropy_bits_at(payload, d.payload_bytes[s], (uint64_t)j * cb, (int)cb) : payload[j];
+            plain[j] = entropy_kind_packed(kind) ? (uint8_t)entropy_bits_at(payload, d.payload_bytes[s], (uint64_t)j * cb, (int)cb) : payload[j];
         }
         return;
     }
@@ -385,7 +389,8 @@ __global__ void __launch_bounds__(64) entropy_check_kernel(EntropyDecode d, unsi
 void entropy_decode(const EntropyDecode &d, unsigned long long *status_host, uint32_t tag, hipStream_t s) {
     if (d.st.total_blocks) {
         CW_LAUNCH("entropy_block_decode", entropy_block_decode_kernel, dim3(d.st.total_blocks), dim3(64), 0, s, d);
-        CW_LAUNCH("entropy_repack", entropy_repack_kernel, dim3((unsigned)(((size_t)d.st.nleaves + 32u * EB - 1) / (32u * EB))), dim3(EB), 0, s, d);
+        if (d.colours)
+            CW_LAUNCH("entropy_repack", entropy_repack_kernel, dim3((unsigned)(((size_t)d.st.nleaves + 32u * EB - 1) / (32u * EB))), dim3(EB), 0, s, d);
     }
     CW_LAUNCH("entropy_check", entropy_check_kernel, dim3(1), dim3(64), 0, s, d, status_host, tag);
 }

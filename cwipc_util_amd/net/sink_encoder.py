@@ -3,7 +3,8 @@
 The interface of reference python/cwipc/net/sink_encoder.py (`cwipc_sink_encoder(sink, verbose, nodrop)` with `set_encoder_params`,
 `add_stream` through the raw sink, `feed`, `statistics`); written for this library's octree codec (cwipc_util_amd.codec), whose
 packets are NOT interoperable with cwipc_codec.  One encoder per tile x octree_bits x jpeg_quality, all in one encoder group, one
-stream of the raw sink per encoder, in that order.
+stream of the raw sink per encoder, in that order.  With `gop_size` set the encoders code inter-frame (RULE P: key and delta
+packets); an encoder group takes no such encoders, so they are lone encoders then, each fed in turn.
 
 The raw sink is any object with `feed(packet, stream_index=...)` and, optionally, `add_stream(tile_index, tile_description,
 quality_description)`, `set_fourcc`, `start`, `stop`, `set_producer`, `statistics`; a plain list works too: it is filled with one list of
@@ -69,6 +70,8 @@ class _SinkEncoder:
         self.octree_bits: List[int] = [DEFAULT_OCTREE_BITS]
         self.jpeg_quality: List[int] = [DEFAULT_JPEG_QUALITY]
         self.entropy = False
+        self.gop_size: Optional[int] = None
+        self.exp_factor = 1.0
         self.encoder_group: Optional[codec.cwipc_encodergroup_wrapper] = None
         self.encoders: List[codec.cwipc_encoder_wrapper] = []
         self.streams: List[int] = []
@@ -80,11 +83,15 @@ class _SinkEncoder:
         self.stopped = False
 
     def set_encoder_params(self, tiles: Optional[List[cwipc_tileinfo_dict]], octree_bits: Union[int, Sequence[int], None] = None,
-                           jpeg_quality: Union[int, Sequence[int], None] = None, entropy: bool = False) -> None:
+                           jpeg_quality: Union[int, Sequence[int], None] = None, entropy: bool = False, gop_size: Optional[int] = None,
+                           exp_factor: Optional[float] = None) -> None:
         """entropy=True: every encoder delivers the entropy-coded form of its packets (cwipc_util_amd.codec, RULE E); a
-        cwipc_source_decoder takes both forms."""
-        assert self.encoder_group is None, "set_encoder_params comes before the first cloud"
+        cwipc_source_decoder takes both forms.  gop_size (2 or more), with exp_factor (default 1.25): inter-frame coding, a key
+        packet every gop_size frames and delta packets in between (RULE P)."""
+        assert self.encoder_group is None and not self.encoders, "set_encoder_params comes before the first cloud"
         self.entropy = bool(entropy)
+        self.gop_size = int(gop_size) if gop_size is not None else None
+        self.exp_factor = float(exp_factor) if exp_factor is not None else (1.25 if self.gop_size is not None else 1.0)
         self.tiledescriptions = tiles if tiles else [{}]
         self.octree_bits = _intlist(octree_bits, self.octree_bits)
         self.jpeg_quality = _intlist(jpeg_quality, self.jpeg_quality)
@@ -101,25 +108,33 @@ class _SinkEncoder:
             self.sink.set_producer(producer)
 
     def _init_encoders(self) -> None:
-        if self.encoder_group is not None:
+        if self.encoder_group is not None or self.encoders:
             return
-        self.encoder_group = codec.cwipc_new_encodergroup()
+        inter = self.gop_size is not None
+        if not inter:
+            self.encoder_group = codec.cwipc_new_encodergroup()
         for tile_index, tile in enumerate(self.tiledescriptions):
             mask = int(tile.get("cameraMask", 0))
             for bits in self.octree_bits:
                 for quality in self.jpeg_quality:
-                    params = codec.cwipc_encoder_params(False, 1, 1.0, bits, quality, 16, mask, 0)
-                    self.encoders.append(self.encoder_group.addencoder(params=params, entropy=self.entropy))
+                    params = codec.cwipc_encoder_params(inter, self.gop_size if inter else 1, self.exp_factor, bits, quality, 16, mask, 0)
+                    if inter:
+                        self.encoders.append(codec.cwipc_new_encoder(params=params, entropy=self.entropy))
+                    else:
+                        self.encoders.append(self.encoder_group.addencoder(params=params, entropy=self.entropy))
                     self.streams.append(self.add_stream(tile_index, tile, dict(octree_bits=bits, jpeg_quality=quality)))
                     if self.verbose:
                         print(f"encoder: stream {self.streams[-1]}: tile={tile_index} mask={mask} octree_bits={bits} jpeg_quality={quality}")
 
     def _encode(self, pc: cwipc_pointcloud_abstract) -> None:
         self._init_encoders()
-        assert self.encoder_group is not None
         self.pointcounts.append(pc.count())
         t0 = time.time()
-        self.encoder_group.feed(pc)
+        if self.encoder_group is not None:
+            self.encoder_group.feed(pc)
+        else:
+            for enc in self.encoders:
+                enc.feed(pc)
         packets = []
         for enc in self.encoders:
             if not enc.available(True):
@@ -183,6 +198,9 @@ class _SinkEncoder:
     def free(self) -> None:
         if self.encoder_group is not None:
             self.encoder_group.free()
+        else:
+            for enc in self.encoders:
+                enc.free()
         self.encoder_group = None
         self.encoders = []
 

@@ -10,6 +10,9 @@ The raw source is any object with `get()` giving a packet (or None) and, optiona
 
 The reference decodes on a thread of its own.  Here `available()` and `get()` pull: a packet goes to the decoder, whose feed returns
 with the kernels in flight, and the cloud that comes back orders whoever uses it behind them.  No thread, no queue to wait on.
+
+Inter-frame packets (RULE P) need the packet before them: a delta packet that the decoder refuses (one was lost on the way, or the
+stream was joined in the middle of a GOP) is logged and skipped, and so are the deltas behind it, until the next key packet.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ from collections import deque
 from typing import Any, Deque, List, Optional, Sequence, Union
 
 from .. import codec
+from ..util import CwipcError
 from ..abstract import cwipc_activesource_abstract, cwipc_pointcloud_abstract, cwipc_source_abstract, cwipc_tileinfo_dict
 
 __all__ = ["cwipc_source_decoder", "cwipc_activesource_decoder"]
@@ -50,6 +54,7 @@ class _Decoder(cwipc_activesource_abstract):
         self.output: Deque[cwipc_pointcloud_abstract] = deque()
         self.times_decode: List[float] = []
         self.pointcounts: List[int] = []
+        self.skipped = 0   # delta packets refused for want of their reference
 
     def free(self) -> None:
         if self.decomp is not None:
@@ -86,7 +91,14 @@ class _Decoder(cwipc_activesource_abstract):
         if self.decomp is None:
             self.decomp = codec.cwipc_new_decoder()
         t0 = time.time()
-        self.decomp.feed(packet)
+        try:
+            self.decomp.feed(packet)
+        except CwipcError as e:
+            if bytes(packet[:4]) != b"cwap" or codec.inter_info_kind(packet) != "delta":
+                raise
+            self.skipped += 1
+            print(f"netdecoder: delta packet skipped, waiting for the next key packet: {e}", flush=True)
+            return False
         if not self.decomp.available(True):
             return False
         pc = self.decomp.get()
@@ -115,6 +127,7 @@ class _Decoder(cwipc_activesource_abstract):
     def statistics(self) -> None:
         self._print1stat("decode_time", self.times_decode)
         self._print1stat("decode_count", self.pointcounts, True)
+        print(f"netdecoder: skipped_deltas: count={self.skipped}")
         if hasattr(self.source, "statistics"):
             self.source.statistics()
 

@@ -3,7 +3,7 @@ point-to-plane (D2) geometry error and colour PSNR in BT.709 YUV, each in both d
 
 The sums are made on the GPU by one call (`cwipc_hip_distortion`, RULE Q of include/cwipc_util_amd/hip_ext.h) and nothing per point
 leaves the device; this module turns them into mean squared errors and PSNRs, and wraps the codec in an encode -> decode -> compare
-loop in which no cloud becomes a host array.
+loop in which no cloud becomes a host array.  `sequence_rate` says what inter-frame coding (RULE P) saves on a sequence of frames.
 
 Not pc_error's: a degraded point inherits the normal of its nearest original point (pc_error averages the normals of equally near
 points); `peak` defaults to the largest extent of the original's finite bounding box; there is no reflectance.
@@ -16,7 +16,7 @@ from typing import Any, Dict, Iterable, List, Optional, Tuple
 from . import util
 from .util import cwipc_hip_distortion_sums, cwipc_pointcloud_wrapper
 
-__all__ = ["DirectionalDistortion", "DistortionResults", "psnr", "default_peak", "cloud_distortion", "codec_distortion", "rate_distortion"]
+__all__ = ["DirectionalDistortion", "DistortionResults", "psnr", "default_peak", "cloud_distortion", "codec_distortion", "rate_distortion", "sequence_rate"]
 
 NAN = float("nan")
 
@@ -176,4 +176,30 @@ def rate_distortion(pc: cwipc_pointcloud_wrapper, settings: Iterable[Dict[str, A
         result, nbytes = codec_distortion(pc, **kw)
         rows.append(dict(settings=s, bytes=nbytes, bits_per_input_point=8.0 * nbytes / count if count else NAN, psnr_d1=result.psnr_d1,
                          psnr_d2=result.psnr_d2, psnr_y=result.psnr_y, psnr_u=result.psnr_u, psnr_v=result.psnr_v))
+    return rows
+
+
+def sequence_rate(frames: Iterable[cwipc_pointcloud_wrapper], *, entropy: bool = False, **encoder_kwargs: Any) -> List[Dict[str, Any]]:
+    """The frames through ONE inter-mode encoder (cwipc_new_encoder's keywords: do_inter_frame=True, gop_size, exp_factor, ...), one row
+    per frame: `kind` ("key" or "delta"), `bytes` of the packet, and `intra_bytes`: the same frame coded on its own in the same cube,
+    which is the packet the delta stands for (cwipc_util_amd.codec.inter_unpack, on the host), entropy-coded when `entropy`."""
+    from . import codec
+    enc = codec.cwipc_new_encoder(entropy=entropy, **encoder_kwargs)
+    rows: List[Dict[str, Any]] = []
+    held: Optional[bytes] = None
+    try:
+        for pc in frames:
+            enc.feed(pc)
+            if not enc.available(True):
+                raise util.CwipcError("sequence_rate: the encoder delivered nothing")
+            packet = bytes(enc.get_bytes())
+            info = codec.inter_info(packet)
+            plain = bytes(codec.inter_unpack(held, packet))
+            if info["kind"] == "key" and info["entropy"]:
+                plain = bytes(codec.entropy_unpack(plain))
+            intra = len(codec.entropy_pack(plain)) if entropy else len(plain)
+            rows.append(dict(kind=info["kind"], gop_index=info["gop_index"], bytes=len(packet), intra_bytes=intra, nleaves=info["nleaves"]))
+            held = plain if info["nleaves"] else None
+    finally:
+        enc.free()
     return rows

@@ -5,6 +5,10 @@ The cloud is encoded and decoded at every combination of the given octree depths
 compared with the original on the GPU: the packet's size, the bits it spends per input point, and the symmetric PSNRs of the
 point-to-point error (D1), the point-to-plane error (D2) and the colour error in BT.709 YUV -- the measures of MPEG's pc_error,
 by this library's RULE Q (include/cwipc_util_amd/hip_ext.h).  No decoded cloud leaves the device.  No reference counterpart.
+
+With --gop the table is another one: a sequence of frames (the synthetic source's, which turns from frame to frame, or the input
+file over and over) goes through one inter-frame encoder (RULE P), and every frame gets a row with its packet's kind and size
+beside the size of the same frame coded on its own.
 """
 import argparse
 from typing import Any, Dict, List, Optional, Sequence
@@ -14,6 +18,7 @@ from .. import quality
 
 __all__ = ["CodecQualityTable", "build_parser", "main"]
 
+GOP_COLUMNS = ("frame", "kind", "bytes", "intra_bytes", "ratio")
 COLUMNS = ("octree_bits", "jpeg_quality", "entropy", "bytes", "bits_per_input_point", "psnr_d1", "psnr_d2", "psnr_y", "psnr_u", "psnr_v")
 
 
@@ -25,7 +30,11 @@ class CodecQualityTable:
         self.octree_bits: Sequence[int] = args.octree_bits or [9]
         self.jpeg_quality: Sequence[int] = args.jpeg_quality or [85]
         self.entropy = bool(args.entropy)
+        self.gop = int(getattr(args, "gop", 0) or 0)
+        self.exp_factor = float(getattr(args, "exp_factor", 1.25))
+        self.nframes = int(getattr(args, "frames", 0) or 0) or 2 * max(self.gop, 1)
         self.input_pc = input_pc
+        self.frames: List[cwipc.cwipc_pointcloud_wrapper] = []
         self.rows: List[Dict[str, Any]] = []
 
     def load_input(self, source: Optional[str], synthetic: int = 0) -> None:
@@ -33,6 +42,8 @@ class CodecQualityTable:
             src = cwipc.cwipc_synthetic(0, synthetic)
             src.start()
             self.input_pc = src.get()
+            if self.gop:
+                self.frames = [self.input_pc] + [src.get() for _ in range(self.nframes - 1)]
             src.stop()
         else:
             assert source
@@ -43,9 +54,19 @@ class CodecQualityTable:
 
     def run(self) -> None:
         assert self.input_pc
-        self.rows = quality.rate_distortion(self.input_pc, self.settings())
+        if self.gop:
+            frames = self.frames or [self.input_pc] * self.nframes
+            self.rows = quality.sequence_rate(frames, entropy=self.entropy, do_inter_frame=True, gop_size=self.gop, exp_factor=self.exp_factor,
+                                              octree_bits=self.octree_bits[0], jpeg_quality=self.jpeg_quality[0])
+        else:
+            self.rows = quality.rate_distortion(self.input_pc, self.settings())
 
     def table(self) -> str:
+        if self.gop:
+            lines = ["%6s %6s %10s %12s %6s" % GOP_COLUMNS]
+            for i, row in enumerate(self.rows):
+                lines.append("%6d %6s %10d %12d %6.3f" % (i, row["kind"], row["bytes"], row["intra_bytes"], row["bytes"] / row["intra_bytes"]))
+            return "\n".join(lines)
         lines = ["%11s %12s %7s %10s %20s %8s %8s %8s %8s %8s" % COLUMNS]
         for row in self.rows:
             flat = dict(row["settings"], **{k: v for k, v in row.items() if k != "settings"})
@@ -61,6 +82,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--octree_bits", type=int, action="append", metavar="BITS", help="Octree depth to encode at. Repeat for each depth (default: 9)")
     parser.add_argument("--jpeg_quality", type=int, action="append", metavar="Q", help="Colour quality to encode at. Repeat for each quality (default: 85)")
     parser.add_argument("--entropy", action="store_true", help="Measure the entropy-coded packets (same distortion, fewer bytes)")
+    parser.add_argument("--gop", type=int, metavar="N", default=0, help="Inter-frame coding with a key packet every N frames (2 or more): print bytes per frame against intra "
+                        "coding, at the first octree depth and quality given")
+    parser.add_argument("--exp_factor", type=float, default=1.25, help="With --gop: how much larger than a key frame's cube the cube of its GOP is (default: 1.25)")
+    parser.add_argument("--frames", type=int, default=0, help="With --gop: the number of frames (default: two GOPs)")
     return parser
 
 

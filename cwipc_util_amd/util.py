@@ -68,6 +68,7 @@ __all__ = [
     'cwipc_hip_decoder_free',
     'cwipc_hip_encoder_set_entropy', 'cwipc_hip_codec_entropy_directory', 'cwipc_hip_codec_entropy_pack', 'cwipc_hip_codec_entropy_unpack',
     'cwipc_hip_codec_entropy_info',
+    'cwipc_hip_codec_inter_directory', 'cwipc_hip_codec_inter_pack', 'cwipc_hip_codec_inter_unpack', 'cwipc_hip_codec_inter_info',
 ]
 
 # reference util.py:86, 346, 348
@@ -322,6 +323,9 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_codec_entropy_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_entropy_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_entropy_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
+    'cwipc_hip_codec_inter_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_inter_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_inter_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
     'cwipc_hip_workspace_bytes': ([], _c.c_size_t),
     'cwipc_hip_comm_unique_id': ([_c.c_void_p, _c.POINTER(_c.c_char_p)], _c.c_int),
     'cwipc_hip_comm_create': ([_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_char_p)], _c.c_void_p),
@@ -2103,6 +2107,16 @@ class cwipc_hip_codec_entropy_directory(ctypes.Structure):
                 ("payload_bytes", ctypes.c_uint64 * 20), ("total_bytes", ctypes.c_uint64)]
 
 
+class cwipc_hip_codec_inter_directory(ctypes.Structure):
+    """An inter-frame packet (hip_ext.h: RULE P) after the container test: the prefix, the header of the packet it stands for, and
+    for a delta packet the added leaves' counts and the directory of its streams."""
+    _fields_ = [("kind", ctypes.c_uint32), ("gop_index", ctypes.c_uint32), ("ref_timestamp", ctypes.c_uint64), ("ref_nleaves", ctypes.c_uint32),
+                ("embedded_entropy", ctypes.c_int32), ("packet", cwipc_hip_codec_info), ("nadded", ctypes.c_uint32), ("nodes_added", ctypes.c_uint32 * 16),
+                ("nstreams", ctypes.c_int32), ("kind_of", ctypes.c_int32 * 21), ("which", ctypes.c_int32 * 21), ("mode", ctypes.c_int32 * 21),
+                ("symbols", ctypes.c_uint32 * 21), ("payload_offset", ctypes.c_uint64 * 21), ("payload_bytes", ctypes.c_uint64 * 21),
+                ("total_bytes", ctypes.c_uint64)]
+
+
 def _codec_handle(name: str, rv: Any, errorString: ctypes.c_char_p) -> int:
     _raise_or_warn(errorString, rv)
     if rv:
@@ -2265,6 +2279,46 @@ def cwipc_hip_codec_entropy_info(packet: Union[bytes, bytearray, memoryview]) ->
 def cwipc_hip_codec_entropy_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
     """The "cwao" packet a "cwae" packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
     return _codec_entropy_convert('cwipc_hip_codec_entropy_unpack', packet, cwipc_hip_codec_entropy_info(packet).packet.total_bytes)
+
+
+def _codec_inter_convert(name: str, args: tuple, capacity: int) -> bytearray:
+    out = bytearray(max(capacity, 1))
+    buffer = (ctypes.c_char * len(out)).from_buffer(out)
+    errorString = ctypes.c_char_p()
+    size = getattr(cwipc_util_dll_load(), name)(*args, ctypes.addressof(buffer), len(out), ctypes.byref(errorString))
+    del buffer
+    if size == 0 or size > len(out):
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else f"{name}: not a valid packet")
+    del out[size:]
+    return out
+
+
+def cwipc_hip_codec_inter_pack(reference: Union[bytes, bytearray, memoryview], packet: Union[bytes, bytearray, memoryview], gop_index: int) -> bytearray:
+    """The delta packet (hip_ext.h: RULE P) of the "cwao" packet `packet` against the "cwao" packet `reference` (host code, no GPU)."""
+    r, p = bytes(reference), bytes(packet)
+    return _codec_inter_convert('cwipc_hip_codec_inter_pack', (r, len(r), p, len(p), gop_index), len(p) + len(r) // 8 + 256)
+
+
+def cwipc_hip_codec_inter_info(packet: Union[bytes, bytearray, memoryview]) -> cwipc_hip_codec_inter_directory:
+    """The container test and the directory of a "cwap" packet (host code, no GPU; the coded blocks are not decoded)."""
+    data = bytes(packet)
+    info = cwipc_hip_codec_inter_directory()
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_codec_inter_info(data, len(data), ctypes.addressof(info), ctypes.byref(errorString))
+    if rv != 0:
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_inter_info: not a valid packet")
+    return info
+
+
+def cwipc_hip_codec_inter_unpack(reference: Optional[Union[bytes, bytearray, memoryview]], packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The "cwao" packet a "cwap" packet stands for after `reference` (host code, no GPU); a key packet's embedded packet verbatim
+    (`reference` may be None); CwipcError with the reason for a packet that is refused."""
+    r, d = (bytes(reference) if reference is not None else None), bytes(packet)
+    info = cwipc_hip_codec_inter_info(d)
+    h = info.packet
+    # a delta's result: RULE C's layout for its header's counts, the occupancy bytes being at most one a leaf and depth
+    capacity = len(d) if info.kind == 0 else 64 + 4 * h.octree_bits + (h.octree_bits + 4) * h.nleaves + 16
+    return _codec_inter_convert('cwipc_hip_codec_inter_unpack', (r, len(r) if r is not None else 0, d, len(d)), capacity)
 
 
 class cwipc_hip_profile:

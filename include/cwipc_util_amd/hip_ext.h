@@ -716,7 +716,8 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  * The packets of this codec are NOT interoperable with cwipc_codec: the interface is the reference's (cwipc_new_encoder,
  * cwipc_new_encodergroup, cwipc_new_decoder as python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is
  * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding,
- * inter-frame coding, per-leaf point counts in the packet, sockets.  (Entropy coding: RULE E below, off unless asked for.)
+ * per-leaf point counts in the packet, sockets.  (Entropy coding: RULE E below, off unless asked for.  Inter-frame coding: RULE P
+ * below, off unless the parameters ask for it; motion compensation is out of scope.)
  *
  * RULE C.  The arithmetic is csrc/codec_terms.hpp (host and device compile it), tests/codec_model.py its numpy restatement.  All
  * arithmetic is float64 unless stated otherwise, every operation rounded on its own.
@@ -744,8 +745,9 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  *     then the tile plane: nleaves bytes, only when tile_mode == 1.
  *  Decoding.  One point per leaf in key order: cell = side / 2^b; p_a = (float)(fl64(min_a) + fl64(fl64(q_a + 0.5) * cell)); the colour
  *           by the colour rule, the tile from the tile byte; the cloud's timestamp is the header's, its cellsize (float) cell.
- *  Parameters.  macroblock_size is accepted and ignored.  do_inter_frame == true, gop_size != 1, exp_factor != 1.0, octree_bits outside
- *           1..16 and jpeg_quality outside 0..100 are refused at construction (errorMessage plus NULL).
+ *  Parameters.  macroblock_size is accepted and ignored.  do_inter_frame == true, gop_size != 1 and exp_factor != 1.0 are refused at
+ *           construction (errorMessage plus NULL) unless all three together turn inter mode on (RULE P); so are octree_bits outside
+ *           1..16 and jpeg_quality outside 0..100.
  *  Validity.  A packet is valid iff magic, version and ranges are right; nodes[0] <= 8 and nodes[L + 1] <= 8 nodes[L]; no occupancy
  *           byte is 0; the popcounts of depth L sum to nodes[L] (for the last depth: nleaves); padding is 0; the length is exact.
  *           Validation is host code, reads the packet once and runs BEFORE anything is launched or allocated on the device.
@@ -802,11 +804,65 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  *           every store is below the stream's symbol count.
  *  Encoding runs on the device after the leaves are made: histograms, frequencies, one wave per block, a plan (sizes, modes, offsets,
  *  directory, total) and a gather.  Only then is the size known: feed returns with that work and the copy of four report words in
- *  flight; whoever polls or takes the result first waits for the report and issues the copy of exactly the packet's bytes. */
+ *  flight; whoever polls or takes the result first waits for the report and issues the copy of exactly the packet's bytes.
+ *
+ * RULE P, inter-frame coding.  The arithmetic is csrc/inter_terms.hpp (host and device compile it), tests/inter_model.py its numpy
+ * restatement.  All integers little endian; fl32 / fl64: rounded to float32 / float64, every operation on its own.
+ *  Parameters.  Inter mode is on iff do_inter_frame == true and 2 <= gop_size <= 65535 and exp_factor is finite in [1, 16].  Each of
+ *           the three alone is refused as under RULE C.  cwipc_hip_encodergroup_addencoder refuses inter parameters (a shared sort
+ *           for inter encoders is out of scope).
+ *  Packets.  An inter-mode encoder delivers only packets with the magic "cwap".  The 32-byte prefix:
+ *      0  u32 magic, the bytes c w a p        4  u32 version = 1            8  u32 kind: 0 key, 1 delta
+ *     12  u32 gop_index (0 for a key; 1 .. gop_size - 1 for a delta)       16  u64 ref_timestamp (0 for a key)
+ *     24  u32 ref_nleaves (0 for a key)      28  u32 0
+ *           Key packet: the prefix, then one complete valid "cwao" packet; after cwipc_hip_encoder_set_entropy(enc, 1) that packet's
+ *           "cwae" form.  Delta packet: the prefix, then bytes 8 .. 48 of P's RULE C header verbatim (timestamp to side, no nodes[]),
+ *           then u32 nadded, then u32 nodesA[b], then u32 S, S entries {u32 mode, u32 payload_bytes}, the payloads.  The length is exact.
+ *  Cube of a key frame.  min_a, max_a, side by RULE C.  side' = fl64(side * (double)exp_factor);  margin = fl64(fl64(side' - side) * 0.5);
+ *           min'_a = fl32(fl64(fl64(min_a) - margin)), a zero being +0.  The frame is quantised by RULE C's Cell and Key rules in
+ *           (min', side'), the clamp included.  With exp_factor == 1 the embedded packet is byte for byte a plain encoder's.
+ *  Contained.  A frame with the float32 extremes lo_a, hi_a is contained in (min', side') iff for every axis lo_a >= min'_a and
+ *           fl64(fl64(fl64(hi_a) - fl64(min'_a)) / side') <= 1.0.
+ *  Sequence.  The encoder holds a counter g (0 at first), the GOP's cube, and a reference R: the frame before as it decodes (keys
+ *           ascending, stored colours, tiles), its timestamp and leaf count.  A frame is a key frame iff g == 0, or no reference is
+ *           held, or P is empty, or the frame is not contained in the GOP's cube; a key frame forced inside a GOP sets g to 0 first;
+ *           a key frame with leaves sets the GOP's cube.  After a frame g = (g + 1) mod gop_size.  An empty P is a key frame (RULE C's
+ *           packet of an empty cloud behind the prefix) and leaves no reference.  cwipc_hip_encoder_at_gop_boundary() is true iff
+ *           g == 0 or no reference is held.
+ *  Delta.   P: the frame's RULE C leaves in the GOP's cube; nR and nleaves are above 0.
+ *           keep: ceil(nR / 8) bytes, bit i mod 8 of byte i div 8 set iff R's leaf i is a leaf of P; unused bits 0.
+ *           A: the leaves of P that are not in R, nadded of them.  nadded > 0: nodesA[] and A's occupancy bytes by RULE C; otherwise
+ *           nodesA is all 0 and there is no occupancy stream.
+ *           Predictor of P's leaf j with key k: ub = the number of R keys <= k, pred = max(0, ub - 1): the same leaf where R has it,
+ *           otherwise R's predecessor in key order.  Colour symbol per channel: (vP[j] - vR[pred]) mod 2^cb.  Tile symbol, only when
+ *           P's tile_mode == 1: tP[j] XOR tR[pred], tR being R's tile_value throughout when R has no tile plane.
+ *           Streams, in this order: keep; A's occupancy of depth 0 .. b - 1 (1, nodesA[0], ... symbols); r, g, b of nleaves symbols
+ *           each; the tile.  S = 1 + (nadded ? b : 0) + 3 + tile_mode.
+ *           Modes, raw and coded payloads, blocks, frequencies and the mode choice are RULE E's, word for word: a stream is coded iff it
+ *           has at least 4096 symbols and is strictly smaller coded.  RULE E's colour prediction is NOT applied on top; a raw colour
+ *           stream is packed at cb bits; f[0] == 0 is demanded of A's occupancy streams only.
+ *  What a delta stands for.  apply(D, R) is exactly one valid "cwao" packet P: its leaves are the merge of the kept R keys and A;
+ *           colour (vR[pred] + symbol) mod 2^cb; tile tR[pred] XOR symbol, or tile_value; occupancy and nodes[] rebuilt from the leaves;
+ *           the header fields from D.  apply(diff(P, R), R) == P byte for byte, and a decoder fed D after R hands out the cloud it
+ *           hands out for P.  Stored values are exact: a chain of deltas does not drift.
+ *  Validity, in two steps as in RULE E.  On the host, BEFORE anything is launched or allocated: the prefix, kind and gop_index
+ *           (1 .. 65534 for a delta, ref_nleaves > 0); the embedded header's ranges; nleaves > 0; nadded <= nleaves and
+ *           nleaves - nadded <= ref_nleaves; nodesA by RULE C's tree rules with nodesA[b - 1] == nadded; S, the modes and the payload
+ *           sizes against those counts and ref_nleaves; the tables and block sizes, the padding, the length; raw occupancy streams by
+ *           RULE C's rules; for a decoder: a reference is held, and its timestamp, leaf count, b, cb, min bits and side equal the
+ *           packet's.  On the device, the flags fetched in one wait: every coded block intact; A's occupancy by RULE C's two
+ *           conditions; keep's padding bits 0; popcount(keep) + nadded == nleaves; no key of A is a key of R.  A refused delta launches
+ *           none of the point-making kernels and leaves the held reference as it was.
+ *  Decoder.  A decoder keeps a reference only after a "cwap" packet (none after one of an empty cloud); "cwao" and "cwae" packets are
+ *           decoded as before and neither keep nor disturb one.
+ *  Encoding a delta waits twice: once as RULE C does (nodes[], the cube, and with them the choice between key and delta, made on the
+ *  device), once for nadded and nodesA[], which size the entropy stage's streams.  Out of scope: sharing inside an encoder group, a
+ *  per-frame choice between the delta and the intra form, a constant-stream mode under the coder's 256 bytes of states per block,
+ *  motion compensation, interoperability with cwipc_codec. */
 typedef struct cwipc_hip_encoder_params {
-    bool do_inter_frame;     /* must be false */
-    int gop_size;            /* must be 1 */
-    float exp_factor;        /* must be 1.0 */
+    bool do_inter_frame;     /* false; true with the two below: inter mode (RULE P) */
+    int gop_size;            /* 1; inter mode: 2..65535 */
+    float exp_factor;        /* 1.0; inter mode: 1.0..16.0 */
     int octree_bits;         /* 1..16 */
     int jpeg_quality;        /* 0..100: the colour shift */
     int macroblock_size;     /* accepted and ignored */
@@ -825,7 +881,7 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_encoder_set_entropy(cwipc_hip_encoder *enc, int
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait);
 _CWIPC_UTIL_EXPORT size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc);               /* of the oldest result; 0: none */
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size);   /* takes the oldest result */
-_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc);                   /* always true */
+_CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_at_gop_boundary(cwipc_hip_encoder *enc);                   /* RULE P; always true without inter mode */
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_eof(cwipc_hip_encoder *enc);                               /* closed and nothing queued */
 _CWIPC_UTIL_EXPORT void cwipc_hip_encoder_close(cwipc_hip_encoder *enc);
 _CWIPC_UTIL_EXPORT cwipc_hip_encodergroup *cwipc_hip_new_encodergroup(char **errorMessage);
@@ -873,6 +929,30 @@ typedef struct cwipc_hip_codec_entropy_directory {
     uint64_t total_bytes;             /* of the "cwae" packet */
 } cwipc_hip_codec_entropy_directory;
 _CWIPC_UTIL_EXPORT int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc_hip_codec_entropy_directory *info, char **errorMessage);
+/* RULE P on the host, without a GPU.  pack: two valid "cwao" packets R and P with leaves, in one cube -> the delta packet diff(P, R);
+ * unpack: R and a "cwap" packet -> the "cwao" packet it stands for after all of RULE P's tests (a key packet: its embedded packet
+ * verbatim, R may be NULL).  The caller-buffer convention is cwipc_hip_codec_entropy_pack's; pack never needs more than
+ * plen + rlen / 8 + 256 bytes, unpack's size comes from a first call with out == NULL. */
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_inter_pack(const void *r, size_t rlen, const void *p, size_t plen, uint32_t gop_index, void *out, size_t capacity,
+                                                     char **errorMessage);
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_inter_unpack(const void *r, size_t rlen, const void *d, size_t dlen, void *out, size_t capacity, char **errorMessage);
+/* A "cwap" packet after the container test (the coded blocks are not decoded): 0 and *info filled, or -1 and the reason. */
+typedef struct cwipc_hip_codec_inter_directory {
+    uint32_t kind, gop_index;         /* the prefix */
+    uint64_t ref_timestamp;
+    uint32_t ref_nleaves;
+    int32_t embedded_entropy;         /* key: the embedded packet is a "cwae" packet */
+    cwipc_hip_codec_info packet;      /* the header; key: of the embedded packet's "cwao" form; delta: nodes[], offsets and total_bytes are 0 */
+    uint32_t nadded, nodes_added[16];
+    int32_t nstreams;                 /* S; 0 for a key packet */
+    int32_t kind_of[21];              /* 0 A's occupancy, 3 bytes (keep: which 0, tile: which 1), 4 a colour residual */
+    int32_t which[21];
+    int32_t mode[21];
+    uint32_t symbols[21];
+    uint64_t payload_offset[21], payload_bytes[21];
+    uint64_t total_bytes;
+} cwipc_hip_codec_inter_directory;
+_CWIPC_UTIL_EXPORT int cwipc_hip_codec_inter_info(const void *bytes, size_t len, cwipc_hip_codec_inter_directory *info, char **errorMessage);
 
 /* ---- intermediate results for parity tests ---- */
 /* Steps 1 to 3 of cwipc_hip_detect_markers: labels (height*width words) receives every dark pixel's component label, -1 for a light
