@@ -14,6 +14,7 @@ import pytest
 
 import codec_model as cm
 import entropy_model as em
+import inter_cases
 import inter_model as im
 from test_inter_model import container_cases, delta, hand_delta, hand_pair, pairs, payload_cases
 
@@ -72,6 +73,26 @@ def test_pack_and_unpack_equal_the_model(host):
     records = b"".join(framed(pairs()[n][0], delta(n)) for n in NAMES)
     for name, (ok, got) in zip(NAMES, results(host("unpack", records), len(NAMES))):
         assert ok and got == pairs()[name][1], name
+
+
+def test_pack_and_unpack_equal_the_model_on_chosen_leaf_sets(host):
+    """Every delta of the streams of tests/inter_cases.py (leaf counts at the wave, the workgroup and the keep byte, 65 793 leaves,
+    1 to 16 bits, key 0 and the last key, every colour depth): the pairs the kernels are held to in test_gpu_inter_edges.py."""
+    pairs_, want = [], []
+    for name, case in inter_cases.cases().items():
+        packets, intra, kinds = case.model()
+        indices = case.gop_indices()
+        for i in range(1, len(packets)):
+            if kinds[i] == "d":
+                pairs_.append((indices[i], intra[i - 1], intra[i]))
+                want.append((f"{name}, frame {i}", packets[i]))
+    assert len(pairs_) > 250
+    got = results(host("pack", b"".join(struct.pack("<I", g) + framed(R, P) for g, R, P in pairs_)), len(pairs_))
+    for (what, D), (ok, packet) in zip(want, got):
+        assert ok and packet == D, what
+    got = results(host("unpack", b"".join(framed(R, D) for (_, R, _), (_, D) in zip(pairs_, want))), len(pairs_))
+    for (what, _), (_, _, P), (ok, packet) in zip(want, pairs_, got):
+        assert ok and packet == P, what
 
 
 def test_hand_worked_delta(host):
