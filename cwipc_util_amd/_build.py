@@ -50,6 +50,7 @@ SOURCES = [
     "kernels_codec.hip",
     "kernels_entropy.hip",
     "kernels_inter.hip",
+    "kernels_transform.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

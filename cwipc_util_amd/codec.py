@@ -14,7 +14,12 @@ every `gop_size` frames (and whenever a frame leaves the GOP's cube, which is th
 packets against the frame before in between.  A decoder fed the packets in order hands out the clouds it would hand out for the
 frames coded one by one.  `inter_pack`, `inter_unpack` and `inter_info` do the same on the host.
 
-Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding, motion compensation, inter-frame coding inside an encoder
+With ``colour_transform=True`` an encoder delivers transform-coded packets (RULE T, magic ``cwat``): the leaves' 8-bit colours go
+through an integer region-adaptive hierarchical transform up the octree, `jpeg_quality` sets the quantiser (100 is exact), and the
+coefficients, occupancy and tiles travel through RULE E's coder.  It is off unless asked for and is refused in inter mode.
+`transform_pack`, `transform_unpack` and `transform_info` do the same on the host.
+
+Out of scope: cwipc_codec's bitstream, JPEG colour coding, transform colour in inter mode, motion compensation, inter-frame coding inside an encoder
 group, per-leaf point counts in the packet, sockets.
 """
 from __future__ import annotations
@@ -29,6 +34,7 @@ __all__ = [
     "cwipc_encoder_params", "cwipc_new_encoder_params", "cwipc_new_encoder", "cwipc_new_encodergroup", "cwipc_new_decoder",
     "cwipc_encoder_wrapper", "cwipc_encodergroup_wrapper", "cwipc_decoder_wrapper", "packet_info",
     "entropy_pack", "entropy_unpack", "entropy_info", "inter_pack", "inter_unpack", "inter_info",
+    "transform_pack", "transform_unpack", "transform_info",
 ]
 
 
@@ -68,6 +74,10 @@ class cwipc_encoder_wrapper:
     def set_entropy(self, on: bool = True) -> None:
         """Deliver the entropy-coded form (RULE E); legal before the first feed, CwipcError afterwards."""
         util.cwipc_hip_encoder_set_entropy(self._handle(), on)
+
+    def set_colour_transform(self, on: bool = True) -> None:
+        """Deliver the transform-coded form (RULE T); legal before the first feed, CwipcError afterwards and in inter mode."""
+        util.cwipc_hip_encoder_set_colour_transform(self._handle(), on)
 
     def eof(self) -> bool:
         return util.cwipc_hip_encoder_eof(self._handle())
@@ -126,10 +136,13 @@ class cwipc_encodergroup_wrapper:
 
     def addencoder(self, version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
         entropy = bool(kwargs.pop("entropy", False))
+        colour_transform = bool(kwargs.pop("colour_transform", False))
         enc = cwipc_encoder_wrapper(util.cwipc_hip_encodergroup_addencoder(self._handle(), _params(params, kwargs)), self)
         self._encoders.append(enc)
         if entropy:
             enc.set_entropy(True)
+        if colour_transform:
+            enc.set_colour_transform(True)
         return enc
 
     def feed(self, pc: cwipc_pointcloud_wrapper) -> None:
@@ -187,11 +200,14 @@ def _params(params: Optional[cwipc_encoder_params], kwargs: Dict[str, Any]) -> c
 
 def cwipc_new_encoder(version: Optional[int] = None, params: Optional[cwipc_encoder_params] = None, **kwargs: Any) -> cwipc_encoder_wrapper:
     """An encoder for `params` (default: cwipc_new_encoder_params()), single parameters overridden by keyword.  entropy=True: it
-    delivers the entropy-coded form of its packets (RULE E)."""
+    delivers the entropy-coded form of its packets (RULE E).  colour_transform=True: it delivers transform-coded packets (RULE T)."""
     entropy = bool(kwargs.pop("entropy", False))
+    colour_transform = bool(kwargs.pop("colour_transform", False))
     enc = cwipc_encoder_wrapper(util.cwipc_hip_new_encoder(_params(params, kwargs)))
     if entropy:
         enc.set_entropy(True)
+    if colour_transform:
+        enc.set_colour_transform(True)
     return enc
 
 
@@ -233,6 +249,31 @@ def entropy_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
                 nodes=list(info.nodes)[:info.octree_bits], unpacked_bytes=info.total_bytes,
                 streams=[(d.mode[i], d.payload_bytes[i]) for i in range(d.nstreams)],
                 kinds=[(names[d.kind[i]], d.which[i], d.symbols[i]) for i in range(d.nstreams)], total_bytes=d.total_bytes)
+
+
+def transform_pack(packet: Union[bytes, bytearray, memoryview], jpeg_quality: int = 100) -> bytearray:
+    """The transform-coded form ("cwat", RULE T) of a valid packet with 8 colour bits at `jpeg_quality` (host code, no GPU)."""
+    return util.cwipc_hip_codec_transform_pack(packet, jpeg_quality)
+
+
+def transform_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The packet a transform-coded packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
+    return util.cwipc_hip_codec_transform_unpack(packet)
+
+
+def transform_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
+    """The header and the directory of a transform-coded packet after the container test (host code, no GPU): packet_info()'s keys for
+    the packet it stands for, `q16`, `dc`, `nescapes`, `streams`: [(mode, payload bytes)], `kinds`: [(kind, which, symbols)],
+    `colour_bytes` (the token and escape payloads with their directory entries) and its own `total_bytes`."""
+    d = util.cwipc_hip_codec_transform_info(packet)
+    info = d.packet
+    names = {0: "occupancy", 2: "tile", 3: "token", 5: "escape"}
+    kinds = [(names[d.kind[i]], d.which[i], d.symbols[i]) for i in range(d.nstreams)]
+    return dict(timestamp=info.timestamp, nleaves=info.nleaves, octree_bits=info.octree_bits, colour_bits=info.colour_bits,
+                tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
+                nodes=list(info.nodes)[:info.octree_bits], unpacked_bytes=info.total_bytes, q16=d.q16, dc=list(d.dc), nescapes=list(d.nescapes),
+                streams=[(d.mode[i], d.payload_bytes[i]) for i in range(d.nstreams)], kinds=kinds,
+                colour_bytes=sum(d.payload_bytes[i] + 8 for i in range(d.nstreams) if kinds[i][0] in ("token", "escape")), total_bytes=d.total_bytes)
 
 
 def inter_pack(reference: Union[bytes, bytearray, memoryview], packet: Union[bytes, bytearray, memoryview], gop_index: int = 1) -> bytearray:

@@ -22,10 +22,17 @@
 // which size the entropy stage's streams; from there on it is the entropy-coded form's path (report, then the copy of exactly the
 // packet's bytes).  Decode: the container test on the host -> upload -> the streams decoded, the added keys expanded, the checks ->
 // ONE wait -> merge, rebuild, points.  Both keep the frame's leaves on the device with the event of the work that made them.
+//
+// Transform colour coding (RULE T: hip_ext.h, transform_terms.hpp; kernels_transform.hip).  Encode: behind codec_emit at shift 0 the
+// leaves' colours become coefficients, their tokens go through the entropy stage with occupancy and tiles, and one more kernel puts
+// the packet together around the escape streams, whose sizes only the device knows; the size arrives as the entropy-coded form's
+// does.  Decode: the container test on the host -> upload -> the streams decoded, tokens and escapes joined and counted -> ONE wait ->
+// the inverse transform into the body's colour plane -> the decode above.
 #include "internal.hpp"
 #include "codec_terms.hpp"
 #include "entropy_terms.hpp"
 #include "inter_terms.hpp"
+#include "transform_terms.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -61,6 +68,7 @@ struct EncJob {
     // inter-frame packets: a key packet's prefix lies in front of `host` (the packet starts at host - prefix); a delta packet has
     // the word S at `head` and the header's tile bytes at `tile_at`
     size_t prefix = 0, head = 0, tile_at = 22;
+    size_t empty_bytes = 4;          // what an empty cloud has behind its header: S = 0; RULE T: the fixed bytes in front of it
     size_t head_bytes() const { return head ? head : CODEC_HEADER_BYTES + 4u * (size_t)layout.bits; }
     size_t packet_bytes() const { return layout.total_bytes ? prefix + (size_t)layout.total_bytes : 0; }
     ~EncJob() {
@@ -121,7 +129,7 @@ struct EncJob {
             layout.tile_mode = uniform ? 0 : 1;
             layout.tile_value = uniform ? (int)(report[2] & 255u) : 0;
         } else {
-            out_bytes = 4;   // an empty cloud: S = 0, written with the header
+            out_bytes = empty_bytes;   // an empty cloud: S = 0, written with the header
         }
         host[tile_at] = (uint8_t)layout.tile_mode;
         host[tile_at + 1] = (uint8_t)layout.tile_value;
@@ -307,8 +315,9 @@ void emit_layout(const Sorted &s, int bits, int shift, uint64_t timestamp, Codec
 // The packet of (bits <= s.bits, colour shift) from a sorted cloud: queued on the calling thread's stream.
 // key_leaves (inter mode): the packet is a key packet, `prefix` bytes are kept free in front of it, and the frame's leaves are taken
 // out of the body into *key_leaves (sized for the packet's leaf count; unused for an empty cloud).
+// transform_q16 != 0 (with entropy, shift 0): the packet is RULE T's, its colours transform coded at that scale.
 std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, int shift, uint64_t timestamp, bool entropy, size_t prefix = 0,
-                                    const k::InterLeavesDev *key_leaves = nullptr) {
+                                    const k::InterLeavesDev *key_leaves = nullptr, uint32_t transform_q16 = 0) {
     ThreadCtx &c = tctx();
     std::unique_ptr<EncJob> job(new EncJob());
     CodecLayout &l = job->layout;
@@ -318,9 +327,20 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     // most bytes it can take from the word S on: a stream never takes more than its raw payload
     k::EntropyStreams st{};
     size_t out_capacity = 4;
+    const bool transform = transform_q16 != 0u;
+    const size_t ncoef = l.nleaves ? (size_t)l.nleaves - 1u : 0u;
+    const uint32_t escape_stride = (uint32_t)(((size_t)l.nleaves + 1u) & ~(size_t)1);   // u16 values a channel: every coefficient, and the padding
     if (entropy) {
-        EntropyStream streams[ENTROPY_MAX_STREAMS];
-        st.nstreams = entropy_streams(l, streams);
+        EntropyStream streams[TRANSFORM_MAX_STREAMS];
+        if (transform) {
+            // RULE T: occupancy, the three token planes and the tile plane go through the stage; the escape streams join them afterwards
+            const uint32_t none[3] = {0, 0, 0};
+            const int all = transform_streams(l, none, streams);
+            for (int i = 0; i < all; i++)
+                if (streams[i].kind != TRANSFORM_ESCAPE) streams[st.nstreams++] = streams[i];
+        } else {
+            st.nstreams = entropy_streams(l, streams);
+        }
         st.colour_bits = l.colour_bits;
         st.nleaves = l.nleaves;
         out_capacity += 8u * (size_t)st.nstreams;
@@ -330,23 +350,39 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
             st.symbols[i] = streams[i].symbols;
             st.first_block[i] = st.total_blocks;
             st.total_blocks += streams[i].nblocks;
-            st.plane_offset[i] = streams[i].kind == ENTROPY_OCCUPANCY ? (uint32_t)entropy_depth_offset(l, (int)streams[i].which) : 0u;
+            st.plane_offset[i] = streams[i].kind == ENTROPY_OCCUPANCY ? (uint32_t)entropy_depth_offset(l, (int)streams[i].which)
+                                 : streams[i].kind == ENTROPY_BYTES   ? (uint32_t)((size_t)streams[i].which * ncoef)
+                                                                      : 0u;
             st.raw_padded[i] = (uint32_t)codec_pad4(streams[i].raw_bytes);
             out_capacity += st.raw_padded[i];
         }
         if (out_capacity > 0x7fffffffull) { note_error(who, "the cloud is too large for the entropy-coded form"); return nullptr; }
         job->entropy = true;
         job->out_capacity = out_capacity;
+        if (transform) {
+            // what the packet can take from the fixed bytes on: three more directory entries and every coefficient an escape
+            const size_t most = TRANSFORM_FIXED_BYTES + out_capacity + (l.nleaves ? 24u + 3u * (size_t)codec_pad4(2u * ncoef) : 0u);
+            if (most > 0x7fffffffull || (uint64_t)l.occupancy_bytes + l.nleaves > 0x7fffffffull) { note_error(who, "the cloud is too large for the transform-coded form"); return nullptr; }
+            job->out_capacity = most;
+            job->empty_bytes = TRANSFORM_FIXED_BYTES + 4u;
+        }
     }
+    const size_t entropy_capacity = out_capacity;   // of the entropy stage's own output
+    if (entropy) out_capacity = job->out_capacity;
     job->host = (uint8_t *)host_alloc(prefix + (entropy ? (size_t)l.occupancy_offset + out_capacity + 16 : (size_t)l.occupancy_offset + body_bytes), &job->pinned);
     if (!job->host) { note_error(who, "out of host memory"); return nullptr; }
     job->host += prefix;
     job->prefix = prefix;
     codec_write_header(job->host, l);
     if (entropy) {
-        const uint32_t magic = ENTROPY_MAGIC, none = 0;
+        const uint32_t magic = transform ? TRANSFORM_MAGIC : ENTROPY_MAGIC, none = 0;
         memcpy(job->host, &magic, 4);
         memcpy(job->host + l.occupancy_offset, &none, 4);
+        if (transform) {   // (an empty cloud's packet ends with these bytes)
+            const uint16_t q = (uint16_t)transform_q16;
+            memset(job->host + l.occupancy_offset, 0, TRANSFORM_FIXED_BYTES + 4u);
+            memcpy(job->host + l.occupancy_offset, &q, 2);
+        }
     }
     if (!l.nleaves) {
         job->finalize();
@@ -357,13 +393,36 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     uint8_t *block = (uint8_t *)pool_alloc(block_bytes);
     if (!block) { note_error(who, "out of device memory"); return nullptr; }
     const k::CodecEmit e = emit_planes(l, block, body_bytes, sums_offset);
-    uint8_t *work = nullptr;
+    uint8_t *work = nullptr, *tblock = nullptr, *stage_out = nullptr;
+    // RULE T's planes: first, weight, the values, the zigzag values, the scans' words, the tokens, the escapes, the report
+    k::TransformTree tree{};
+    size_t tokens_at = 0, escapes_at = 0, treport_at = 0;
+    if (transform) {
+        k::transform_tree_counts(tree, l.bits, l.nodes, l.nleaves, transform_q16);
+        const size_t inner = tree.inner, total = inner + l.nleaves;
+        const size_t first_at = 0, weight_at = first_at + round256(4 * inner), value_at = weight_at + round256(4 * inner), zz_at = value_at + round256(12 * total),
+                     scan_at = zz_at + round256(12 * ncoef + 4);
+        tokens_at = scan_at + round256(4 * k::transform_scan_words(tree));
+        escapes_at = tokens_at + round256(3 * ncoef + 4);
+        treport_at = escapes_at + round256(6 * (size_t)escape_stride);
+        tblock = (uint8_t *)pool_alloc(treport_at + 256);
+        if (tblock) {
+            tree.first = (uint32_t *)(tblock + first_at);
+            tree.weight = (uint32_t *)(tblock + weight_at);
+            tree.value = (int32_t *)(tblock + value_at);
+            tree.zz = (uint32_t *)(tblock + zz_at);
+            tree.scan = (uint32_t *)(tblock + scan_at);
+        }
+    }
     if (entropy) {
         work = (uint8_t *)pool_alloc(k::entropy_encode_work_bytes(st));
         job->out_dev = pool_alloc(round256(out_capacity));
-        if (!work || !job->out_dev) {
+        if (transform) stage_out = (uint8_t *)pool_alloc(round256(entropy_capacity));
+        if (!work || !job->out_dev || (transform && (!tblock || !stage_out))) {
             pool_free(work);
             pool_free(block);
+            pool_free(tblock);
+            pool_free(stage_out);
             note_error(who, "out of device memory");
             return nullptr;
         }
@@ -394,13 +453,45 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
         en.report = (uint32_t *)at; at += 16;
         en.freq = (uint16_t *)at; at += S * 512;
         en.slots = work + round256((size_t)(at - work));
-        en.out = (uint8_t *)job->out_dev;
-        en.out_capacity = out_capacity;
+        en.out = transform ? stage_out : (uint8_t *)job->out_dev;
+        en.out_capacity = entropy_capacity;
         job->report_offset = (size_t)l.occupancy_offset + (size_t)codec_pad4(out_capacity);
-        ok = hipMemsetAsync(en.hist, 0, S * 1024, c.stream) == hipSuccess && hipMemsetAsync(job->out_dev, 0, out_capacity, c.stream) == hipSuccess;
-        if (ok) {
+        ok = hipMemsetAsync(en.hist, 0, S * 1024, c.stream) == hipSuccess && hipMemsetAsync(en.out, 0, entropy_capacity, c.stream) == hipSuccess;
+        const uint32_t *report = en.report;
+        if (ok && transform) {
+            // the coefficients of the leaves' colours, their tokens as the stage's byte planes, and the packet put together behind it
+            tree.occupancy = en.occupancy;
+            uint8_t *tokens = tblock + tokens_at;
+            uint16_t *escapes = (uint16_t *)(tblock + escapes_at);
+            ok = hipMemsetAsync(escapes, 0, 6 * (size_t)escape_stride, c.stream) == hipSuccess;
+            k::transform_prepare(tree, c.stream);
+            k::transform_forward(tree, (const uint8_t *)e.colours, c.stream);
+            k::transform_tokens(tree, tokens, escapes, escape_stride, c.stream);
+            en.planes = tokens;
             k::entropy_encode(en, c.stream);
-            ok = hipMemcpyAsync(job->host + job->report_offset, en.report, 16, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+            k::TransformAssemble a{};
+            a.bits = l.bits;
+            a.entropy_streams = st.nstreams;
+            a.plan = en.plan;
+            a.in_report = en.report;
+            a.in = en.out;
+            a.escapes = escapes;
+            a.escape_stride = escape_stride;
+            for (int ch = 0; ch < 3; ch++) {
+                a.escape_total[ch] = k::transform_escape_total(tree, ch);
+                a.dc[ch] = tree.value + (size_t)ch * ((size_t)tree.inner + l.nleaves);
+            }
+            a.q16 = transform_q16;
+            a.out = (uint8_t *)job->out_dev;
+            a.out_capacity = out_capacity;
+            a.report = (uint32_t *)(tblock + treport_at);
+            k::transform_assemble(a, c.stream);
+            report = a.report;
+        } else if (ok) {
+            k::entropy_encode(en, c.stream);
+        }
+        if (ok) {
+            ok = hipMemcpyAsync(job->host + job->report_offset, report, 16, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
             ok = ok && hipGetLastError() == hipSuccess;
         }
     }
@@ -408,6 +499,8 @@ std::unique_ptr<EncJob> emit_packet(const char *who, const Sorted &s, int bits, 
     ok = ok && job->done && hipEventRecord(job->done, c.stream) == hipSuccess;
     c.free_later(block);
     c.free_later(work);
+    c.free_later(tblock);
+    c.free_later(stage_out);
     if (!ok) {
         (void)c.sync();
         hip_failed(hipGetLastError(), "octree encode", __FILE__, __LINE__);
@@ -626,6 +719,7 @@ struct cwipc_hip_encoder {
     bool closed = false;
     bool in_group = false;
     bool entropy = false;   // deliver the entropy-coded form (RULE E); chosen before the first feed
+    bool transform = false; // deliver RULE T's form ("cwat"): the colours transform coded, the rest as under RULE E
     bool fed = false;
     // inter mode (RULE P): the sequence, the GOP's cube and the reference, under a lock of their own that a feed holds throughout
     bool inter = false;
@@ -824,7 +918,8 @@ int encoder_feed_inter(const char *who, cwipc_hip_encoder *enc, const std::share
 }
 
 int encoder_feed_sorted(const char *who, cwipc_hip_encoder *enc, const Sorted &s, uint64_t timestamp) {
-    auto job = emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp, enc->entropy);
+    auto job = enc->transform ? emit_packet(who, s, enc->params.octree_bits, 0, timestamp, true, 0, nullptr, transform_q16(enc->params.jpeg_quality))
+                              : emit_packet(who, s, enc->params.octree_bits, codec_colour_shift(enc->params.jpeg_quality), timestamp, enc->entropy);
     if (!job) return -1;
     std::lock_guard<std::mutex> l(enc->lock);
     enc->queue.push_back(std::move(job));
@@ -886,6 +981,19 @@ extern "C" int cwipc_hip_encoder_set_entropy(cwipc_hip_encoder *enc, int on) {
     std::lock_guard<std::mutex> l(enc->lock);
     if (enc->fed) { note_error(who, "the encoder has been fed: the packet form is chosen before the first feed"); return -1; }
     enc->entropy = on != 0;
+    return 0;
+}
+
+extern "C" int cwipc_hip_encoder_set_colour_transform(cwipc_hip_encoder *enc, int on) {
+    const char *who = "cwipc_hip_encoder_set_colour_transform";
+    if (enc == nullptr) { note_error(who, "NULL argument"); return -1; }
+    std::lock_guard<std::mutex> l(enc->lock);
+    if (enc->fed) { note_error(who, "the encoder has been fed: the packet form is chosen before the first feed"); return -1; }
+    if (on != 0 && enc->inter) {
+        note_error(who, "inter mode: a delta's colour differences are exact residuals to the reference; transform colour under RULE P is out of scope");
+        return -1;
+    }
+    enc->transform = on != 0;
     return 0;
 }
 
@@ -1078,6 +1186,56 @@ extern "C" int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc
 }
 
 // ---------------------------------------------------------------------------
+// transform colour coding on the host (no GPU)
+// ---------------------------------------------------------------------------
+extern "C" size_t cwipc_hip_codec_transform_pack(const void *bytes, size_t len, int jpeg_quality, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_transform_pack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = transform_pack((const uint8_t *)bytes, len, jpeg_quality, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" size_t cwipc_hip_codec_transform_unpack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_transform_unpack";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = transform_unpack((const uint8_t *)bytes, len, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
+extern "C" int cwipc_hip_codec_transform_info(const void *bytes, size_t len, cwipc_hip_codec_transform_directory *info, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_transform_info";
+    ErrorbufScope scope(errorMessage);
+    TransformLayout t;
+    if (const char *problem = transform_validate((const uint8_t *)bytes, len, t)) { note_error(who, problem); return -1; }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        fill_info(t.cwao, &info->packet);
+        info->q16 = t.q16;
+        for (int ch = 0; ch < 3; ch++) {
+            info->dc[ch] = t.dc[ch];
+            info->nescapes[ch] = t.nescapes[ch];
+        }
+        info->nstreams = t.nstreams;
+        for (int i = 0; i < t.nstreams; i++) {
+            info->kind[i] = (int32_t)t.stream[i].kind;
+            info->which[i] = (int32_t)t.stream[i].which;
+            info->mode[i] = (int32_t)t.stream[i].mode;
+            info->symbols[i] = t.stream[i].symbols;
+            info->payload_offset[i] = t.stream[i].payload_offset;
+            info->payload_bytes[i] = t.stream[i].payload_bytes;
+        }
+        info->total_bytes = t.total_bytes;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // inter-frame packets on the host (no GPU)
 // ---------------------------------------------------------------------------
 extern "C" size_t cwipc_hip_codec_inter_pack(const void *r, size_t rlen, const void *p, size_t plen, uint32_t gop_index, void *out, size_t capacity,
@@ -1224,6 +1382,163 @@ int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *byte
     } else if (keep_reference) {
         replace_reference(dec->reference, nullptr);
     }
+    auto *cloud = new cwipc_hip_pointcloud();
+    cloud->adopt_device(dst, l.timestamp, (float)cell);
+    job.cloud = cloud;
+    job.planes = dst;
+    std::lock_guard<std::mutex> lk(dec->lock);
+    dec->queue.push_back(job);
+    return 0;
+}
+
+// A "cwat" packet (RULE T) into a cloud on the decoder's queue: the container test on the host -> upload -> the streams decoded
+// (occupancy and tiles into the body the octree decoder reads, the tokens into byte planes), the tree's first children, the tokens and
+// escapes joined -> ONE wait for the entropy stage's status and the three counts of tokens equal to 255 (a packet that fails is refused
+// there) -> weights, the inverse transform into the body's colour plane, the octree decoder.
+int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, size_t len) {
+    TransformLayout tl;
+    if (const char *problem = transform_validate(bytes, len, tl)) { note_error(who, problem); return -1; }
+    const CodecLayout &l = tl.cwao;
+    if (tl.total_bytes > 0x7fffffffull || (uint64_t)l.occupancy_bytes + l.nleaves > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
+    if (!device_available(who)) return -1;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const double cell = codec_cellsize(l.side, l.bits);
+    auto dst = soa_alloc(l.nleaves);
+    if (!dst) { note_error(who, "out of device memory"); return -1; }
+    if (l.nleaves) {
+        const size_t n = l.nleaves, ncoef = n - 1, body = (size_t)(l.total_bytes - l.occupancy_offset);
+        k::CodecDecode cd{};
+        cd.bits = l.bits;
+        cd.colour_bits = 8;
+        cd.tile_value = l.tile_value;
+        cd.nleaves = l.nleaves;
+        for (int i = 0; i < l.bits; i++) cd.nodes[i] = l.nodes[i];
+        for (int a = 0; a < 3; a++) cd.mn[a] = l.mn[a];
+        cd.cell = cell;
+        cd.colour_words = codec_pad4(l.colour_bytes) / 4;
+        // the entropy stage's streams: every stream but the escapes, which the transform's kernels read where the upload put them
+        k::EntropyDecode d{};
+        uint32_t escape_offset[3] = {0, 0, 0};
+        d.st.colour_bits = 8;
+        d.st.nleaves = l.nleaves;
+        int stream_of[ENTROPY_MAX_STREAMS];
+        for (int i = 0; i < tl.nstreams; i++) {
+            const EntropyStream &s = tl.stream[i];
+            if (s.kind == TRANSFORM_ESCAPE) { escape_offset[s.which] = (uint32_t)(s.payload_offset - tl.directory_offset); continue; }
+            const int j = d.st.nstreams++;
+            stream_of[j] = i;
+            d.st.kind[j] = s.kind;
+            d.st.which[j] = s.which;
+            d.st.symbols[j] = s.symbols;
+            d.st.first_block[j] = d.st.total_blocks;
+            d.st.total_blocks += s.nblocks;
+            d.st.plane_offset[j] = s.kind == ENTROPY_OCCUPANCY ? (uint32_t)entropy_depth_offset(l, (int)s.which) : s.kind == ENTROPY_BYTES ? (uint32_t)(s.which * ncoef) : 0u;
+            d.st.raw_padded[j] = (uint32_t)codec_pad4(s.raw_bytes);
+            d.mode[j] = s.mode;
+            d.payload_offset[j] = (uint32_t)(s.payload_offset - tl.directory_offset);
+            d.payload_bytes[j] = (uint32_t)s.payload_bytes;
+            d.children[j] = s.kind == ENTROPY_OCCUPANCY ? l.nodes[s.which] : 0u;
+        }
+        k::TransformTree tree{};
+        k::transform_tree_counts(tree, l.bits, l.nodes, l.nleaves, tl.q16);
+        const size_t inner = tree.inner, total = inner + n;
+        const size_t body_bytes = round256(body + 8), ping_bytes = round256(n * 8), scratch_bytes = round256(k::codec_decode_scratch_words(cd) * 4);
+        const size_t in_bytes = (size_t)(tl.total_bytes - tl.directory_offset), table_offset = (in_bytes + 7) & ~(size_t)7, table_bytes = 8u * (size_t)d.st.total_blocks,
+                     upload_bytes = round256(table_offset + table_bytes), flag_bytes = round256(4u * (size_t)(1 + d.st.nstreams));
+        const size_t first_at = 0, weight_at = first_at + round256(4 * inner), value_at = weight_at + round256(4 * inner), zz_at = value_at + round256(12 * total),
+                     scan_at = zz_at + round256(12 * ncoef + 4), tokens_at = scan_at + round256(4 * k::transform_scan_words(tree)),
+                     tree_bytes = tokens_at + round256(3 * ncoef + 4);
+        bool pinned = false;
+        uint8_t *host = (uint8_t *)host_alloc(upload_bytes, &pinned);
+        uint8_t *block = (uint8_t *)pool_alloc(body_bytes + 2 * ping_bytes + scratch_bytes);
+        uint8_t *dev = (uint8_t *)pool_alloc(upload_bytes + flag_bytes);
+        uint8_t *tblock = (uint8_t *)pool_alloc(tree_bytes);
+        auto give_back = [&]() {
+            if (host) host_free(host, pinned);
+            pool_free(block);
+            pool_free(dev);
+            pool_free(tblock);
+        };
+        if (!host || !block || !dev || !tblock) {
+            give_back();
+            note_error(who, "out of memory");
+            return -1;
+        }
+        memcpy(host, bytes + tl.directory_offset, in_bytes);
+        uint32_t *table = (uint32_t *)(host + table_offset);
+        memset(table, 0, table_bytes);
+        for (int j = 0; j < d.st.nstreams; j++) {
+            const EntropyStream &s = tl.stream[stream_of[j]];
+            if (s.mode != 1u) continue;
+            uint32_t at = d.payload_offset[j] + ENTROPY_TABLE_BYTES + 4u * s.nblocks;   // (the container test has held the sizes to the payload)
+            for (uint32_t b = 0; b < s.nblocks; b++) {
+                const uint32_t size = codec_read<uint32_t>(bytes + s.payload_offset + ENTROPY_TABLE_BYTES + 4u * (size_t)b);
+                table[2 * (d.st.first_block[j] + b)] = at;
+                table[2 * (d.st.first_block[j] + b) + 1] = size;
+                at += size;
+            }
+        }
+        uint8_t *colours = block + (l.colour_offset - l.occupancy_offset);
+        d.in = dev;
+        d.block_at = (const uint32_t *)(dev + table_offset);
+        d.planes = tblock + tokens_at;
+        d.flags = (uint32_t *)(dev + upload_bytes);
+        d.occupancy = block;
+        d.tiles = block + (l.tile_offset - l.occupancy_offset);
+        tree.occupancy = block;
+        tree.first = (uint32_t *)(tblock + first_at);
+        tree.weight = (uint32_t *)(tblock + weight_at);
+        tree.value = (int32_t *)(tblock + value_at);
+        tree.zz = (uint32_t *)(tblock + zz_at);
+        tree.scan = (uint32_t *)(tblock + scan_at);
+        PinnedReport report = c.report();
+        const uint32_t tag = report.arm(0, 4);   // word 0: the entropy stage's status; words 1 .. 3: the tokens equal to 255 of Y, Co, Cg
+        bool ok = hipMemcpyAsync(dev, host, table_offset + table_bytes, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+                  hipMemsetAsync(d.flags, 0, flag_bytes, c.stream) == hipSuccess;
+        if (ok) {
+            k::entropy_decode(d, report.device(), tag, c.stream);
+            k::transform_prepare(tree, c.stream);
+            k::transform_untoken(tree, d.planes, dev, escape_offset, tl.nescapes, report.device() + 1, tag, c.stream);
+            ok = hipGetLastError() == hipSuccess;
+        }
+        ok = c.sync() && ok;   // the one wait
+        host_free(host, pinned);
+        host = nullptr;
+        if (!ok || !report.landed(tag, 0, 4)) {
+            give_back();
+            hip_failed(hipGetLastError(), "octree decode (transform stage)", __FILE__, __LINE__);
+            return -1;
+        }
+        const uint32_t status = report.value(0);
+        const char *problem = status & 1u   ? "entropy-coded block is not intact"
+                              : status & 2u ? "occupancy byte is 0"
+                              : status & 4u ? "occupancy bits differ from the node count"
+                                            : nullptr;
+        for (int ch = 0; ch < 3 && !problem; ch++)
+            if (report.value(1 + ch) != tl.nescapes[ch]) problem = "tokens equal to 255 differ from the escape count";
+        if (problem) {
+            give_back();
+            note_error(who, problem);
+            return -1;
+        }
+        cd.colours = (const uint32_t *)colours;
+        cd.tiles = l.tile_mode == 1 ? d.tiles : nullptr;
+        k::transform_inverse(tree, tl.dc, colours, c.stream);
+        k::codec_decode(block, cd, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
+                        (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
+        ok = hipGetLastError() == hipSuccess;
+        c.free_later(block);
+        c.free_later(dev);
+        c.free_later(tblock);
+        if (!ok) {
+            (void)c.sync();
+            hip_failed(hipGetLastError(), "octree decode", __FILE__, __LINE__);
+            return -1;
+        }
+        dst->mark_pending(c.stream);
+    }
+    cwipc_hip_decoder::Job job;
     auto *cloud = new cwipc_hip_pointcloud();
     cloud->adopt_device(dst, l.timestamp, (float)cell);
     job.cloud = cloud;
@@ -1381,6 +1696,7 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
     return guarded(who, -1, [&]() -> int {
         if (dec == nullptr) { note_error(who, "NULL argument"); return -1; }
         if (dec->closed) { note_error(who, "the decoder has been closed"); return -1; }
+        if (bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == TRANSFORM_MAGIC) return decoder_feed_transform(who, dec, (const uint8_t *)bytes, len);
         if (bytes == nullptr || len < 4 || codec_read<uint32_t>((const uint8_t *)bytes) != INTER_MAGIC) return decoder_feed_plain(who, dec, bytes, len, false);
         // an inter-frame packet: the container test, with the reference held, before anything is launched or allocated
         std::lock_guard<std::mutex> guard(dec->inter_lock);

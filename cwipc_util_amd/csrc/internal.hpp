@@ -655,6 +655,54 @@ struct EntropyDecode {
 };
 void entropy_decode(const EntropyDecode &d, unsigned long long *status_host, uint32_t tag, hipStream_t s);
 
+// ---- kernels_transform.hip: transform colour coding (RULE T: hip_ext.h; the arithmetic: transform_terms.hpp) ----
+// One packet's tree with the nodes numbered across depths (transform_terms.hpp): inner node i is occupancy byte i, the leaves are
+// the numbers inner .. inner + nleaves - 1.  Depth L's parents are depth_begin[L] .. + depth_count[L].
+struct TransformTree {
+    int bits;
+    uint32_t nleaves, inner;
+    uint32_t depth_begin[16], depth_count[16];
+    uint32_t q16[3], leaf_step[3];   // per channel: the scale, and the step of a butterfly of two leaves
+    const uint8_t *occupancy;        // inner bytes
+    uint32_t *first, *weight;        // inner words each: an inner node's first child, and the leaves beneath it
+    int32_t *value;                  // 3 planes of inner + nleaves
+    uint32_t *zz;                    // 3 planes of nleaves - 1: the zigzag values in coefficient order
+    uint32_t *scan;                  // transform_scan_words() words
+};
+size_t transform_scan_words(const TransformTree &t);
+// the planes' fields from the header's counts and the quality's scale
+void transform_tree_counts(TransformTree &t, int bits, const uint32_t *nodes, uint32_t nleaves, uint32_t q16);
+// first[] from the occupancy bytes
+void transform_prepare(const TransformTree &t, hipStream_t s);
+// colours: RULE C's colour plane at 8 bits.  -> zz[], and the root's values (dc) in value[ch * (inner + nleaves)]
+void transform_forward(const TransformTree &t, const uint8_t *colours, hipStream_t s);
+// zz[] -> tokens (3 planes of nleaves - 1 bytes) and escapes (3 planes of escape_stride u16, zeroed by the caller); the number of
+// escapes of channel ch is left in transform_escape_total(t, ch)
+void transform_tokens(const TransformTree &t, uint8_t *tokens, uint16_t *escapes, uint32_t escape_stride, hipStream_t s);
+const uint32_t *transform_escape_total(const TransformTree &t, int ch);
+// The packet from the fixed bytes (Q16) on: what the entropy stage left in `in` (its plan, its report) for the streams occupancy,
+// three token planes and the tile plane, with the escape streams put in their places.  report (device, 4 words): as EntropyEncode's.
+struct TransformAssemble {
+    int bits, entropy_streams;
+    const uint32_t *plan, *in_report;
+    const uint8_t *in;
+    const uint16_t *escapes;
+    uint32_t escape_stride;
+    const uint32_t *escape_total[3];
+    const int32_t *dc[3];
+    uint32_t q16;
+    uint8_t *out;
+    uint64_t out_capacity;
+    uint32_t *report;
+};
+void transform_assemble(const TransformAssemble &a, hipStream_t s);
+// tokens and the raw escape streams (in + escape_offset[ch], nescapes[ch] u16 values) -> zz[]; the number of tokens equal to 255 of
+// channel ch goes to totals_host[ch] (pinned) below `tag`
+void transform_untoken(const TransformTree &t, const uint8_t *tokens, const uint8_t *in, const uint32_t escape_offset[3], const uint32_t nescapes[3],
+                       unsigned long long *totals_host, uint32_t tag, hipStream_t s);
+// weight[], then zz[] and dc -> the leaves' colours into RULE C's colour plane at 8 bits (3 nleaves bytes)
+void transform_inverse(const TransformTree &t, const int32_t dc[3], uint8_t *colours, hipStream_t s);
+
 // ---- kernels_inter.hip: inter-frame coding (RULE P: hip_ext.h; the arithmetic: inter_terms.hpp) ----
 // A frame's leaves as a decoder has them: keys ascending, the stored colours as three byte planes of n, the tiles.
 struct InterLeavesDev {

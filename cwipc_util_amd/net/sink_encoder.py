@@ -70,6 +70,7 @@ class _SinkEncoder:
         self.octree_bits: List[int] = [DEFAULT_OCTREE_BITS]
         self.jpeg_quality: List[int] = [DEFAULT_JPEG_QUALITY]
         self.entropy = False
+        self.colour_transform = False
         self.gop_size: Optional[int] = None
         self.exp_factor = 1.0
         self.encoder_group: Optional[codec.cwipc_encodergroup_wrapper] = None
@@ -84,12 +85,14 @@ class _SinkEncoder:
 
     def set_encoder_params(self, tiles: Optional[List[cwipc_tileinfo_dict]], octree_bits: Union[int, Sequence[int], None] = None,
                            jpeg_quality: Union[int, Sequence[int], None] = None, entropy: bool = False, gop_size: Optional[int] = None,
-                           exp_factor: Optional[float] = None) -> None:
+                           exp_factor: Optional[float] = None, colour_transform: bool = False) -> None:
         """entropy=True: every encoder delivers the entropy-coded form of its packets (cwipc_util_amd.codec, RULE E); a
         cwipc_source_decoder takes both forms.  gop_size (2 or more), with exp_factor (default 1.25): inter-frame coding, a key
-        packet every gop_size frames and delta packets in between (RULE P)."""
+        packet every gop_size frames and delta packets in between (RULE P).  colour_transform=True: every encoder delivers transform-coded
+        packets (RULE T), jpeg_quality being the quantiser; not together with gop_size."""
         assert self.encoder_group is None and not self.encoders, "set_encoder_params comes before the first cloud"
         self.entropy = bool(entropy)
+        self.colour_transform = bool(colour_transform)
         self.gop_size = int(gop_size) if gop_size is not None else None
         self.exp_factor = float(exp_factor) if exp_factor is not None else (1.25 if self.gop_size is not None else 1.0)
         self.tiledescriptions = tiles if tiles else [{}]
@@ -119,9 +122,9 @@ class _SinkEncoder:
                 for quality in self.jpeg_quality:
                     params = codec.cwipc_encoder_params(inter, self.gop_size if inter else 1, self.exp_factor, bits, quality, 16, mask, 0)
                     if inter:
-                        self.encoders.append(codec.cwipc_new_encoder(params=params, entropy=self.entropy))
+                        self.encoders.append(codec.cwipc_new_encoder(params=params, entropy=self.entropy, colour_transform=self.colour_transform))
                     else:
-                        self.encoders.append(self.encoder_group.addencoder(params=params, entropy=self.entropy))
+                        self.encoders.append(self.encoder_group.addencoder(params=params, entropy=self.entropy, colour_transform=self.colour_transform))
                     self.streams.append(self.add_stream(tile_index, tile, dict(octree_bits=bits, jpeg_quality=quality)))
                     if self.verbose:
                         print(f"encoder: stream {self.streams[-1]}: tile={tile_index} mask={mask} octree_bits={bits} jpeg_quality={quality}")

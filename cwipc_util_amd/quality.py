@@ -126,10 +126,10 @@ def cloud_distortion(original: cwipc_pointcloud_wrapper, degraded: cwipc_pointcl
     return DistortionResults(forward, backward, default_peak(original) if peak is None else peak)
 
 
-def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwargs: Dict[str, Any]) -> Tuple[cwipc_pointcloud_wrapper, int]:
+def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwargs: Dict[str, Any], colour_transform: bool = False) -> Tuple[cwipc_pointcloud_wrapper, int]:
     """(the decoded cloud, device-resident; the packet's size in bytes)"""
     from . import codec
-    enc = codec.cwipc_new_encoder(entropy=entropy, **encoder_kwargs)
+    enc = codec.cwipc_new_encoder(entropy=entropy, colour_transform=colour_transform, **encoder_kwargs)
     dec = codec.cwipc_new_decoder()
     try:
         enc.feed(pc)
@@ -148,17 +148,18 @@ def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwar
         dec.free()
 
 
-def codec_distortion(pc: cwipc_pointcloud_wrapper, *, entropy: bool = False, **kwargs: Any) -> Tuple[DistortionResults, int]:
+def codec_distortion(pc: cwipc_pointcloud_wrapper, *, entropy: bool = False, colour_transform: bool = False, **kwargs: Any) -> Tuple[DistortionResults, int]:
     """cwipc_new_encoder(**encoder keywords) -> cwipc_new_decoder -> cloud_distortion: (the distortion of the decoded cloud against
     `pc`, the packet's bytes).  The keywords max_distance, normals, radius, max_nn, plane and peak go to cloud_distortion, every
-    other one to the encoder.  The decoded cloud never becomes a host array."""
+    other one to the encoder.  colour_transform=True: the packet is the transform-coded form (RULE T), jpeg_quality its quantiser.  The
+    decoded cloud never becomes a host array."""
     measure = {k: kwargs.pop(k) for k in ("max_distance", "normals", "radius", "max_nn", "plane", "peak") if k in kwargs}
-    decoded, nbytes = _through_the_codec(pc, entropy, kwargs)
+    decoded, nbytes = _through_the_codec(pc, entropy, kwargs, colour_transform)
     return cloud_distortion(pc, decoded, **measure), nbytes
 
 
 def rate_distortion(pc: cwipc_pointcloud_wrapper, settings: Iterable[Dict[str, Any]]) -> List[Dict[str, Any]]:
-    """One row per entry of `settings` (dicts of codec_distortion's keywords, `entropy` among them): `settings`, `bytes`,
+    """One row per entry of `settings` (dicts of codec_distortion's keywords, `entropy` and `colour_transform` among them): `settings`, `bytes`,
     `bits_per_input_point` and the symmetric `psnr_d1`, `psnr_d2`, `psnr_y`, `psnr_u`, `psnr_v`.  The original's normals are estimated
     once (cwipc_hip_estimate_normals, with the first `radius` and `max_nn` found in the settings, else 0.02 and 30) and passed to
     every comparison."""

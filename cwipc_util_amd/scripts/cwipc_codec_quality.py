@@ -30,6 +30,7 @@ class CodecQualityTable:
         self.octree_bits: Sequence[int] = args.octree_bits or [9]
         self.jpeg_quality: Sequence[int] = args.jpeg_quality or [85]
         self.entropy = bool(args.entropy)
+        self.colour_transform = bool(getattr(args, "colour_transform", False))
         self.gop = int(getattr(args, "gop", 0) or 0)
         self.exp_factor = float(getattr(args, "exp_factor", 1.25))
         self.nframes = int(getattr(args, "frames", 0) or 0) or 2 * max(self.gop, 1)
@@ -50,7 +51,8 @@ class CodecQualityTable:
             self.input_pc = cwipc.cwipc_read(source, 0)
 
     def settings(self) -> List[Dict[str, Any]]:
-        return [dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy) for b in self.octree_bits for q in self.jpeg_quality]
+        extra = dict(colour_transform=True) if self.colour_transform else {}
+        return [dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy, **extra) for b in self.octree_bits for q in self.jpeg_quality]
 
     def run(self) -> None:
         assert self.input_pc
@@ -82,6 +84,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--octree_bits", type=int, action="append", metavar="BITS", help="Octree depth to encode at. Repeat for each depth (default: 9)")
     parser.add_argument("--jpeg_quality", type=int, action="append", metavar="Q", help="Colour quality to encode at. Repeat for each quality (default: 85)")
     parser.add_argument("--entropy", action="store_true", help="Measure the entropy-coded packets (same distortion, fewer bytes)")
+    parser.add_argument("--colour-transform", dest="colour_transform", action="store_true",
+                        help="Measure transform-coded packets: --jpeg_quality sets the quantiser of the colour transform (100 is exact). Not with --gop")
     parser.add_argument("--gop", type=int, metavar="N", default=0, help="Inter-frame coding with a key packet every N frames (2 or more): print bytes per frame against intra "
                         "coding, at the first octree depth and quality given")
     parser.add_argument("--exp_factor", type=float, default=1.25, help="With --gop: how much larger than a key frame's cube the cube of its GOP is (default: 1.25)")
@@ -94,6 +98,8 @@ def main() -> None:
     args = parser.parse_args()
     if bool(args.input) == bool(args.synthetic):
         parser.error("give either an input file or --synthetic NPOINTS")
+    if args.colour_transform and args.gop:
+        parser.error("--colour-transform is not available with --gop")
     creator = CodecQualityTable(args)
     creator.load_input(args.input, args.synthetic)
     creator.run()

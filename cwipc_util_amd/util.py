@@ -69,6 +69,8 @@ __all__ = [
     'cwipc_hip_encoder_set_entropy', 'cwipc_hip_codec_entropy_directory', 'cwipc_hip_codec_entropy_pack', 'cwipc_hip_codec_entropy_unpack',
     'cwipc_hip_codec_entropy_info',
     'cwipc_hip_codec_inter_directory', 'cwipc_hip_codec_inter_pack', 'cwipc_hip_codec_inter_unpack', 'cwipc_hip_codec_inter_info',
+    'cwipc_hip_encoder_set_colour_transform', 'cwipc_hip_codec_transform_directory', 'cwipc_hip_codec_transform_pack', 'cwipc_hip_codec_transform_unpack',
+    'cwipc_hip_codec_transform_info',
 ]
 
 # reference util.py:86, 346, 348
@@ -323,6 +325,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_codec_entropy_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_entropy_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_entropy_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
+    'cwipc_hip_encoder_set_colour_transform': ([_c.c_void_p, _c.c_int], _c.c_int),
+    'cwipc_hip_codec_transform_pack': ([_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_transform_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
+    'cwipc_hip_codec_transform_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
     'cwipc_hip_codec_inter_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_inter_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_inter_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
@@ -2107,6 +2113,15 @@ class cwipc_hip_codec_entropy_directory(ctypes.Structure):
                 ("payload_bytes", ctypes.c_uint64 * 20), ("total_bytes", ctypes.c_uint64)]
 
 
+class cwipc_hip_codec_transform_directory(ctypes.Structure):
+    """The directory of a transform-coded packet (hip_ext.h: RULE T): the header of the packet it stands for, the quantiser scale, the
+    root's values, the escape counts, and per stream its kind (0 occupancy, 2 tile, 3 tokens, 5 escapes), mode, symbol count and payload."""
+    _fields_ = [("packet", cwipc_hip_codec_info), ("q16", ctypes.c_uint32), ("dc", ctypes.c_int32 * 3), ("nescapes", ctypes.c_uint32 * 3),
+                ("nstreams", ctypes.c_int32), ("kind", ctypes.c_int32 * 23), ("which", ctypes.c_int32 * 23), ("mode", ctypes.c_int32 * 23),
+                ("symbols", ctypes.c_uint32 * 23), ("payload_offset", ctypes.c_uint64 * 23), ("payload_bytes", ctypes.c_uint64 * 23),
+                ("total_bytes", ctypes.c_uint64)]
+
+
 class cwipc_hip_codec_inter_directory(ctypes.Structure):
     """An inter-frame packet (hip_ext.h: RULE P) after the container test: the prefix, the header of the packet it stands for, and
     for a delta packet the added leaves' counts and the directory of its streams."""
@@ -2279,6 +2294,43 @@ def cwipc_hip_codec_entropy_info(packet: Union[bytes, bytearray, memoryview]) ->
 def cwipc_hip_codec_entropy_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
     """The "cwao" packet a "cwae" packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
     return _codec_entropy_convert('cwipc_hip_codec_entropy_unpack', packet, cwipc_hip_codec_entropy_info(packet).packet.total_bytes)
+
+
+def cwipc_hip_encoder_set_colour_transform(enc: int, on: bool) -> None:
+    """The encoder delivers the transform-coded form (hip_ext.h: RULE T) from its first packet on; CwipcError once it has been fed, and
+    for an inter-mode encoder."""
+    if cwipc_util_dll_load().cwipc_hip_encoder_set_colour_transform(enc, 1 if on else 0) != 0:
+        raise _codec_last_error('cwipc_hip_encoder_set_colour_transform')
+
+
+def cwipc_hip_codec_transform_pack(packet: Union[bytes, bytearray, memoryview], jpeg_quality: int) -> bytearray:
+    """A valid "cwao" packet with 8 colour bits in its transform-coded form "cwat" at `jpeg_quality` (host code, no GPU)."""
+    data = bytes(packet)
+    out = bytearray(3 * len(data) + 300)
+    buffer = (ctypes.c_char * len(out)).from_buffer(out)
+    errorString = ctypes.c_char_p()
+    size = cwipc_util_dll_load().cwipc_hip_codec_transform_pack(data, len(data), int(jpeg_quality), ctypes.addressof(buffer), len(out), ctypes.byref(errorString))
+    del buffer
+    if size == 0 or size > len(out):
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_transform_pack: not a valid packet")
+    del out[size:]
+    return out
+
+
+def cwipc_hip_codec_transform_info(packet: Union[bytes, bytearray, memoryview]) -> cwipc_hip_codec_transform_directory:
+    """The container test and the directory of a "cwat" packet (host code, no GPU; the coded blocks are not decoded)."""
+    data = bytes(packet)
+    info = cwipc_hip_codec_transform_directory()
+    errorString = ctypes.c_char_p()
+    rv = cwipc_util_dll_load().cwipc_hip_codec_transform_info(data, len(data), ctypes.addressof(info), ctypes.byref(errorString))
+    if rv != 0:
+        raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_transform_info: not a valid packet")
+    return info
+
+
+def cwipc_hip_codec_transform_unpack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:
+    """The "cwao" packet a "cwat" packet stands for (host code, no GPU); CwipcError with the reason for one that is refused."""
+    return _codec_entropy_convert('cwipc_hip_codec_transform_unpack', packet, cwipc_hip_codec_transform_info(packet).packet.total_bytes)
 
 
 def _codec_inter_convert(name: str, args: tuple, capacity: int) -> bytearray:

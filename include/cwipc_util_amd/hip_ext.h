@@ -715,9 +715,10 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
 /* ---- the octree codec: encoder, encoder group, decoder (csrc/codec.cpp, csrc/kernels_codec.hip) ----
  * The packets of this codec are NOT interoperable with cwipc_codec: the interface is the reference's (cwipc_new_encoder,
  * cwipc_new_encodergroup, cwipc_new_decoder as python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is
- * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, transform or JPEG colour coding,
+ * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, JPEG colour coding,
  * per-leaf point counts in the packet, sockets.  (Entropy coding: RULE E below, off unless asked for.  Inter-frame coding: RULE P
- * below, off unless the parameters ask for it; motion compensation is out of scope.)
+ * below, off unless the parameters ask for it; motion compensation is out of scope.  Transform colour coding: RULE T below, off
+ * unless asked for.)
  *
  * RULE C.  The arithmetic is csrc/codec_terms.hpp (host and device compile it), tests/codec_model.py its numpy restatement.  All
  * arithmetic is float64 unless stated otherwise, every operation rounded on its own.
@@ -858,13 +859,72 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  *  Encoding a delta waits twice: once as RULE C does (nodes[], the cube, and with them the choice between key and delta, made on the
  *  device), once for nadded and nodesA[], which size the entropy stage's streams.  Out of scope: sharing inside an encoder group, a
  *  per-frame choice between the delta and the intra form, a constant-stream mode under the coder's 256 bytes of states per block,
- *  motion compensation, interoperability with cwipc_codec. */
+ *  motion compensation, interoperability with cwipc_codec.
+ *
+ * RULE T, transform colour coding (an integer region-adaptive hierarchical transform, RAHT).  A packet with the magic "cwat" stands
+ * for exactly one valid RULE C packet with 8 colour bits: unpack(T) has T's header, occupancy and tiles and the colours the inverse
+ * transform gives, and a decoder fed T hands out the cloud it hands out for unpack(T).  pack(P, quality) is a function of a valid
+ * 8-bit "cwao" packet P and the quality; unpack(pack(P, 100)) == P byte for byte.  An encoder delivers it only after
+ * cwipc_hip_encoder_set_colour_transform(enc, 1).  The arithmetic is csrc/transform_terms.hpp (host and device compile it),
+ * tests/transform_model.py its numpy restatement.  Integers only, little endian; >> is an arithmetic shift; / on non-negative values
+ * truncates; floor() rounds towards minus infinity.
+ *  Input.   The leaves of RULE C as the same encoder makes them with s = 0: keys ascending, the 8-bit rounded means m, tiles.  The
+ *           header's colour bits are 8.  jpeg_quality selects the quantiser, not a shift.
+ *  Scale.   q = max(1, jpeg_quality);  sc = q < 50 ? 5000 / q : 200 - 2 q;  Q16 = min(1024, 16 + (12 sc) / 10).  Q16 travels in the
+ *           packet (100 gives 16, 85: 52, 50: 136, 25: 256, 1 and 0: 1024); a decoder never sees jpeg_quality.
+ *  Colour.  Per leaf, reversible YCoCg-R:  Co = R - B;  t = B + (Co >> 1);  Cg = G - t;  Y = t + (Cg >> 1).  Back:  t = Y - (Cg >> 1);
+ *           G = Cg + t;  B = t - (Co >> 1);  R = B + Co;  then every channel is clamped to 0..255.  The channel scale Q16c is Q16 for
+ *           Y and min(1024, 2 Q16) for Co and Cg; at Q16 == 16 it is 16 for all three.
+ *  Tree.    A node's weight is the number of leaves beneath it, a leaf's is 1.  A parent merges its present children in three stages
+ *           over the child index c = 4x + 2y + z: stage z pairs (c, c ^ 1); stage y pairs the results of (0,1) with (2,3) and of (4,5)
+ *           with (6,7); stage x pairs the two halves.  A pair with one side empty passes the other side through, value and weight.
+ *           A pair with both sides present is a butterfly of (a, w1), the side of the lower index, and (b, w2);  W = w1 + w2:
+ *           d = b - a;  l = a + floor((w2 d + (W >> 1)) / W) in 64 bits;  the merged node has the value l and the weight W.
+ *           A parent of k children yields k - 1 coefficients d; a channel has nleaves - 1 of them and the root's l as dc.
+ *  Step.    Of a butterfly, in unsigned 64 bits:  t = (Q16c Q16c (w1 + w2)) / (w1 w2);  step = max(1, (isqrt(t) + 8) >> 4), isqrt the
+ *           exact floor of the square root.  (RAHT's sqrt(w1 w2 / (w1 + w2)) folded into the step.)  Q16c == 16 gives step 1 throughout.
+ *  Quantiser.  c = sign(d) ((|d| + step / 2) / step);  reconstructed d^ = c step.  The encoder is open loop: it quantises the exact d.
+ *  Inverse.  From dc down.  A butterfly with its l^:  a^ = l^ - floor((w2 d^ + (W >> 1)) / W);  b^ = a^ + d^.  Nothing is clamped
+ *           inside the tree.  With step 1 everywhere the inverse is exact.
+ *  Order.   Of the coefficients of a channel: by the depth of the parent, the root first; the parents of a depth in ascending prefix
+ *           order; within a parent the x butterfly, then the y butterflies (low half first), then the z butterflies in ascending c,
+ *           those that exist.  (With the nodes numbered across depths, root 0, a parent i whose first child is s has its first
+ *           coefficient at s - i - 1.)
+ *  Symbols.  zz = c >= 0 ? 2 c : -2 c - 1;  token = min(zz, 255);  a coefficient with zz >= 255 also appends zz - 255 as a u16 to its
+ *           channel's escape stream, in coefficient order (the encoder's |d| is at most 510, so zz - 255 fits).
+ *  Streams, in this order: the occupancy bytes of depth 0 .. b - 1 as in RULE E; for Y, Co, Cg in turn the token stream (nleaves - 1
+ *           symbols) and then the escape stream; the tile plane when tile_mode == 1.  S = b + 6 + tile_mode, 0 for nleaves == 0.
+ *           Token, occupancy and tile streams take RULE E's modes, blocks, frequencies and mode choice word for word (coded iff at
+ *           least 4096 symbols and strictly smaller coded); nothing is predicted.  An escape stream is always raw: its u16 values,
+ *           padded with zeros to a multiple of 4.  A stream without symbols has mode 0 and an empty payload.
+ *  Packet, its total length exact:
+ *      0  u32 magic, the bytes c w a t        4  u32 version = 1
+ *      8  bytes 8 .. 48 + 4 b of the RULE C packet verbatim (colour bits 8)
+ *     then u16 Q16, i16 dc[3] (Y, Co, Cg), u32 nescapes[3], then u32 S, S entries {u32 mode, u32 payload_bytes}, the payloads.
+ *     nleaves == 0: dc and nescapes are 0, S = 0 and nothing behind it.
+ *  Validity, in two steps as in RULE E.  On the host, BEFORE anything is launched or allocated: magic, version, the embedded header by
+ *           RULE C's range and tree rules with colour bits == 8; 16 <= Q16 <= 1024; nescapes[i] <= nleaves - 1 (0 and dc 0 for an
+ *           empty cloud); S, every mode (an escape stream's is 0) and payload size against the header's counts and nescapes; tables,
+ *           block sizes, padding, the length; raw occupancy streams by RULE C's rules.  On the device, fetched in the one wait inside
+ *           cwipc_hip_decoder_feed: every coded block intact; coded occupancy by RULE C's two conditions; per channel the number of
+ *           tokens equal to 255 is nescapes[i].  A refused packet launches none of the point-making kernels.
+ *  Bounds.  For ANY payload bytes zz <= 255 + 65535, so |d^| <= 32895 * 91, and at most 3 b additions of it and 1 reach a leaf from
+ *           dc: every value stays far inside 32 bits, every product inside 64.  Every load is inside the packet or the tree's node
+ *           count, every store below the header's counts.
+ *  Parameters.  cwipc_hip_encoder_set_colour_transform is legal before the first feed and implies RULE E's container for geometry and
+ *           tiles.  An inter-mode encoder refuses it: a delta's colour differences are exact residuals to the reference, and a lossy
+ *           transform under RULE P needs a design of its own.  An encoder of a group may have it on.
+ *  Header's choices (the rule's text left them open): version 1 shares RULE C's version test; a packet of one leaf has three token
+ *           streams without symbols; the escape streams' directory entries count their padded bytes; Q16 of an empty cloud's packet is
+ *           the quality's.  Out of scope: transform colour under RULE P, per-depth frequency tables or contexts, a constant-stream
+ *           mode under the coder's 256 bytes of states per block, prediction between levels, closed-loop quantisation, per-leaf point
+ *           counts as weights, interoperability with cwipc_codec or G-PCC. */
 typedef struct cwipc_hip_encoder_params {
     bool do_inter_frame;     /* false; true with the two below: inter mode (RULE P) */
     int gop_size;            /* 1; inter mode: 2..65535 */
     float exp_factor;        /* 1.0; inter mode: 1.0..16.0 */
     int octree_bits;         /* 1..16 */
-    int jpeg_quality;        /* 0..100: the colour shift */
+    int jpeg_quality;        /* 0..100: the colour shift; with RULE T on: the quantiser scale */
     int macroblock_size;     /* accepted and ignored */
     int tilenumber;          /* 0: every point */
     float voxelsize;         /* > 0: cwipc_downsample first */
@@ -878,6 +938,10 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_encoder_feed(cwipc_hip_encoder *enc, cwipc_poin
 /* on != 0: the encoder delivers RULE E's entropy-coded form ("cwae") of the packets it would deliver otherwise.  Legal before the first
  * feed, also on an encoder of a group (the group's sort is shared all the same); afterwards -1 and the reason in cwipc_hip_last_error(). */
 _CWIPC_UTIL_EXPORT int cwipc_hip_encoder_set_entropy(cwipc_hip_encoder *enc, int on);
+/* on != 0: the encoder delivers RULE T's transform-coded form ("cwat"): colours at 8 bits through the integer transform, quantised by
+ * jpeg_quality; geometry and tiles as under RULE E.  Legal before the first feed, also on an encoder of a group; -1 and the reason in
+ * cwipc_hip_last_error() afterwards, and for an inter-mode encoder. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_encoder_set_colour_transform(cwipc_hip_encoder *enc, int on);
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_available(cwipc_hip_encoder *enc, bool wait);
 _CWIPC_UTIL_EXPORT size_t cwipc_hip_encoder_get_encoded_size(cwipc_hip_encoder *enc);               /* of the oldest result; 0: none */
 _CWIPC_UTIL_EXPORT bool cwipc_hip_encoder_copy_data(cwipc_hip_encoder *enc, void *buffer, size_t size);   /* takes the oldest result */
@@ -929,6 +993,27 @@ typedef struct cwipc_hip_codec_entropy_directory {
     uint64_t total_bytes;             /* of the "cwae" packet */
 } cwipc_hip_codec_entropy_directory;
 _CWIPC_UTIL_EXPORT int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc_hip_codec_entropy_directory *info, char **errorMessage);
+/* RULE T on the host, without a GPU.  pack: a valid "cwao" packet with 8 colour bits and a jpeg_quality in 0..100 -> its "cwat" form
+ * (never more than 3 * len + 300 bytes); unpack: a "cwat" packet -> the "cwao" packet it stands for, after the container test, the blocks'
+ * integrity, the occupancy rules and the escape counts (cwipc_hip_codec_transform_info()'s packet.total_bytes).  The caller-buffer
+ * convention is cwipc_hip_codec_entropy_pack's. */
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_transform_pack(const void *bytes, size_t len, int jpeg_quality, void *out, size_t capacity, char **errorMessage);
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_transform_unpack(const void *bytes, size_t len, void *out, size_t capacity, char **errorMessage);
+/* A "cwat" packet after the container test (the coded blocks are not decoded, the tokens not counted): 0 and *info filled, or -1 and the reason. */
+typedef struct cwipc_hip_codec_transform_directory {
+    cwipc_hip_codec_info packet;      /* the header; offsets and total_bytes are those of the "cwao" packet it stands for */
+    uint32_t q16;
+    int32_t dc[3];                    /* Y, Co, Cg */
+    uint32_t nescapes[3];
+    int32_t nstreams;                 /* S */
+    int32_t kind[23];                 /* 0 occupancy, 2 tile, 3 tokens, 5 escapes */
+    int32_t which[23];                /* occupancy: the depth; tokens and escapes: the channel */
+    int32_t mode[23];                 /* 0 raw, 1 coded */
+    uint32_t symbols[23];
+    uint64_t payload_offset[23], payload_bytes[23];
+    uint64_t total_bytes;             /* of the "cwat" packet */
+} cwipc_hip_codec_transform_directory;
+_CWIPC_UTIL_EXPORT int cwipc_hip_codec_transform_info(const void *bytes, size_t len, cwipc_hip_codec_transform_directory *info, char **errorMessage);
 /* RULE P on the host, without a GPU.  pack: two valid "cwao" packets R and P with leaves, in one cube -> the delta packet diff(P, R);
  * unpack: R and a "cwap" packet -> the "cwao" packet it stands for after all of RULE P's tests (a key packet: its embedded packet
  * verbatim, R may be NULL).  The caller-buffer convention is cwipc_hip_codec_entropy_pack's; pack never needs more than
