@@ -51,6 +51,7 @@ SOURCES = [
     "kernels_entropy.hip",
     "kernels_inter.hip",
     "kernels_transform.hip",
+    "kernels_lod.hip",
 ]
 
 # -ffp-contract=off: the parity contract is stated in separately rounded fp32/f64

@@ -19,7 +19,12 @@ through an integer region-adaptive hierarchical transform up the octree, `jpeg_q
 coefficients, occupancy and tiles travel through RULE E's coder.  It is off unless asked for and is refused in inter mode.
 `transform_pack`, `transform_unpack` and `transform_info` do the same on the host.
 
-Out of scope: cwipc_codec's bitstream, JPEG colour coding, transform colour in inter mode, motion compensation, inter-frame coding inside an encoder
+A decoder made with ``max_octree_bits=t`` (or told so later by `set_max_octree_bits`) hands out, for every packet of more than `t`
+octree bits, the cloud of that packet's cut to `t` bits (RULE L): the geometry of the same cloud coded at `t` bits, each point's
+colour the rounded mean of the leaves beneath it.  All four packet forms are covered; in a ``cwap`` chain the decoder's reference
+stays the full frame.  `lod(packet, t)` makes the cut packet itself on the host, for ``cwao`` and ``cwae`` packets.
+
+Out of scope: thinning ``cwat`` or ``cwap`` packets in one call, an encoder-side level-of-detail option, cwipc_codec's bitstream, JPEG colour coding, transform colour in inter mode, motion compensation, inter-frame coding inside an encoder
 group, per-leaf point counts in the packet, sockets.
 """
 from __future__ import annotations
@@ -34,7 +39,7 @@ __all__ = [
     "cwipc_encoder_params", "cwipc_new_encoder_params", "cwipc_new_encoder", "cwipc_new_encodergroup", "cwipc_new_decoder",
     "cwipc_encoder_wrapper", "cwipc_encodergroup_wrapper", "cwipc_decoder_wrapper", "packet_info",
     "entropy_pack", "entropy_unpack", "entropy_info", "inter_pack", "inter_unpack", "inter_info",
-    "transform_pack", "transform_unpack", "transform_info",
+    "transform_pack", "transform_unpack", "transform_info", "lod",
 ]
 
 
@@ -178,6 +183,11 @@ class cwipc_decoder_wrapper:
         """CwipcError with the reason for a packet that is not valid; such a packet never reaches the device."""
         util.cwipc_hip_decoder_feed(self._handle(), buffer)
 
+    def set_max_octree_bits(self, bits: Optional[int]) -> None:
+        """From the next feed on, a packet of more than `bits` octree bits gives the cloud of its cut to `bits` (RULE L); None or 0:
+        off.  CwipcError for anything outside 0..16."""
+        util.cwipc_hip_decoder_set_max_octree_bits(self._handle(), 0 if bits is None else bits)
+
     def available(self, wait: bool) -> bool:
         return util.cwipc_hip_decoder_available(self._handle(), wait)
 
@@ -215,8 +225,12 @@ def cwipc_new_encodergroup() -> cwipc_encodergroup_wrapper:
     return cwipc_encodergroup_wrapper(util.cwipc_hip_new_encodergroup())
 
 
-def cwipc_new_decoder() -> cwipc_decoder_wrapper:
-    return cwipc_decoder_wrapper(util.cwipc_hip_new_decoder())
+def cwipc_new_decoder(max_octree_bits: Optional[int] = None) -> cwipc_decoder_wrapper:
+    """A decoder; max_octree_bits=t: it hands out clouds of at most t octree bits (RULE L, `set_max_octree_bits`)."""
+    dec = cwipc_decoder_wrapper(util.cwipc_hip_new_decoder())
+    if max_octree_bits:
+        dec.set_max_octree_bits(max_octree_bits)
+    return dec
 
 
 def packet_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
@@ -226,6 +240,12 @@ def packet_info(packet: Union[bytes, bytearray, memoryview]) -> Dict[str, Any]:
                 tile_mode=info.tile_mode, tile_value=info.tile_value, min=tuple(info.min), side=info.side,
                 nodes=list(info.nodes)[:info.octree_bits], occupancy_offset=info.occupancy_offset, colour_offset=info.colour_offset,
                 tile_offset=info.tile_offset, total_bytes=info.total_bytes)
+
+
+def lod(packet: Union[bytes, bytearray, memoryview], bits: int) -> bytearray:
+    """The cut of a valid "cwao" packet to `bits` octree bits (RULE L), or of a "cwae" packet in that form (host code, no GPU);
+    CwipcError with the reason for "cwat" and "cwap" packets, a packet that is not valid, bits < 1 and bits above the packet's."""
+    return util.cwipc_hip_codec_lod(packet, bits)
 
 
 def entropy_pack(packet: Union[bytes, bytearray, memoryview]) -> bytearray:

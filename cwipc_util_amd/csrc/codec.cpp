@@ -28,11 +28,18 @@
 // the packet together around the escape streams, whose sizes only the device knows; the size arrives as the entropy-coded form's
 // does.  Decode: the container test on the host -> upload -> the streams decoded, tokens and escapes joined and counted -> ONE wait ->
 // the inverse transform into the body's colour plane -> the decode above.
+//
+// Level-of-detail decoding (RULE L: hip_ext.h, lod_terms.hpp; kernels_lod.hip).  A decoder told to hand out at most t octree bits does
+// everything above up to the packet's body (or, for "cwap", the frame's leaves, which stay the FULL frame as the reference) and then,
+// for a packet of b > t bits, makes the cloud of L(P, t) instead of the full one: the leaf runs of the nodes of depth t, the keys of
+// depth t alone, the runs' sums, the points.  From a body nothing more is waited for; from a frame's leaves the number of runs is one
+// more wait.  cwipc_hip_codec_lod is the host twin: it makes the packet L(P, t).
 #include "internal.hpp"
 #include "codec_terms.hpp"
 #include "entropy_terms.hpp"
 #include "inter_terms.hpp"
 #include "transform_terms.hpp"
+#include "lod_terms.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -748,9 +755,98 @@ struct cwipc_hip_decoder {
     // the frame of the last "cwap" packet (RULE P), under a lock of its own that a feed of such a packet holds throughout
     std::mutex inter_lock;
     std::unique_ptr<InterRefDev> reference;
+    std::atomic<int> max_bits{0};   // RULE L: 0, or the most octree bits of a cloud handed out; read once a feed
 };
 
 namespace {
+
+// the octree bits of the cloud a decoder with `max_bits` hands out for a packet of `bits`
+int lod_out_bits(int bits, int max_bits) { return max_bits > 0 && bits > max_bits ? max_bits : bits; }
+
+// RULE L from a packet's body on the device (occupancy bytes at `body`; `full`: the decode of all l.bits, its colour and tile planes
+// in place): the cloud of L(P, t), t < l.bits, into dst (l.nodes[t - 1] points), queued on the calling thread's stream.
+// first: the tree's first children where the caller has them (transform_prepare), or nullptr: made here.
+bool lod_from_body(const char *who, ThreadCtx &c, const uint8_t *body, const CodecLayout &l, const k::CodecDecode &full, int t, const uint32_t *first,
+                   const DeviceSoA &dst) {
+    const uint32_t nruns = l.nodes[t - 1];
+    if ((uint64_t)l.occupancy_bytes + l.nleaves > 0x7fffffffull) { note_error(who, "the packet is too large for level-of-detail decoding"); return false; }   // (the tree's node numbers are 32 bits)
+    k::TransformTree tree{};
+    k::transform_tree_counts(tree, l.bits, l.nodes, l.nleaves, TRANSFORM_Q16_MIN);
+    k::CodecDecode d = full;
+    d.bits = t;
+    d.nleaves = nruns;
+    d.cell = codec_cellsize(l.side, t);
+    const size_t first_bytes = first ? 0 : round256(4 * (size_t)tree.inner), scan_bytes = first ? 0 : round256(4 * k::transform_scan_words(tree)),
+                 start_bytes = round256(4 * ((size_t)nruns + 1)), ping_bytes = round256(8 * (size_t)nruns), scratch_bytes = round256(k::codec_decode_scratch_words(d) * 4),
+                 sums_bytes = round256((size_t)nruns * sizeof(k::CodecLeafSum));
+    uint8_t *block = (uint8_t *)pool_alloc(first_bytes + scan_bytes + start_bytes + 2 * ping_bytes + scratch_bytes + sums_bytes);
+    if (!block) { note_error(who, "out of device memory"); return false; }
+    uint8_t *at = block;
+    if (!first) {
+        tree.occupancy = body;
+        tree.first = (uint32_t *)at; at += first_bytes;
+        tree.scan = (uint32_t *)at; at += scan_bytes;
+        k::transform_prepare(tree, c.stream);
+        first = tree.first;
+    }
+    uint32_t *start = (uint32_t *)at; at += start_bytes;
+    unsigned long long *ping = (unsigned long long *)at, *pong = (unsigned long long *)(at + ping_bytes); at += 2 * ping_bytes;
+    uint32_t *scratch = (uint32_t *)at; at += scratch_bytes;
+    k::lod_runs_of_tree(first, tree.inner, tree.depth_begin[t], l.bits - t, nruns, l.nleaves, start, c.stream);
+    const unsigned long long *cut = k::codec_expand(body, d, ping, pong, scratch, c.stream);
+    const k::LodSource src{l.nleaves, full.colour_bits, full.tile_value, full.colours, full.colour_words, nullptr, full.tiles};
+    const bool ok = k::lod_points(src, start, nruns, cut, (k::CodecLeafSum *)at, d, dst, c.stream);
+    c.free_later(block);
+    return ok;
+}
+
+// RULE L from a frame's leaves on the device (RULE P's reference, the full frame of l.bits): the cloud of L(P, t), t < l.bits, after
+// ONE wait for the number of its points.  nullptr: failed (logged).
+std::shared_ptr<DeviceSoA> lod_from_leaves(const char *who, ThreadCtx &c, const k::InterLeavesDev &leaves, const CodecLayout &l, int t) {
+    const size_t n = leaves.n;
+    const size_t start_bytes = round256(4 * (n + 1)), cut_bytes = round256(8 * n), counts_bytes = round256(4 * k::lod_key_runs_words(n));
+    uint8_t *block = (uint8_t *)pool_alloc(start_bytes + cut_bytes + counts_bytes);
+    if (!block) { note_error(who, "out of device memory"); return nullptr; }
+    uint32_t *start = (uint32_t *)block;
+    unsigned long long *cut = (unsigned long long *)(block + start_bytes);
+    PinnedReport report = c.report();
+    const uint32_t tag = report.arm(0, 1);
+    k::lod_runs_of_keys(leaves.keys, leaves.n, l.bits, t, start, cut, (uint32_t *)(block + start_bytes + cut_bytes), report.device(), tag, c.stream);
+    bool ok = hipGetLastError() == hipSuccess;
+    ok = c.sync() && ok;   // the wait: how many points the cloud has
+    ok = ok && report.landed(tag, 0);
+    const uint32_t nruns = ok ? report.value(0) : 0u;
+    if (!ok || nruns < 1 || nruns > n) {
+        pool_free(block);
+        if (!ok) hip_failed(hipGetLastError(), "octree decode (level of detail)", __FILE__, __LINE__);
+        else note_error(who, "the leaf runs lost count");
+        return nullptr;
+    }
+    auto dst = soa_alloc(nruns);
+    k::CodecLeafSum *sums = (k::CodecLeafSum *)pool_alloc(round256((size_t)nruns * sizeof(k::CodecLeafSum)));
+    if (!dst || !sums) {
+        pool_free(block);
+        pool_free(sums);
+        note_error(who, "out of device memory");
+        return nullptr;
+    }
+    k::CodecDecode d{};
+    d.bits = t;
+    d.colour_bits = l.colour_bits;
+    d.nleaves = nruns;
+    for (int a = 0; a < 3; a++) d.mn[a] = l.mn[a];
+    d.cell = codec_cellsize(l.side, t);
+    const k::LodSource src{leaves.n, l.colour_bits, 0, nullptr, 0, leaves.colour, leaves.tiles};
+    ok = k::lod_points(src, start, nruns, cut, sums, d, *dst, c.stream) && hipGetLastError() == hipSuccess;
+    c.free_later(block);
+    c.free_later(sums);
+    if (!ok) {
+        (void)c.sync();
+        hip_failed(hipGetLastError(), "octree decode (level of detail)", __FILE__, __LINE__);
+        return nullptr;
+    }
+    return dst;
+}
 
 void release_upload(cwipc_hip_decoder::Job &j) {
     if (j.host) {
@@ -1288,6 +1384,19 @@ extern "C" int cwipc_hip_codec_inter_info(const void *bytes, size_t len, cwipc_h
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// level-of-detail cuts of packets on the host (no GPU)
+// ---------------------------------------------------------------------------
+extern "C" size_t cwipc_hip_codec_lod(const void *bytes, size_t len, int bits, void *out, size_t capacity, char **errorMessage) {
+    const char *who = "cwipc_hip_codec_lod";
+    ErrorbufScope scope(errorMessage);
+    return guarded(who, (size_t)0, [&]() -> size_t {
+        std::vector<uint8_t> made;
+        if (const char *problem = lod_convert((const uint8_t *)bytes, len, bits, made)) { note_error(who, problem); return 0; }
+        return hand_out(made, out, capacity);
+    });
+}
+
 extern "C" cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage) {
     ErrorbufScope scope(errorMessage);
     cwipc_hip_decoder *d = new (std::nothrow) cwipc_hip_decoder();
@@ -1299,7 +1408,8 @@ namespace {
 
 // A "cwao" or "cwae" packet into a cloud on the decoder's queue.  keep_reference (the packet is a key packet's, RULE P; the caller
 // holds the decoder's inter_lock): the frame's leaves become the decoder's reference, none for an empty cloud.
-int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *bytes, size_t len, bool keep_reference) {
+// max_bits (RULE L): a packet of more bits gives the cloud of its cut; the reference is the full frame all the same.
+int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *bytes, size_t len, bool keep_reference, int max_bits) {
     // the validity test: host code, before anything is launched or allocated on the device
     CodecLayout l;
     EntropyLayout el;
@@ -1315,10 +1425,15 @@ int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *byte
     if (!device_available(who)) return -1;
     ThreadCtx &c = tctx();
     if (!c.ensure()) return -1;
-    const double cell = codec_cellsize(l.side, l.bits);
+    const int out_bits = lod_out_bits(l.bits, max_bits);
+    const bool cut = out_bits < l.bits && l.nleaves;
+    const double cell = codec_cellsize(l.side, out_bits);
     cwipc_hip_decoder::Job job;
-    auto dst = soa_alloc(l.nleaves);
-    if (!dst) { note_error(who, "out of device memory"); return -1; }
+    std::shared_ptr<DeviceSoA> dst;   // (the cut of a key packet's frame is made from the reference's leaves, below)
+    if (!(cut && keep_reference)) {
+        dst = soa_alloc(cut ? l.nodes[out_bits - 1] : l.nleaves);
+        if (!dst) { note_error(who, "out of device memory"); return -1; }
+    }
     if (l.nleaves) {
         const size_t body = (size_t)(l.total_bytes - l.occupancy_offset);
         k::CodecDecode d{};
@@ -1353,9 +1468,12 @@ int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *byte
             ok = hipMemcpyAsync(block, job.host, body, hipMemcpyHostToDevice, c.stream) == hipSuccess;
         }
         if (ok) {
-            k::codec_decode(block, d, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
-                            (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
-            ok = hipGetLastError() == hipSuccess;
+            unsigned long long *ping = (unsigned long long *)(block + body_bytes), *pong = (unsigned long long *)(block + body_bytes + ping_bytes);
+            uint32_t *scratch = (uint32_t *)(block + body_bytes + 2 * ping_bytes);
+            if (!cut) k::codec_decode(block, d, ping, pong, scratch, *dst, c.stream);
+            else if (keep_reference) (void)k::codec_expand(block, d, ping, pong, scratch, c.stream);   // the full keys, for the reference
+            else ok = lod_from_body(who, c, block, l, d, out_bits, nullptr, *dst);
+            ok = ok && hipGetLastError() == hipSuccess;
         }
         c.free_later(block);
         if (!ok) {
@@ -1377,6 +1495,13 @@ int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *byte
             k::inter_leaves_of_planes(d.colours, d.colour_words, d.tiles, d.tile_value, l.colour_bits, next->leaves, c.stream);
             if (!next->published(c.stream)) (void)c.sync();
             replace_reference(dec->reference, std::move(next));
+            if (cut) {
+                dst = lod_from_leaves(who, c, dec->reference->leaves, l, out_bits);
+                if (!dst) {
+                    if (job.host) host_free(job.host, job.pinned);
+                    return -1;
+                }
+            }
         }
         dst->mark_pending(c.stream);
     } else if (keep_reference) {
@@ -1395,7 +1520,7 @@ int decoder_feed_plain(const char *who, cwipc_hip_decoder *dec, const void *byte
 // (occupancy and tiles into the body the octree decoder reads, the tokens into byte planes), the tree's first children, the tokens and
 // escapes joined -> ONE wait for the entropy stage's status and the three counts of tokens equal to 255 (a packet that fails is refused
 // there) -> weights, the inverse transform into the body's colour plane, the octree decoder.
-int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, size_t len) {
+int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, size_t len, int max_bits) {
     TransformLayout tl;
     if (const char *problem = transform_validate(bytes, len, tl)) { note_error(who, problem); return -1; }
     const CodecLayout &l = tl.cwao;
@@ -1403,8 +1528,10 @@ int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_
     if (!device_available(who)) return -1;
     ThreadCtx &c = tctx();
     if (!c.ensure()) return -1;
-    const double cell = codec_cellsize(l.side, l.bits);
-    auto dst = soa_alloc(l.nleaves);
+    const int out_bits = lod_out_bits(l.bits, max_bits);
+    const bool cut = out_bits < l.bits && l.nleaves;   // RULE L on the 8-colour-bit packet this one stands for: the inverse transform runs in full
+    const double cell = codec_cellsize(l.side, out_bits);
+    auto dst = soa_alloc(cut ? l.nodes[out_bits - 1] : l.nleaves);
     if (!dst) { note_error(who, "out of device memory"); return -1; }
     if (l.nleaves) {
         const size_t n = l.nleaves, ncoef = n - 1, body = (size_t)(l.total_bytes - l.occupancy_offset);
@@ -1525,9 +1652,10 @@ int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_
         cd.colours = (const uint32_t *)colours;
         cd.tiles = l.tile_mode == 1 ? d.tiles : nullptr;
         k::transform_inverse(tree, tl.dc, colours, c.stream);
-        k::codec_decode(block, cd, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
-                        (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
-        ok = hipGetLastError() == hipSuccess;
+        if (cut) ok = lod_from_body(who, c, block, l, cd, out_bits, tree.first, *dst);
+        else k::codec_decode(block, cd, (unsigned long long *)(block + body_bytes), (unsigned long long *)(block + body_bytes + ping_bytes),
+                             (uint32_t *)(block + body_bytes + 2 * ping_bytes), *dst, c.stream);
+        ok = ok && hipGetLastError() == hipSuccess;
         c.free_later(block);
         c.free_later(dev);
         c.free_later(tblock);
@@ -1551,7 +1679,7 @@ int decoder_feed_transform(const char *who, cwipc_hip_decoder *dec, const uint8_
 // A delta packet (RULE P) that has passed inter_validate() against the reference held (the caller holds the decoder's inter_lock):
 // upload, the streams decoded into byte planes, the added keys expanded, the checks, ONE wait; a delta that fails a check ends there,
 // with the reference as it was.  Then the merge, the colours and tiles, the points; the frame becomes the reference.
-int decoder_feed_delta(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, const InterLayout &il) {
+int decoder_feed_delta(const char *who, cwipc_hip_decoder *dec, const uint8_t *bytes, const InterLayout &il, int max_bits) {
     if (!device_available(who)) return -1;
     ThreadCtx &c = tctx();
     if (!c.ensure()) return -1;
@@ -1678,11 +1806,17 @@ int decoder_feed_delta(const char *who, cwipc_hip_decoder *dec, const uint8_t *b
         hip_failed(hipGetLastError(), "octree decode (delta)", __FILE__, __LINE__);
         return -1;
     }
-    dst->mark_pending(c.stream);
     replace_reference(dec->reference, std::move(next));
+    // RULE L: the reference stays the full frame, so the chain does not drift; only the cloud handed out is cut, from the frame's leaves
+    const int out_bits = lod_out_bits(l.bits, max_bits);
+    if (out_bits < l.bits && l.nleaves) {
+        dst = lod_from_leaves(who, c, dec->reference->leaves, l, out_bits);
+        if (!dst) return -1;
+    }
+    dst->mark_pending(c.stream);
     cwipc_hip_decoder::Job job;
     auto *cloud = new cwipc_hip_pointcloud();
-    cloud->adopt_device(dst, l.timestamp, (float)cell);
+    cloud->adopt_device(dst, l.timestamp, (float)codec_cellsize(l.side, out_bits));
     job.cloud = cloud;
     job.planes = dst;
     std::lock_guard<std::mutex> lk(dec->lock);
@@ -1696,8 +1830,9 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
     return guarded(who, -1, [&]() -> int {
         if (dec == nullptr) { note_error(who, "NULL argument"); return -1; }
         if (dec->closed) { note_error(who, "the decoder has been closed"); return -1; }
-        if (bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == TRANSFORM_MAGIC) return decoder_feed_transform(who, dec, (const uint8_t *)bytes, len);
-        if (bytes == nullptr || len < 4 || codec_read<uint32_t>((const uint8_t *)bytes) != INTER_MAGIC) return decoder_feed_plain(who, dec, bytes, len, false);
+        const int max_bits = dec->max_bits.load();
+        if (bytes != nullptr && len >= 4 && codec_read<uint32_t>((const uint8_t *)bytes) == TRANSFORM_MAGIC) return decoder_feed_transform(who, dec, (const uint8_t *)bytes, len, max_bits);
+        if (bytes == nullptr || len < 4 || codec_read<uint32_t>((const uint8_t *)bytes) != INTER_MAGIC) return decoder_feed_plain(who, dec, bytes, len, false, max_bits);
         // an inter-frame packet: the container test, with the reference held, before anything is launched or allocated
         std::lock_guard<std::mutex> guard(dec->inter_lock);
         InterReference held;
@@ -1705,9 +1840,17 @@ extern "C" int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes,
         InterLayout il;
         if (const char *problem = inter_validate((const uint8_t *)bytes, len, &held, il)) { note_error(who, problem); return -1; }
         if (il.total_bytes > 0x7fffffffull) { note_error(who, "the packet is too large"); return -1; }
-        if (il.kind == INTER_KEY) return decoder_feed_plain(who, dec, (const uint8_t *)bytes + INTER_PREFIX_BYTES, len - INTER_PREFIX_BYTES, true);
-        return decoder_feed_delta(who, dec, (const uint8_t *)bytes, il);
+        if (il.kind == INTER_KEY) return decoder_feed_plain(who, dec, (const uint8_t *)bytes + INTER_PREFIX_BYTES, len - INTER_PREFIX_BYTES, true, max_bits);
+        return decoder_feed_delta(who, dec, (const uint8_t *)bytes, il, max_bits);
     });
+}
+
+extern "C" int cwipc_hip_decoder_set_max_octree_bits(cwipc_hip_decoder *dec, int bits) {
+    const char *who = "cwipc_hip_decoder_set_max_octree_bits";
+    if (dec == nullptr) { note_error(who, "NULL argument"); return -1; }
+    if (bits < 0 || bits > CODEC_MAX_BITS) { note_error(who, "bits must be 0 (off) or in 1..16"); return -1; }
+    dec->max_bits.store(bits);
+    return 0;
 }
 
 extern "C" bool cwipc_hip_decoder_available(cwipc_hip_decoder *dec, bool wait) {

@@ -742,6 +742,29 @@ void inter_check(const InterLeavesDev &R, const uint8_t *keep, const unsigned lo
 void inter_apply(const InterLeavesDev &R, const uint8_t *keep, const uint32_t *rank, const unsigned long long *added, uint32_t nadded, const uint8_t *res,
                  const CodecDecode &d, int tile_mode, const InterLeavesDev &P, const DeviceSoA &dst, hipStream_t s);
 
+// ---- kernels_lod.hip: level-of-detail decoding (RULE L: hip_ext.h; the arithmetic: lod_terms.hpp) ----
+// A frame's leaves as the reduction reads them: the stored colours as RULE C's bit-packed plane (packed != nullptr) or as three byte
+// planes of nleaves (RULE P's reference); tiles == nullptr: tile_value throughout.
+struct LodSource {
+    uint32_t nleaves;
+    int colour_bits, tile_value;
+    const uint32_t *packed;
+    uint64_t colour_words;
+    const uint8_t *planes, *tiles;
+};
+// start[j], j < nruns: the first leaf under node j of depth t, `steps` = b - t lookups in first[] (transform_prepare) below the node's
+// number begin + j; start[nruns] = nleaves
+void lod_runs_of_tree(const uint32_t *first, uint32_t inner, uint32_t begin, int steps, uint32_t nruns, uint32_t nleaves, uint32_t *start, hipStream_t s);
+// The same from n ascending keys of b triples: start (n + 1 words) and the runs' keys of t triples (cut, n words); the number of runs
+// goes to total_host (pinned, under tag).  counts: lod_key_runs_words(n) words.
+size_t lod_key_runs_words(size_t n);
+void lod_runs_of_keys(const unsigned long long *keys, uint32_t n, int b, int t, uint32_t *start, unsigned long long *cut, uint32_t *counts,
+                      unsigned long long *total_host, uint32_t tag, hipStream_t s);
+// The cloud of L(P, t): the sums of every run (sums: nruns entries, zeroed here), then per new leaf the point of its key (cut, depth
+// d.bits = t, d.nleaves = nruns, d.colour_bits as the packet's) with the rounded means and the tiles' OR.
+bool lod_points(const LodSource &src, const uint32_t *start, uint32_t nruns, const unsigned long long *cut, CodecLeafSum *sums, const CodecDecode &d,
+                const DeviceSoA &dst, hipStream_t s);
+
 }  // namespace k
 
 // Voxel-grid downsample (kernels_voxel.hip).  Returns the new cloud's planes or

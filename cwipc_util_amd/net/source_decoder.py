@@ -44,7 +44,8 @@ class _ListSource:
 
 
 class _Decoder(cwipc_activesource_abstract):
-    def __init__(self, source: Any, verbose: bool = False):
+    def __init__(self, source: Any, verbose: bool = False, max_octree_bits: Optional[int] = None):
+        self.max_octree_bits = max_octree_bits
         self.source = _ListSource(source) if isinstance(source, list) else source
         if hasattr(self.source, "set_fourcc"):
             self.source.set_fourcc(FOURCC)
@@ -89,7 +90,7 @@ class _Decoder(cwipc_activesource_abstract):
         if not packet:
             return False
         if self.decomp is None:
-            self.decomp = codec.cwipc_new_decoder()
+            self.decomp = codec.cwipc_new_decoder(max_octree_bits=self.max_octree_bits)
         t0 = time.time()
         try:
             self.decomp.feed(packet)
@@ -165,13 +166,14 @@ class _Decoder(cwipc_activesource_abstract):
         raise NotImplementedError
 
 
-def cwipc_activesource_decoder(source: Any, verbose: bool = False) -> cwipc_activesource_abstract:
-    """A source that reads packets from an active raw source (started and stopped with it) and decompresses them."""
-    return _Decoder(source, verbose=verbose)
+def cwipc_activesource_decoder(source: Any, verbose: bool = False, max_octree_bits: Optional[int] = None) -> cwipc_activesource_abstract:
+    """A source that reads packets from an active raw source (started and stopped with it) and decompresses them.  max_octree_bits=t:
+    clouds of at most t octree bits (RULE L), whatever the sender coded."""
+    return _Decoder(source, verbose=verbose, max_octree_bits=max_octree_bits)
 
 
-def cwipc_source_decoder(source: Any, verbose: bool = False) -> cwipc_source_abstract:
-    """A source that reads packets from a raw source and decompresses them; it is running when it is returned."""
-    rv = _Decoder(source, verbose=verbose)
+def cwipc_source_decoder(source: Any, verbose: bool = False, max_octree_bits: Optional[int] = None) -> cwipc_source_abstract:
+    """A source that reads packets from a raw source and decompresses them; it is running when it is returned.  max_octree_bits: as above."""
+    rv = _Decoder(source, verbose=verbose, max_octree_bits=max_octree_bits)
     rv.start(startsource=False)
     return rv

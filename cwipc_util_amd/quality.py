@@ -126,11 +126,12 @@ def cloud_distortion(original: cwipc_pointcloud_wrapper, degraded: cwipc_pointcl
     return DistortionResults(forward, backward, default_peak(original) if peak is None else peak)
 
 
-def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwargs: Dict[str, Any], colour_transform: bool = False) -> Tuple[cwipc_pointcloud_wrapper, int]:
+def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwargs: Dict[str, Any], colour_transform: bool = False,
+                       decode_bits: Optional[int] = None) -> Tuple[cwipc_pointcloud_wrapper, int]:
     """(the decoded cloud, device-resident; the packet's size in bytes)"""
     from . import codec
     enc = codec.cwipc_new_encoder(entropy=entropy, colour_transform=colour_transform, **encoder_kwargs)
-    dec = codec.cwipc_new_decoder()
+    dec = codec.cwipc_new_decoder(max_octree_bits=decode_bits)
     try:
         enc.feed(pc)
         if not enc.available(True):
@@ -148,13 +149,15 @@ def _through_the_codec(pc: cwipc_pointcloud_wrapper, entropy: bool, encoder_kwar
         dec.free()
 
 
-def codec_distortion(pc: cwipc_pointcloud_wrapper, *, entropy: bool = False, colour_transform: bool = False, **kwargs: Any) -> Tuple[DistortionResults, int]:
+def codec_distortion(pc: cwipc_pointcloud_wrapper, *, entropy: bool = False, colour_transform: bool = False, decode_bits: Optional[int] = None,
+                     **kwargs: Any) -> Tuple[DistortionResults, int]:
     """cwipc_new_encoder(**encoder keywords) -> cwipc_new_decoder -> cloud_distortion: (the distortion of the decoded cloud against
     `pc`, the packet's bytes).  The keywords max_distance, normals, radius, max_nn, plane and peak go to cloud_distortion, every
-    other one to the encoder.  colour_transform=True: the packet is the transform-coded form (RULE T), jpeg_quality its quantiser.  The
-    decoded cloud never becomes a host array."""
+    other one to the encoder.  colour_transform=True: the packet is the transform-coded form (RULE T), jpeg_quality its quantiser.
+    decode_bits=t: the decoder hands out at most t octree bits (RULE L): "coded at octree_bits, decoded at t".  The decoded cloud never
+    becomes a host array."""
     measure = {k: kwargs.pop(k) for k in ("max_distance", "normals", "radius", "max_nn", "plane", "peak") if k in kwargs}
-    decoded, nbytes = _through_the_codec(pc, entropy, kwargs, colour_transform)
+    decoded, nbytes = _through_the_codec(pc, entropy, kwargs, colour_transform, decode_bits)
     return cloud_distortion(pc, decoded, **measure), nbytes
 
 

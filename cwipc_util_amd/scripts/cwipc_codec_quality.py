@@ -6,6 +6,9 @@ compared with the original on the GPU: the packet's size, the bits it spends per
 point-to-point error (D1), the point-to-plane error (D2) and the colour error in BT.709 YUV -- the measures of MPEG's pc_error,
 by this library's RULE Q (include/cwipc_util_amd/hip_ext.h).  No decoded cloud leaves the device.  No reference counterpart.
 
+With --decode-bits T every packet is also decoded by a decoder that hands out at most T octree bits (RULE L): the row "coded at b,
+decoded at T" stands beside the row "coded at T", whose packet is the smaller one.
+
 With --gop the table is another one: a sequence of frames (the synthetic source's, which turns from frame to frame, or the input
 file over and over) goes through one inter-frame encoder (RULE P), and every frame gets a row with its packet's kind and size
 beside the size of the same frame coded on its own.
@@ -31,6 +34,7 @@ class CodecQualityTable:
         self.jpeg_quality: Sequence[int] = args.jpeg_quality or [85]
         self.entropy = bool(args.entropy)
         self.colour_transform = bool(getattr(args, "colour_transform", False))
+        self.decode_bits: Sequence[int] = getattr(args, "decode_bits", None) or []
         self.gop = int(getattr(args, "gop", 0) or 0)
         self.exp_factor = float(getattr(args, "exp_factor", 1.25))
         self.nframes = int(getattr(args, "frames", 0) or 0) or 2 * max(self.gop, 1)
@@ -52,7 +56,12 @@ class CodecQualityTable:
 
     def settings(self) -> List[Dict[str, Any]]:
         extra = dict(colour_transform=True) if self.colour_transform else {}
-        return [dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy, **extra) for b in self.octree_bits for q in self.jpeg_quality]
+        rows = []
+        for b in self.octree_bits:
+            for q in self.jpeg_quality:
+                rows.append(dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy, **extra))
+                rows += [dict(octree_bits=b, jpeg_quality=q, entropy=self.entropy, decode_bits=t, **extra) for t in self.decode_bits if t < b]
+        return rows
 
     def run(self) -> None:
         assert self.input_pc
@@ -69,10 +78,12 @@ class CodecQualityTable:
             for i, row in enumerate(self.rows):
                 lines.append("%6d %6s %10d %12d %6.3f" % (i, row["kind"], row["bytes"], row["intra_bytes"], row["bytes"] / row["intra_bytes"]))
             return "\n".join(lines)
-        lines = ["%11s %12s %7s %10s %20s %8s %8s %8s %8s %8s" % COLUMNS]
+        cut = bool(self.decode_bits)   # one more column, in front: the octree bits the decoder handed out
+        lines = [("%11s " % "decode_bits" if cut else "") + "%11s %12s %7s %10s %20s %8s %8s %8s %8s %8s" % COLUMNS]
         for row in self.rows:
             flat = dict(row["settings"], **{k: v for k, v in row.items() if k != "settings"})
-            lines.append("%11d %12d %7s %10d %20.4f %8.2f %8.2f %8.2f %8.2f %8.2f" % tuple(flat[c] for c in COLUMNS))
+            lines.append(("%11d " % flat.get("decode_bits", flat["octree_bits"]) if cut else "") +
+                         "%11d %12d %7s %10d %20.4f %8.2f %8.2f %8.2f %8.2f %8.2f" % tuple(flat[c] for c in COLUMNS))
         return "\n".join(lines)
 
 
@@ -86,6 +97,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--entropy", action="store_true", help="Measure the entropy-coded packets (same distortion, fewer bytes)")
     parser.add_argument("--colour-transform", dest="colour_transform", action="store_true",
                         help="Measure transform-coded packets: --jpeg_quality sets the quantiser of the colour transform (100 is exact). Not with --gop")
+    parser.add_argument("--decode-bits", dest="decode_bits", type=int, action="append", metavar="T",
+                        help="Also decode every packet of more than T octree bits at T bits (level-of-detail decoding). Repeat for each T. Not with --gop")
     parser.add_argument("--gop", type=int, metavar="N", default=0, help="Inter-frame coding with a key packet every N frames (2 or more): print bytes per frame against intra "
                         "coding, at the first octree depth and quality given")
     parser.add_argument("--exp_factor", type=float, default=1.25, help="With --gop: how much larger than a key frame's cube the cube of its GOP is (default: 1.25)")
@@ -100,6 +113,8 @@ def main() -> None:
         parser.error("give either an input file or --synthetic NPOINTS")
     if args.colour_transform and args.gop:
         parser.error("--colour-transform is not available with --gop")
+    if args.decode_bits and args.gop:
+        parser.error("--decode-bits is not available with --gop")
     creator = CodecQualityTable(args)
     creator.load_input(args.input, args.synthetic)
     creator.run()

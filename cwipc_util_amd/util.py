@@ -71,6 +71,7 @@ __all__ = [
     'cwipc_hip_codec_inter_directory', 'cwipc_hip_codec_inter_pack', 'cwipc_hip_codec_inter_unpack', 'cwipc_hip_codec_inter_info',
     'cwipc_hip_encoder_set_colour_transform', 'cwipc_hip_codec_transform_directory', 'cwipc_hip_codec_transform_pack', 'cwipc_hip_codec_transform_unpack',
     'cwipc_hip_codec_transform_info',
+    'cwipc_hip_decoder_set_max_octree_bits', 'cwipc_hip_codec_lod',
 ]
 
 # reference util.py:86, 346, 348
@@ -329,6 +330,8 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_codec_transform_pack': ([_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_transform_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_transform_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
+    'cwipc_hip_decoder_set_max_octree_bits': ([_c.c_void_p, _c.c_int], _c.c_int),
+    'cwipc_hip_codec_lod': ([_c.c_void_p, _c.c_size_t, _c.c_int, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_inter_pack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_uint32, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_inter_unpack': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_size_t, _ERR], _c.c_size_t),
     'cwipc_hip_codec_inter_info': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _ERR], _c.c_int),
@@ -2222,6 +2225,33 @@ def cwipc_hip_decoder_feed(dec: int, packet: Union[bytes, bytearray, memoryview]
     data = bytes(packet)
     if cwipc_util_dll_load().cwipc_hip_decoder_feed(dec, data, len(data)) != 0:
         raise _codec_last_error('cwipc_hip_decoder_feed')
+
+
+def cwipc_hip_decoder_set_max_octree_bits(dec: int, bits: int) -> None:
+    """The decoder hands out clouds of at most `bits` octree bits from its next feed on (hip_ext.h: RULE L); 0: off.  CwipcError for
+    anything but 0..16."""
+    if cwipc_util_dll_load().cwipc_hip_decoder_set_max_octree_bits(dec, int(bits)) != 0:
+        raise _codec_last_error('cwipc_hip_decoder_set_max_octree_bits')
+
+
+def cwipc_hip_codec_lod(packet: Union[bytes, bytearray, memoryview], bits: int) -> bytearray:
+    """The cut L(P, bits) of a "cwao" packet, or of a "cwae" packet in that form (hip_ext.h: RULE L; host code, no GPU); CwipcError with
+    the reason for a packet or a `bits` that is refused."""
+    data = bytes(packet)
+    capacity = len(data) + 4 + 11 * 20
+    for _ in range(2):
+        out = bytearray(capacity)
+        buffer = (ctypes.c_char * len(out)).from_buffer(out)
+        errorString = ctypes.c_char_p()
+        size = cwipc_util_dll_load().cwipc_hip_codec_lod(data, len(data), int(bits), ctypes.addressof(buffer), len(out), ctypes.byref(errorString))
+        del buffer
+        if size == 0:
+            raise CwipcError(errorString.value.decode('utf8') if errorString.value else "cwipc_hip_codec_lod: not a valid packet")
+        if size <= len(out):
+            del out[size:]
+            return out
+        capacity = size   # (an entropy-coded cut that is larger than the packet it was cut from)
+    raise CwipcError("cwipc_hip_codec_lod: the size of the result changed between two calls")
 
 
 def cwipc_hip_decoder_available(dec: int, wait: bool) -> bool:

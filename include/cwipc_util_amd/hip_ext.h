@@ -718,7 +718,8 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, JPEG colour coding,
  * per-leaf point counts in the packet, sockets.  (Entropy coding: RULE E below, off unless asked for.  Inter-frame coding: RULE P
  * below, off unless the parameters ask for it; motion compensation is out of scope.  Transform colour coding: RULE T below, off
- * unless asked for.)
+ * unless asked for.  Level-of-detail decoding and packet thinning: RULE L below, a decoder's choice, off unless asked for; an
+ * encoder-side option, thinning a "cwat" or "cwap" packet in one call and an inverse transform that stops early are out of scope.)
  *
  * RULE C.  The arithmetic is csrc/codec_terms.hpp (host and device compile it), tests/codec_model.py its numpy restatement.  All
  * arithmetic is float64 unless stated otherwise, every operation rounded on its own.
@@ -918,7 +919,34 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig
  *           streams without symbols; the escape streams' directory entries count their padded bytes; Q16 of an empty cloud's packet is
  *           the quality's.  Out of scope: transform colour under RULE P, per-depth frequency tables or contexts, a constant-stream
  *           mode under the coder's 256 bytes of states per block, prediction between levels, closed-loop quantisation, per-leaf point
- *           counts as weights, interoperability with cwipc_codec or G-PCC. */
+ *           counts as weights, interoperability with cwipc_codec or G-PCC.
+ *
+ * RULE L, level-of-detail cuts.  By RULE C's cell rule q_a(b - 1) == q_a(b) >> 1, so the first t triples of a b-bit key are the key of
+ * the same point at t bits: a packet's first t depths ARE the geometry of the same cloud coded at t bits.  The arithmetic is
+ * csrc/lod_terms.hpp (host and device compile it), tests/lod_model.py its numpy restatement.  Integers only.
+ *  For a valid "cwao" packet P with b octree bits, cb colour bits and nleaves > 0, and a target t with 1 <= t < b, L(P, t) is the
+ *  "cwao" packet with:
+ *  Header.  timestamp, min, side and cb as P's; octree_bits = t; nodes' = nodes[0 .. t - 1]; nleaves' = nodes[t - 1].
+ *  Occupancy.  The occupancy bytes of depths 0 .. t - 1 verbatim, padded anew.
+ *  Colours.  One leaf per distinct key prefix of t triples, ascending.  A new leaf's members are P's leaves under it: a contiguous run
+ *           of n >= 1 leaves in key order.  Per channel on the STORED values (cb bits): v' = (sum v + n / 2) div n in integers.  The
+ *           sum is exact for any n up to nleaves: it is kept in 64 bits.
+ *  Tiles.   tile' = OR of the members' tiles (tile_value for all of them when P has tile_mode 0).  tile_mode' and tile_value' are decided
+ *           anew by the encoder's rule: mode 0 iff all new leaves share one value.  A tile plane can therefore disappear.
+ *  Fixed points and limits.  L(P, b) == P byte for byte, whatever P's tile mode.  An empty P maps to RULE C's empty packet of t bits
+ *           with P's timestamp and colour bits.  t < 1 and t > b are refused by the packet function; for a decoder t >= b means the
+ *           packet as it is.
+ *  Not promised.  L(L(P, t), u) == L(P, u): those are means of means.  Equality of L(P, t)'s colours with those of the same cloud
+ *           encoded at t bits: that encode takes its means over points, and a packet holds no point counts.  Everything but the
+ *           colours IS equal: bytes 24 .. 48, nodes', the occupancy section, nleaves' and the tile fields and plane.
+ *  Decoder.  cwipc_hip_decoder_set_max_octree_bits(dec, bits): for a packet that stands for a "cwao" packet P with b > bits the decoder
+ *           hands out exactly the cloud that decoding L(P, bits) gives: points, colours, tiles, timestamp, cellsize = side / 2^bits.
+ *           "cwat": L applies to the 8-colour-bit packet it stands for, the inverse transform runs in full.  "cwap": the reference the
+ *           decoder keeps stays the FULL frame, so chains do not drift and later deltas validate as before; only the cloud handed
+ *           out is cut.  Every validity test and refusal is as without the setting and comes before any kernel of csrc/kernels_lod.hip.
+ *  Out of scope.  Thinning "cwat" or "cwap" packets in one call (compose with their unpack functions); an inverse transform that stops
+ *           early (RULE T's low-pass values are weighted, they are not RULE L's colours); point counts in packets; an encoder-side
+ *           option; any change to RULES C, E, P, T or their packets. */
 typedef struct cwipc_hip_encoder_params {
     bool do_inter_frame;     /* false; true with the two below: inter mode (RULE P) */
     int gop_size;            /* 1; inter mode: 2..65535 */
@@ -959,6 +987,9 @@ _CWIPC_UTIL_EXPORT void cwipc_hip_encodergroup_free(cwipc_hip_encodergroup *grou
 _CWIPC_UTIL_EXPORT cwipc_hip_decoder *cwipc_hip_new_decoder(char **errorMessage);
 /* 0 ok; -1 and the reason in cwipc_hip_last_error() for a packet that is not valid (nothing launched, nothing allocated) or a device failure */
 _CWIPC_UTIL_EXPORT int cwipc_hip_decoder_feed(cwipc_hip_decoder *dec, const void *bytes, size_t len);
+/* RULE L: the most octree bits of a cloud handed out.  bits 0: off, the default; 1..16: packets of more bits give the cloud of their cut;
+ * anything else: -1 and the reason in cwipc_hip_last_error().  Callable between feeds; it applies to later feeds. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_decoder_set_max_octree_bits(cwipc_hip_decoder *dec, int bits);
 _CWIPC_UTIL_EXPORT bool cwipc_hip_decoder_available(cwipc_hip_decoder *dec, bool wait);
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_decoder_get(cwipc_hip_decoder *dec);                  /* device-resident; NULL: none */
 _CWIPC_UTIL_EXPORT bool cwipc_hip_decoder_eof(cwipc_hip_decoder *dec);
@@ -993,6 +1024,11 @@ typedef struct cwipc_hip_codec_entropy_directory {
     uint64_t total_bytes;             /* of the "cwae" packet */
 } cwipc_hip_codec_entropy_directory;
 _CWIPC_UTIL_EXPORT int cwipc_hip_codec_entropy_info(const void *bytes, size_t len, cwipc_hip_codec_entropy_directory *info, char **errorMessage);
+/* RULE L on the host, without a GPU: a valid "cwao" packet P -> L(P, bits); a "cwae" packet Q -> entropy_pack(L(entropy_unpack(Q), bits)).
+ * "cwat" and "cwap" packets are refused (compose with cwipc_hip_codec_transform_unpack / cwipc_hip_codec_inter_unpack), and so are bits < 1
+ * and bits above the packet's.  The caller-buffer convention is cwipc_hip_codec_entropy_pack's; a "cwao" result never needs more than
+ * len bytes, a "cwae" result's size comes from a first call with out == NULL. */
+_CWIPC_UTIL_EXPORT size_t cwipc_hip_codec_lod(const void *bytes, size_t len, int bits, void *out, size_t capacity, char **errorMessage);
 /* RULE T on the host, without a GPU.  pack: a valid "cwao" packet with 8 colour bits and a jpeg_quality in 0..100 -> its "cwat" form
  * (never more than 3 * len + 300 bytes); unpack: a "cwat" packet -> the "cwao" packet it stands for, after the container test, the blocks'
  * integrity, the occupancy rules and the escape counts (cwipc_hip_codec_transform_info()'s packet.total_bytes).  The caller-buffer
