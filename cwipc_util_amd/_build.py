@@ -33,7 +33,9 @@ SOURCES = [
     "registration.cpp",
     "render.cpp",
     "rgbd.cpp",
-    "codec.cpp",
+    "codec_encode.cpp",
+    "codec_decode.cpp",
+    "codec_host.cpp",
     "exchange.cpp",
     "kernels_basic.hip",
     "kernels_voxel.hip",

@@ -1,5 +1,5 @@
 // codec_terms.hpp -- the arithmetic and the packet layout of RULE C, the octree codec (the rule in full: hip_ext.h; its numpy
-// restatement: tests/codec_model.py).  Compiles for host and device: kernels_codec.hip, codec.cpp and the stand-alone host program
+// restatement: tests/codec_model.py).  Compiles for host and device: kernels_codec.hip, the codec_*.cpp files and the stand-alone host program
 // of the tests (tests/abi/codec_packet_host.cpp) include this one text.  Every operation is rounded on its own: build with
 // -ffp-contract=off.  The packets are this library's own (magic "cwao"); they are NOT cwipc_codec's bitstream.
 #pragma once

@@ -1,7 +1,7 @@
 // entropy_terms.hpp -- RULE E, the entropy-coded form of the octree codec's packets (the rule in full: hip_ext.h; its numpy
 // restatement: tests/entropy_model.py).  A "cwae" packet stands for exactly one valid "cwao" packet (RULE C, codec_terms.hpp): the same
 // header, and every stream of the body either as it is (raw) or coded with a 64-lane interleaved rANS.  Compiles for host and device:
-// kernels_entropy.hip, codec.cpp and the stand-alone host program of the tests (tests/abi/entropy_host.cpp) include this one text.
+// kernels_entropy.hip, the codec_*.cpp files and the stand-alone host program of the tests (tests/abi/entropy_host.cpp) include this one text.
 // The per-symbol steps, the slot search, the bounded word read and the end-of-block test are the very functions the kernels call; the
 // block loops below run them lane by lane where a kernel runs them on the 64 lanes of a wave.  The normalisation is serial here and
 // runs on a wave in the kernel (the same steps, its maxima taken across lanes); the GPU tests hold the two to each other.

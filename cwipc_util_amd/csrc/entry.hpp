@@ -1,5 +1,5 @@
 // entry.hpp -- how the C entry points of filters.cpp, registration.cpp and render.cpp resolve their cloud arguments and wrap their
-// results.  (codec.cpp and exchange.cpp resolve their inputs with error semantics of their own.)
+// results.  (codec_encode.cpp and exchange.cpp resolve their inputs with error semantics of their own.)
 #pragma once
 
 #include "internal.hpp"

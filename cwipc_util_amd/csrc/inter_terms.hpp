@@ -3,7 +3,7 @@
 // packet, which stands for exactly one valid "cwao" packet P given the packet R before it: the leaves of R that stay (a bit each), the
 // leaves that are new (an octree of their own), and per leaf of P the difference of its stored colour and tile to a leaf of R.  The
 // streams are coded by RULE E's coder (entropy_terms.hpp), without its colour prediction.  Compiles for host and device:
-// kernels_inter.hip, codec.cpp and the stand-alone host program of the tests (tests/abi/inter_host.cpp) include this one text.
+// kernels_inter.hip, the codec_*.cpp files and the stand-alone host program of the tests (tests/abi/inter_host.cpp) include this one text.
 // Every operation is rounded on its own: build with -ffp-contract=off.
 #pragma once
 

@@ -10,7 +10,11 @@
 //   registration.cpp  C entry points of the registration tooling: distances, KDE, ICP, the floor and tile helpers, bounds
 //   render.cpp      C entry points of the renderer and the marker detector
 //   entry.hpp       how those three resolve and wrap their clouds
-//   codec.cpp       cwipc_hip_new_encoder / _encodergroup / _decoder: the octree codec (packets out, packets in)
+//   codec_encode.cpp  cwipc_hip_new_encoder / _encodergroup: the octree codec, packets out
+//   codec_decode.cpp  cwipc_hip_new_decoder: the octree codec, packets in
+//   codec_host.cpp    the codec's entry points that never touch the GPU: packet information and the host conversions
+//   codec_stage.hpp   the structs the codec's kernels are handed and the staging arithmetic that fills them (free of HIP)
+//   codec_shared.hpp  what the encoder and the decoder share on the host
 //   rgbd.cpp        cwipc_hip_from_rgbd, cwipc_hip_rgbd_rig_*: the RGB-D source end (images in, device-resident cloud out)
 //   kernels_*.hip   the HIP kernels (gfx950)
 #pragma once
@@ -34,6 +38,7 @@
 #include "rgbd_depthfilter.hpp"
 #include "rgbd_decimate.hpp"
 #include "pinned_report.hpp"
+#include "codec_stage.hpp"
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -564,31 +569,7 @@ struct CodecBounds {
     float lo[3], hi[3];
     uint32_t count, pad;
 };
-struct CodecLeafSum {
-    unsigned long long r, g, b;
-    uint32_t count, tile;
-};
-// One packet's body on the device, zeroed: occupancy (words; occupancy_bytes of them count), colours (colour_words words), the tile
-// plane (nleaves bytes), tile_stats (2 words); and the leaf sums (nleaves, zeroed).  depth_offset[L]: the first occupancy byte of depth L.
-struct CodecEmit {
-    int bits;
-    uint32_t nleaves;
-    uint64_t depth_offset[16];
-    uint64_t occupancy_bytes, colour_words;
-    uint32_t *occupancy, *colours, *tile_stats;
-    uint8_t *tiles;
-    CodecLeafSum *sums;
-};
-struct CodecDecode {
-    int bits, colour_bits, tile_value;
-    uint32_t nleaves;
-    uint32_t nodes[16];
-    float mn[3];
-    double cell;
-    uint64_t colour_words;
-    const uint32_t *colours;   // device, 4-byte aligned
-    const uint8_t *tiles;      // device, or nullptr: tile_value
-};
+// (CodecLeafSum, CodecEmit, CodecDecode: codec_stage.hpp)
 size_t codec_blocks(size_t n);
 size_t codec_bounds_bytes(size_t n);
 // the cube of the points whose coordinates are all finite; partial: codec_bounds_bytes() of device memory
@@ -610,65 +591,12 @@ void codec_decode(const uint8_t *occupancy, const CodecDecode &d, unsigned long 
                   hipStream_t s);
 
 // ---- kernels_entropy.hip: the entropy-coded packet form (RULE E: hip_ext.h; the arithmetic: entropy_terms.hpp) ----
-constexpr int ENTROPY_STREAMS = 21;                      // RULE E: octree_bits + 3 + 1 at the most; RULE P: one more (keep)
-constexpr size_t ENTROPY_SLOT_BYTES = 256 + 2 * 4096;    // a block's states and the most words it can emit
-// The streams of one packet, in RULE E's order; block b of stream i is the global block first_block[i] + b.
-struct EntropyStreams {
-    int nstreams, colour_bits;
-    uint32_t nleaves, total_blocks;
-    uint32_t kind[ENTROPY_STREAMS], which[ENTROPY_STREAMS], symbols[ENTROPY_STREAMS], first_block[ENTROPY_STREAMS];
-    uint32_t plane_offset[ENTROPY_STREAMS];   // occupancy: where the depth starts in the occupancy plane; ENTROPY_BYTES / _BITS: in `planes`
-    uint32_t raw_padded[ENTROPY_STREAMS];     // the raw payload with its padding
-};
-// Encode: the body that codec_emit made (the tile stream is listed last and leaves when tile_stats says the tiles are uniform) -> `out`,
-// zeroed by the caller, from the word S on.  report (device, 4 words): the bytes of `out` that count, S, and the two tile words.
-struct EntropyEncode {
-    EntropyStreams st;
-    const uint8_t *planes;     // the byte planes of ENTROPY_BYTES / ENTROPY_BITS streams (RULE P), or nullptr
-    const uint8_t *occupancy, *tiles;
-    const uint32_t *colours, *tile_stats;
-    uint64_t colour_words;
-    uint32_t *hist;            // nstreams x 256, zeroed by the caller
-    uint16_t *freq;            // nstreams x 256
-    uint32_t *block_words, *block_bytes, *block_offset;   // total_blocks each
-    uint8_t *slots;            // total_blocks x ENTROPY_SLOT_BYTES: states, then the words at the END of the slot in decoder order
-    uint32_t *plan;            // nstreams x (mode, payload offset in `out`, payload bytes)
-    uint32_t *report;
-    uint8_t *out;
-    uint64_t out_capacity;
-};
-size_t entropy_encode_work_bytes(const EntropyStreams &st);
+// (EntropyStreams, EntropyEncode, EntropyDecode and the encoder's work block, stage_encode_work(): codec_stage.hpp)
 void entropy_encode(const EntropyEncode &e, hipStream_t s);
-// Decode: `in` is the packet from the word S on; per global block its offset in `in` and its size (coded streams; 0, 0 otherwise).
-// The streams go to the body the octree decoder reads: occupancy bytes, the bit-packed colour plane (through `channels`, 3 x nleaves
-// bytes), the tile plane.  status (pinned): tag << 32 | 1 a block is not intact | 2 an occupancy byte is 0 | 4 occupancy bits differ.
-struct EntropyDecode {
-    EntropyStreams st;
-    uint32_t mode[ENTROPY_STREAMS], payload_offset[ENTROPY_STREAMS], payload_bytes[ENTROPY_STREAMS], children[ENTROPY_STREAMS];
-    const uint8_t *in;
-    const uint32_t *block_at;   // 2 x total_blocks: offset, bytes
-    uint8_t *planes;            // where ENTROPY_BYTES / ENTROPY_BITS streams go (RULE P), or nullptr
-    uint8_t *occupancy, *tiles, *channels;
-    uint32_t *colours;          // nullptr: no colour plane is packed (RULE P's streams)
-    uint64_t colour_words;
-    uint32_t *flags;            // 1 + nstreams words, zeroed by the caller
-};
 void entropy_decode(const EntropyDecode &d, unsigned long long *status_host, uint32_t tag, hipStream_t s);
 
 // ---- kernels_transform.hip: transform colour coding (RULE T: hip_ext.h; the arithmetic: transform_terms.hpp) ----
-// One packet's tree with the nodes numbered across depths (transform_terms.hpp): inner node i is occupancy byte i, the leaves are
-// the numbers inner .. inner + nleaves - 1.  Depth L's parents are depth_begin[L] .. + depth_count[L].
-struct TransformTree {
-    int bits;
-    uint32_t nleaves, inner;
-    uint32_t depth_begin[16], depth_count[16];
-    uint32_t q16[3], leaf_step[3];   // per channel: the scale, and the step of a butterfly of two leaves
-    const uint8_t *occupancy;        // inner bytes
-    uint32_t *first, *weight;        // inner words each: an inner node's first child, and the leaves beneath it
-    int32_t *value;                  // 3 planes of inner + nleaves
-    uint32_t *zz;                    // 3 planes of nleaves - 1: the zigzag values in coefficient order
-    uint32_t *scan;                  // transform_scan_words() words
-};
+// (TransformTree and its planes' layout, stage_tree_planes(): codec_stage.hpp)
 size_t transform_scan_words(const TransformTree &t);
 // the planes' fields from the header's counts and the quality's scale
 void transform_tree_counts(TransformTree &t, int bits, const uint32_t *nodes, uint32_t nleaves, uint32_t q16);

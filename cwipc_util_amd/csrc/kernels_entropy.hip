@@ -279,11 +279,6 @@ __global__ void __launch_bounds__(EB) entropy_gather_kernel(EntropyEncode e) {
     }
 }
 
-size_t entropy_encode_work_bytes(const EntropyStreams &st) {
-    const size_t S = (size_t)(st.nstreams ? st.nstreams : 1), nb = st.total_blocks ? st.total_blocks : 1;
-    return S * 256 * 4 + S * 256 * 2 + 3 * nb * 4 + S * 12 + 64 + nb * ENTROPY_SLOT_BYTES + 1024;
-}
-
 void entropy_encode(const EntropyEncode &e, hipStream_t s) {
     if (!e.st.nstreams || !e.st.total_blocks) return;
     CW_LAUNCH("entropy_hist", entropy_hist_kernel, dim3(e.st.total_blocks), dim3(EB), 0, s, e);

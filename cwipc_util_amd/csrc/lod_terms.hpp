@@ -1,5 +1,5 @@
 // lod_terms.hpp -- the arithmetic of RULE L, level-of-detail cuts of octree packets (the rule in full: hip_ext.h; its numpy
-// restatement: tests/lod_model.py).  Compiles for host and device: kernels_lod.hip, codec.cpp and the stand-alone host program of the
+// restatement: tests/lod_model.py).  Compiles for host and device: kernels_lod.hip, the codec_*.cpp files and the stand-alone host program of the
 // tests (tests/abi/lod_host.cpp) include this one text.  Integers only.  The host half (lod_cut, lod_convert) is the twin of the
 // kernels: it makes the packet L(P, t); the decoder's kernels make the cloud that decoding that packet gives.
 #pragma once

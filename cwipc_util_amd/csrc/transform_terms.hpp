@@ -3,7 +3,7 @@
 // codec_terms.hpp): the same header, occupancy and tiles, and the colours that the integer transform gives back.  The transform is a
 // weighted Haar lifting up the octree (RAHT with integer steps), exactly invertible at Q16 == 16; its quantised coefficients travel as
 // byte tokens and u16 escapes through RULE E's container (entropy_terms.hpp).  Compiles for host and device: kernels_transform.hip,
-// codec.cpp and the stand-alone host program of the tests (tests/abi/transform_host.cpp) include this one text.  Integers only.
+// the codec_*.cpp files and the stand-alone host program of the tests (tests/abi/transform_host.cpp) include this one text.  Integers only.
 //
 // Nodes are numbered across depths: the root is 0, the nodes of a depth follow those of the depth above in ascending prefix order, so
 // an inner node's number is the index of its occupancy byte, its children are 1 + (the occupancy bits in front of that byte) onwards,

@@ -712,7 +712,7 @@ _CWIPC_UTIL_EXPORT const double *cwipc_hip_rgbd_rig_ray_table(const cwipc_hip_rg
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_map2d3d(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int d, float out[3]);
 _CWIPC_UTIL_EXPORT int cwipc_hip_rgbd_rig_mapcolordepth(const cwipc_hip_rgbd_rig *rig, int cam, int u, int v, int out[2]);
 
-/* ---- the octree codec: encoder, encoder group, decoder (csrc/codec.cpp, csrc/kernels_codec.hip) ----
+/* ---- the octree codec: encoder, encoder group, decoder (csrc/codec_encode.cpp, codec_decode.cpp, codec_host.cpp; csrc/kernels_codec.hip) ----
  * The packets of this codec are NOT interoperable with cwipc_codec: the interface is the reference's (cwipc_new_encoder,
  * cwipc_new_encodergroup, cwipc_new_decoder as python/cwipc/net/sink_encoder.py and source_decoder.py use them), the bitstream is
  * this library's own and carries its own magic.  Out of scope: cwipc_codec's bitstream, JPEG colour coding,
