@@ -1,6 +1,7 @@
 """RULE L's host code (csrc/lod_terms.hpp: the packet function of "cwao" and "cwae" packets) compiled as a stand-alone program
 (tests/abi/lod_host.cpp, its own main) with -fsanitize=address,undefined -fno-sanitize-recover=all and held to the numpy model
-(tests/lod_model.py) as raw bytes.  Every damaged packet must be refused with a message and with the sanitizers silent.  The same
+(tests/lod_model.py) as raw bytes.  Every damaged packet must be refused with a message and with the sanitizers silent; the trees of
+tests/tree_cases.py (runs of chosen lengths and places, exact halves of the mean) are cut here as the model cuts them.  The same
 packets then go through the built library's host entry in Python, unsanitised.  CPU only."""
 import os
 import shutil
@@ -137,3 +138,36 @@ def test_host_entry_of_the_built_library(cwipc, packets, damaged):
         with pytest.raises(cwipc.CwipcError) as err:
             codec.lod(data, 1)
         assert len(str(err.value)) > 0, what
+
+
+# ---------------------------------------------------------------------------
+# the trees of tests/tree_cases.py: runs of chosen lengths and places, exact halves, every colour width
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def tree_cuts():
+    """[(name, t, P, em.pack(P), the model's cut)] of every cut of the table that lies inside its packet."""
+    import tree_cases
+    coded = {}
+    out = []
+    for name, t in tree_cases.lod_runs():
+        case = tree_cases.cases()[name]
+        if t <= case.octree_bits:
+            if name not in coded:
+                coded[name] = em.pack(case.packet)
+            out.append((name, t, case.packet, coded[name], lm.lod(case.packet, t)))
+    return out
+
+
+def test_every_tree_case_is_cut_as_the_model_cuts_it(host, tree_cuts):
+    assert len(tree_cuts) > 60
+    for (name, t, _, _, cut), (ok, got) in zip(tree_cuts, host([(t, P) for _, t, P, _, _ in tree_cuts])):
+        assert ok and got == cut, (name, t, got if not ok else "bytes differ")
+    for (name, t, _, _, cut), (ok, got) in zip(tree_cuts, host([(t, E) for _, t, _, E, _ in tree_cuts])):
+        assert ok and got == em.pack(cut), (name, t, got if not ok else "bytes differ")
+
+
+def test_host_entry_of_the_built_library_on_the_tree_cases(cwipc, tree_cuts):
+    import cwipc_util_amd.codec as codec
+    for name, t, P, E, cut in tree_cuts:
+        assert bytes(codec.lod(P, t)) == cut, (name, t)
+        assert bytes(codec.lod(E, t)) == em.pack(cut), (name, t)

@@ -2,7 +2,8 @@
 packets) compiled as a stand-alone program (tests/abi/transform_host.cpp, its own main) with -fsanitize=address,undefined
 -fno-sanitize-recover=all and held to the numpy model (tests/transform_model.py) as raw bytes.  The validator must refuse every
 single-field damage of three packets, and unpack every payload damage that the validator lets through, with a message or a result
-and with the sanitizers silent.  The same packets then go through the built library's host entries in Python, unsanitised.  CPU only."""
+and with the sanitizers silent.  The trees of tests/tree_cases.py (chosen leaf keys; hostile but valid packets) are packed and
+unpacked here before any kernel sees them.  The same packets then go through the built library's host entries in Python, unsanitised.  CPU only."""
 import os
 import shutil
 import struct
@@ -205,3 +206,48 @@ def test_library_entries_refuse_the_damages(codec):
             else:
                 with pytest.raises(CwipcError, match="cwipc_hip_codec_transform_unpack"):
                     codec.transform_unpack(data)
+
+
+# ---------------------------------------------------------------------------
+# the trees of tests/tree_cases.py: chosen leaf keys, and the hostile packets before any kernel sees them
+# ---------------------------------------------------------------------------
+def tree_models():
+    """[(name, quality, P, tm.pack(P, quality))] of every transform run of the table, made once."""
+    import tree_cases
+    if not _tree_models:
+        _tree_models.extend((name, q, tree_cases.cases()[name].packet, tm.pack(tree_cases.cases()[name].packet, q)) for name, q in tree_cases.transform_runs())
+    return _tree_models
+
+
+_tree_models = []
+
+
+def test_every_tree_case_packs_and_unpacks_as_the_model(host):
+    runs = tree_models()
+    packed = results(host("pack", b"".join(struct.pack("<I", q) + framed(P) for _, q, P, _ in runs)), len(runs))
+    for (name, q, _, T), (ok, got) in zip(runs, packed):
+        assert ok and got == T, (name, q)
+    unpacked = results(host("unpack", framed(*[T for _, _, _, T in runs])), len(runs))
+    for (name, q, P, T), (ok, got) in zip(runs, unpacked):
+        assert ok and got == tm.unpack(T), (name, q)
+        if q == 100:
+            assert got == P, name
+
+
+def test_hostile_packets_are_answered_in_bounds(host):
+    import tree_cases
+    packets = tree_cases.hostile()
+    got = results(host("unpack", framed(*packets.values())), len(packets))
+    for (name, T), (ok, answer) in zip(packets.items(), got):
+        assert ok and answer == tm.unpack(T), name
+    assert host("validate", framed(*packets.values()))[0] == 1
+
+
+def test_library_entries_equal_the_model_on_the_tree_cases(codec):
+    import tree_cases
+    for name, q, P, T in tree_models():
+        assert bytes(codec.transform_pack(P, q)) == T, (name, q)
+        assert bytes(codec.transform_unpack(T)) == tm.unpack(T), (name, q)
+    for name, T in tree_cases.hostile().items():
+        assert bytes(codec.transform_unpack(T)) == tm.unpack(T), name
+        assert codec.transform_info(T)["nescapes"] == [tm.parse(T)["nleaves"] - 1] * 3
