@@ -33,6 +33,7 @@ SOURCES = [
     "registration.cpp",
     "render.cpp",
     "rgbd.cpp",
+    "rgbd_rig.cpp",
     "codec_encode.cpp",
     "codec_decode.cpp",
     "codec_host.cpp",

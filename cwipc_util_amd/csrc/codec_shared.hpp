@@ -1,35 +1,17 @@
 // codec_shared.hpp -- what the octree codec's encoder (codec_encode.cpp), decoder (codec_decode.cpp) and host entry points
-// (codec_host.cpp) share on the host: the C boundary's guards, the holders that give device blocks and a coded packet's upload back
-// on every exit, and RULE P's reference on the device.  (The staging arithmetic: codec_stage.hpp, through internal.hpp.)
+// (codec_host.cpp) share on the host: the holders that give device blocks and a coded packet's upload back on every exit, and RULE P's
+// reference on the device.  (The staging arithmetic: codec_stage.hpp, through internal.hpp; the C boundary's guards: c_boundary.hpp.)
 #pragma once
 
 #include "internal.hpp"   // (with codec_stage.hpp and, through it, the terms headers of RULE C, E, P and T)
+#include "c_boundary.hpp"   // (ErrorbufScope, guarded())
 #include "lod_terms.hpp"
 
 #include <deque>
-#include <exception>
 
 namespace cwipc_amd {
 
 inline size_t round256(size_t n) { return stage_round256(n); }
-
-struct ErrorbufScope {
-    explicit ErrorbufScope(char **errorMessage) { cwipc_log_set_errorbuf(errorMessage); }
-    ~ErrorbufScope() { cwipc_log_set_errorbuf(nullptr); }
-};
-
-// No exception crosses the C boundary: what the standard library throws in a call's body (memory) is logged and becomes its error value.
-template <typename T, typename Body>
-T guarded(const char *who, T failed, Body &&body) {
-    try {
-        return body();
-    } catch (const std::exception &e) {
-        note_error(who, e.what());
-    } catch (...) {
-        note_error(who, "unknown exception");
-    }
-    return failed;
-}
 
 // an event has come (wait: wait for it)
 inline bool event_done(hipEvent_t ev, bool wait) {

@@ -15,7 +15,11 @@
 //   codec_host.cpp    the codec's entry points that never touch the GPU: packet information and the host conversions
 //   codec_stage.hpp   the structs the codec's kernels are handed and the staging arithmetic that fills them (free of HIP)
 //   codec_shared.hpp  what the encoder and the decoder share on the host
-//   rgbd.cpp        cwipc_hip_from_rgbd, cwipc_hip_rgbd_rig_*: the RGB-D source end (images in, device-resident cloud out)
+//   c_boundary.hpp    the guards of the C boundary that the codec's and the RGB-D source's entries share
+//   rgbd.cpp        cwipc_hip_from_rgbd and its two mappings: the RGB-D source end for aligned images (images in, device-resident cloud out)
+//   rgbd_rig.cpp    cwipc_hip_rgbd_rig_*: the same for raw sensor pairs, a rig's create, grabs, history and queries
+//   rgbd_stage.hpp  the structs the RGB-D kernels are handed, the refusals, a grab's plan and every device block's carve (free of HIP)
+//   rgbd_shared.hpp what rgbd.cpp and rgbd_rig.cpp share on the host: uploads, the finished cloud, the attached images
 //   kernels_*.hip   the HIP kernels (gfx950)
 #pragma once
 
@@ -33,12 +37,9 @@
 
 #include "cwipc_util/api.h"
 #include "cwipc_util_amd/hip_ext.h"
-#include "rgbd_terms.hpp"
-#include "rgbd_lens.hpp"
-#include "rgbd_depthfilter.hpp"
-#include "rgbd_decimate.hpp"
 #include "pinned_report.hpp"
 #include "codec_stage.hpp"
+#include "rgbd_stage.hpp"   // (with the four RGB-D terms headers)
 
 // ---------------------------------------------------------------------------
 // logging (reference include/cwipc_util/internal/logging.hpp:11-21)
@@ -489,15 +490,7 @@ MarkerWorkspace marker_launch(const uint8_t *dev_rgb, int width, int height, con
 void marker_labels_out(const uint32_t *label, size_t npix, int32_t *out, hipStream_t s);
 
 // ---- kernels_rgbd.hip: cwipc_hip_from_rgbd (the contract is in rgbd_terms.hpp and hip_ext.h) ----
-// One camera of a frame as the kernels see it; the cameras' pixels are numbered through, camera after camera, row-major: `first` is
-// the number of this camera's pixel (0, 0).  depth and colour are device memory; colour is 4-byte aligned with at least 8 readable
-// bytes behind its last pixel.
-struct RgbdCamDev {
-    RgbdCamTerms t;
-    const uint16_t *depth;
-    const uint8_t *colour;
-    uint32_t width, bpp, tile, first;
-};
+// (RgbdCamDev, one camera of a frame as the kernels see it: rgbd_stage.hpp)
 size_t rgbd_blocks(uint32_t total_pixels);
 // Pass 1: per workgroup the number of pixels that give a point, then the exclusive scan of those: counts (rgbd_blocks() + 1 device
 // words) ends up holding offsets and the total, which also goes to *total_host (pinned) below `tag`.  Frames of up to 256 k pixels:
@@ -508,25 +501,7 @@ void rgbd_count(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const R
 void rgbd_scatter(const RgbdCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,
                   hipStream_t s);
 // ---- the raw entry, cwipc_hip_rgbd_rig_grab (the contract is in rgbd_lens.hpp and hip_ext.h) ----
-// One camera of a rig.  The RgbdCamDev part is the camera as count and scatter see it once the registration has run: depth is the
-// (eroded, cleared) depth image, colour the REGISTERED image on the depth grid, bpp 3.  depth_rw and registered are those two again,
-// to write through.  rays: the ray table (2 doubles per depth pixel), nullptr for a sensor without depth lens coefficients.
-// raw_colour: the colour image as the camera sent it (raw_bpp bytes per pixel, ct.width x ct.height, 4-byte aligned, 8 readable
-// bytes behind it).  The validity words of the erosion: wpr words per row, this camera's first is number wfirst.  The occlusion
-// test's z-buffer: one word per colour pixel, row-major, this camera's first is number zfirst.  A decimated rig (rgbd_decimate.hpp): all
-// of the above is on the decimated grid; full_depth is the depth image as the sensor delivers it, full_width pixels wide, 16-byte
-// aligned with readable bytes up to the next 16-byte boundary behind it; nullptr without decimation.
-struct RgbdRawCamDev : RgbdCamDev {
-    uint16_t *depth_rw;
-    uint8_t *registered;
-    const double *rays;
-    const uint8_t *raw_colour;
-    RgbdColourTerms ct;
-    uint32_t raw_bpp, height, wpr, wfirst;
-    size_t zfirst;
-    const uint16_t *full_depth;
-    uint32_t full_width;
-};
+// (RgbdRawCamDev, one camera of a rig: rgbd_stage.hpp)
 void rgbd_count(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, uint32_t *counts, uint32_t *ticket,
                 unsigned long long *total_host, uint32_t tag, hipStream_t s);
 void rgbd_scatter(const RgbdRawCamDev *cams, int ncam, uint32_t total_pixels, const RgbdFilterTerms &f, const uint32_t *offsets, const DeviceSoA &dst,

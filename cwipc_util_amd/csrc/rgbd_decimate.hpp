@@ -1,7 +1,7 @@
 // rgbd_decimate.hpp -- the arithmetic of the raw entry's depth decimation (cwipc_hip_rgbd_rig_create_decimated) and hole filling
 // (cwipc_hip_rgbd_rig_grab_filled), DESIGN 3.23: the derived sensor of a decimated rig, the value of a decimated pixel from the k * k
 // source pixels of its block, the fill operator of mode 1 and the pick of modes 2 and 3.  No HIP type: kernels_rgbd.hip includes it for
-// the device, rgbd.cpp for the derived sensors, and a host test (tests/test_rgbd_decimate_host.py, through
+// the device, rgbd_stage.hpp for the derived sensors, and a host test (tests/test_rgbd_decimate_host.py, through
 // tests/abi/rgbd_decimate_host.cpp) compiles the same text with the host C++ compiler.  tests/rgbd_decimate_model.py is its numpy
 // statement.
 //
@@ -102,7 +102,7 @@ CWIPC_HOST_DEVICE CWIPC_FORCEINLINE uint16_t rgbd_block_value(const uint16_t (&v
     }
 }
 
-// Decimated pixel (U, V) of a source image `width` wide (host side: rgbd.cpp has no use for it, the test program has).
+// Decimated pixel (U, V) of a source image `width` wide (host side: rgbd_rig.cpp has no use for it, the test program has).
 template <int K>
 inline uint16_t rgbd_decimated_pixel(const uint16_t *src, size_t width, size_t U, size_t V) {
     uint16_t v[K * K];

@@ -1,6 +1,6 @@
 // rgbd_lens.hpp -- the arithmetic of the RGB-D source's RAW entry (cwipc_hip_rgbd_rig_grab): lens distortion, the depth
 // camera's ray table, the projection of a depth pixel's point into the colour camera, and the erosion rule.  No HIP type:
-// kernels_rgbd.hip includes it for the device, rgbd.cpp for the ray tables and the host mappings, and a host test
+// kernels_rgbd.hip includes it for the device, rgbd_rig.cpp for the ray tables and the host mappings, and a host test
 // (tests/test_rgbd_lens_host.py, through tests/abi/rgbd_lens_host.cpp) compiles the same text with the host C++ compiler.
 // tests/rgbd_lens_model.py is its numpy statement.  rgbd_terms.hpp (the world point and the four filters) is used as it is.
 //

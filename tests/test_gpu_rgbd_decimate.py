@@ -3,7 +3,7 @@ byte for byte: decimation 1 against cwipc_hip_rgbd_rig_create; a decimated rig f
 model's derived sensors and fed the model's decimated frames (tests/rgbd_decimate_model.py), through every grab entry, with the
 temporal state compared after each grab; image shapes where the decimation kernel goes wrong; the three fill modes against the model on
 rows that begin with holes, have none, and have their only depth in column 0 at the widths where the scan's chunks end; the Python
-source; the refusals.  No tolerance anywhere: clouds, attached images, ray tables and the state (doubles as bit patterns) are compared
+source; one rig whose device block has every kind of part at odd sizes, with every stage on; the refusals.  No tolerance anywhere: clouds, attached images, ray tables and the state (doubles as bit patterns) are compared
 for equality."""
 import gc
 import struct
@@ -15,7 +15,7 @@ import rgbd_decimate_model as cm
 import rgbd_lens_model as lm
 from test_gpu_rgbd import FILTERS, assert_cloud, to_filter
 from test_gpu_rgbd_depthfilter import assert_history, banded, colour_for, histories, identity_pair
-from test_gpu_rgbd_occlusion import attached, cloud_bytes, frame_structs
+from test_gpu_rgbd_occlusion import attached, cloud_bytes, frame_structs, pinhole_pair
 from test_gpu_rgbd_raw import raw_images, raw_pair
 from cwipc_util_amd.rgbd import RgbdDepthFilter, RgbdHoleFill, RgbdOcclusion, RgbdPrep, RgbdRig, RgbdRigSource, RgbdSensor
 
@@ -362,7 +362,40 @@ def test_rig_source_decimated_and_filled(gpu, raw):
     plain.free()
 
 
-# ---- 6: refusals ----
+# ---- 6: every kind of part of the rig's device block at once ----
+
+def test_every_part_of_the_rigs_block_with_every_stage_on(gpu):
+    """One decimated rig whose device block has every kind of part at odd sizes -- a ray table (camera 0's rational lens) and none
+    (camera 1's pinhole), depth planes of 33 x 22 and 65 x 4 pixels, colour images of 33 x 21 R, G, B and 64 x 48 B, G, R, A bytes,
+    registered images, full-size planes of 67 x 45 and 130 x 9 -- and two consecutive grabs from ordinary memory with every stage on,
+    so that every part, the z-buffer, the state (read by the second grab) and the fill plane are written and read: cloud, attached
+    images and history against the models."""
+    rng = np.random.default_rng(1717)
+    intr, cintr = (117.0, 143.0, 62.4, 4.77), (57.6, 70.4, 30.7, 24.0)
+    pairs = [raw_pair(67, 45, 33, 21, 2, "odd", 3, rng), pinhole_pair(130, 9, 64, 48, intr, cintr, tile=4, serial="flat", bpp=4)]
+    sensors, models = [p[0] for p in pairs], [p[1] for p in pairs]
+    df, fill, prep, occ = RgbdDepthFilter(1, 0.5, 20.0, True, 0.4, 20.0, 3), RgbdHoleFill(2), RgbdPrep(1, 1), RgbdOcclusion(1, 0.02)
+    derived = [cm.derived_sensor(m, 2) for m in models]
+    tables = [lm.ray_table(m.width, m.height, m.fx, m.fy, m.cx, m.cy, m.coeffs) for m in derived]
+    hists = histories(derived)
+    with RgbdRig(sensors, 2) as rig:
+        assert [(g.width, g.height) for g in rig.grid_sensors] == [(33, 22), (65, 4)]
+        for n in range(2):
+            frame = [(banded(rng, s.width, s.height, 20.0, 0.3, 1500 + 10 * n), colour_for(rng, s)) for s in sensors]
+            pc, kernels = kernels_of(gpu, lambda: rig.grab(frame, to_filter(FILTERS["depth"]), prep, 30 + n, 0.25, flags_of(gpu), occ, df, fill))
+            want = cm.cloud(models, frame, 2, hists, df, 2, FILTERS["depth"], 1, 1, (1, 0.02), tables)[1]
+            assert_cloud(pc, want[0], 30 + n, 0.25)
+            assert len(want[0]) > 0 and {m.tile for m in models} == set(np.unique(want[0]['tile']).tolist())   # (both cameras give points)
+            for (rgb, depth), want_depth, want_rgb in zip(attached(pc, rig.grid_sensors), want[1], want[2]):
+                assert np.array_equal(depth, want_depth) and np.array_equal(rgb, want_rgb)
+            assert_history(rig, hists)
+            for name in ("rgbd_decimate", "rgbd_temporal", "rgbd_zsplat", "rgbd_register_occluded"):
+                assert kernels[name][1] == 1, name
+            assert kernels["rgbd_holefill_around"][1] == 2 and "rgbd_register" not in kernels
+        assert all((h.history == 3).any() for h in hists)                         # (depth in both grabs: the second one read the first one's state)
+
+
+# ---- 7: refusals ----
 
 def test_refusals_leave_nothing_behind(gpu, raw):
     sensors, _models, frames = raw
