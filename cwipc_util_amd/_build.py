@@ -49,6 +49,7 @@ SOURCES = [
     "kernels_floor.hip",
     "kernels_render.hip",
     "kernels_markers.hip",
+    "kernels_cluster.hip",
     "kernels_rgbd.hip",
     "kernels_codec.hip",
     "kernels_entropy.hip",

@@ -1,6 +1,6 @@
 // filters.cpp -- C entry points of the per-point filter hot path and their host
 // orchestration: the compaction driver, the exact filters, the join, the downsample entry, outlier removal,
-// the direction filter and normals.  Reference: src/cwipc_filters.cpp (wrapping logic, NULL/ERROR
+// the direction filter and normals, Euclidean clusters.  Reference: src/cwipc_filters.cpp (wrapping logic, NULL/ERROR
 // conventions, timestamp/cellsize propagation) -- the per-point work itself is in
 // kernels_*.hip.  There is NO CPU fallback: without a usable GPU every filter
 // logs an ERROR and returns NULL.
@@ -683,4 +683,100 @@ extern "C" int cwipc_hip_estimate_normals(cwipc_pointcloud *pc, float radius, in
     }
     pool_free(block);
     return ok ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------
+// Euclidean clusters (RULE K of hip_ext.h; no reference counterpart: PCL users know it as EuclideanClusterExtraction)
+// ---------------------------------------------------------------------------
+namespace {
+
+// the refusals that the two entries and the statistics share; the cloud's planes on success
+std::shared_ptr<DeviceSoA> cluster_input(const char *who, cwipc_pointcloud *pc, double radius, int flags, std::unique_ptr<cwipc_hip_pointcloud> &keep) {
+    if (pc == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return nullptr;
+    }
+    if (!(radius > 0.0) || !std::isfinite(radius)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "radius must be positive and finite");
+        return nullptr;
+    }
+    if ((flags & ~CWIPC_HIP_CLUSTER_SAME_TILE) != 0) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "unknown flag bits");
+        return nullptr;
+    }
+    return device_input(who, pc, keep);
+}
+
+// labels | sizes | nclusters to the host in one copy and one wait
+int clusters_to_host(const char *who, cwipc_pointcloud *pc, double radius, int flags, uint32_t *labels, uint32_t *sizes, size_t cap, uint32_t *nclusters,
+                     uint64_t *stats4) {
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = cluster_input(who, pc, radius, flags, keep);
+    if (!src) return -1;
+    const size_t n = src->npoints;
+    if ((labels || sizes) && cap < n) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "cap is smaller than the cloud");
+        return -1;
+    }
+    if (nclusters) *nclusters = 0;
+    if (stats4) stats4[0] = stats4[1] = stats4[2] = stats4[3] = 0;
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    ClusterWork w;
+    if (!cluster_work_alloc(n, w)) { pool_free(w.block); return -1; }
+    bool ok = cluster_labels(*src, radius * radius, (flags & CWIPC_HIP_CLUSTER_SAME_TILE) != 0, w, stats4 != nullptr);
+    const size_t nb = n * sizeof(uint32_t);
+    char *stage = ok ? (char *)c.staging(2 * nb + 64) : nullptr;
+    ok = ok && stage;
+    ok = ok && hipMemcpyAsync(stage, w.labels, nb, hipMemcpyDeviceToHost, c.stream) == hipSuccess &&
+         hipMemcpyAsync(stage + nb, w.sizes, nb, hipMemcpyDeviceToHost, c.stream) == hipSuccess &&
+         hipMemcpyAsync(stage + 2 * nb, w.nclusters, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess &&
+         hipMemcpyAsync(stage + 2 * nb + 8, w.stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(w.block);
+    if (!ok) return -1;
+    uint32_t C = 0;
+    memcpy(&C, stage + 2 * nb, sizeof(C));
+    if (C > n) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "inconsistent cluster count");
+        return -1;
+    }
+    if (labels) memcpy(labels, stage, nb);
+    if (sizes) memcpy(sizes, stage + nb, (size_t)C * sizeof(uint32_t));
+    if (nclusters) *nclusters = C;
+    if (stats4) memcpy(stats4, stage + 2 * nb + 8, 4 * sizeof(uint64_t));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cwipc_hip_clusters(cwipc_pointcloud *pc, double radius, int flags, uint32_t *labels, uint32_t *sizes, size_t cap, uint32_t *nclusters) {
+    return clusters_to_host("cwipc_hip_clusters", pc, radius, flags, labels, sizes, cap, nclusters, nullptr);
+}
+
+extern "C" int cwipc_hip_cluster_link_stats(cwipc_pointcloud *pc, double radius, int flags, uint64_t stats[4]) {
+    if (stats == nullptr) return -1;
+    return clusters_to_host("cwipc_hip_cluster_link_stats", pc, radius, flags, nullptr, nullptr, 0, nullptr, stats);
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_cluster_filter(cwipc_pointcloud *pc, double radius, int flags, uint64_t min_points, uint32_t max_clusters) {
+    const char *who = "cwipc_hip_cluster_filter";
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = cluster_input(who, pc, radius, flags, keep);
+    if (!src) return nullptr;
+    const size_t n = src->npoints;
+    if (n == 0) return wrap(soa_alloc(0), pc->timestamp(), pc->cellsize());
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    ClusterWork w;
+    if (!cluster_work_alloc(n, w)) { pool_free(w.block); return nullptr; }
+    std::shared_ptr<DeviceSoA> out;
+    // labels, sizes, ranking and keep flags back to back; the one wait is the compaction's, for the count that sizes the result
+    if (cluster_labels(*src, radius * radius, (flags & CWIPC_HIP_CLUSTER_SAME_TILE) != 0, w, false) && cluster_keep_flags(w, min_points, max_clusters))
+        out = sor_select(*src, w.drop, 0.5);
+    if (!out) (void)c.sync();   // kernels that write the block may still be in flight
+    pool_free(w.block);
+    if (out) out->set_tiles_from(*src);   // (a subset of the points: what could not occur still cannot)
+    return wrap(out, pc->timestamp(), pc->cellsize());
 }

@@ -344,7 +344,7 @@ void count_dealloc();
 
 // ---------------------------------------------------------------------------
 // kernel launchers (kernels_basic.hip, kernels_voxel.hip, kernels_sor.hip, kernels_direction.hip, kernels_nn.hip, kernels_kde.hip, kernels_icp.hip,
-// kernels_floor.hip, kernels_render.hip, kernels_markers.hip;
+// kernels_floor.hip, kernels_render.hip, kernels_markers.hip, kernels_cluster.hip;
 // the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
@@ -697,6 +697,26 @@ std::shared_ptr<DeviceSoA> sor_threshold_and_select(const DeviceSoA &src, const 
 constexpr int DIRECTION_MAX_NN = 128;
 bool direction_normals(const DeviceSoA &src, float radius, int max_nn, const double dir[3], double threshold, float *drop, float *normals,
                        size_t stride, uint32_t *nn_count, double *centroid_dev);
+
+// Euclidean clusters (kernels_cluster.hip; RULE K of hip_ext.h).  One pool block holds everything a call computes, n > 0 points:
+//   labels[n], sizes[n] (the first *nclusters are written), nclusters (one word), drop[n] (the keep plane of cluster_keep_flags: 0 keep,
+//   1 drop -- what sor_select takes with the threshold 0.5), stats (cluster_labels with with_stats: links seen | unions issued | parent
+//   words loaded | most loaded by one union); the rest is the kernels' own.
+struct ClusterWork {
+    void *block = nullptr;
+    size_t n = 0;
+    uint32_t *labels = nullptr, *sizes = nullptr;
+    const uint32_t *nclusters = nullptr;
+    float *drop = nullptr;
+    unsigned long long *stats = nullptr;
+    uint32_t *parent = nullptr, *root = nullptr, *rootsize = nullptr, *flag = nullptr, *number = nullptr, *state = nullptr;
+};
+bool cluster_work_alloc(size_t n, ClusterWork &w);   // false: out of memory; the caller gives w.block back to the pool
+// labels, sizes and nclusters of src (w.n == src.npoints > 0) for links with d2 < r2.  No wait behind the grid (grid_and_search's sparse
+// flow waits inside for the box and the census, as for every search).  False on failure (logged).
+bool cluster_labels(const DeviceSoA &src, double r2, bool same_tile, const ClusterWork &w, bool with_stats);
+// drop[] from the labels and sizes (RULE K's filter; max_clusters 0: no limit).  No wait.
+bool cluster_keep_flags(const ClusterWork &w, uint64_t min_points, uint32_t max_clusters);
 
 // The registration analyzer's search (kernels_nn.hip): per point of `source` the squared f64 distance to its (nth + 1)-th nearest
 // point of `reference` among those closer than max_distance (inf: no bound), +inf when there are fewer, into dev_out (source.npoints

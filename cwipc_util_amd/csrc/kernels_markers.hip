@@ -32,10 +32,11 @@
 //
 // Kernels: grey + row scan, column scan, threshold (+ union-find initialisation), merge, flatten, per-label area and bounding
 // box, candidate list, three extreme-point passes, decode (one wave per candidate).  Launches on one stream are ordered, and one
-// kernel's stores are visible to the next; inside the merge kernel, the only one in which workgroups read what others write, every
-// access to the parent array is an agent-scope atomic.
+// kernel's stores are visible to the next; inside the merge and the flatten kernel, the only ones in which workgroups read what
+// others write (the finds halve paths), every access to a dark pixel's word of the parent array is an agent-scope atomic.
 #include "internal.hpp"
 #include "block_scan.hpp"
+#include "union_find.hpp"
 
 namespace cwipc_amd {
 namespace k {
@@ -120,36 +121,16 @@ __global__ void __launch_bounds__(MBLOCK) marker_threshold_kernel(const uint8_t 
 }
 
 // ---- 3. union-find ----
-// Invariant: parent[x] <= x for every dark x, at all times.  It holds after the threshold kernel (parent[x] = x), and the only
-// store into parent is atomicMin(&parent[a], b) with b < a.  So parent values only ever decrease.
-//
-// marker_find terminates: it leaves x alone when the value read is >= x (the root, or MNONE for safety) and otherwise moves to
-// that value, which is strictly smaller; x is a non-negative integer, so at most x steps are taken, whatever other lanes store
-// meanwhile.
+// The atomic union-find of union_find.hpp (its invariant, termination and correctness arguments are written there): parent[x] <= x
+// for every dark x at all times -- it holds after the threshold kernel (parent[x] = x) -- and a light pixel's MNONE is never reached
+// from a dark one.
 __device__ inline uint32_t marker_find(uint32_t *parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p >= x) return x;
-        x = p;
-    }
+    UfDeviceAtomics at;
+    return uf_find(parent, x, at);
 }
-
-// marker_union terminates: a step either returns or replaces the larger of the pair (a, after the swap) by `old`, which the
-// atomicMin read from parent[a] and which differs from a, hence is < a by the invariant; the finds never increase a or b.  So
-// a + b strictly decreases from step to step and is bounded below by 0: no more than a + b steps, whatever other lanes do.
-// Correctness: when old != a somebody else linked a below old in the meantime.  After the atomicMin parent[a] = min(old, b):
-// a hangs below one of the two, and uniting the other two, old and b, as the next step does, keeps all three in one tree.
 __device__ inline void marker_union(uint32_t *parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = marker_find(parent, a);
-        b = marker_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(parent + a, b);
-        if (old == a) return;   // a was a root and hangs below b now
-        if (old > a) return;    // (cannot happen, by the invariant; leaving keeps the loop's bound independent of it)
-        a = old;
-    }
+    UfDeviceAtomics at;
+    (void)uf_union(parent, a, b, at);
 }
 
 __global__ void __launch_bounds__(MBLOCK) marker_merge_kernel(const uint8_t *__restrict__ dark, int width, int height, uint32_t *parent) {
@@ -163,7 +144,7 @@ __global__ void __launch_bounds__(MBLOCK) marker_merge_kernel(const uint8_t *__r
 }
 
 // label[i] = the root of i's tree, the component's smallest index (every member's chain of parents ends at the root and never
-// rises, so the root is <= every member and is a member itself).  The merge kernel is done: parent is only read here.
+// rises, so the root is <= every member and is a member itself).  The merge kernel is done: the finds here only halve paths.
 // A root's area and bounding box are set to their neutral values.
 __global__ void __launch_bounds__(MBLOCK) marker_flatten_kernel(uint32_t *parent, size_t npix, uint32_t *__restrict__ label, uint32_t *__restrict__ area,
                                                                uint32_t *__restrict__ box /* 4 planes: min c, min r, max c, max r */) {

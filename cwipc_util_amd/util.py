@@ -43,6 +43,7 @@ __all__ = [
     'cwipc_hip_profile', 'cwipc_hip_knn_mean_dist', 'cwipc_hip_from_device_aos', 'cwipc_hip_from_device_slots', 'cwipc_hip_copy_device_aos',
     'cwipc_transform', 'cwipc_offset_scale', 'cwipc_hip_flatten_y', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
+    'CWIPC_HIP_CLUSTER_SAME_TILE', 'cwipc_cluster_labels', 'cwipc_cluster_filter', 'cwipc_hip_cluster_link_stats',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde', 'NNJob', 'cwipc_hip_nn_distance_jobs', 'compact_job_rows',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
@@ -254,6 +255,9 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_knn_mean_dist': ([cwipc_pointcloud_p, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_double), _c.c_float], _c.c_int),
     'cwipc_hip_direction_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_float, _c.c_int], cwipc_pointcloud_p),
     'cwipc_hip_estimate_normals': ([cwipc_pointcloud_p, _c.c_float, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_clusters': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint32)], _c.c_int),
+    'cwipc_hip_cluster_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint32], cwipc_pointcloud_p),
+    'cwipc_hip_cluster_link_stats': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p], _c.c_int),
     'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_correspondences': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_icp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
@@ -1726,6 +1730,47 @@ def cwipc_direction_filter(pc: cwipc_pointcloud_wrapper, direction: Union[Tuple[
     assert d.shape == (3,)
     rv = cwipc_util_dll_load().cwipc_hip_direction_filter(pc.as_cwipc_p(), float(d[0]), float(d[1]), float(d[2]), float(threshold), float(radius), int(max_nn))
     return _wrap_filter_result('cwipc_hip_direction_filter', rv)
+
+
+CWIPC_HIP_CLUSTER_SAME_TILE = 1
+
+
+def cwipc_cluster_labels(pc: cwipc_pointcloud_wrapper, radius: float, same_tile: bool = False) -> Tuple[numpy.ndarray, numpy.ndarray]:
+    """Euclidean clusters of a cloud (include/cwipc_util_amd/hip_ext.h, RULE K): the connected components of "closer than radius",
+    strictly, in float64.  Returns (labels, sizes), both uint32: labels[i] is the number of point i's cluster -- clusters are numbered
+    in order of first appearance in the input -- or 0xFFFFFFFF for a point with a non-finite coordinate; sizes[c] is the point count of
+    cluster c.  same_tile: only points with equal tile bytes are linked."""
+    if pc is None:
+        raise CwipcError("cwipc_cluster_labels: NULL pointcloud")
+    n = pc.count()
+    labels = numpy.zeros(max(n, 1), dtype=numpy.uint32)
+    sizes = numpy.zeros(max(n, 1), dtype=numpy.uint32)
+    nclusters = ctypes.c_uint32(0)
+    flags = CWIPC_HIP_CLUSTER_SAME_TILE if same_tile else 0
+    rc = cwipc_util_dll_load().cwipc_hip_clusters(pc.as_cwipc_p(), float(radius), flags, labels.ctypes.data, sizes.ctypes.data, labels.size, ctypes.byref(nclusters))
+    if rc != 0:
+        raise CwipcError("cwipc_hip_clusters failed")
+    return labels[:n], sizes[:nclusters.value].copy()
+
+
+def cwipc_cluster_filter(pc: cwipc_pointcloud_wrapper, radius: float, min_points: int = 1, max_clusters: int = 0, same_tile: bool = False) -> cwipc_pointcloud_wrapper:
+    """Keep the points whose Euclidean cluster (cwipc_cluster_labels) has at least min_points points and is among the max_clusters
+    largest (0: no limit; ties go to the cluster that appears first).  Input order, colours, tiles, timestamp and cellsize are kept."""
+    if pc is None:
+        raise CwipcError("cwipc_cluster_filter: NULL pointcloud")
+    flags = CWIPC_HIP_CLUSTER_SAME_TILE if same_tile else 0
+    rv = cwipc_util_dll_load().cwipc_hip_cluster_filter(pc.as_cwipc_p(), float(radius), flags, int(min_points), int(max_clusters))
+    return _wrap_filter_result('cwipc_hip_cluster_filter', rv)
+
+
+def cwipc_hip_cluster_link_stats(pc: cwipc_pointcloud_wrapper, radius: float, same_tile: bool = False) -> Dict[str, int]:
+    """What the clusters' link kernel did on this cloud, for measurements: links seen (each unordered pair once), unions issued, parent
+    words loaded by the finds, the most loaded by one union.  The last three depend on scheduling."""
+    out = numpy.zeros(4, dtype=numpy.uint64)
+    flags = CWIPC_HIP_CLUSTER_SAME_TILE if same_tile else 0
+    if cwipc_util_dll_load().cwipc_hip_cluster_link_stats(pc.as_cwipc_p(), float(radius), flags, out.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_cluster_link_stats failed")
+    return {"links": int(out[0]), "unions": int(out[1]), "find_loads": int(out[2]), "max_loads_one_union": int(out[3])}
 
 
 def cwipc_center(pc: cwipc_pointcloud_wrapper) -> Tuple[float, float, float]:

@@ -168,6 +168,39 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_tilefilter_masked(cwipc_pointclou
  * The reference's radius and max_nn are 0.02 and 30.  NULL on error (logged), also for radius <= 0 or not finite, max_nn < 1 or > 128. */
 _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud *pc, double dx, double dy, double dz, double threshold, float radius, int max_nn);
 
+/* ---- Euclidean clusters: the connected components of "closer than radius" (what PCL users know as EuclideanClusterExtraction; no
+ * reference counterpart).  The clean-up that stands beside cwipc_remove_outliers in a chain: a density test passes a dense clump of
+ * flying pixels, a size test on its component does not.  tests/cluster_model.py is the numpy and scipy model of this text.
+ *
+ * RULE K.
+ *  Links.     Points i != j are linked iff both have three finite coordinates and d2 < r2, strictly:  dx = (double)x_i - (double)x_j,
+ *             dy, dz alike;  d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded on its own;  r2 = radius * radius in float64 --
+ *             the arithmetic and the strictness of cwipc_hip_correspondences.  Identical coordinates are linked (0 < r2).
+ *             With CWIPC_HIP_CLUSTER_SAME_TILE a link also needs equal tile bytes.
+ *  Clusters.  The connected components of that graph.  A component's ROOT is its smallest original index.  Clusters are numbered
+ *             0 .. C - 1 in ascending order of root, that is, in order of first appearance in the input.  label[i] is the number of
+ *             i's cluster, sizes[c] its point count.  A point with a non-finite coordinate has label 0xFFFFFFFF: it belongs to no
+ *             cluster and links to nothing.  Nothing in the result depends on grid layout, launch shape or scheduling.
+ *  Ranking.   Clusters are ranked by (size descending, number ascending).
+ *  Filter.    Point i is kept iff its cluster's size is at least min_points AND its cluster's rank is below max_clusters
+ *             (max_clusters == 0: no limit).  Kept points keep input order, colours, tiles; timestamp and cellsize are the input's.
+ *             Unlabelled points are dropped.  An empty cloud gives an empty cloud.
+ *  Refusals.  -1 / NULL, logged as an ERROR, before anything is launched: a NULL cloud, a radius that is NaN, infinite or <= 0, flag
+ *             bits other than the one below, a cap below the cloud's count (with labels or sizes given).
+ * The cloud is neither consumed nor changed.  Cost grows with the number of points within radius of a point: a radius beyond the
+ * whole cloud is n * n / 2 distance tests. */
+#define CWIPC_HIP_CLUSTER_SAME_TILE 1
+/* labels, sizes: host arrays of cap >= count(pc) entries, either may be NULL; the first *nclusters entries of sizes are written,
+ * *nclusters <= count(pc).  One wait.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_clusters(cwipc_pointcloud *pc, double radius, int flags, uint32_t *labels, uint32_t *sizes, size_t cap, uint32_t *nclusters);
+/* The filter.  The result is device-resident like every other filter's; the call waits once, for the count that sizes its result
+ * (clouds of 2^20 points and more: and where the point grid's sparse layout waits, as every search on it does). */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_cluster_filter(cwipc_pointcloud *pc, double radius, int flags, uint64_t min_points, uint32_t max_clusters);
+/* What the link kernel did, for measurements (the labels are computed and thrown away; the counting kernel is a variant of its own, a
+ * little slower): stats[0] links seen, each unordered pair once; [1] unions issued (links not skipped because the other end already
+ * hung under the lane's root); [2] parent words loaded by all finds; [3] the most loaded by one union.  These depend on scheduling.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_cluster_link_stats(cwipc_pointcloud *pc, double radius, int flags, uint64_t stats[4]);
+
 /* ---- floor and tile helpers of the registration pipeline (reference python/cwipc/registration/util.py:146-229) ----
  * A point is FLOOR iff (double)y < level; a NaN y is not floor.  The reference compares the float32 column with a Python scalar,
  * which numpy rounds to float32 first: the caller passes that value (the Python wrappers do).  NULL (or -1) on error (logged):
