@@ -760,6 +760,46 @@ extern "C" int cwipc_hip_cluster_link_stats(cwipc_pointcloud *pc, double radius,
     return clusters_to_host("cwipc_hip_cluster_link_stats", pc, radius, flags, nullptr, nullptr, 0, nullptr, stats);
 }
 
+// An entry for tests: the filter's ranking and keep kernels on sizes that the caller gives, as if cluster c had the one point c.
+extern "C" int cwipc_hip_cluster_rank_keep(const uint32_t *sizes, size_t nclusters, uint64_t min_points, uint32_t max_clusters, uint8_t *keep) {
+    const char *who = "cwipc_hip_cluster_rank_keep";
+    if (sizes == nullptr || keep == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL sizes or keep");
+        return -1;
+    }
+    if (nclusters >= 0xFFFFFFFFull) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "more clusters than a label can number");
+        return -1;
+    }
+    const size_t n = nclusters;
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    ClusterWork w;
+    if (!cluster_work_alloc(n, w)) { pool_free(w.block); return -1; }
+    // pinned: sizes | labels | count | drop
+    const size_t nb = n * sizeof(uint32_t);
+    char *stage = (char *)c.staging(3 * nb + 64);
+    bool ok = stage != nullptr;
+    if (ok) {
+        uint32_t *up = (uint32_t *)stage;
+        memcpy(up, sizes, nb);
+        for (size_t k = 0; k < n; k++) up[n + k] = (uint32_t)k;
+        up[2 * n] = (uint32_t)n;
+        ok = hipMemcpyAsync(w.sizes, up, nb, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+             hipMemcpyAsync(w.labels, up + n, nb, hipMemcpyHostToDevice, c.stream) == hipSuccess &&
+             hipMemcpyAsync(const_cast<uint32_t *>(w.nclusters), up + 2 * n, sizeof(uint32_t), hipMemcpyHostToDevice, c.stream) == hipSuccess;
+    }
+    ok = ok && cluster_keep_flags(w, min_points, max_clusters);
+    float *drop = ok ? (float *)(stage + 2 * nb + 64) : nullptr;
+    ok = ok && hipMemcpyAsync(drop, w.drop, n * sizeof(float), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(w.block);
+    if (!ok) return -1;
+    for (size_t k = 0; k < n; k++) keep[k] = drop[k] == 0.f ? 1 : 0;
+    return 0;
+}
+
 extern "C" cwipc_pointcloud *cwipc_hip_cluster_filter(cwipc_pointcloud *pc, double radius, int flags, uint64_t min_points, uint32_t max_clusters) {
     const char *who = "cwipc_hip_cluster_filter";
     std::unique_ptr<cwipc_hip_pointcloud> keep;

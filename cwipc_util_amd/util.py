@@ -43,7 +43,7 @@ __all__ = [
     'cwipc_hip_profile', 'cwipc_hip_knn_mean_dist', 'cwipc_hip_from_device_aos', 'cwipc_hip_from_device_slots', 'cwipc_hip_copy_device_aos',
     'cwipc_transform', 'cwipc_offset_scale', 'cwipc_hip_flatten_y', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
-    'CWIPC_HIP_CLUSTER_SAME_TILE', 'cwipc_cluster_labels', 'cwipc_cluster_filter', 'cwipc_hip_cluster_link_stats',
+    'CWIPC_HIP_CLUSTER_SAME_TILE', 'cwipc_cluster_labels', 'cwipc_cluster_filter', 'cwipc_hip_cluster_link_stats', 'cwipc_hip_cluster_rank_keep',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde', 'NNJob', 'cwipc_hip_nn_distance_jobs', 'compact_job_rows',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
@@ -258,6 +258,7 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_clusters': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_uint32)], _c.c_int),
     'cwipc_hip_cluster_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint32], cwipc_pointcloud_p),
     'cwipc_hip_cluster_link_stats': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p], _c.c_int),
+    'cwipc_hip_cluster_rank_keep': ([_c.c_void_p, _c.c_size_t, _c.c_uint64, _c.c_uint32, _c.c_void_p], _c.c_int),
     'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_correspondences': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_icp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
@@ -1771,6 +1772,18 @@ def cwipc_hip_cluster_link_stats(pc: cwipc_pointcloud_wrapper, radius: float, sa
     if cwipc_util_dll_load().cwipc_hip_cluster_link_stats(pc.as_cwipc_p(), float(radius), flags, out.ctypes.data) != 0:
         raise CwipcError("cwipc_hip_cluster_link_stats failed")
     return {"links": int(out[0]), "unions": int(out[1]), "find_loads": int(out[2]), "max_loads_one_union": int(out[3])}
+
+
+def cwipc_hip_cluster_rank_keep(sizes, min_points: int = 1, max_clusters: int = 0) -> numpy.ndarray:
+    """An entry for tests: the cluster filter's ranking and keep kernels on cluster sizes that the caller gives (uint32, any values).
+    Returns a bool array, keep[c]: sizes[c] >= min_points and cluster c among the max_clusters largest (0: no limit; ties go to the
+    lower number)."""
+    sizes = numpy.ascontiguousarray(sizes, dtype=numpy.uint32).reshape(-1)
+    keep = numpy.zeros(max(sizes.size, 1), dtype=numpy.uint8)
+    probe = sizes if sizes.size else numpy.zeros(1, dtype=numpy.uint32)
+    if cwipc_util_dll_load().cwipc_hip_cluster_rank_keep(probe.ctypes.data, sizes.size, int(min_points), int(max_clusters), keep.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_cluster_rank_keep failed")
+    return keep[:sizes.size].astype(bool)
 
 
 def cwipc_center(pc: cwipc_pointcloud_wrapper) -> Tuple[float, float, float]:

@@ -175,7 +175,9 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_direction_filter(cwipc_pointcloud
  * RULE K.
  *  Links.     Points i != j are linked iff both have three finite coordinates and d2 < r2, strictly:  dx = (double)x_i - (double)x_j,
  *             dy, dz alike;  d2 = (dx*dx + dy*dy) + dz*dz, every operation rounded on its own;  r2 = radius * radius in float64 --
- *             the arithmetic and the strictness of cwipc_hip_correspondences.  Identical coordinates are linked (0 < r2).
+ *             the arithmetic and the strictness of cwipc_hip_correspondences.  Identical coordinates are linked whenever r2 > 0 (d2 = 0 < r2);
+ *             a radius below about 1.5e-162 is accepted, squares to r2 = 0 and links nothing, not even identical coordinates.
+ *             A radius above about 1.3e154 squares to r2 = inf and links every pair of finite points.
  *             With CWIPC_HIP_CLUSTER_SAME_TILE a link also needs equal tile bytes.
  *  Clusters.  The connected components of that graph.  A component's ROOT is its smallest original index.  Clusters are numbered
  *             0 .. C - 1 in ascending order of root, that is, in order of first appearance in the input.  label[i] is the number of
@@ -200,6 +202,12 @@ _CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_cluster_filter(cwipc_pointcloud *
  * little slower): stats[0] links seen, each unordered pair once; [1] unions issued (links not skipped because the other end already
  * hung under the lane's root); [2] parent words loaded by all finds; [3] the most loaded by one union.  These depend on scheduling.  0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_cluster_link_stats(cwipc_pointcloud *pc, double radius, int flags, uint64_t stats[4]);
+/* An entry for tests: RULE K's Ranking and Filter on sizes that the caller gives -- a cluster of 2^24 points needs a cloud of 16 M
+ * points, a size word of 2^24 does not.  The filter's own ranking and keep kernels run as if cluster c consisted of the one point c:
+ * keep[c] = 1 iff sizes[c] >= min_points AND c's rank is below max_clusters (0: no limit), else 0.  A size of 0, which no cloud
+ * produces, ranks last like any other value.  One wait.  0 ok; nclusters == 0 is ok and writes nothing; -1 (logged) for a NULL
+ * pointer or nclusters >= 2^32 - 1. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_cluster_rank_keep(const uint32_t *sizes, size_t nclusters, uint64_t min_points, uint32_t max_clusters, uint8_t *keep);
 
 /* ---- floor and tile helpers of the registration pipeline (reference python/cwipc/registration/util.py:146-229) ----
  * A point is FLOOR iff (double)y < level; a NaN y is not floor.  The reference compares the float32 column with a Python scalar,

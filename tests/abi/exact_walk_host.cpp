@@ -1,6 +1,6 @@
 // exact_walk_host.cpp -- the exact grid walk (csrc/exact_walk.hpp: cell_of, GridRows<SPARSE>::range, walk_exact) as a stand-alone
 // host program, for tests/test_exact_walk_host.py (built with -ffp-contract=off -fsanitize=address,undefined).
-//   exact_walk_host CASE OUT dense|sparse nearest|kth WANT
+//   exact_walk_host CASE OUT dense|sparse nearest|kth|within WANT
 // CASE (little endian):
 //   int32 x 8     'XWLK', points, queries, dim[0], dim[1], dim[2], 0, 0
 //   float x 4     mn[0..2], 0
@@ -18,9 +18,13 @@
 //   nearest icp_correspond_kernel's cell (floor of the f64 value, clamped before the conversion) and candidate rule: d2 < max2,
 //           the smaller d2 wins, equal d2 goes to the smaller original index
 //   kth     nn_distance2_kernel's cell (cell_coord of the float) and sorted list of 2, 4 or 32 for WANT = nth + 1
+//   within  cluster_link_kernel's cell (cell_coord of the float), the CONSTANT limit() = max2 and its candidate rule d2 < max2: every
+//           candidate under the limit is taken, not the best one (WANT is read and ignored)
 // OUT:
 //   points  x 4   uint32 original index of sorted[e]
 //   queries x 16  uint32 answer's index (0xFFFFFFFF: none; kth: 0), uint32 scans of this query, double answer (d2; inf: none)
+//                 within: uint32 candidates taken, uint32 scans, uint32 sum (mod 2^32) and uint32 xor of their original indices --
+//                 a range scanned twice, which the walk promises not to do, shows in the count
 //   scans   x 16  uint32 first, uint32 last, double limit() at the scan's entry -- all queries' scans, in order
 #include "exact_walk.hpp"
 
@@ -191,8 +195,42 @@ void run_kth(const Case &cs, const GridRows<SPARSE> &rows, const Cells &cells, i
 }
 
 template <bool SPARSE>
-void run(const Case &cs, const GridRows<SPARSE> &rows, const Cells &cells, bool nearest, int want, Out &out) {
-    if (nearest) run_nearest(cs, rows, cells, out);
+void run_within(const Case &cs, const GridRows<SPARSE> &rows, const Cells &cells, Out &out) {
+    const Grid &g = rows.g;
+    const Point *sorted = cells.sorted.data();
+    for (size_t qi = 0; qi < cs.max2.size(); qi++) {
+        const float qf[3] = {(float)cs.q[3 * qi], (float)cs.q[3 * qi + 1], (float)cs.q[3 * qi + 2]};
+        const double q[3] = {(double)qf[0], (double)qf[1], (double)qf[2]};
+        const double max2 = cs.max2[qi];
+        const int c[3] = {cell_coord(g, qf[0], 0), cell_coord(g, qf[1], 1), cell_coord(g, qf[2], 2)};
+        uint32_t taken = 0, sum = 0, x = 0, nscan = 0;
+        auto limit = [&]() { return max2; };
+        auto scan = [&](uint32_t first, uint32_t last) {
+            out.scans.push_back(ScanRec{first, last, limit()});
+            nscan++;
+            for (uint32_t e = first; e < last; e++) {
+                const Point &p = sorted[e];
+                const double dx = q[0] - (double)p.x, dy = q[1] - (double)p.y, dz = q[2] - (double)p.z;
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                if (!(d2 < max2)) continue;
+                taken++;
+                sum += p.id;
+                x ^= p.id;
+            }
+        };
+        walk_exact(rows, q, c, limit, scan);
+        Answer a{taken, nscan, 0.0};
+        const uint32_t words[2] = {sum, x};
+        memcpy(&a.d2, words, sizeof(words));
+        out.answers.push_back(a);
+    }
+}
+
+template <bool SPARSE>
+void run(const Case &cs, const GridRows<SPARSE> &rows, const Cells &cells, const char *kind, int want, Out &out) {
+    const bool nearest = !strcmp(kind, "nearest");
+    if (!strcmp(kind, "within")) run_within(cs, rows, cells, out);
+    else if (nearest) run_nearest(cs, rows, cells, out);
     else if (want <= 2) run_kth<2>(cs, rows, cells, want, out);
     else if (want <= 4) run_kth<4>(cs, rows, cells, want, out);
     else run_kth<32>(cs, rows, cells, want, out);
@@ -201,10 +239,10 @@ void run(const Case &cs, const GridRows<SPARSE> &rows, const Cells &cells, bool 
 }  // namespace
 
 int main(int argc, char **argv) {
-    const bool usage = argc == 6 && (!strcmp(argv[3], "dense") || !strcmp(argv[3], "sparse")) && (!strcmp(argv[4], "nearest") || !strcmp(argv[4], "kth"));
+    const bool usage = argc == 6 && (!strcmp(argv[3], "dense") || !strcmp(argv[3], "sparse")) && (!strcmp(argv[4], "nearest") || !strcmp(argv[4], "kth") || !strcmp(argv[4], "within"));
     const int want = usage ? atoi(argv[5]) : 0;
     if (!usage || want < 1 || want > 32) {
-        fprintf(stderr, "usage: exact_walk_host CASE OUT dense|sparse nearest|kth WANT(1..32)\n");
+        fprintf(stderr, "usage: exact_walk_host CASE OUT dense|sparse nearest|kth|within WANT(1..32)\n");
         return 2;
     }
     Case cs;
@@ -212,19 +250,19 @@ int main(int argc, char **argv) {
         fprintf(stderr, "exact_walk_host: cannot read the case %s\n", argv[1]);
         return 2;
     }
-    const bool sparse = !strcmp(argv[3], "sparse"), nearest = !strcmp(argv[4], "nearest");
+    const bool sparse = !strcmp(argv[3], "sparse");
     Cells cells;
     Out out;
     if (sparse) {
         build_sparse(cs, cells);
         const GridRows<true> rows(cs.g, nullptr, cells.starts.data(), cells.counts.data(), nullptr);
-        run(cs, rows, cells, nearest, want, out);
+        run(cs, rows, cells, argv[4], want, out);
     } else {
         build_dense(cs, cells);
         GridMeta meta{};
         meta.g = cs.g;
         const GridRows<false> rows(Grid{}, &meta, cells.starts.data(), cells.counts.data(), nullptr);
-        run(cs, rows, cells, nearest, want, out);
+        run(cs, rows, cells, argv[4], want, out);
     }
     FILE *f = fopen(argv[2], "wb");
     if (!f) return 3;

@@ -72,10 +72,10 @@ def test_new_symbols_are_exported_bound_and_declared(cwipc):
     header = open(os.path.join(ROOT, "include", "cwipc_util_amd", "hip_ext.h")).read()
     assert "RULE K." in header
     assert "#define CWIPC_HIP_CLUSTER_SAME_TILE 1" in header and cwipc.CWIPC_HIP_CLUSTER_SAME_TILE == 1
-    for name in ("cwipc_hip_clusters", "cwipc_hip_cluster_filter", "cwipc_hip_cluster_link_stats"):
+    for name in ("cwipc_hip_clusters", "cwipc_hip_cluster_filter", "cwipc_hip_cluster_link_stats", "cwipc_hip_cluster_rank_keep"):
         assert hasattr(dll, name) and name in _SIGNATURES, name
         assert re.search(r"_CWIPC_UTIL_EXPORT[^;]*\b%s\(" % name, header), name
-    for public in ("cwipc_cluster_labels", "cwipc_cluster_filter", "cwipc_hip_cluster_link_stats", "CWIPC_HIP_CLUSTER_SAME_TILE"):
+    for public in ("cwipc_cluster_labels", "cwipc_cluster_filter", "cwipc_hip_cluster_link_stats", "cwipc_hip_cluster_rank_keep", "CWIPC_HIP_CLUSTER_SAME_TILE"):
         assert public in cwipc.util.__all__ and hasattr(cwipc, public), public
     pc_p = _SIGNATURES["cwipc_hip_direction_filter"][0][0]
     # the header's parameter lists against the wrapper's argument types
@@ -86,6 +86,9 @@ def test_new_symbols_are_exported_bound_and_declared(cwipc):
     params = re.search(r"cwipc_hip_cluster_filter\(([^)]*)\)", header).group(1)
     assert [p.strip().rsplit(" ", 1)[0] for p in params.split(",")] == ["cwipc_pointcloud", "double", "int", "uint64_t", "uint32_t"]
     assert _SIGNATURES["cwipc_hip_cluster_filter"] == ([pc_p, ctypes.c_double, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32], pc_p)
+    params = re.search(r"cwipc_hip_cluster_rank_keep\(([^)]*)\)", header).group(1)
+    assert [p.strip().rsplit(" ", 1)[0] for p in params.split(",")] == ["const uint32_t", "size_t", "uint64_t", "uint32_t", "uint8_t"]
+    assert _SIGNATURES["cwipc_hip_cluster_rank_keep"] == ([ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p], ctypes.c_int)
 
 
 def test_factory_entry(cwipc):
@@ -108,3 +111,24 @@ def test_refusals_need_no_gpu(cwipc):
     assert dll.cwipc_hip_clusters(None, 0.1, 0, labels.ctypes.data, None, 4, ctypes.byref(n)) == -1
     assert not dll.cwipc_hip_cluster_filter(None, 0.1, 0, 1, 0)
     assert dll.cwipc_hip_cluster_link_stats(None, 0.1, 0, None) == -1
+    keep = np.full(4, 7, dtype=np.uint8)
+    assert dll.cwipc_hip_cluster_rank_keep(None, 4, 1, 0, keep.ctypes.data) == -1
+    assert dll.cwipc_hip_cluster_rank_keep(labels.ctypes.data, 4, 1, 0, None) == -1
+    assert dll.cwipc_hip_cluster_rank_keep(labels.ctypes.data, 0, 1, 0, keep.ctypes.data) == 0 and np.all(keep == 7)     # no cluster: nothing written
+
+
+def test_edge_case_constructions_do_what_their_names_say():
+    """The inputs of tests/test_gpu_cluster_edges.py's three-flow cases, built and held to their purpose by the model alone: the
+    bridge of another tile cuts the chain, twins at identical coordinates fall apart by tile, the far outliers are the clusters the
+    rule's arithmetic gives, the translated cloud's coordinates tie.  A wrong generator fails here, without a GPU."""
+    import test_gpu_cluster_edges as edges
+    cases, want = edges.edge_answers()
+    assert set(cases) == set(want) and len(cases) == 19
+    assert sum(same for _, _, same in cases.values()) == 7
+
+
+def test_scale_case_is_as_large_as_its_purpose():
+    """1 061 208 points (more than 4096 workgroups of 256 hold) in more than 262 144 clusters (more than the histogram's launch holds)."""
+    import test_gpu_cluster_edges as edges
+    pts, radius, labels, sizes, _ = edges.scale_case()
+    assert len(pts) > 4096 * 256 and len(sizes) > 262144 and sizes.sum() == len(pts) and labels.max() == len(sizes) - 1

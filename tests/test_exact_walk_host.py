@@ -15,7 +15,11 @@ root of), bit for bit:
     scan's entry.  Per axis the row distance is max(gap - 2e-6 h, 0) from the cell's faces in f64: the walk states its bounds short
     by 1e-6 of a cell plus 1e-9 of themselves, which on grids of a few dozen cells is far less than another 1e-6 of a cell, so twice
     1e-6 h is derived from the walk's statement, not measured;
-  * the dense and the sparse layout walk the same elements: the two outputs are the same bytes."""
+  * the dense and the sparse layout walk the same elements: the two outputs are the same bytes.
+
+A third mode, `within`, is cluster_link_kernel's use of the walk (kernels_cluster.hip): a constant limit() = max2 and every candidate
+with d2 < max2 taken.  Per query the count, the sum and the xor of the indices taken equal brute force's (check_within, on every case
+above): a missed candidate that is not the nearest passes `nearest` and `kth`, and changes all three here."""
 import os
 import shutil
 import subprocess
@@ -30,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WANTS = (1, 2, 4, 32)
 ANSWER = np.dtype([("idx", "<u4"), ("scans", "<u4"), ("d2", "<f8")])
 SCAN = np.dtype([("first", "<u4"), ("last", "<u4"), ("limit", "<f8")])
+WITHIN = np.dtype([("count", "<u4"), ("scans", "<u4"), ("sum", "<u4"), ("xor", "<u4")])     # the `within` mode's use of an answer's 16 bytes
 
 
 class Grid:
@@ -172,6 +177,34 @@ def near_pairs(queries, ref, reach):
     return tuple(np.concatenate(v) for v in zip(*out))
 
 
+def check_within(host, grid, ref, queries, max2, seed=0):
+    """The `within` mode -- the clusters' link kernel's use of the walk: a constant limit, EVERY candidate with d2 < max2 taken --
+    against brute force in f64: per query the count, the sum and the xor of the original indices taken.  A missed candidate that is
+    not the nearest, which `nearest` and `kth` both let pass, changes all three; a range scanned twice changes the count.  Dense and
+    sparse: the same bytes.  -> the number of candidates taken"""
+    ref = np.asarray(ref, dtype=np.float32).reshape(-1, 3)
+    queries = np.asarray(queries, dtype=np.float32).reshape(-1, 3)
+    max2 = np.ascontiguousarray(np.broadcast_to(np.asarray(max2, dtype=np.float64), (len(queries),)))
+    q, r = queries.astype(np.float64), ref.astype(np.float64)
+    idx = np.arange(len(ref), dtype=np.int64)
+    count, total, xor = (np.zeros(len(q), dtype=np.int64) for _ in range(3))
+    for lo in range(0, len(q), 4096):
+        b = q[lo:lo + 4096]
+        dx, dy, dz = b[:, None, 0] - r[None, :, 0], b[:, None, 1] - r[None, :, 1], b[:, None, 2] - r[None, :, 2]
+        take = ((dx * dx + dy * dy) + dz * dz) < max2[lo:lo + 4096, None]
+        count[lo:lo + 4096] = take.sum(axis=1)
+        total[lo:lo + 4096] = (take * idx[None, :]).sum(axis=1)
+        xor[lo:lo + 4096] = np.bitwise_xor.reduce(np.where(take, idx[None, :], 0), axis=1) if len(ref) else 0
+    raw, ids, answers, scans = host(grid, ref, queries, max2, "dense", "within", seed=seed)
+    got = answers.view(WITHIN)
+    assert np.array_equal(np.sort(ids), np.arange(len(ref), dtype=np.uint32))
+    assert np.array_equal(got["count"], count), (int(np.sum(got["count"] != count)), int((got["count"].astype(np.int64) - count).max()))
+    assert np.array_equal(got["sum"], total & 0xFFFFFFFF) and np.array_equal(got["xor"], xor)
+    assert scans["limit"].tobytes() == np.repeat(max2, got["scans"].astype(np.int64)).tobytes()      # the limit never moves
+    assert host(grid, ref, queries, max2, "sparse", "within", seed=seed)[0] == raw
+    return int(count.sum())
+
+
 def check_case(host, grid, ref, queries, max2, wants=WANTS, trace_wants=WANTS, seed=0, base=None, every=1):
     """All of the module's assertions for one grid, reference, queries and bounds.  -> scanned candidates of the traced runs"""
     ref = np.asarray(ref, dtype=np.float32).reshape(-1, 3)
@@ -196,6 +229,7 @@ def check_case(host, grid, ref, queries, max2, wants=WANTS, trace_wants=WANTS, s
         if w in trace_wants:
             scanned += check_trace(grid, ref, queries, max2, ids, answers, scans, near, near_reach)
         assert host(grid, ref, queries, max2, "sparse", "kth", w, seed=seed)[0] == raw
+    check_within(host, grid, ref, queries, max2, seed=seed)
     return scanned
 
 
@@ -245,6 +279,11 @@ def test_dyadic_lattice(host, dim, duplicated, max2):
     # widths at the two ends
     scanned = check_case(host, grid, ref, queries, max2, trace_wants=WANTS if np.isfinite(max2) else (1, 32), base=base, every=16)
     print("lattice %s, %d points, %d queries: %d scanned candidates checked" % (dim, len(ref), len(queries), scanned))
+    if np.isfinite(max2):
+        # every candidate under a constant limit: at the tie distance itself (check_case above) the equally distant ones are all left
+        # out, one step above it they are all taken -- 2, 4 or 8 more per query that sits between lattice points
+        at, above = check_within(host, grid, ref, queries, max2), check_within(host, grid, ref, queries, np.nextafter(max2, 1))
+        assert above >= at + 2 * len(ref)
     # the construction: the model's answers hold ties of 2, 4 and 8 (twice that with duplicates), across faces
     if np.isinf(max2):
         r, q = ref.astype(np.float64), queries[::7].astype(np.float64)
@@ -373,3 +412,31 @@ def test_far_query_scans_the_whole_grid_once(host):
             for k in s:
                 seen[scans["first"][k]:scans["last"][k]] += 1
             assert np.all(seen == 1)
+
+
+# ---------------------------------------------------------------------------
+# every point in one cell
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", [(1, 1, 1), (7, 5, 3)], ids=["a grid of one cell", "one cell of many"])
+def test_all_points_in_a_single_cell(host, dim):
+    """What outliers do to a cloud's grid: 500 points, duplicates among them, all in ONE cell -- the grid's only cell, or cell
+    (3, 2, 1) of 7 x 5 x 3 -- queries on the points, elsewhere in the grid and outside it.  Bounds from a fraction of the cluster
+    of points to beyond the grid, the distances between chosen pairs exactly and one step above, and none."""
+    rng = np.random.default_rng(500)
+    dim = np.array(dim)
+    grid = Grid((-0.4, 0.2, 1.0), dim, 0.25)
+    cell = np.array([3, 2, 1]) if dim[0] > 1 else np.zeros(3)
+    ref = (np.float64(grid.mn) + (cell + rng.uniform(0.02, 0.98, size=(500, 3))) * grid.h).astype(np.float32)
+    ref[400:] = ref[:100]
+    for a in range(3):
+        assert np.all(grid.coord(ref[:, a], a) == cell[a])
+    queries = (np.float64(grid.mn) + rng.uniform(-0.3, 1.3, size=(900, 3)) * dim * grid.h).astype(np.float32)
+    queries[:500] = ref
+    pair = ref[rng.integers(0, 500, size=900)].astype(np.float64) - queries.astype(np.float64)
+    tie = (pair[:, 0] * pair[:, 0] + pair[:, 1] * pair[:, 1]) + pair[:, 2] * pair[:, 2]
+    bound = rng.uniform(0.05, 8.0, size=900) * grid.h
+    k = np.arange(900) % 4
+    max2 = np.where(k == 0, np.inf, np.where(k == 1, bound * bound, np.where(k == 2, tie, np.nextafter(tie, np.inf))))
+    check_case(host, grid, ref, queries, np.where(k % 2 == 0, np.inf, bound * bound), seed=int(dim[0]))   # (the models take the root of a bound)
+    taken = check_within(host, grid, ref, queries, max2, seed=int(dim[0]))
+    assert taken > 225 * 500       # (the unbounded queries alone take every point)
