@@ -50,6 +50,7 @@ SOURCES = [
     "kernels_render.hip",
     "kernels_markers.hip",
     "kernels_cluster.hip",
+    "kernels_neigh.hip",
     "kernels_rgbd.hip",
     "kernels_codec.hip",
     "kernels_entropy.hip",

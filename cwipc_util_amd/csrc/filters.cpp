@@ -1,10 +1,11 @@
 // filters.cpp -- C entry points of the per-point filter hot path and their host
 // orchestration: the compaction driver, the exact filters, the join, the downsample entry, outlier removal,
-// the direction filter and normals, Euclidean clusters.  Reference: src/cwipc_filters.cpp (wrapping logic, NULL/ERROR
+// the direction filter and normals, Euclidean clusters, fixed-radius neighbourhoods.  Reference: src/cwipc_filters.cpp (wrapping logic, NULL/ERROR
 // conventions, timestamp/cellsize propagation) -- the per-point work itself is in
 // kernels_*.hip.  There is NO CPU fallback: without a usable GPU every filter
 // logs an ERROR and returns NULL.
 #include "entry.hpp"
+#include "smooth_terms.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -819,4 +820,112 @@ extern "C" cwipc_pointcloud *cwipc_hip_cluster_filter(cwipc_pointcloud *pc, doub
     pool_free(w.block);
     if (out) out->set_tiles_from(*src);   // (a subset of the points: what could not occur still cannot)
     return wrap(out, pc->timestamp(), pc->cellsize());
+}
+
+// ---------------------------------------------------------------------------
+// Fixed-radius neighbourhoods (RULE N of hip_ext.h; no reference counterpart: PCL users know them as RadiusOutlierRemoval and
+// first-order MovingLeastSquares)
+// ---------------------------------------------------------------------------
+namespace {
+
+bool neigh_flags_ok(const char *who, int flags) {
+    if ((flags & ~CWIPC_HIP_NEIGH_SAME_TILE) == 0) return true;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "unknown flag bits");
+    return false;
+}
+
+bool smooth_radius_refused(const char *who, double radius) {
+    if (smooth_radius_ok(radius)) return false;
+    cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "radius must be finite and within [1e-30, 1e30]");
+    return true;
+}
+
+}  // namespace
+
+extern "C" int cwipc_hip_radius_counts(cwipc_pointcloud *pc, double radius, int flags, uint32_t *counts, size_t cap) {
+    const char *who = "cwipc_hip_radius_counts";
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = cluster_input(who, pc, radius, flags, keep);   // (RULE K's refusals; the flag bit is the clusters')
+    if (!src) return -1;
+    const size_t n = src->npoints;
+    if (cap < n || (n && counts == nullptr)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "cap is smaller than the cloud");
+        return -1;
+    }
+    if (n == 0) return 0;
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return -1;
+    const size_t nb = n * sizeof(uint32_t);
+    uint32_t *dev = (uint32_t *)pool_alloc(nb);
+    if (!dev) return -1;
+    bool ok = neigh_counts(*src, radius * radius, (flags & CWIPC_HIP_NEIGH_SAME_TILE) != 0, dev);
+    void *stage = ok ? c.staging(nb) : nullptr;
+    ok = ok && stage && hipMemcpyAsync(stage, dev, nb, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    ok = c.sync() && ok;
+    pool_free(dev);
+    if (!ok) return -1;
+    memcpy(counts, stage, nb);
+    return 0;
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_radius_outlier_filter(cwipc_pointcloud *pc, double radius, int flags, uint64_t min_neighbours) {
+    const char *who = "cwipc_hip_radius_outlier_filter";
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = cluster_input(who, pc, radius, flags, keep);
+    if (!src) return nullptr;
+    const size_t n = src->npoints;
+    if (n == 0) return wrap(soa_alloc(0), pc->timestamp(), pc->cellsize());
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    // one block: counts (n words) | the keep plane (n floats)
+    const size_t words = (n + 63) & ~(size_t)63;
+    uint32_t *block = (uint32_t *)pool_alloc(2 * words * sizeof(uint32_t));
+    if (!block) return nullptr;
+    float *drop = (float *)(block + words);
+    std::shared_ptr<DeviceSoA> out;
+    // counts and keep flags back to back; the one wait is the compaction's, for the count that sizes the result
+    if (neigh_counts(*src, radius * radius, (flags & CWIPC_HIP_NEIGH_SAME_TILE) != 0, block) && neigh_keep_flags(*src, block, min_neighbours, drop))
+        out = sor_select(*src, drop, 0.5);
+    if (!out) (void)c.sync();   // kernels that write the block may still be in flight
+    pool_free(block);
+    if (out) out->set_tiles_from(*src);   // (a subset of the points: what could not occur still cannot)
+    return wrap(out, pc->timestamp(), pc->cellsize());
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_smooth(cwipc_pointcloud *pc, double radius, int flags, uint32_t min_neighbours) {
+    const char *who = "cwipc_hip_smooth";
+    if (pc == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return nullptr;
+    }
+    if (smooth_radius_refused(who, radius) || !neigh_flags_ok(who, flags)) return nullptr;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input(who, pc, keep);
+    if (!src) return nullptr;
+    if (src->npoints == 0) return wrap(soa_alloc(0), pc->timestamp(), pc->cellsize());
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return nullptr;
+    auto dst = soa_with_new_xyz(src);   // colours and tiles do not change: the result holds the very same words
+    if (!dst) return nullptr;
+    if (!neigh_smooth(*src, radius, (flags & CWIPC_HIP_NEIGH_SAME_TILE) != 0, min_neighbours, *dst)) {
+        (void)c.sync();   // `dst` goes back to the pool: nothing may still be writing it
+        return nullptr;
+    }
+    // no wait: the result carries its `ready` event, the input is kept until the kernel has read it
+    dst->mark_pending(c.stream);
+    src->note_reader(c.stream);
+    dst->set_tiles_from(*src);
+    return wrap(dst, pc->timestamp(), pc->cellsize());
+}
+
+extern "C" int cwipc_hip_smooth_host(const cwipc_point *pts, size_t n, double radius, int flags, uint32_t min_neighbours, cwipc_point *out) {
+    const char *who = "cwipc_hip_smooth_host";
+    if (smooth_radius_refused(who, radius) || !neigh_flags_ok(who, flags)) return -1;
+    if (n == 0) return 0;
+    if (pts == nullptr || out == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL points");
+        return -1;
+    }
+    smooth_brute_force(pts, n, radius, (flags & CWIPC_HIP_NEIGH_SAME_TILE) != 0, min_neighbours, out);
+    return 0;
 }

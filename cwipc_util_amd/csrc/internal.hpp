@@ -718,6 +718,15 @@ bool cluster_labels(const DeviceSoA &src, double r2, bool same_tile, const Clust
 // drop[] from the labels and sizes (RULE K's filter; max_clusters 0: no limit).  No wait.
 bool cluster_keep_flags(const ClusterWork &w, uint64_t min_points, uint32_t max_clusters);
 
+// Fixed-radius neighbourhoods (kernels_neigh.hip; RULE N of hip_ext.h), src.npoints > 0.  No wait behind the grid (grid_and_search's
+// sparse flow waits inside, as for every search).  False on failure (logged).
+// counts[i] (n device words) = |N(i)| - 1, 0 for a point with a non-finite coordinate
+bool neigh_counts(const DeviceSoA &src, double r2, bool same_tile, uint32_t *counts);
+// drop[i] (n device floats) = 0 (keep) iff point i is finite and counts[i] >= min_neighbours, else 1: what sor_select takes with 0.5
+bool neigh_keep_flags(const DeviceSoA &src, const uint32_t *counts, uint64_t min_neighbours, float *drop);
+// dst's coordinate planes (dst: src's count and stride) = src smoothed; the CALLER HAS CHECKED the radius (smooth_radius_ok)
+bool neigh_smooth(const DeviceSoA &src, double radius, bool same_tile, uint32_t min_neighbours, const DeviceSoA &dst);
+
 // The registration analyzer's search (kernels_nn.hip): per point of `source` the squared f64 distance to its (nth + 1)-th nearest
 // point of `reference` among those closer than max_distance (inf: no bound), +inf when there are fewer, into dev_out (source.npoints
 // device doubles, the source's order).  No wait inside.  False on failure (logged), also for nth outside 0..NN_MAX_NTH and a

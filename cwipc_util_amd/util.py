@@ -44,6 +44,7 @@ __all__ = [
     'cwipc_transform', 'cwipc_offset_scale', 'cwipc_hip_flatten_y', 'get_tiles_used', 'cwipc_downsample_pertile', 'cwipc_hip_simulatecams', 'cwipc_hip_comm', 'cwipc_hip_comm_unique_id',
     'cwipc_direction_filter', 'cwipc_center', 'cwipc_hip_estimate_normals',
     'CWIPC_HIP_CLUSTER_SAME_TILE', 'cwipc_cluster_labels', 'cwipc_cluster_filter', 'cwipc_hip_cluster_link_stats', 'cwipc_hip_cluster_rank_keep',
+    'CWIPC_HIP_NEIGH_SAME_TILE', 'cwipc_radius_counts', 'cwipc_radius_outlier_filter', 'cwipc_smooth', 'cwipc_hip_smooth_host',
     'cwipc_hip_nn_distance', 'cwipc_hip_gaussian_kde', 'NNJob', 'cwipc_hip_nn_distance_jobs', 'compact_job_rows',
     'cwipc_hip_correspondences', 'cwipc_hip_icp_sums', 'cwipc_hip_icp_point2point', 'cwipc_hip_icp_plane_sums', 'cwipc_hip_icp_point2plane',
     'cwipc_hip_gicp_covariances', 'cwipc_hip_icp_gicp_sums', 'cwipc_hip_icp_generalized',
@@ -259,6 +260,10 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_cluster_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_uint64, _c.c_uint32], cwipc_pointcloud_p),
     'cwipc_hip_cluster_link_stats': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p], _c.c_int),
     'cwipc_hip_cluster_rank_keep': ([_c.c_void_p, _c.c_size_t, _c.c_uint64, _c.c_uint32, _c.c_void_p], _c.c_int),
+    'cwipc_hip_radius_counts': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_void_p, _c.c_size_t], _c.c_int),
+    'cwipc_hip_radius_outlier_filter': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_uint64], cwipc_pointcloud_p),
+    'cwipc_hip_smooth': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_uint32], cwipc_pointcloud_p),
+    'cwipc_hip_smooth_host': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_int, _c.c_uint32, _c.c_void_p], _c.c_int),
     'cwipc_hip_nn_distance2': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_correspondences': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_icp_sums': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
@@ -1784,6 +1789,55 @@ def cwipc_hip_cluster_rank_keep(sizes, min_points: int = 1, max_clusters: int = 
     if cwipc_util_dll_load().cwipc_hip_cluster_rank_keep(probe.ctypes.data, sizes.size, int(min_points), int(max_clusters), keep.ctypes.data) != 0:
         raise CwipcError("cwipc_hip_cluster_rank_keep failed")
     return keep[:sizes.size].astype(bool)
+
+
+CWIPC_HIP_NEIGH_SAME_TILE = 1
+
+
+def cwipc_radius_counts(pc: cwipc_pointcloud_wrapper, radius: float, same_tile: bool = False) -> numpy.ndarray:
+    """Per point, how many OTHER points lie closer than radius (include/cwipc_util_amd/hip_ext.h, RULE N: strictly, in float64); 0
+    for a point with a non-finite coordinate.  uint32.  same_tile: only points with the point's own tile byte count."""
+    if pc is None:
+        raise CwipcError("cwipc_radius_counts: NULL pointcloud")
+    n = pc.count()
+    counts = numpy.zeros(max(n, 1), dtype=numpy.uint32)
+    flags = CWIPC_HIP_NEIGH_SAME_TILE if same_tile else 0
+    if cwipc_util_dll_load().cwipc_hip_radius_counts(pc.as_cwipc_p(), float(radius), flags, counts.ctypes.data, counts.size) != 0:
+        raise CwipcError("cwipc_hip_radius_counts failed")
+    return counts[:n]
+
+
+def cwipc_radius_outlier_filter(pc: cwipc_pointcloud_wrapper, radius: float, min_neighbours: int = 1, same_tile: bool = False) -> cwipc_pointcloud_wrapper:
+    """Keep the points with at least min_neighbours other points closer than radius (cwipc_radius_counts).  Input order, colours,
+    tiles, timestamp and cellsize are kept."""
+    if pc is None:
+        raise CwipcError("cwipc_radius_outlier_filter: NULL pointcloud")
+    flags = CWIPC_HIP_NEIGH_SAME_TILE if same_tile else 0
+    rv = cwipc_util_dll_load().cwipc_hip_radius_outlier_filter(pc.as_cwipc_p(), float(radius), flags, int(min_neighbours))
+    return _wrap_filter_result('cwipc_hip_radius_outlier_filter', rv)
+
+
+def cwipc_smooth(pc: cwipc_pointcloud_wrapper, radius: float, min_neighbours: int = 2, same_tile: bool = False) -> cwipc_pointcloud_wrapper:
+    """Every point with at least max(2, min_neighbours) other points closer than radius moved onto the plane fitted to them with a
+    compact biweight (first-order moving least squares; include/cwipc_util_amd/hip_ext.h, RULE N).  No point is removed; colours,
+    tiles, order, timestamp and cellsize are kept.  The result stays on the device and is handed back with its kernel in flight."""
+    if pc is None:
+        raise CwipcError("cwipc_smooth: NULL pointcloud")
+    flags = CWIPC_HIP_NEIGH_SAME_TILE if same_tile else 0
+    rv = cwipc_util_dll_load().cwipc_hip_smooth(pc.as_cwipc_p(), float(radius), flags, int(min_neighbours))
+    return _wrap_filter_result('cwipc_hip_smooth', rv)
+
+
+def cwipc_hip_smooth_host(points: numpy.ndarray, radius: float, min_neighbours: int = 2, same_tile: bool = False) -> numpy.ndarray:
+    """The host twin of cwipc_smooth on a structured array of cwipc_point records: the same arithmetic (csrc/smooth_terms.hpp) by
+    brute force over all pairs, O(n * n), no GPU.  For tests and small clouds."""
+    points = numpy.ascontiguousarray(points, dtype=cwipc_point_numpy_dtype).reshape(-1)
+    out = numpy.zeros(max(points.size, 1), dtype=cwipc_point_numpy_dtype)
+    flags = CWIPC_HIP_NEIGH_SAME_TILE if same_tile else 0
+    probe = points if points.size else out
+    if cwipc_util_dll_load().cwipc_hip_smooth_host(probe.ctypes.data, points.size, float(radius), flags, int(min_neighbours), out.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_smooth_host failed")
+    return out[:points.size]
 
 
 def cwipc_center(pc: cwipc_pointcloud_wrapper) -> Tuple[float, float, float]:

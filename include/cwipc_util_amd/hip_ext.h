@@ -209,6 +209,50 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_cluster_link_stats(cwipc_pointcloud *pc, double
  * pointer or nclusters >= 2^32 - 1. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_cluster_rank_keep(const uint32_t *sizes, size_t nclusters, uint64_t min_points, uint32_t max_clusters, uint8_t *keep);
 
+/* ---- fixed-radius neighbourhoods: neighbour counts, radius outlier removal (what PCL users know as RadiusOutlierRemoval) and
+ * first-order moving-least-squares smoothing (PCL's MovingLeastSquares without a polynomial: each point moved onto the plane fitted
+ * to its neighbourhood); no reference counterpart.  The radius is a distance in the cloud's units, so the outlier test can be set once
+ * for a rig -- cwipc_remove_outliers removes a share of any cloud, however clean -- and smoothing removes no point at all.
+ * tests/neigh_model.py is the numpy and scipy model of this text; csrc/smooth_terms.hpp holds the per-point arithmetic of Smoothing.
+ *
+ * RULE N.
+ *  Arithmetic.     All of it float64, every operation rounded on its own; the order written here is the contract.
+ *  Neighbourhood.  r2 = radius * radius.  For points i, j with three finite coordinates each:  d_a = (double)p_j[a] - (double)p_i[a];
+ *                  d2 = (d_x*d_x + d_y*d_y) + d_z*d_z;  N(i) = { j finite : d2 < r2 }, strictly, as in RULE K; i itself is in N(i)
+ *                  whenever r2 > 0.  With CWIPC_HIP_NEIGH_SAME_TILE only j with i's tile byte belong.  A point with a non-finite
+ *                  coordinate is nobody's neighbour and has N = {}.
+ *  Counts.         count[i] = |N(i)| - 1 for a finite point, 0 for a non-finite one.  The radius at its extremes as in RULE K: r2 == 0
+ *                  gives all zeros, r2 == inf every finite point of the same tile set.
+ *  Outlier filter. Point i is kept iff it is finite and count[i] >= min_neighbours.  Kept points keep input order, colours, tiles;
+ *                  timestamp and cellsize are the input's.
+ *  Smoothing.      s = 65536.0 / radius.  Per neighbour j of i, i itself included:  o_a = (int64) rint(d_a * s), so |o_a| <= 65536;
+ *                  t = 1.0 - d2 / r2;  w = (int64) rint(4096.0 * (t * t)) -- a compact biweight kernel, no exp.  Exact integer sums
+ *                  in 64-bit words with wrapping arithmetic:  W = sum w;  S1_a = sum w * o_a;  S2_ab = sum w * o_a * o_b (six);
+ *                  cnt = |N(i)|.  A term is at most 2^44: the sums are exact for cnt <= 2^18.
+ *                  Point i is MOVED iff it is finite AND cnt - 1 >= max(2, min_neighbours) AND cnt <= 262144; otherwise its
+ *                  coordinates are copied bit for bit.  For a moved point:  M_ab = (double)W * (double)S2_ab - (double)S1_a * (double)S1_b
+ *                  (int64 -> double rounds to nearest even);  n = smallest_eigvec(M) (csrc/smallest_eigvec.hpp);  c_a = (double)S1_a /
+ *                  (double)W;  h = (n_x*c_x + n_y*c_y) + n_z*c_z;  p'_a = (float)((double)p_a + (n_a * h) / s).  The sign of n cancels.
+ *                  Colours, tiles, order, count, timestamp and cellsize are the input's.
+ *  Nothing in a result depends on grid layout, launch shape, the order of points inside a cell, or scheduling.
+ *  Refusals.       -1 / NULL, logged as an ERROR, before anything is launched: a NULL cloud, flag bits other than the one below, a cap
+ *                  below the cloud's count; for counts and the outlier filter a radius that is NaN, infinite or <= 0 (RULE K's); for
+ *                  smoothing a radius that is not finite or lies outside [1e-30, 1e30].
+ * The cloud is neither consumed nor changed; an empty cloud gives an empty cloud (0 for the counts).  Cost grows with the number of
+ * points within radius of a point. */
+#define CWIPC_HIP_NEIGH_SAME_TILE 1
+/* counts: a host array of cap >= count(pc) entries.  One wait.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_radius_counts(cwipc_pointcloud *pc, double radius, int flags, uint32_t *counts, size_t cap);
+/* The outlier filter.  The result is device-resident; the call waits once, for the count that sizes its result (and where the point
+ * grid's sparse layout waits, as every search on it does). */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_radius_outlier_filter(cwipc_pointcloud *pc, double radius, int flags, uint64_t min_neighbours);
+/* Smoothing.  The result is device-resident, shares the input's colour / tile words and is handed back with the kernel in flight: the
+ * call does not wait (but where the point grid's sparse layout does). */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_smooth(cwipc_pointcloud *pc, double radius, int flags, uint32_t min_neighbours);
+/* The host twin of cwipc_hip_smooth: the same header text (csrc/smooth_terms.hpp) by brute force over all pairs, O(n * n), no GPU.
+ * out: n points, not overlapping pts.  0 ok; -1 (logged) for NULL pointers with n > 0 and for what cwipc_hip_smooth refuses. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_smooth_host(const struct cwipc_point *pts, size_t n, double radius, int flags, uint32_t min_neighbours, struct cwipc_point *out);
+
 /* ---- floor and tile helpers of the registration pipeline (reference python/cwipc/registration/util.py:146-229) ----
  * A point is FLOOR iff (double)y < level; a NaN y is not floor.  The reference compares the float32 column with a Python scalar,
  * which numpy rounds to float32 first: the caller passes that value (the Python wrappers do).  NULL (or -1) on error (logged):
