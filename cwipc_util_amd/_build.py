@@ -47,6 +47,7 @@ SOURCES = [
     "kernels_kde.hip",
     "kernels_icp.hip",
     "kernels_floor.hip",
+    "kernels_plane.hip",
     "kernels_render.hip",
     "kernels_markers.hip",
     "kernels_cluster.hip",

@@ -348,6 +348,8 @@ void count_dealloc();
 // the point grid they search on: point_grid.hpp, kernels_grid.hip)
 // All work on the calling thread's stream; none synchronises unless stated.
 // ---------------------------------------------------------------------------
+struct PlaneRule;   // plane_seg_terms.hpp
+
 namespace k {
 
 // AoS (device) <-> SoA
@@ -447,6 +449,47 @@ void tile_histogram(const DeviceSoA &src, int nonfloor_only, double level, unsig
 // per workgroup min x, y, z, max x, y, z (NaN skipped per coordinate; +inf / -inf where there is nothing): bounds_blocks(n) x 6 floats
 unsigned bounds_blocks(size_t n);
 void bounds_partial(const DeviceSoA &src, float *partial, hipStream_t s);
+// The same partition with RULE S's classes (hip_ext.h): A = the inliers of a plane (PLANE_KEEP_INLIERS; with PLANE_BELOW_IS_INLIER
+// everything with e <= distance), B = the other points (PLANE_KEEP_REST).
+struct PlaneArgs {
+    double plane[4];
+    double distance;
+    int flags;   // CWIPC_HIP_PLANE_KEEP_* and CWIPC_HIP_PLANE_BELOW_IS_INLIER of hip_ext.h
+};
+void floor_count(const DeviceSoA &src, const PlaneArgs &a, uint32_t *counts, hipStream_t s);
+void floor_scatter(const DeviceSoA &src, const PlaneArgs &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s);
+
+// ---- kernels_plane.hip: the plane search of RULE S (hip_ext.h; the arithmetic is plane_seg_terms.hpp's) ----
+constexpr int PLANE_SCORE_TILE = 2048;    // points a workgroup of the score kernel holds in registers at a time
+constexpr int PLANE_SCORE_GRID = 512;     // its largest grid.x: workgroup (x, y) takes tiles x, x + grid.x, ...
+constexpr int PLANE_SCORE_HBLOCK = 64;    // hypotheses whose counts it keeps in LDS at a time: blocks y, y + grid.y, ...
+// What plane_best leaves in device memory and the refit adds its sums to: one read-back for both.
+struct PlaneBest {
+    double plane[4];
+    double anchor[3];
+    uint32_t h, count, nvalid, found;
+    uint32_t triple[3], pad;
+    unsigned long long sums[10];
+};
+// One pool block: the table (planes 4 H doubles, triples 3 H words, valid H words, counts H words), the best record, the score
+// kernel's partial counts (grid x H words).
+struct PlaneWork {
+    double *planes = nullptr;
+    uint32_t *triples = nullptr, *valid = nullptr, *counts = nullptr, *partial = nullptr;
+    PlaneBest *best = nullptr;
+    unsigned grid = 1;
+};
+unsigned plane_score_grid(size_t n, uint32_t H);
+size_t plane_work_bytes(size_t n, uint32_t H);
+void plane_work_layout(void *block, size_t n, uint32_t H, PlaneWork &w);
+// No wait in any of them.  The table of the rule's H hypotheses:
+void plane_hypotheses(const DeviceSoA &src, const PlaneRule &r, const PlaneWork &w, hipStream_t s);
+// counts[0, H) of the table's valid rows -- or, with `one`, counts[0] of that plane alone (the recount)
+void plane_score(const DeviceSoA &src, double distance, uint32_t H, const PlaneWork &w, const double *one, hipStream_t s);
+// the best record from table and counts (its sums zeroed) ...
+void plane_best(const DeviceSoA &src, uint32_t H, const PlaneWork &w, hipStream_t s);
+// ... and the refit's sums over the best hypothesis' inliers, added to it (nothing when found == 0)
+void plane_refit_sums(const DeviceSoA &src, double distance, const PlaneWork &w, hipStream_t s);
 
 // ---- kernels_render.hip: cwipc_hip_render (the contract is at the top of that file and in hip_ext.h) ----
 struct RenderArgs {

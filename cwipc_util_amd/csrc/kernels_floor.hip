@@ -9,6 +9,7 @@
 // the caller's (util.py: _threshold); a NaN y is therefore not floor.
 #include "internal.hpp"
 #include "counter_rng.hpp"
+#include "plane_seg_terms.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -79,6 +80,28 @@ __device__ __forceinline__ void classify(const FloorArgs &a, const float *__rest
     }
 }
 
+// The same two masks under RULE S (hip_ext.h): class A the inliers of a plane -- with PLANE_BELOW_IS_INLIER everything with
+// e <= distance --, class B the other points; a non-finite point gives a NaN or an infinity and is not an inlier.
+__device__ __forceinline__ void classify(const PlaneArgs &a, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
+                                         size_t base, size_t n, unsigned &ma, unsigned &mb) {
+    ma = mb = 0;
+    if (base >= n) return;
+    float vx[FITEMS], vy[FITEMS], vz[FITEMS];
+    load_items<float4>(x, base, n, 0.f, vx);
+    load_items<float4>(y, base, n, 0.f, vy);
+    load_items<float4>(z, base, n, 0.f, vz);
+    const bool keep_in = (a.flags & CWIPC_HIP_PLANE_KEEP_INLIERS) != 0, keep_rest = (a.flags & CWIPC_HIP_PLANE_KEEP_REST) != 0;
+    const bool below = (a.flags & CWIPC_HIP_PLANE_BELOW_IS_INLIER) != 0;
+#pragma unroll
+    for (int j = 0; j < FITEMS; j++) {
+        if (base + j >= n) break;
+        const double e = plane_e(a.plane, (double)vx[j], (double)vy[j], (double)vz[j]);
+        const bool in = below ? plane_below(e, a.distance) : plane_inlier(e, a.distance);
+        if (keep_in && in) ma |= 1u << j;
+        if (keep_rest && !in) mb |= 1u << j;
+    }
+}
+
 // Points of the wave's lanes in front of this lane, and in the whole wave, that a mask selects: one ballot and one
 // popcount per item (the points run lane-major, a lane's four in a row).
 __device__ __forceinline__ void wave_rank(unsigned m, uint32_t &before, uint32_t &total) {
@@ -93,7 +116,8 @@ __device__ __forceinline__ void wave_rank(unsigned m, uint32_t &before, uint32_t
 }
 
 // counts[b] = class A points of workgroup b's tile, counts[gridDim.x + b] = class B points
-__global__ void __launch_bounds__(FBLOCK) floor_count_kernel(FloorArgs a, const float *__restrict__ x, const float *__restrict__ y,
+template <class Args>
+__global__ void __launch_bounds__(FBLOCK) floor_count_kernel(Args a, const float *__restrict__ x, const float *__restrict__ y,
                                                             const float *__restrict__ z, size_t n, uint32_t *__restrict__ counts) {
     __shared__ uint32_t wave_tot[2][FWAVES];
     const size_t base = (size_t)blockIdx.x * FTILE + (size_t)threadIdx.x * FITEMS;
@@ -149,7 +173,8 @@ __global__ void __launch_bounds__(FSCAN) floor_scan_kernel(uint32_t *__restrict_
 }
 
 // Every class A point to offsets[b] + its rank in the tile, every class B point to total A + offsets[nb + b] + its rank.
-__global__ void __launch_bounds__(FBLOCK) floor_scatter_kernel(FloorArgs a, const float *__restrict__ x, const float *__restrict__ y,
+template <class Args>
+__global__ void __launch_bounds__(FBLOCK) floor_scatter_kernel(Args a, const float *__restrict__ x, const float *__restrict__ y,
                                                               const float *__restrict__ z, const uint32_t *__restrict__ rgbt, size_t n,
                                                               const uint32_t *__restrict__ offsets, float *__restrict__ ox, float *__restrict__ oy,
                                                               float *__restrict__ oz, uint32_t *__restrict__ ow, size_t out_n) {
@@ -184,21 +209,32 @@ __global__ void __launch_bounds__(FBLOCK) floor_scatter_kernel(FloorArgs a, cons
     }
 }
 
-void floor_count(const DeviceSoA &src, const FloorArgs &a, uint32_t *counts, hipStream_t s) {
+template <class Args>
+static void partition_count(const char *name, const DeviceSoA &src, const Args &a, uint32_t *counts, hipStream_t s) {
     const size_t nb = floor_blocks(src.npoints);
     if (!nb) return;
-    CW_LAUNCH("floor_count", floor_count_kernel, dim3((unsigned)nb), dim3(FBLOCK), 0, s, a, src.x(), src.y(), src.z(), src.npoints, counts);
+    CW_LAUNCH(name, floor_count_kernel<Args>, dim3((unsigned)nb), dim3(FBLOCK), 0, s, a, src.x(), src.y(), src.z(), src.npoints, counts);
 }
 
 void floor_scan(uint32_t *counts, size_t nb, unsigned long long *total_host, uint32_t tag, hipStream_t s) {
     CW_LAUNCH("floor_scan", floor_scan_kernel, dim3(1), dim3(FSCAN), 0, s, counts, nb, total_host, tag);
 }
 
-void floor_scatter(const DeviceSoA &src, const FloorArgs &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s) {
+template <class Args>
+static void partition_scatter(const char *name, const DeviceSoA &src, const Args &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s) {
     const size_t nb = floor_blocks(src.npoints);
     if (!nb || !dst.npoints) return;
-    CW_LAUNCH("floor_scatter", floor_scatter_kernel, dim3((unsigned)nb), dim3(FBLOCK), 0, s, a, src.x(), src.y(), src.z(), src.rgbt(), src.npoints, offsets,
+    CW_LAUNCH(name, floor_scatter_kernel<Args>, dim3((unsigned)nb), dim3(FBLOCK), 0, s, a, src.x(), src.y(), src.z(), src.rgbt(), src.npoints, offsets,
               dst.x(), dst.y(), dst.z(), dst.rgbt(), dst.npoints);
+}
+
+void floor_count(const DeviceSoA &src, const FloorArgs &a, uint32_t *counts, hipStream_t s) { partition_count("floor_count", src, a, counts, s); }
+void floor_count(const DeviceSoA &src, const PlaneArgs &a, uint32_t *counts, hipStream_t s) { partition_count("plane_count", src, a, counts, s); }
+void floor_scatter(const DeviceSoA &src, const FloorArgs &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s) {
+    partition_scatter("floor_scatter", src, a, offsets, dst, s);
+}
+void floor_scatter(const DeviceSoA &src, const PlaneArgs &a, const uint32_t *offsets, const DeviceSoA &dst, hipStream_t s) {
+    partition_scatter("plane_scatter", src, a, offsets, dst, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // their jobs, the kernel density estimate, every ICP and GICP entry, the distortion measure, the floor and tile helpers, bounds.  The per-point work is in
 // kernels_nn.hip, kernels_kde.hip, kernels_icp.hip and kernels_floor.hip.  There is NO CPU fallback.
 #include "entry.hpp"
+#include "plane_seg_terms.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -388,8 +389,9 @@ extern "C" int cwipc_hip_distortion(cwipc_pointcloud *original, cwipc_pointcloud
 // ---------------------------------------------------------------------------
 namespace {
 
-// count -> scan -> (wait: the two totals size the result) -> scatter -> wait
-std::shared_ptr<DeviceSoA> floor_partition(const std::shared_ptr<DeviceSoA> &src, const k::FloorArgs &a, uint64_t *n_first) {
+// count -> scan -> (wait: the two totals size the result) -> scatter -> wait.  Args: k::FloorArgs, or k::PlaneArgs for RULE S's classes.
+template <class Args>
+std::shared_ptr<DeviceSoA> floor_partition(const std::shared_ptr<DeviceSoA> &src, const Args &a, uint64_t *n_first) {
     ThreadCtx &c = tctx();
     if (!c.ensure()) return nullptr;
     if (n_first) *n_first = 0;
@@ -530,5 +532,223 @@ extern "C" int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]) {
             minmax[a] = fminf(minmax[a], host[b * 6 + a]);
             minmax[3 + a] = fmaxf(minmax[3 + a], host[b * 6 + 3 + a]);
         }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// no reference counterpart: plane segmentation (RULE S of hip_ext.h; kernels_plane.hip, the plane classifier of kernels_floor.hip,
+// plane_seg_terms.hpp) -- the entry of a cloud whose floor is not yet at y = 0 into the helpers above
+// ---------------------------------------------------------------------------
+namespace {
+
+// The refusals of RULE S that concern the parameters; `r` and `refine` are set when they pass.
+bool plane_params_refused(const char *who, const cwipc_hip_plane_params *p, PlaneRule &r, bool &refine) {
+    if (p == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL parameters");
+        return true;
+    }
+    if ((p->flags & ~CWIPC_HIP_PLANE_REFINE) != 0) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "unknown flag bits");
+        return true;
+    }
+    if (!plane_rule_ok(p->distance, p->iterations, p->axis, p->min_abs_cos)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "distance must be finite and within [1e-30, 1e30], iterations in 1 .. 65536, min_abs_cos in [0, 1], the axis finite");
+        return true;
+    }
+    r = plane_rule(p->distance, p->iterations, p->seed, p->axis, p->min_abs_cos);
+    refine = (p->flags & CWIPC_HIP_PLANE_REFINE) != 0;
+    return false;
+}
+
+bool plane_given_refused(const char *who, const double plane[4], double distance) {
+    if (plane == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL plane");
+        return true;
+    }
+    bool finite = true;
+    for (int a = 0; a < 4; a++) finite = finite && std::isfinite(plane[a]);
+    if (!finite || (plane[0] == 0.0 && plane[1] == 0.0 && plane[2] == 0.0)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the plane must be finite and its normal not zero");
+        return true;
+    }
+    if (!plane_distance_ok(distance)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "distance must be finite and within [1e-30, 1e30]");
+        return true;
+    }
+    return false;
+}
+
+void plane_result_out(const PlaneFound &f, cwipc_hip_plane_result *out) {
+    memset(out, 0, sizeof(*out));
+    for (int a = 0; a < 4; a++) { out->plane[a] = f.plane[a]; out->hypothesis[a] = f.hypothesis[a]; }
+    for (int i = 0; i < 10; i++) out->sums[i] = (int64_t)f.sums[i];
+    for (int i = 0; i < 6; i++) out->M[i] = f.M[i];
+    out->best = f.best;
+    for (int k = 0; k < 3; k++) out->triple[k] = f.triple[k];
+    out->count = f.count; out->recount = f.recount; out->valid = f.valid;
+    out->found = f.found; out->refined = f.refined;
+}
+
+// hypotheses -> score -> [best -> refit sums] -> (wait) -> [host solve -> recount -> (wait)].  table_only: no best, no refit.
+bool plane_search(const char *who, const DeviceSoA &src, const PlaneRule &r, bool refine, bool table_only, PlaneFound &f, double *planes, uint32_t *counts,
+                  uint32_t *triples, uint8_t *valid) {
+    const size_t n = src.npoints;
+    const uint32_t H = r.iterations;
+    if (n >= ((size_t)1 << 32)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the cloud has 2^32 points or more");
+        return false;
+    }
+    ThreadCtx &c = tctx();
+    if (!c.ensure()) return false;
+    void *block = pool_alloc(k::plane_work_bytes(n, H));
+    if (!block) return false;
+    k::PlaneWork w;
+    k::plane_work_layout(block, n, H, w);
+    // the read-back: the best record, then the table where it is wanted
+    const bool table = planes || counts || triples || valid;
+    const size_t at_planes = 256, at_counts = at_planes + (size_t)H * 32, at_triples = at_counts + (size_t)H * 4, at_valid = at_triples + (size_t)H * 12;
+    char *stage = (char *)c.staging(table ? at_valid + (size_t)H * 4 : at_planes);
+    if (!stage) { pool_free(block); return false; }
+    static_assert(sizeof(k::PlaneBest) <= 256, "the read-back's layout");
+    k::plane_hypotheses(src, r, w, c.stream);
+    k::plane_score(src, r.distance, H, w, nullptr, c.stream);
+    if (!table_only) {
+        k::plane_best(src, H, w, c.stream);
+        if (refine) k::plane_refit_sums(src, r.distance, w, c.stream);
+    }
+    bool ok = hipGetLastError() == hipSuccess;
+    if (!table_only) ok = ok && hipMemcpyAsync(stage, w.best, sizeof(k::PlaneBest), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    if (table) {
+        ok = ok && hipMemcpyAsync(stage + at_planes, w.planes, (size_t)H * 32, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(stage + at_counts, w.counts, (size_t)H * 4, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(stage + at_triples, w.triples, (size_t)H * 12, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(stage + at_valid, w.valid, (size_t)H * 4, hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+    }
+    ok = c.sync() && ok;   // (also on failure: kernels that write the block may still be in flight)
+    if (ok && table) {
+        if (planes) memcpy(planes, stage + at_planes, (size_t)H * 32);
+        if (counts) memcpy(counts, stage + at_counts, (size_t)H * 4);
+        if (triples) memcpy(triples, stage + at_triples, (size_t)H * 12);
+        const uint32_t *v = (const uint32_t *)(stage + at_valid);
+        for (uint32_t h = 0; valid && h < H; h++) valid[h] = v[h] ? 1 : 0;
+    }
+    f = PlaneFound();
+    if (ok && !table_only) {
+        k::PlaneBest b;
+        memcpy(&b, stage, sizeof(b));
+        f.found = b.found ? 1 : 0;
+        f.valid = b.nvalid;
+        if (f.found) {
+            f.best = b.h; f.count = b.count;
+            for (int a = 0; a < 4; a++) f.hypothesis[a] = b.plane[a];
+            for (int k = 0; k < 3; k++) f.triple[k] = b.triple[k];
+            for (int i = 0; i < 10; i++) f.sums[i] = b.sums[i];
+            double refit[4] = {0, 0, 0, 0};
+            uint32_t recount = 0;
+            const bool recounted = refine && plane_refit_wanted(r, f, b.anchor, refit);
+            if (recounted) {
+                k::plane_score(src, r.distance, H, w, refit, c.stream);
+                ok = hipGetLastError() == hipSuccess;
+                ok = ok && hipMemcpyAsync(stage, w.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream) == hipSuccess;
+                ok = c.sync() && ok;
+                memcpy(&recount, stage, sizeof(recount));
+            }
+            if (ok) plane_conclude(r, f, recounted, refit, recount);
+        }
+    }
+    pool_free(block);
+    if (!ok) hip_failed(hipGetLastError(), who, __FILE__, __LINE__);
+    return ok;
+}
+
+}  // namespace
+
+extern "C" int cwipc_hip_plane_find(cwipc_pointcloud *pc, const cwipc_hip_plane_params *params, cwipc_hip_plane_result *result) {
+    const char *who = "cwipc_hip_plane_find";
+    if (result) memset(result, 0, sizeof(*result));
+    if (pc == nullptr || result == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, pc ? "NULL result" : "NULL pointcloud");
+        return -1;
+    }
+    PlaneRule r;
+    bool refine = false;
+    if (plane_params_refused(who, params, r, refine)) return -1;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input(who, pc, keep);
+    if (!src) return -1;
+    PlaneFound f;
+    if (!plane_search(who, *src, r, refine, false, f, nullptr, nullptr, nullptr, nullptr)) return -1;
+    plane_result_out(f, result);
+    return 0;
+}
+
+extern "C" int cwipc_hip_plane_scores(cwipc_pointcloud *pc, const cwipc_hip_plane_params *params, double *planes, uint32_t *counts, uint32_t *triples,
+                                      uint8_t *valid) {
+    const char *who = "cwipc_hip_plane_scores";
+    if (pc == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return -1;
+    }
+    PlaneRule r;
+    bool refine = false;
+    if (plane_params_refused(who, params, r, refine)) return -1;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input(who, pc, keep);
+    if (!src) return -1;
+    PlaneFound f;
+    return plane_search(who, *src, r, false, true, f, planes, counts, triples, valid) ? 0 : -1;
+}
+
+extern "C" cwipc_pointcloud *cwipc_hip_plane_partition(cwipc_pointcloud *pc, const double plane[4], double distance, int flags, uint64_t *n_first) {
+    const char *who = "cwipc_hip_plane_partition";
+    if (n_first) *n_first = 0;
+    if (pc == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointcloud");
+        return nullptr;
+    }
+    if ((flags & ~(CWIPC_HIP_PLANE_KEEP_INLIERS | CWIPC_HIP_PLANE_KEEP_REST | CWIPC_HIP_PLANE_BELOW_IS_INLIER)) != 0) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "unknown flag bits");
+        return nullptr;
+    }
+    if (plane_given_refused(who, plane, distance)) return nullptr;
+    std::unique_ptr<cwipc_hip_pointcloud> keep;
+    auto src = device_input(who, pc, keep);
+    if (!src) return nullptr;
+    const k::PlaneArgs a{{plane[0], plane[1], plane[2], plane[3]}, distance, flags};
+    return wrap(floor_partition(src, a, n_first), pc->timestamp(), pc->cellsize());
+}
+
+extern "C" int cwipc_hip_plane_level_matrix(const double plane[4], double m16[16]) {
+    const char *who = "cwipc_hip_plane_level_matrix";
+    if (m16 == nullptr) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL matrix");
+        return -1;
+    }
+    if (plane_given_refused(who, plane, 1.0)) return -1;
+    if (!plane_level_matrix(plane, m16)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "the normal's length is not a finite positive number");
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int cwipc_hip_plane_find_host(const cwipc_point *pts, size_t n, const cwipc_hip_plane_params *params, cwipc_hip_plane_result *result, double *planes,
+                                         uint32_t *counts, uint8_t *valid) {
+    const char *who = "cwipc_hip_plane_find_host";
+    if (result) memset(result, 0, sizeof(*result));
+    if (result == nullptr || (n && pts == nullptr)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "NULL pointer");
+        return -1;
+    }
+    PlaneRule r;
+    bool refine = false;
+    if (plane_params_refused(who, params, r, refine)) return -1;
+    if (n >= ((size_t)1 << 32)) {
+        cwipc_log(CWIPC_LOG_LEVEL_ERROR, who, "2^32 points or more");
+        return -1;
+    }
+    PlaneFound f;
+    plane_find_brute(pts, n, r, refine, f, planes, counts, valid);
+    plane_result_out(f, result);
     return 0;
 }

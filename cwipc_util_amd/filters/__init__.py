@@ -1,7 +1,7 @@
 """Filter plugins of the hot path (reference python/cwipc/filters/__init__.py:19-48).
 
 Only the filters on the MI355X path exist here: voxelize, remove_outliers, crop,
-colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth (plus passthrough).  The factory accepts the reference's FILTERDESC
+colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth, plane, level_floor (plus passthrough).  The factory accepts the reference's FILTERDESC
 syntax -- "name" or "name(args)" -- but parses the arguments with
 ast.literal_eval instead of eval.
 """
@@ -9,9 +9,9 @@ import ast
 from typing import cast
 
 from .abstract import cwipc_abstract_filter
-from . import passthrough, voxelize, crop, remove_outliers, colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth
+from . import passthrough, voxelize, crop, remove_outliers, colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth, plane, level_floor
 
-all_filters = [passthrough, voxelize, crop, remove_outliers, colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth]
+all_filters = [passthrough, voxelize, crop, remove_outliers, colorize, transform, transform44, simulatecams, direction, randomize_floor, analyze, noise, cluster, radius_outliers, smooth, plane, level_floor]
 _by_name = {m.CustomFilter.filtername: m for m in all_filters if m is not transform44}
 # (the reference's factory looks a filter up by its MODULE's name; transform44's filtername is "transform" there too)
 _by_name['transform44'] = transform44

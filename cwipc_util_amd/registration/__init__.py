@@ -21,6 +21,9 @@ reference opens a window), and `deproject` takes image corners back to 3D.  The 
 reference calls cv2.aruco); with `MultiCameraCoarseAruco.set_marker_dictionary` render and detection are one call and no image leaves the
 GPU (cwipc_hip_render_detect_markers).  The user supplies the dictionary's bit patterns.  `multicoarse.MultiCameraCoarseArucoRgb` looks for
 the markers in the cameras' own colour and depth images instead, which a grabber (`cwipc_util_amd.rgbd.RgbdSource`) attaches to the cloud.
+
+Without any marker, `floor.find_floor` and `floor.level_to_floor` find the floor as the dominant near-horizontal plane of the cloud on the
+GPU and move the cloud so that it lies at y = 0, which is what cwipc_floor_filter and `MultiCameraToFloor` assume.
 """
 from .abstract import (AnalysisResults, AnalysisAlgorithm, OverlapAnalysisResults, AlignmentAlgorithm, MulticamAlgorithm,   # noqa: F401
                        MulticamAlignmentAlgorithm)
@@ -35,3 +38,4 @@ from .multicamera import (BaseMulticamAlignmentAlgorithm, MultiCameraOneToAllOth
 from .render import PinholeView, default_view, look_at, render_pointcloud, deproject, deproject_depth, mean_depth   # noqa: F401
 from .markers import MarkerDictionary, detect_markers, gpu_marker_detector   # noqa: F401
 from .multicoarse import MultiCameraCoarse, MultiCameraCoarseAruco, MultiCameraCoarseArucoRgb, MarkerPosition, MarkerPositions   # noqa: F401
+from .floor import find_floor, level_to_floor   # noqa: F401

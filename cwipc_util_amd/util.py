@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+import math
 import os
 import sys
 import warnings
@@ -53,6 +54,11 @@ __all__ = [
     'cwipc_hip_floor_partition', 'cwipc_hip_floor_radius_stats', 'cwipc_hip_tile_counts', 'cwipc_hip_bounds',
     'CWIPC_HIP_FLOOR_KEEP_FLOOR', 'CWIPC_HIP_FLOOR_KEEP_REST', 'CWIPC_HIP_FLOOR_LIMIT_RADIUS',
     'cwipc_hip_noise', 'cwipc_hip_simulatecams_soft',
+    'CWIPC_HIP_PLANE_REFINE', 'CWIPC_HIP_PLANE_KEEP_INLIERS', 'CWIPC_HIP_PLANE_KEEP_REST', 'CWIPC_HIP_PLANE_BELOW_IS_INLIER',
+    'CWIPC_HIP_PLANE_SCORE_TILE', 'CWIPC_HIP_PLANE_SCORE_GRID', 'CWIPC_HIP_PLANE_SCORE_HBLOCK',
+    'cwipc_hip_plane_params', 'cwipc_hip_plane_result', 'cwipc_plane_result', 'cwipc_plane_constraint',
+    'cwipc_find_plane', 'cwipc_hip_plane_scores', 'cwipc_hip_plane_partition', 'cwipc_plane_filter', 'cwipc_hip_plane_level_matrix',
+    'cwipc_level_to_plane', 'cwipc_find_planes', 'cwipc_hip_plane_find_host',
     'cwipc_hip_view', 'cwipc_hip_render',
     'cwipc_hip_marker_params', 'cwipc_hip_detect_markers', 'cwipc_hip_render_detect_markers', 'cwipc_hip_marker_labels',
     'cwipc_hip_rgbd_camera', 'cwipc_hip_rgbd_filter', 'CWIPC_HIP_RGBD_ATTACH_RGB', 'CWIPC_HIP_RGBD_ATTACH_DEPTH', 'cwipc_hip_from_rgbd',
@@ -281,6 +287,11 @@ _SIGNATURES: Dict[str, Tuple[list, Any]] = {
     'cwipc_hip_gaussian_kde': ([_c.c_void_p, _c.c_size_t, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_partition': ([cwipc_pointcloud_p, _c.c_double, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
     'cwipc_hip_randomize_floor': ([cwipc_pointcloud_p, _c.c_double, _c.c_uint64], cwipc_pointcloud_p),
+    'cwipc_hip_plane_find': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_plane_scores': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_plane_partition': ([cwipc_pointcloud_p, _c.c_void_p, _c.c_double, _c.c_int, _c.POINTER(_c.c_uint64)], cwipc_pointcloud_p),
+    'cwipc_hip_plane_level_matrix': ([_c.c_void_p, _c.c_void_p], _c.c_int),
+    'cwipc_hip_plane_find_host': ([_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p], _c.c_int),
     'cwipc_hip_floor_radius_stats': ([cwipc_pointcloud_p, _c.c_double, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_float)], _c.c_int),
     'cwipc_hip_nn_distance2_jobs': ([cwipc_pointcloud_p, cwipc_pointcloud_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_size_t], _c.c_int),
     'cwipc_hip_tile_counts': ([cwipc_pointcloud_p, _c.c_int, _c.c_double, _c.POINTER(_c.c_uint64)], _c.c_int),
@@ -1838,6 +1849,210 @@ def cwipc_hip_smooth_host(points: numpy.ndarray, radius: float, min_neighbours: 
     if cwipc_util_dll_load().cwipc_hip_smooth_host(probe.ctypes.data, points.size, float(radius), flags, int(min_neighbours), out.ctypes.data) != 0:
         raise CwipcError("cwipc_hip_smooth_host failed")
     return out[:points.size]
+
+
+# ---- plane segmentation (include/cwipc_util_amd/hip_ext.h, RULE S; no reference counterpart) ----
+CWIPC_HIP_PLANE_REFINE = 1
+CWIPC_HIP_PLANE_KEEP_INLIERS = 1
+CWIPC_HIP_PLANE_KEEP_REST = 2
+CWIPC_HIP_PLANE_BELOW_IS_INLIER = 4
+# the score kernel's shape (csrc/internal.hpp), for tests that sit on its edges
+CWIPC_HIP_PLANE_SCORE_TILE = 2048
+CWIPC_HIP_PLANE_SCORE_GRID = 512
+CWIPC_HIP_PLANE_SCORE_HBLOCK = 64
+
+
+class cwipc_hip_plane_params(ctypes.Structure):
+    _fields_ = [("distance", ctypes.c_double), ("seed", ctypes.c_uint64), ("axis", ctypes.c_double * 3), ("min_abs_cos", ctypes.c_double),
+                ("iterations", ctypes.c_uint32), ("flags", ctypes.c_int32)]
+
+
+class cwipc_hip_plane_result(ctypes.Structure):
+    _fields_ = [("plane", ctypes.c_double * 4), ("hypothesis", ctypes.c_double * 4), ("sums", ctypes.c_int64 * 10), ("M", ctypes.c_double * 6),
+                ("best", ctypes.c_uint32), ("triple", ctypes.c_uint32 * 3), ("count", ctypes.c_uint32), ("recount", ctypes.c_uint32),
+                ("valid", ctypes.c_uint32), ("found", ctypes.c_int32), ("refined", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class cwipc_plane_result:
+    """What a plane search found.  plane: the returned plane (n_x, n_y, n_z, d) as float64, oriented towards the axis (+Y when
+    unconstrained); hypothesis: the best triple's plane; found / refined: bools; best, triple, count: the best hypothesis, its point
+    indices and inliers; refit_count, sums, M: the refit's; recount: inliers of the refit plane; valid: number of valid hypotheses.
+    raw is the C structure, whose bytes tests compare."""
+
+    def __init__(self, raw: cwipc_hip_plane_result):
+        self.raw = raw
+        self.plane = numpy.array(raw.plane[:], dtype=numpy.float64)
+        self.hypothesis = numpy.array(raw.hypothesis[:], dtype=numpy.float64)
+        self.sums = numpy.array(raw.sums[:], dtype=numpy.int64)
+        self.M = numpy.array(raw.M[:], dtype=numpy.float64)
+        self.best = int(raw.best)
+        self.triple = tuple(int(v) for v in raw.triple)
+        self.count = int(raw.count)
+        self.recount = int(raw.recount)
+        self.refit_count = int(raw.sums[0])
+        self.valid = int(raw.valid)
+        self.found = bool(raw.found)
+        self.refined = bool(raw.refined)
+
+    def tobytes(self) -> bytes:
+        return bytes(self.raw)
+
+    def __repr__(self) -> str:
+        return "cwipc_plane_result(found=%r, plane=%r, count=%d, refined=%r, recount=%d)" % (self.found, self.plane.tolist(), self.count, self.refined, self.recount)
+
+
+def cwipc_plane_constraint(axis: Any = None, max_angle: Optional[float] = None) -> Tuple[Tuple[float, float, float], float]:
+    """(unit axis, min_abs_cos) of RULE S from an axis and the largest angle, in DEGREES, between it and the plane's normal.  Neither
+    given: unconstrained, ((0, 0, 0), 0).  max_angle alone: about +Y.  The trigonometry happens here, not in the rule."""
+    if axis is None and max_angle is None:
+        return (0.0, 0.0, 0.0), 0.0
+    if max_angle is None:
+        raise ValueError("cwipc_plane_constraint: an axis needs max_angle")
+    a = numpy.array((0.0, 1.0, 0.0) if axis is None else axis, dtype=numpy.float64).reshape(-1)
+    if a.shape != (3,) or not numpy.all(numpy.isfinite(a)) or not numpy.any(a != 0):
+        raise ValueError("cwipc_plane_constraint: the axis must be three finite numbers, not all zero")
+    if not (0.0 <= float(max_angle) <= 90.0):
+        raise ValueError("cwipc_plane_constraint: max_angle must lie between 0 and 90 degrees")
+    a = a / math.sqrt(float(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]))
+    return (float(a[0]), float(a[1]), float(a[2])), min(1.0, max(0.0, math.cos(math.radians(float(max_angle)))))
+
+
+def _plane_params(who: str, distance: float, iterations: int, seed: int, axis: Any, max_angle: Optional[float], refine: bool) -> cwipc_hip_plane_params:
+    distance = float(distance)
+    if not (1e-30 <= distance <= 1e30):
+        raise ValueError("%s: distance must be finite and within [1e-30, 1e30]" % who)
+    if not (1 <= int(iterations) <= 65536):
+        raise ValueError("%s: iterations must lie between 1 and 65536" % who)
+    if not (0 <= int(seed) < 2 ** 64):
+        raise ValueError("%s: seed must be a uint64" % who)
+    unit, mac = cwipc_plane_constraint(axis, max_angle)
+    p = cwipc_hip_plane_params()
+    p.distance = distance
+    p.seed = int(seed)
+    p.axis[0], p.axis[1], p.axis[2] = unit
+    p.min_abs_cos = mac
+    p.iterations = int(iterations)
+    p.flags = CWIPC_HIP_PLANE_REFINE if refine else 0
+    return p
+
+
+def _plane4(who: str, plane: Any) -> numpy.ndarray:
+    if isinstance(plane, cwipc_plane_result):
+        if not plane.found:
+            raise ValueError("%s: the search found no plane" % who)
+        plane = plane.plane
+    p = numpy.ascontiguousarray(numpy.asarray(plane, dtype=numpy.float64)).reshape(-1)
+    if p.shape != (4,) or not numpy.all(numpy.isfinite(p)) or not numpy.any(p[:3] != 0):
+        raise ValueError("%s: a plane is four finite numbers (n_x, n_y, n_z, d) with a normal that is not zero" % who)
+    return p
+
+
+def cwipc_find_plane(pc: cwipc_pointcloud_wrapper, distance: float, iterations: int = 1024, seed: int = 0, axis: Any = None,
+                     max_angle: Optional[float] = None, refine: bool = True) -> cwipc_plane_result:
+    """The dominant plane of the cloud by random-sample consensus on the GPU (RULE S): `iterations` seeded triples, each scored by
+    the number of points within `distance`; the best one, refitted to its inliers when refine.  axis / max_angle (degrees) keep
+    only planes whose normal lies within max_angle of the axis (cwipc_plane_constraint).  result.found is False when no triple gave
+    a plane (fewer than 3 points, all points equal or collinear, ...)."""
+    if pc is None:
+        raise CwipcError("cwipc_find_plane: NULL pointcloud")
+    params = _plane_params("cwipc_find_plane", distance, iterations, seed, axis, max_angle, refine)
+    raw = cwipc_hip_plane_result()
+    if cwipc_util_dll_load().cwipc_hip_plane_find(pc.as_cwipc_p(), ctypes.addressof(params), ctypes.addressof(raw)) != 0:
+        raise CwipcError("cwipc_hip_plane_find failed")
+    return cwipc_plane_result(raw)
+
+
+def cwipc_hip_plane_scores(pc: cwipc_pointcloud_wrapper, distance: float, iterations: int = 1024, seed: int = 0, axis: Any = None,
+                           max_angle: Optional[float] = None) -> Dict[str, numpy.ndarray]:
+    """The whole hypothesis table of cwipc_find_plane, for tests and diagnostics: planes (H x 4 float64), counts (uint32), triples
+    (H x 3 uint32), valid (bool)."""
+    if pc is None:
+        raise CwipcError("cwipc_hip_plane_scores: NULL pointcloud")
+    params = _plane_params("cwipc_hip_plane_scores", distance, iterations, seed, axis, max_angle, False)
+    H = int(iterations)
+    planes = numpy.zeros((H, 4), dtype=numpy.float64)
+    counts = numpy.zeros(H, dtype=numpy.uint32)
+    triples = numpy.zeros((H, 3), dtype=numpy.uint32)
+    valid = numpy.zeros(H, dtype=numpy.uint8)
+    if cwipc_util_dll_load().cwipc_hip_plane_scores(pc.as_cwipc_p(), ctypes.addressof(params), planes.ctypes.data, counts.ctypes.data, triples.ctypes.data,
+                                                    valid.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_plane_scores failed")
+    return {"planes": planes, "counts": counts, "triples": triples, "valid": valid.astype(bool)}
+
+
+def cwipc_hip_plane_partition(pc: cwipc_pointcloud_wrapper, plane: Any, distance: float, flags: int) -> Tuple[cwipc_pointcloud_wrapper, int]:
+    """Stable two-class partition by a plane on the GPU (RULE S): (cloud, number of class A points).  Class A, first: the points
+    within `distance` of the plane (CWIPC_HIP_PLANE_KEEP_INLIERS; with CWIPC_HIP_PLANE_BELOW_IS_INLIER everything at most `distance`
+    above it); class B: the others (CWIPC_HIP_PLANE_KEEP_REST).  Colours, tiles, timestamp and cellsize are the input's."""
+    if pc is None:
+        raise CwipcError("cwipc_hip_plane_partition: NULL pointcloud")
+    p = _plane4("cwipc_hip_plane_partition", plane)
+    n_first = ctypes.c_uint64(0)
+    rv = cwipc_util_dll_load().cwipc_hip_plane_partition(pc.as_cwipc_p(), p.ctypes.data, float(distance), int(flags), ctypes.byref(n_first))
+    return _wrap_filter_result('cwipc_hip_plane_partition', rv), int(n_first.value)
+
+
+def cwipc_plane_filter(pc: cwipc_pointcloud_wrapper, plane: Any, distance: float, keep: str = "rest", below: bool = False) -> cwipc_pointcloud_wrapper:
+    """Remove the points of a plane (keep="rest"), keep only them ("inliers") or put them first ("both").  below: everything under
+    the plane counts as the plane -- the floor and what lies beneath it."""
+    flags = {"rest": CWIPC_HIP_PLANE_KEEP_REST, "inliers": CWIPC_HIP_PLANE_KEEP_INLIERS, "both": CWIPC_HIP_PLANE_KEEP_INLIERS | CWIPC_HIP_PLANE_KEEP_REST}.get(keep)
+    if flags is None:
+        raise ValueError("cwipc_plane_filter: keep is 'rest', 'inliers' or 'both'")
+    return cwipc_hip_plane_partition(pc, plane, distance, flags | (CWIPC_HIP_PLANE_BELOW_IS_INLIER if below else 0))[0]
+
+
+def cwipc_hip_plane_level_matrix(plane: Any) -> numpy.ndarray:
+    """The 4x4 motion that makes the plane y = 0: the minimal rotation taking its normal (towards +Y) to (0, 1, 0), then the shift
+    along y (RULE S, Levelling).  Host arithmetic, no GPU."""
+    p = _plane4("cwipc_hip_plane_level_matrix", plane)
+    m = numpy.zeros((4, 4), dtype=numpy.float64)
+    if cwipc_util_dll_load().cwipc_hip_plane_level_matrix(p.ctypes.data, m.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_plane_level_matrix failed")
+    return m
+
+
+def cwipc_level_to_plane(pc: cwipc_pointcloud_wrapper, plane: Any) -> cwipc_pointcloud_wrapper:
+    """The cloud moved so that the plane becomes y = 0 with its normal up: cwipc_hip_plane_level_matrix, then cwipc_transform."""
+    return cwipc_transform(pc, cwipc_hip_plane_level_matrix(plane))
+
+
+def cwipc_find_planes(pc: cwipc_pointcloud_wrapper, distance: float, max_planes: int, min_inliers: int = 3, iterations: int = 1024, seed: int = 0,
+                      axis: Any = None, max_angle: Optional[float] = None, refine: bool = True) -> Tuple[List[cwipc_plane_result], cwipc_pointcloud_wrapper]:
+    """Peel planes off the cloud: find the dominant plane, stop when it has fewer than min_inliers points within `distance` (the
+    returned plane's: the recount when refined, else the count), otherwise take its inliers out and search what is left; at most
+    max_planes times.  Every search uses the same seed.  The cloud stays on the device throughout.  Returns the planes and the
+    remainder (the input itself when nothing was peeled)."""
+    planes: List[cwipc_plane_result] = []
+    rest = pc
+    for _ in range(int(max_planes)):
+        found = cwipc_find_plane(rest, distance, iterations, seed, axis, max_angle, refine)
+        inliers = found.recount if found.refined else found.count
+        if not found.found or inliers < int(min_inliers):
+            break
+        planes.append(found)
+        peeled = cwipc_plane_filter(rest, found.plane, distance, keep="rest")
+        if rest is not pc:
+            rest.free()
+        rest = peeled
+    return planes, rest
+
+
+def cwipc_hip_plane_find_host(points: numpy.ndarray, distance: float, iterations: int = 1024, seed: int = 0, axis: Any = None,
+                              max_angle: Optional[float] = None, refine: bool = True) -> Tuple[cwipc_plane_result, Dict[str, numpy.ndarray]]:
+    """The host twin of cwipc_find_plane and cwipc_hip_plane_scores on a structured array of cwipc_point records: the same
+    arithmetic (csrc/plane_seg_terms.hpp) by brute force, O(n * iterations), no GPU.  (result, {planes, counts, valid})."""
+    points = numpy.ascontiguousarray(points, dtype=cwipc_point_numpy_dtype).reshape(-1)
+    params = _plane_params("cwipc_hip_plane_find_host", distance, iterations, seed, axis, max_angle, refine)
+    H = int(iterations)
+    planes = numpy.zeros((H, 4), dtype=numpy.float64)
+    counts = numpy.zeros(H, dtype=numpy.uint32)
+    valid = numpy.zeros(H, dtype=numpy.uint8)
+    raw = cwipc_hip_plane_result()
+    probe = points if points.size else numpy.zeros(1, dtype=cwipc_point_numpy_dtype)
+    if cwipc_util_dll_load().cwipc_hip_plane_find_host(probe.ctypes.data, points.size, ctypes.addressof(params), ctypes.addressof(raw), planes.ctypes.data,
+                                                       counts.ctypes.data, valid.ctypes.data) != 0:
+        raise CwipcError("cwipc_hip_plane_find_host failed")
+    return cwipc_plane_result(raw), {"planes": planes, "counts": counts, "valid": valid.astype(bool)}
 
 
 def cwipc_center(pc: cwipc_pointcloud_wrapper) -> Tuple[float, float, float]:

@@ -280,6 +280,92 @@ _CWIPC_UTIL_EXPORT int cwipc_hip_tile_counts(cwipc_pointcloud *pc, int nonfloor_
  * analyze filter); a coordinate without a value (an empty cloud) has min +inf and max -inf.  0 ok. */
 _CWIPC_UTIL_EXPORT int cwipc_hip_bounds(cwipc_pointcloud *pc, float minmax[6]);
 
+/* ---- plane segmentation: the dominant plane of a cloud by random-sample consensus (what PCL users know as SACSegmentation, open3d's
+ * segment_plane), a refit over its inliers, the partition by a plane and the rotation that makes the plane y = 0; no reference
+ * counterpart.  It is the entry of a cloud whose floor is NOT yet at y = 0 into the floor helpers above.  tests/plane_model.py is the
+ * numpy model of this text; csrc/plane_seg_terms.hpp holds the per-hypothesis and per-point arithmetic.
+ *
+ * RULE S.
+ *  Arithmetic.   All of it float64, every operation rounded on its own, in the order written here, no contraction.
+ *  Parameters.   distance finite and within [1e-30, 1e30];  iterations = H in 1 .. 65536;  seed any uint64;  axis[3] and min_abs_cos
+ *                in [0, 1] the optional constraint: min_abs_cos == 0 or a zero axis means unconstrained.  The caller passes a unit
+ *                axis (the Python wrapper normalises it and turns an angle into the cosine: no trigonometry enters the rule).
+ *                flags: CWIPC_HIP_PLANE_REFINE.
+ *  Draws.        b = rng_base(seed, RNG_TAG_PLANE), RNG_TAG_PLANE = 0x706c616e65 ("plane"; csrc/counter_rng.hpp).  Hypothesis h takes
+ *                x_k = rng_draw(b, 3 h + k), k = 0, 1, 2, and i_k = ((x_k >> 32) * n) >> 32 in 64-bit integers, n the cloud's count
+ *                (< 2^32).  The constraint does not change which triples are drawn.
+ *  Hypothesis.   p_k = point i_k as doubles;  u = p1 - p0;  v = p2 - p0;  c = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x);
+ *                l2 = (c_x c_x + c_y c_y) + c_z c_z.  VALID iff the three indices differ AND all nine coordinates are finite AND l2 is
+ *                finite and > 0 AND, with a constraint, |(n_x a_x + n_y a_y) + n_z a_z| >= min_abs_cos.  n = c / sqrt(l2), component
+ *                by component;  d = -((n_x p0_x + n_y p0_y) + n_z p0_z).  The table row of an invalid hypothesis is four +0.0.
+ *  Score.        e(p) = ((n_x x + n_y y) + n_z z) + d;  p is an INLIER iff fabs(e) <= distance (a non-finite point never is).
+ *                count[h] = the number of inliers; 0 for an invalid hypothesis, which is not scored.
+ *  Best.         Among the valid hypotheses the largest count, then the smallest h.  found = 0 when none is valid (n < 3 included):
+ *                not an error.
+ *  Refit.        (REFINE, over the best hypothesis' inliers.)  Anchor a = p0 of the best triple;  s = 16.0 / distance;
+ *                o_a = rint((p_a - a_a) * s);  an inlier takes part iff all |o_a| <= 262144.  cnt, S1[3] = sum o_a, S2[6] = sum o_a o_b
+ *                (xx xy xz yy yz zz) are exact 64-bit integers for cnt <= 2^26.  On the host M_ab = cnt * S2_ab - S1_a * S1_b exactly in
+ *                128-bit integers, converted to double once (to nearest even);  n' = smallest_eigvec(M) (csrc/smallest_eigvec.hpp),
+ *                turned so that (n'_x n_x + n'_y n_y) + n'_z n_z >= 0;  c_a = a_a + ((double)S1_a / (double)cnt) / s;
+ *                d' = -((n'_x c_x + n'_y c_y) + n'_z c_z).  The score runs once more for (n', d') alone: the recount.  The refined
+ *                plane is RETURNED iff 3 <= cnt <= 2^26 AND n' is finite AND the constraint holds for n' AND recount >= count;
+ *                otherwise the hypothesis is.  `refined` says which.
+ *  Orientation.  The returned plane (n, d) is negated (exactly) iff (n_x a_x + n_y a_y) + n_z a_z < 0, a the caller's axis, or
+ *                (0, 1, 0) when unconstrained.  The hypothesis in the result is the table's row, not turned.
+ *  Partition.    Class A: the inliers of a GIVEN plane and distance; with CWIPC_HIP_PLANE_BELOW_IS_INLIER the points with
+ *                e <= distance (the floor and everything under it).  Class B: the other points, non-finite ones included.  A stable
+ *                two-class partition with KEEP_INLIERS / KEEP_REST and *n_first as cwipc_hip_floor_partition has it; colours, tiles,
+ *                timestamp and cellsize are the input's.
+ *  Levelling.    A plane with n_y < 0 is negated first; (n, d) is divided by |n|.  R is the minimal rotation taking n to (0, 1, 0)
+ *                (Rodrigues about n x Y): rows (1 - f n_x n_x, -n_x, -f n_x n_z), (n_x, n_y, n_z), (-f n_x n_z, -n_z, 1 - f n_z n_z) with
+ *                f = 1 / (1 + n_y);  t = (0, d, 0).  Worked out in long double and rounded once, as plane_motion (csrc/plane_fit.hpp)
+ *                does: every entry of R^T R - I stays within PLANE_FIT_ORTHO_BOUND.
+ *  Refusals.     -1 / NULL, logged as an ERROR, before anything is launched: a NULL cloud or pointer, parameters outside the ranges
+ *                above, unknown flag bits, for partition and levelling a non-finite plane, a zero normal or a distance that find refuses.
+ *  Nothing depends on launch shape or scheduling: all device-side sums are integers.
+ * The cloud is neither consumed nor changed.  Cost: count(pc) * iterations plane tests. */
+#define CWIPC_HIP_PLANE_REFINE 1
+#define CWIPC_HIP_PLANE_KEEP_INLIERS 1     /* class A, first in the result */
+#define CWIPC_HIP_PLANE_KEEP_REST 2        /* class B, behind them */
+#define CWIPC_HIP_PLANE_BELOW_IS_INLIER 4  /* class A is e <= distance instead of |e| <= distance */
+#define CWIPC_HIP_PLANE_MAX_ITERATIONS 65536
+typedef struct cwipc_hip_plane_params {
+    double distance;
+    uint64_t seed;
+    double axis[3];
+    double min_abs_cos;
+    uint32_t iterations;
+    int32_t flags;
+} cwipc_hip_plane_params;
+typedef struct cwipc_hip_plane_result {
+    double plane[4];        /* the returned plane n_x, n_y, n_z, d (oriented); zeros when found == 0 */
+    double hypothesis[4];   /* the best hypothesis' table row */
+    int64_t sums[10];       /* the refit's cnt, S1[3], S2[6]; zeros without REFINE */
+    double M[6];            /* the refit's matrix xx xy xz yy yz zz; zeros unless 3 <= cnt <= 2^26 */
+    uint32_t best;          /* h of the best hypothesis */
+    uint32_t triple[3];     /* its point indices */
+    uint32_t count;         /* its inliers */
+    uint32_t recount;       /* inliers of the refit plane (0 when it was not scored) */
+    uint32_t valid;         /* number of valid hypotheses */
+    int32_t found;
+    int32_t refined;        /* 1: plane is the refit's, 0: the hypothesis' */
+    int32_t reserved;
+} cwipc_hip_plane_result;
+/* The dominant plane.  Without REFINE one wait; with it one for best and sums (chained on the device), a host solve, one for the
+ * recount.  0 ok (found == 0 included). */
+_CWIPC_UTIL_EXPORT int cwipc_hip_plane_find(cwipc_pointcloud *pc, const cwipc_hip_plane_params *params, cwipc_hip_plane_result *result);
+/* The whole table, for tests and diagnostics: planes (4 H doubles), counts (H), triples (3 H), valid (H bytes); each may be NULL. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_plane_scores(cwipc_pointcloud *pc, const cwipc_hip_plane_params *params, double *planes, uint32_t *counts, uint32_t *triples,
+                                              uint8_t *valid);
+/* Partition by a given plane.  The result is device-resident; two waits as the floor partition's. */
+_CWIPC_UTIL_EXPORT cwipc_pointcloud *cwipc_hip_plane_partition(cwipc_pointcloud *pc, const double plane[4], double distance, int flags, uint64_t *n_first);
+/* Levelling: m16 = the row-major 4x4 [R t; 0 1] that cwipc_hip_transform takes.  Host only, no GPU.  0 ok. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_plane_level_matrix(const double plane[4], double m16[16]);
+/* The host twin of cwipc_hip_plane_find and cwipc_hip_plane_scores: the same header text by brute force, O(n * H), no GPU.  planes,
+ * counts and valid as above, each may be NULL.  0 ok; -1 (logged) for what cwipc_hip_plane_find refuses and n >= 2^32. */
+_CWIPC_UTIL_EXPORT int cwipc_hip_plane_find_host(const struct cwipc_point *pts, size_t n, const cwipc_hip_plane_params *params, cwipc_hip_plane_result *result,
+                                                 double *planes, uint32_t *counts, uint8_t *valid);
+
 /* ---- the registration analyzer's arithmetic (reference python/cwipc/registration/analyze.py) ---- */
 /* Per point of `source` the SQUARED distance, in f64, to its (nth + 1)-th nearest point of `reference` among those closer than
  * max_distance (strictly; INFINITY: no bound), +inf when there are fewer: d2 = (dx*dx + dy*dy) + dz*dz with dx = (double)qx - (double)px,
